@@ -33,6 +33,7 @@ import subprocess
 import sys
 import tempfile
 import time
+import zlib
 from pathlib import Path
 
 ROOT = Path(__file__).resolve().parent
@@ -75,6 +76,10 @@ def parse_args():
                     help="do not write the sidecar bench_detail.json (child runs of this file must not overwrite the parent's)")
     ap.add_argument("--no-step-trace", action="store_true",
                     help="skip the rocprofv3 kernel trace / PMC passes of the timed loop (roofline.c2 = null)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step handed its caller to DIR/<name>.npy (rank 0): "
+                         "the step's metrics as fetched to the host, every variable after the step's update and the gradient "
+                         "it applied (float32 / float64, at most 64 MB; larger arrays as a fixed seeded sample)")
     return ap.parse_args()
 
 
@@ -499,6 +504,46 @@ def other_configs_section(timeout_s=240):
 
 
 # ------------------------------------------------------------------------------------------------------------------
+# --dump-outputs: the last timed step's results, for comparing two builds output for output
+# ------------------------------------------------------------------------------------------------------------------
+DUMP_LIMIT_BYTES = 64 << 20
+DUMP_SAMPLE_MIN = 4096        # arrays at most this long are always written whole
+
+
+def _dump_name(name):
+    return "".join(c if c.isalnum() or c in "_-." else "_" for c in name.replace("/", "."))
+
+
+def dump_outputs(out_dir, model, metrics):
+    """Write the finite metrics of the last timed step (host values, float64 scalars) and, for every variable of the model, its
+    value after that step's update (`var.<name>`) and the gradient the update applied (`grad.<name>`, float32) as <name>.npy
+    under out_dir.  A metric that is not finite is left out (micro-F1 is NaN, as in the reference, when the step predicts no
+    positive label), so every file holds numbers two builds can be compared on.  When the files would exceed DUMP_LIMIT_BYTES, every array longer than DUMP_SAMPLE_MIN is cut to the same fraction
+    of its entries, picked with a generator seeded from the array's name (same arguments -> same entries), flattened in index
+    order.  Returns {name: entries written}."""
+    arrays = {"metric." + _dump_name(k): np.asarray(float(v), dtype=np.float64) for k, v in sorted(metrics.items())
+              if isinstance(v, (int, float, np.floating, np.integer)) and not isinstance(v, bool) and np.isfinite(v)}
+    for name in model.variables.names():
+        p = model.variables[name]
+        arrays["var." + _dump_name(name)] = p.detach().float().cpu().numpy()
+        if p.grad is not None:
+            arrays["grad." + _dump_name(name)] = p.grad.detach().float().cpu().numpy()
+    budget = DUMP_LIMIT_BYTES - 256 * len(arrays)           # (room for the .npy headers)
+    long_bytes = sum(a.nbytes for a in arrays.values() if a.size > DUMP_SAMPLE_MIN)
+    short_bytes = sum(a.nbytes for a in arrays.values() if a.size <= DUMP_SAMPLE_MIN)
+    keep = 1.0 if long_bytes + short_bytes <= budget else max(0.0, budget - short_bytes) / long_bytes
+    os.makedirs(out_dir, exist_ok=True)
+    written = {}
+    for name, a in arrays.items():
+        if keep < 1.0 and a.size > DUMP_SAMPLE_MIN:
+            rng = np.random.default_rng(zlib.crc32(name.encode()))
+            a = a.reshape(-1)[np.sort(rng.choice(a.size, max(1, int(a.size * keep)), replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        written[name] = int(a.size)
+    return written
+
+
+# ------------------------------------------------------------------------------------------------------------------
 # secondary host/transfer figures
 # ------------------------------------------------------------------------------------------------------------------
 def time_h2d(mb, device, iters=7):
@@ -860,6 +905,7 @@ def main():
             m = m.get()                               # the host sync of sess.run's fetch (:293), one step late: waits for the
             state["host_wait"] += time.perf_counter() - t_wait   # D2H copy enqueued right behind THAT step (MetricsReadback)
             state["loss"] = m['loss']
+            state["metrics"] = m
             m['f1_score']
             state["fetched"] += 1
 
@@ -947,6 +993,11 @@ def main():
                 "step_ms": [round(float(x), 3) for x in step_ms]}
 
     run = timed_loop(primary_kind, args.steps, args.warmup)
+    if args.dump_outputs and rank == 0:       # before anything else runs on the model
+        dumped = dump_outputs(args.dump_outputs, model, run["state"]["metrics"])
+        left_out = sorted(k for k, v in run["state"]["metrics"].items() if "metric." + _dump_name(k) not in dumped)
+        print("bench.py: %d arrays of the last timed step under %s%s" % (len(dumped), args.dump_outputs,
+              " (not finite, left out: %s)" % ", ".join(left_out) if left_out else ""))
     elapsed, per_rank, edges_rs, state, reducer_info = run["elapsed"], run["per_rank"], run["edges_rs"], run["state"], run["reducer"]
     overlap_reduce = primary_kind == "overlap"
     other_run = None

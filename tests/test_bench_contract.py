@@ -180,9 +180,13 @@ def test_live_short_run_prints_one_json_line():
 
 @pytest.mark.gpu
 def test_live_multi_rank_line_is_small_too():
-    """8 ranks sharing this box's GPU over gloo (launch-path rehearsal): the line obeys the same size bound."""
+    """Several ranks sharing this box's GPU over gloo (launch-path rehearsal): the line obeys the same size bound.  Three ranks: with
+    this process, bench.py's launcher and the torch.distributed.run agent that makes six processes with the GPU open, the most a
+    shared machine allows one job.  The bound at 8 ranks is asserted on the committed 8-rank record
+    (test_the_printed_line_is_small_and_keeps_the_contract_on_every_committed_record)."""
+    n = 3
     env = dict(os.environ, RELGNN_BENCH_SHARE_GPU="1")
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "3", "--warmup", "1",
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--steps", "3", "--warmup", "1",
                         "--no-roofline", "--no-cpu-baseline", "--no-extras", "--no-detail",
                         "--task-param-overrides", '{"graphs_per_rank": 16}'], capture_output=True, text=True, cwd=ROOT,
                        timeout=1500, env=env)
@@ -191,7 +195,7 @@ def test_live_multi_rank_line_is_small_too():
     assert len(lines) == 1 and len(lines[0]) < LINE_LIMIT
     d = json.loads(lines[0])
     _check_line(d, full=False)
-    assert d["n_gpus"] == d["nranks"] == 8 and len(d["per_rank"]["gpu_step_ms_median"]) == 8
+    assert d["n_gpus"] == d["nranks"] == n and len(d["per_rank"]["gpu_step_ms_median"]) == n
 
 
 @pytest.mark.gpu
@@ -202,3 +206,82 @@ def test_asking_for_more_gpus_than_the_box_has_is_an_error():
                         "--no-roofline", "--no-cpu-baseline", "--no-extras"], capture_output=True, text=True, cwd=ROOT,
                        timeout=900, env={k: v for k, v in os.environ.items() if k != "RELGNN_BENCH_SHARE_GPU"})
     assert p.returncode != 0 and not any(l.startswith("{") for l in p.stdout.splitlines())
+
+
+class _Vars:
+    def __init__(self, d):
+        self._d = d
+
+    def names(self):
+        return list(self._d)
+
+    def __getitem__(self, name):
+        return self._d[name]
+
+
+def _fake_model(seed):
+    import torch
+    g = torch.Generator().manual_seed(seed)
+    d = {}
+    for name, shape in (("graph_model/w_0", (300, 200)), ("graph_model/b_0", (200,)), ("out/w", (50, 40))):
+        p = torch.nn.Parameter(torch.rand(shape, generator=g))
+        p.grad = torch.rand(shape, generator=g)
+        d[name] = p
+    return type("M", (), {"variables": _Vars(d)})()
+
+
+def test_dump_outputs_writes_metrics_variables_and_gradients(tmp_path, monkeypatch):
+    """--dump-outputs: one .npy per finite metric (float64), variable and gradient (float32) under DIR (a NaN metric — micro-F1
+    with no positive prediction — is left out); past the byte limit the long arrays become the same seeded sample on every
+    call, and the whole dump stays within the limit."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    model = _fake_model(0)
+    metrics = {"loss": 1.25, "total_loss": 80.0, "f1_score": 0.5}
+    assert "metric.f1_score" not in bench.dump_outputs(str(tmp_path / "nan"), model, dict(metrics, f1_score=float("nan")))
+    written = bench.dump_outputs(str(tmp_path / "whole"), model, metrics)
+    assert set(written) == {"metric.loss", "metric.total_loss", "metric.f1_score", "var.graph_model.w_0", "var.graph_model.b_0",
+                            "var.out.w", "grad.graph_model.w_0", "grad.graph_model.b_0", "grad.out.w"}
+    assert np.load(tmp_path / "whole" / "metric.loss.npy").dtype == np.float64
+    assert float(np.load(tmp_path / "whole" / "metric.loss.npy")) == 1.25
+    w = np.load(tmp_path / "whole" / "var.graph_model.w_0.npy")
+    assert w.dtype == np.float32 and np.array_equal(w, model.variables["graph_model/w_0"].detach().numpy())
+    assert np.array_equal(np.load(tmp_path / "whole" / "grad.out.w.npy"), model.variables["out/w"].grad.numpy())
+    # a limit below the arrays' size: the 60000-entry arrays are sampled, the short ones stay whole, twice the same entries
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 200000)
+    a = bench.dump_outputs(str(tmp_path / "a"), model, metrics)
+    b = bench.dump_outputs(str(tmp_path / "b"), _fake_model(0), metrics)
+    assert a == b and a["var.graph_model.w_0"] < 60000 and a["grad.graph_model.w_0"] < 60000
+    assert a["var.out.w"] == 2000 and a["var.graph_model.b_0"] == 200
+    for name in a:
+        assert np.array_equal(np.load(tmp_path / "a" / (name + ".npy")), np.load(tmp_path / "b" / (name + ".npy")))
+    assert sum(f.stat().st_size for f in (tmp_path / "a").iterdir()) <= bench.DUMP_LIMIT_BYTES
+    full = model.variables["graph_model/w_0"].detach().numpy().reshape(-1)
+    assert np.isin(np.load(tmp_path / "a" / "var.graph_model.w_0.npy"), full).all()
+
+
+
+@pytest.mark.gpu
+def test_live_dump_outputs_are_the_same_inputs_run_to_run(tmp_path):
+    """bench.py --dump-outputs DIR twice with the same arguments: the same arrays (metrics of the last timed step, every variable
+    after its update and its gradient), float32 / float64, within 64 MB, and the same numbers up to the order of floating-point
+    accumulations."""
+    import numpy as np
+    dumps = []
+    for i in range(2):
+        d = tmp_path / ("run%d" % i)
+        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                            "--no-roofline", "--no-cpu-baseline", "--no-extras", "--no-detail", "--dump-outputs", str(d)],
+                           capture_output=True, text=True, cwd=ROOT, timeout=900)
+        assert p.returncode == 0, p.stderr[-2000:]
+        line = json.loads([l for l in p.stdout.splitlines() if l.strip()][-1])
+        assert line["steps"] == 3
+        dumps.append({f.name[:-4]: np.load(f) for f in sorted(d.glob("*.npy"))})
+    a, b = dumps
+    assert set(a) == set(b) and "metric.loss" in a and any(k.startswith("var.") for k in a) and any(k.startswith("grad.") for k in a)
+    assert np.isfinite(a["metric.loss"]) and sum(f.stat().st_size for f in (tmp_path / "run0").iterdir()) <= 64 << 20
+    for k in a:
+        assert a[k].dtype in (np.float32, np.float64) and a[k].shape == b[k].shape, k
+        assert np.isfinite(a[k]).all(), k
+        assert np.allclose(a[k], b[k], rtol=1e-4, atol=1e-6), (k, float(np.abs(a[k] - b[k]).max()))

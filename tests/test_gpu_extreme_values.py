@@ -110,10 +110,6 @@ FWD_ROUTES = [("limb_dense", 256), ("limb_dense_nt", 256), ("limb_weight_image",
 @pytest.mark.parametrize("M,K", [(5000, 256), (4133, 48), (36096, 128)])
 def test_forward_products_of_huge_and_tiny_finite_rows(gpu_device, route, N, M, K):
     from tf_gnn_samples_amd import config
-    if M > 6000 and route not in ("limb_dense", "limb_sel", "limb16_pair"):
-        pytest.skip("the large height once per kernel family")
-    if route == "limb16_pair_groups" and K % 32:
-        pytest.skip("two k-groups per row need K % 32 == 0")
     a = _extreme_left_operand(M, K, gpu_device, M + K)
     w = _small_weights(K, N, gpu_device, N + K)
     out = _forward_product(route, a, w, config.settings)
