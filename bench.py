@@ -12,15 +12,18 @@ A step = ONE training step of the reference's model the way the reference's epoc
 metrics are fetched to the host (one step late, so the fetch never idles the GPU).  The data fold is resident in
 HBM when the timed region starts (tasks/resident.py); nothing is cached across steps.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--full]
   N > 1: one rank per GPU over RCCL.  Either launched through torch.distributed.run (RANK/LOCAL_RANK/WORLD_SIZE in
   the environment) or, when WORLD_SIZE is unset, bench.py re-launches itself through torch.distributed.run with N
   ranks.  Graphs are sharded across ranks by edge count (weak scaling: 64 graphs per rank), message passing needs
   no collective, ONE RCCL all-reduce of the flat gradient per step.
 
-Prints ONE JSON line on rank 0 with `roofline` (the gather/segment-reduce kernel, timed live with HIP events on the
-launch stream at four working-set sizes, HBM bytes from live rocprofv3 PMC passes) and `cpu_baseline` (the
-reference-order CPU restatement timed on this box's host cores on a bounded sample of the same batch).
+Prints ONE JSON line on rank 0.  A plain run does only what the headline needs: set-up, warm-up, the timed steps,
+--dump-outputs, the line.  `--full` adds the secondary measurements behind it: `roofline` (the gather/segment-reduce
+kernel, timed live with HIP events on the launch stream at four working-set sizes, HBM bytes from live rocprofv3 PMC
+passes, the same kernel inside the timed loop), `cpu_baseline` (the reference-order CPU restatement timed on this
+box's host cores on the same batch), the same-batch step, the other two arithmetics, the other BASELINE configs and,
+at N > 1, the other form of the gradient all-reduce.
 """
 import argparse
 import csv
@@ -47,40 +50,51 @@ import torch.distributed as dist
 GRAPHS_PER_BATCH = 16         # BASELINE.json configs[1]: ~2 M edges per batch
 
 
-def parse_args():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=60)
     ap.add_argument("--warmup", type=int, default=12)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true", help="skip the kernel roofline section (rank 0, N=1 only)")
-    ap.add_argument("--no-pmc", action="store_true", help="skip the live rocprofv3 --pmc passes (roofline.traffic = null)")
-    ap.add_argument("--no-extras", action="store_true", help="skip the secondary measurements (same-batch step, forward only, H2D)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run every secondary measurement (the --no-* switches below leave out single "
+                         "ones): kernel roofline with PMC passes and the in-step trace, same-batch step / forward only / host feed, "
+                         "the other two arithmetics and the other BASELINE configs in child runs, the CPU baseline, and at N > 1 "
+                         "the other form of the gradient all-reduce.  Without it a run sets up, warms up, times the steps, writes "
+                         "--dump-outputs and prints the line")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-roofline", action="store_true", help="--full: skip the kernel roofline section (rank 0, N=1 only)")
+    ap.add_argument("--no-pmc", action="store_true", help="--full: skip the live rocprofv3 --pmc passes (roofline.traffic = null)")
+    ap.add_argument("--no-extras", action="store_true",
+                    help="--full: skip the secondary measurements (same-batch step, forward only, H2D, the other arithmetics, the "
+                         "other BASELINE configs)")
     ap.add_argument("--config", default="C2", choices=["C2", "C5"],
                     help="C2 (default): BASELINE configs[1], RGCN on PPI-shaped batches — the headline metric.  C5: BASELINE "
                          "configs[4], GNN-FiLM on VarMisuse-shaped batches (23 edge types, h=128, 10 layers), ~1.2 M edges per rank "
                          "and step, sharded by graph with ONE all-reduce of the ~46 MB FiLM gradient per step")
     ap.add_argument("--cpu-sample-graphs", type=int, default=GRAPHS_PER_BATCH,
-                    help="graphs of the bench batch the CPU baseline's TRAINING leg runs on (default: all %d = the whole C2 batch, "
-                         "~11 s per step on 16 host threads)" % GRAPHS_PER_BATCH)
+                    help="--full: graphs of the bench batch the CPU baseline's TRAINING leg runs on (default: all %d = the whole "
+                         "C2 batch, ~11 s per step on 16 host threads)" % GRAPHS_PER_BATCH)
     ap.add_argument("--model-param-overrides", default=None,
                     help="JSON dict of model hyper-parameters laid over the config's (the reference's train.py:38-59 layering: class "
                          "defaults -> the config's values -> this), e.g. '{\"graph_num_layers\": 4}'.  A run with overrides is NOT "
                          "the BASELINE workload any more: the line says so in config.model_param_overrides")
     ap.add_argument("--task-param-overrides", default=None,
                     help="JSON dict laid over the synthetic fold's generator parameters (graphs_per_rank, mean_nodes, ...)")
-    ap.add_argument("--kernel-iters", type=int, default=20)
+    ap.add_argument("--kernel-iters", type=int, default=20, help="--full: HIP-event launches per roofline size")
     ap.add_argument("--no-allreduce-compare", action="store_true",
-                    help="N > 1: skip the second loop that times the other form of the gradient all-reduce")
+                    help="--full, N > 1: skip the second loop that times the other form of the gradient all-reduce")
     ap.add_argument("--no-detail", action="store_true",
                     help="do not write the sidecar bench_detail.json (child runs of this file must not overwrite the parent's)")
     ap.add_argument("--no-step-trace", action="store_true",
-                    help="skip the rocprofv3 kernel trace / PMC passes of the timed loop (roofline.c2 = null)")
+                    help="--full: skip the rocprofv3 kernel trace / PMC passes of the timed loop (roofline.c2 = null)")
     ap.add_argument("--dump-outputs", default=None, metavar="DIR",
                     help="after the timed steps, write what the last timed step handed its caller to DIR/<name>.npy (rank 0): "
                          "the step's metrics as fetched to the host, every variable after the step's update and the gradient "
                          "it applied (float32 / float64, at most 64 MB; larger arrays as a fixed seeded sample)")
-    return ap.parse_args()
+    args = ap.parse_args(argv)
+    if not args.full:           # a plain run: nothing past the headline's own set-up, steps, dump and line
+        args.no_cpu_baseline = args.no_roofline = args.no_extras = args.no_allreduce_compare = True
+    return args
 
 
 # ------------------------------------------------------------------------------------------------------------------

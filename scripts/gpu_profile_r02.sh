@@ -12,7 +12,7 @@ R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out/r02_profile
 rm -rf $O; mkdir -p $O
 cd $R
-( time timeout 900 python bench.py --steps 60 --warmup 12 2>$O/bench.err >$O/bench.json ) 2>&1 | tail -3
+( time timeout 900 python bench.py --full --steps 60 --warmup 12 2>$O/bench.err >$O/bench.json ) 2>&1 | tail -3
 cd /tmp
 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace_bench -o bench -- \
     python $R/bench.py --steps 40 --warmup 10 --no-roofline --no-extras --no-cpu-baseline > $O/bench_under_rocprof.json 2> $O/bench_under_rocprof.err

@@ -22,7 +22,7 @@ RELGNN_LIMB=pair timeout 1500 python -m pytest tests -m gpu -q > $O/gpu_tests_li
 RELGNN_GEMM=lib timeout 1500 python -m pytest tests -m gpu -q > $O/gpu_tests_gemm_lib.txt 2>&1; echo "gpu tests rc=$?" >> $O/gpu_tests_gemm_lib.txt
 cp $O/parity_margin.json $O/parity_baseline_size.json $O/gradient_parity_by_seed.json $O/limb16_tn_column_range.json gpurun_out/ 2>/dev/null
 timeout 300 python scripts/parity_margins.py 2> /dev/null | sed -n '/^{/,$p' > $O/parity_margins.json
-( time RELGNN_BENCH_KEEP_TRACE=$O timeout 1200 python bench.py 2>$O/bench.err >$O/bench.json ) 2>&1 | tail -3
+( time RELGNN_BENCH_KEEP_TRACE=$O timeout 1200 python bench.py --full 2>$O/bench.err >$O/bench.json ) 2>&1 | tail -3
 timeout 300 python bench.py --config C5 --steps 10 --warmup 3 --no-roofline --no-extras --no-cpu-baseline > $O/bench_c5.json 2>> $O/bench.err
 cd /tmp
 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace_giant_uniform -o g -- \

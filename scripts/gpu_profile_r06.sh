@@ -1,7 +1,7 @@
 #!/bin/bash
 # rocprofv3 evidence for profiles/ (round 6).  Run through gpurun; outputs under gpurun_out/r06_profile/.
 #  (1) smoke + the full GPU test suite on the default switches (exact split), then with RELGNN_LIMB=pair and with RELGNN_GEMM=lib
-#  (2) the bench line AS THE DRIVER RUNS IT (python bench.py --gpus 1 --steps 20 --warmup 5): the printed line (bench.json, < 6 KB) and
+#  (2) the bench line with every section (python bench.py --full --gpus 1 --steps 20 --warmup 5): the printed line (bench.json, < 6 KB) and
 #      the sidecar (bench_detail.json); the stats table of the timed loop is kept
 #  (3) bench.py --config C5 (distinct batches)
 #  (4) kernel trace + stats of the roofline workload the line is quoted on (giant_uniform, cold protocol only)
@@ -20,7 +20,7 @@ timeout 1800 python -m pytest tests -m gpu -q > $O/gpu_tests.txt 2>&1; echo "gpu
 cp gpurun_out/parity_margin.json gpurun_out/parity_baseline_size.json gpurun_out/gradient_parity_by_seed.json gpurun_out/adam_outliers.json $O/ 2>/dev/null
 RELGNN_LIMB=pair timeout 1800 python -m pytest tests -m gpu -q > $O/gpu_tests_limb_pair.txt 2>&1; echo "gpu tests rc=$?" >> $O/gpu_tests_limb_pair.txt
 RELGNN_GEMM=lib timeout 1800 python -m pytest tests -m gpu -q > $O/gpu_tests_gemm_lib.txt 2>&1; echo "gpu tests rc=$?" >> $O/gpu_tests_gemm_lib.txt
-( time RELGNN_BENCH_KEEP_TRACE=$O timeout 1200 python bench.py --gpus 1 --steps 20 --warmup 5 2>$O/bench.err >$O/bench.json ) 2>&1 | tail -3
+( time RELGNN_BENCH_KEEP_TRACE=$O timeout 1200 python bench.py --full --gpus 1 --steps 20 --warmup 5 2>$O/bench.err >$O/bench.json ) 2>&1 | tail -3
 cp bench_detail.json $O/bench_detail.json; wc -c $O/bench.json
 timeout 300 python bench.py --config C5 --steps 24 --warmup 8 --no-roofline --no-extras --no-cpu-baseline --no-detail > $O/bench_c5.json 2>> $O/bench.err
 cd /tmp
@@ -37,7 +37,7 @@ cd $R
 find $O -name "*kernel_trace.csv" -delete; rm -rf $O/trace_giant_uniform $O/trace_C5 $O/trace_C3
 GRAFT_REPO_ROOT=$R timeout 900 bash scripts/profile_edge_pmc.sh > $O/edge_pmc.log 2>&1; cp gpurun_out/prof_edge_pmc/edge_kernels_pmc.csv $O/ 2>/dev/null
 for n in 2 8; do
-  RELGNN_BENCH_SHARE_GPU=1 timeout 900 python bench.py --gpus $n --steps 6 --warmup 3 --no-roofline --no-cpu-baseline --no-extras --no-detail \
+  RELGNN_BENCH_SHARE_GPU=1 timeout 900 python bench.py --full --gpus $n --steps 6 --warmup 3 --no-roofline --no-cpu-baseline --no-extras --no-detail \
       --task-param-overrides '{"graphs_per_rank": 32}' > $O/bench_${n}ranks_one_gpu_gloo.json 2> $O/bench_${n}ranks.err
   wc -c $O/bench_${n}ranks_one_gpu_gloo.json
 done

@@ -4,6 +4,7 @@ import json
 import os
 import subprocess
 import sys
+import time
 
 import pytest
 
@@ -140,9 +141,9 @@ def test_committed_bench_line_keeps_the_contract():
 
 
 def test_committed_multi_rank_rehearsal_times_both_forms_of_the_all_reduce():
-    """bench.py --gpus N (here: 2 and 8 ranks sharing ONE MI355X over gloo — a launch-path rehearsal, not a scaling number): the
-    timed region runs the default (flat) all-reduce, the same loop right behind it the bucketed one, and the line carries both as
-    scalars next to the per-rank lists."""
+    """bench.py --full --gpus N (here: 2 and 8 ranks sharing ONE MI355X over gloo — a launch-path rehearsal, not a scaling number):
+    the timed region runs the default (flat) all-reduce, the same loop right behind it the bucketed one, and the line carries both
+    as scalars next to the per-rank lists."""
     for n in (2, 8):
         d = json.load(open(os.path.join(ROOT, "profiles", "r05_bench_%dranks_one_gpu_gloo.json" % n)))
         _check_line(d, full=False)
@@ -151,6 +152,22 @@ def test_committed_multi_rank_rehearsal_times_both_forms_of_the_all_reduce():
         assert d["allreduce_compare"]["allreduce"] == "overlap" and d["allreduce_compare"]["buckets"] >= 2
         assert len(d["per_rank"]["allreduce_ms_mean"]) == n and d["allreduce_ms"] == max(d["per_rank"]["allreduce_ms_mean"])
         assert 1.0 <= d["edge_imbalance"] <= 1.10
+
+
+def test_a_plain_run_leaves_every_secondary_measurement_to_full():
+    """Without --full, bench.py runs the headline only (set-up, warm-up, timed steps, --dump-outputs, the line): every section
+    behind the --no-* switches is off.  --full turns them all on, and each switch still leaves out its own section there."""
+    if ROOT not in sys.path:
+        sys.path.insert(0, ROOT)
+    import bench
+    switches = ("no_cpu_baseline", "no_roofline", "no_extras", "no_allreduce_compare")
+    plain = bench.parse_args(["--gpus", "1", "--steps", "4", "--warmup", "2"])
+    assert not plain.full and all(getattr(plain, k) for k in switches)
+    full = bench.parse_args(["--gpus", "1", "--steps", "4", "--warmup", "2", "--full"])
+    assert full.full and not any(getattr(full, k) for k in switches) and not full.no_pmc and not full.no_step_trace
+    some = bench.parse_args(["--full", "--no-cpu-baseline", "--no-pmc"])
+    assert some.no_cpu_baseline and some.no_pmc and not (some.no_roofline or some.no_extras or some.no_allreduce_compare)
+    assert (plain.steps, plain.warmup, plain.dump_outputs) == (full.steps, full.warmup, full.dump_outputs) == (4, 2, None)
 
 
 def test_bench_refuses_to_run_without_a_gpu_or_with_too_few():
@@ -176,6 +193,29 @@ def test_live_short_run_prints_one_json_line():
     # the sidecar holds the full record and the line is its compaction
     detail = json.load(open(os.path.join(ROOT, d["detail"])))
     assert _compact(detail) == d and "dense_products" in detail and "generator" in detail["config"]
+
+
+@pytest.mark.gpu
+def test_live_plain_run_is_the_headline_alone():
+    """`bench.py --gpus 1 --steps K --warmup W` as the driver runs it (sidecar write included): the line carries the headline and
+    none of the sections that only --full runs, and the run spends at most 30 s outside its steps (wall time of the process from
+    start to exit, less (K + W) x ms_per_step).  Inside the suite the host's file caches are warm, so this bounds a warm start;
+    a cold first run after build() is not what it measures."""
+    t0 = time.perf_counter()
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5"],
+                       capture_output=True, text=True, cwd=ROOT, timeout=900)
+    wall = time.perf_counter() - t0
+    assert p.returncode == 0, p.stderr[-2000:]
+    lines = [l for l in p.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    _check_line(d, full=False)
+    assert d["steps"] == 20 and d["warmup"] == 5 and d["n_gpus"] == 1
+    for k in ("roofline", "cpu_baseline", "other_configs", "same_batch_ms_per_step", "exact_fp32_lib_ms_per_step",
+              "pair_route_ms_per_step"):
+        assert k not in d, k
+    outside = wall - (d["steps"] + d["warmup"]) * d["ms_per_step"] * 1e-3
+    assert outside <= 30.0, outside
 
 
 @pytest.mark.gpu
