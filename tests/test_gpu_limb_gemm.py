@@ -197,8 +197,8 @@ def test_weight_limb_images_equal_single_splits(gpu_device):
     """relgnn_limb_split_multi_f32 (one launch for the weights of a step) writes the images relgnn_limb_split_f32 writes, for the
     three operand kinds, incl. the stacked [W_0 | W_1 | ..] operand that is never formed in fp32, and for more matrices than one
     launch takes."""
-    from tf_gnn_samples_amd import dense as DN
-    DN._WEIGHT_LIMBS.clear()
+    from tf_gnn_samples_amd import dense as DN, weight_images
+    weight_images.clear()
     W = _rand((3, 256, 256), gpu_device, 1, 0.1)
     Wd = _rand((256, 512), gpu_device, 2, 0.1)
     a = DN.weight_limbs(W.view(768, 256), DN.WEIGHT_NN)
@@ -221,16 +221,16 @@ def test_weight_limb_images_equal_single_splits(gpu_device):
     got = [DN.weight_limbs(m, DN.WEIGHT_NT) for m in many]            # the first request re-splits all 30 + the 3 above
     for m, g in zip(many, got):
         assert torch.equal(g, DN.limb_split(m).data)
-    DN._WEIGHT_LIMBS.clear()
+    weight_images.clear()
 
 
 def test_weight_limb_cache_follows_the_weights(gpu_device):
     """A cached image is replaced after an in-place write (version counter), after weights_changed() (writes through raw
     pointers, as the fused optimizer launch does), and when another tensor takes the address."""
-    from tf_gnn_samples_amd import config, dense as DN
+    from tf_gnn_samples_amd import config, dense as DN, weight_images
     if not config.settings.limb_gemm:
         pytest.skip("the public Dense entry takes another route in this run (RELGNN_GEMM)")
-    DN._WEIGHT_LIMBS.clear()
+    weight_images.clear()
     x = _rand((4608, 256), gpu_device, 3)
     w = _rand((256, 256), gpu_device, 4, 0.1)
     y0 = DN.lib_gemm(DN.GEMM_NN, x, w, weight=True)
@@ -249,7 +249,7 @@ def test_weight_limb_cache_follows_the_weights(gpu_device):
     w2 = _rand((256, 256), gpu_device, 5, 0.1)
     if w2.data_ptr() == ptr:
         assert torch.equal(DN.lib_gemm(DN.GEMM_NN, x, w2, weight=True), DN.lib_gemm(DN.GEMM_NN, x, w2))
-    DN._WEIGHT_LIMBS.clear()
+    weight_images.clear()
 
 
 def test_grouped_gemms_equal_the_stacked_products(gpu_device):
@@ -276,7 +276,7 @@ def test_grouped_gemms_equal_the_stacked_products(gpu_device):
 def test_training_steps_with_and_without_the_weight_limb_cache(gpu_device):
     """Three fused clip + Adam steps of the C2-shaped model: the parameters are the same bits whether the weights' limbs are
     split per product or once per step."""
-    from tf_gnn_samples_amd import dense as DN
+    from tf_gnn_samples_amd import dense as DN, weight_images
     from tf_gnn_samples_amd import config
     from tf_gnn_samples_amd.models import RGCN_Model
     from tf_gnn_samples_amd.tasks import DataFold, DeviceBatch, PPI_Task
@@ -284,7 +284,7 @@ def test_training_steps_with_and_without_the_weight_limb_cache(gpu_device):
     mb = next(task.make_minibatch_iterator(task._loaded_data[DataFold.TRAIN], DataFold.VALIDATION, 10 ** 9))
     results = []
     for cached in (True, False):
-        DN._WEIGHT_LIMBS.clear()
+        weight_images.clear()
         config.settings.weight_limb_cache = "1" if cached else "0"
         try:
             torch.manual_seed(0)
@@ -302,7 +302,7 @@ def test_training_steps_with_and_without_the_weight_limb_cache(gpu_device):
     assert mb.num_nodes >= 4096                                       # (the limb route is what ran)
     for a, b in zip(*results):
         assert torch.equal(a, b)
-    DN._WEIGHT_LIMBS.clear()
+    weight_images.clear()
 
 
 @pytest.mark.parametrize("rps,tiles,last", [(128, 300, 128), (256, 140, 200), (384, 90, 1), (512, 70, 300), (512, 65, 512)])
@@ -940,6 +940,42 @@ def test_panel_products_take_cached_weight_images_and_give_the_same_bits(gpu_dev
     assert torch.equal(a1, a0)
     assert float((a1.double() - torch.tanh(x.double() @ k.double() + b.double())).abs().max()) <= 2e-6
     assert torch.equal(DN.lib_gemm(DN.GEMM_NN, x, k, b, weight=True, act=_lib.ACT_TANH), a0)      # the route the Dense layers take
+
+
+def test_panel_product_follows_a_parameter_whose_storage_is_replaced(gpu_device):
+    """`p.data = other` (what `module.to(...)` does to parameters) moves a weight to another storage without moving its version,
+    and nobody calls weights_changed().  The image that sel_image() finds by the identity of the tensor objects must not be handed
+    out for the new storage: the product after the swap equals the uncached relgnn_limb_dense_sel_f32 product on the new values.
+    (Before the identity index shared the general index's validity rule — same object, version, ADDRESS and row stride — the
+    third request below returned the image of the old storage, i.e. the product with the old weights.)"""
+    from tf_gnn_samples_amd import config as _config
+    if not _config.settings.limb_gemm:
+        pytest.skip("the cached panel images belong to the limb route (RELGNN_GEMM is set to another route in this run)")
+    from tf_gnn_samples_amd import dense as DN
+    dev = gpu_device
+    L, tiles = 5, 24
+    P = tiles * 512
+    g = torch.Generator(device="cpu").manual_seed(1)
+    tile_type = torch.sort(torch.randint(0, L, (tiles,), generator=g)).values.to(torch.int32).to(dev)
+    x = _rand((P, 128), dev, 2)
+    for layout in (DN.GEMM_NN, DN.GEMM_NT):
+        Ws = [torch.nn.Parameter(_rand((128, 128), dev, 30 + l, 0.1)) for l in range(L)]
+
+        def product():
+            return DN.limb_dense_sel(layout, x, Ws, b_select=tile_type, rows_per_select=512, image=DN.sel_image(Ws, layout))
+
+        def uncached():
+            return DN.limb_dense_sel(layout, x, torch.stack([w.detach() for w in Ws]), b_select=tile_type, rows_per_select=512)
+
+        before = product()
+        assert DN.sel_image(Ws, layout) is DN.sel_image(Ws, layout)                    # (by identity from the second lookup on)
+        assert torch.equal(product(), before) and torch.equal(before, uncached())
+        version = Ws[2]._version
+        Ws[2].data = _rand((128, 128), dev, 77, 0.1)
+        assert Ws[2]._version == version                                              # (nothing torch counts has happened)
+        after = product()
+        assert torch.equal(after, uncached())
+        assert not torch.equal(after, before)
 
 
 def test_dense_multi_is_the_product_with_the_concatenated_kernels(gpu_device):

@@ -33,7 +33,11 @@ import torch
 # float64 on the C2 shapes neither arithmetic is systematically closer end to end (profiles/r04_*);
 # `triple` keeps the exact split everywhere.
 from .config import settings as _cfg
-
+# the limb images of the weights (weight_images.py: one cache, one validity rule), under the names the products below and the
+# callers of this module use — weights_changed() is the documented contract: tf_gnn_samples_amd.dense.weights_changed()
+from .weight_images import (GEMM_NN, GEMM_NT, GEMM_TN, WEIGHT_NN, WEIGHT_NT, _PerStream, _weight_image_items, _weight_image_shape,
+                            _weight_matrices, capture_image_cache, clear as _clear_weight_images, sel_image, sel_weights_cacheable,
+                            weight_image, weight_image_ok, weight_limbs, weights_changed)
 
 
 def _ops():
@@ -42,7 +46,6 @@ def _ops():
 
 
 _LIMB_MIN_ROWS, _LIMB_MAX_K = 4096, 1024
-GEMM_NN, GEMM_NT, GEMM_TN = 0, 1, 2
 _WARNED_UNSUPPORTED = False
 
 
@@ -134,32 +137,6 @@ def _premask_operand_ok(y: torch.Tensor, rows: int, cols: int) -> bool:
             and y.stride(1) == 1 and y.stride(0) % 4 == 0 and y.stride(0) >= cols and y.data_ptr() % 16 == 0)
 
 
-class _PerStream(dict):
-    """Scratch keyed by (device, raw stream handle): products issued on different streams may run concurrently and must not
-    share it.  Bounded: at most `limit` streams per cache are remembered, the least recently used entry goes first (a process
-    that keeps creating streams — graph captures, user streams — would otherwise pin 64 MB per stream for its lifetime, and a
-    recycled stream handle would find another stream's entry).  Dropping an entry only returns its memory to torch's caching
-    allocator, which hands it out again in stream order of the stream it was allocated on; clear_caches() empties all of them."""
-
-    def __init__(self, limit: int = 4):
-        super().__init__()
-        self.limit = limit
-
-    def lookup(self, key):
-        v = self.get(key)
-        if v is not None:                      # move to the back: most recently used
-            del self[key]
-            self[key] = v
-        return v
-
-    def store(self, key, value):
-        self.pop(key, None)
-        while len(self) >= self.limit:
-            del self[next(iter(self))]
-        self[key] = value
-        return value
-
-
 _LIMB_WS = _PerStream()
 _WORKSPACE = _PerStream()
 
@@ -169,9 +146,7 @@ def clear_caches() -> None:
     request).  For callers that retire streams or devices; never needed for correctness."""
     _LIMB_WS.clear()
     _WORKSPACE.clear()
-    _WEIGHT_LIMBS.clear()
-    _FAST_IMAGES.clear()
-    _SPLIT_ARGS.clear()
+    _clear_weight_images()
     _ZEROS.clear()
 
 
@@ -457,223 +432,6 @@ def _limb_route_ok(layout: int, a: torch.Tensor, b: torch.Tensor, bias, columns:
             and (bias is None or (bias.is_cuda and bias.is_contiguous() and bias.dtype == torch.float32 and bias.data_ptr() % 16 == 0)))
 
 
-# ---- the limbs of the step's WEIGHT operands: split once per optimizer step, all of them in one launch ----------------------------
-# A weight is the right operand of two or three products per step (forward, input gradient) and changes once per step.  Its limb
-# image is kept per (device, stream) until the weights change: the optimizer's fused update writes through raw pointers (tensor
-# versions do not move) and says so through weights_changed(); every other in-place write moves the tensor's version, which is
-# compared too.  The first request after a change re-splits every image that the previous step used (relgnn_limb_split_multi_f32);
-# an image may be several matrices side by side along k (the per-edge-type kernels of a layer), so neither the stacked
-# [L*Din, Dout] operand of the forward product nor the stacked W^T of the input gradient is ever formed in fp32.
-# C2: 8 split launches + 3 stacks + 3 re-layouts per step -> 1 launch.  Under stream capture nothing is cached (a replay re-runs
-# kernels, not this code): the image is split on every request.
-_WEIGHT_LIMBS = _PerStream(limit=8)      # (device, stream) -> {operand key: _WeightImage}
-_WEIGHT_GEN = [0]
-WEIGHT_NN, WEIGHT_NT = "nn", "nt"
-
-
-_CAPTURE_IMAGES = {"on": False, "images": {}}
-
-
-class capture_image_cache:
-    """Around the capture of ONE training step into a hipGraph: limb images split inside the capture are reused by later products of
-    the same capture (forward -> backward) until weights_changed() — which the captured optimizer update calls — drops them."""
-
-    def __enter__(self):
-        _CAPTURE_IMAGES["on"], _CAPTURE_IMAGES["images"] = True, {}
-        return self
-
-    def __exit__(self, *exc):
-        _CAPTURE_IMAGES["on"], _CAPTURE_IMAGES["images"] = False, {}
-        return False
-
-
-def weights_changed() -> None:
-    """Tell the limb-image cache that parameters were rewritten in place by something torch's version counters do not see:
-    a kernel that writes through raw pointers (models/sparse_graph_model.py: the fused clip + Adam launch; a hipGraph replay of
-    it), `p.data.copy_()` / `p.data.mul_()`, a third-party optimizer that updates `.data`, a parameter broadcast.  Ordinary
-    in-place tensor operations on the parameter itself (`p.add_()`, `p.copy_()` under no_grad) move its version and are noticed
-    without this call.  PUBLIC CONTRACT of the default route (config gemm=limb, weight_limb_cache=1): whoever writes weights
-    behind torch's back calls tf_gnn_samples_amd.dense.weights_changed() (cheap: a counter) — or runs with
-    RELGNN_WEIGHT_LIMB_CACHE=0, which re-splits on every product."""
-    _WEIGHT_GEN[0] += 1
-    _CAPTURE_IMAGES["images"] = {}
-
-
-class _WeightImage:
-    # (no strong reference to the weights; pair: two fp16 limbs, `wmax` = the device float the image's scale comes from)
-    __slots__ = ("refs", "items", "versions", "gen", "used_gen", "buf", "pair", "wmax")
-
-
-def _weight_matrices(w):
-    """A weight operand as a list of 2-D matrices laid side by side along k: a matrix, a [L, ., .] stack or a sequence."""
-    if torch.is_tensor(w):
-        return [w] if w.dim() == 2 else list(w.unbind(0))
-    return list(w)
-
-
-def _weight_image_shape(ws, kind: str):
-    """(N, K) of B [N, K] = [w_0^T | w_1^T | ..] (WEIGHT_NN: w_l [K_l, N]) or [w_0 | w_1 | ..] (WEIGHT_NT: w_l [N, K_l])."""
-    # (a single matrix whose k extent is not a multiple of 16 — the 121-label head — fills its last k-tile with zeros)
-    k = sum(m.shape[0] if kind == WEIGHT_NN else m.shape[1] for m in ws)
-    if len(ws) == 1:
-        k = (k + 15) // 16 * 16
-    return (ws[0].shape[1] if kind == WEIGHT_NN else ws[0].shape[0]), k
-
-
-def weight_image_ok(ws, kind: str) -> bool:
-    ws = _weight_matrices(ws)
-    n = ws[0].shape[1] if kind == WEIGHT_NN else ws[0].shape[0]
-    for m in ws:
-        if not (m.is_cuda and m.dtype == torch.float32 and m.dim() == 2 and m.stride(1) == 1 and m.stride(0) >= m.shape[1]
-                and (len(ws) == 1 or (m.stride(0) % 4 == 0 and m.data_ptr() % 16 == 0))):
-            return False                   # (a single matrix may have rows of any alignment — [256, 121]: the split reads element-wise)
-        if (m.shape[1] if kind == WEIGHT_NN else m.shape[0]) != n or ((m.shape[0] if kind == WEIGHT_NN else m.shape[1]) % 16 != 0
-                                                                     and len(ws) > 1):
-            return False
-    return True
-
-
-def _weight_image_items(ws, kind: str, buf: torch.Tensor):
-    """(X, ldx, rows, cols, transpose, out, kt_offset, kt_total) per matrix of the image."""
-    total = _weight_image_shape(ws, kind)[1] // 16
-    items, kt = [], 0
-    for m in ws:
-        items.append((m.data_ptr(), m.stride(0), m.shape[0], m.shape[1], 1 if kind == WEIGHT_NN else 0, buf.data_ptr(), kt, total))
-        kt += ((m.shape[0] if kind == WEIGHT_NN else m.shape[1]) + 15) // 16
-    return items
-
-
-_SPLIT_ARGS = {}
-
-
-def _split_weight_images(images) -> None:
-    import ctypes
-    from . import _lib
-    lib = _lib.load_library()
-    triples = [im for im in images if not im.pair]
-    pairs = [im for im in images if im.pair]
-    if triples:
-        # the argument arrays of a set of images are the same every step (an image's items never change): built once per set — a
-        # 23-type, 10-layer model re-splits ~1400 matrices per step, and marshalling them anew cost milliseconds of host time
-        key = tuple(map(id, triples))
-        ent = _SPLIT_ARGS.get(key)
-        if ent is None or len(ent[0]) != len(triples) or any(a is not b for a, b in zip(ent[0], triples)):
-            items = [it for im in triples for it in im.items]
-            n = len(items)
-            cols = list(zip(*items))
-            vp, i64, i32 = ctypes.c_void_p * n, ctypes.c_int64 * n, ctypes.c_int32 * n
-            ent = (list(triples), n, (vp(*cols[0]), i64(*cols[1]), i32(*cols[2]), i32(*cols[3]), i32(*cols[4]), vp(*cols[5]),
-                                      i32(*cols[6]), i32(*cols[7])))
-            if len(_SPLIT_ARGS) > 64:
-                _SPLIT_ARGS.clear()
-            if len(triples) > 4:                       # (small sets are cheap to marshal and vary more)
-                _SPLIT_ARGS[key] = ent
-        _lib.check(lib.relgnn_limb_split_multi_f32(ent[1], *ent[2], _lib.current_stream()), "relgnn_limb_split_multi_f32")
-    if pairs:           # two fp16 limbs: one magnitude per image first (its power-of-two scale), then the limbs — three launches
-        wm = torch.empty(len(pairs), dtype=torch.float32, device=pairs[0].buf.device)
-        items, image = [], []
-        for i, im in enumerate(pairs):
-            im.wmax = wm[i:i + 1]
-            items += im.items
-            image += [i] * len(im.items)
-        n = len(items)
-        cols = list(zip(*items))
-        vp, i64, i32 = ctypes.c_void_p * n, ctypes.c_int64 * n, ctypes.c_int32 * n
-        _lib.check(lib.relgnn_limb16_split_multi_f32(n, vp(*cols[0]), i64(*cols[1]), i32(*cols[2]), i32(*cols[3]), i32(*cols[4]),
-                                                     vp(*cols[5]), i32(*cols[6]), i32(*cols[7]), i32(*image), len(pairs),
-                                                     wm.data_ptr(), _lib.current_stream()), "relgnn_limb16_split_multi_f32")
-
-
-def weight_limbs(w, kind: str) -> torch.Tensor:
-    """The bf16-triple limb image (flat buffer) of a weight operand: weight_image(w, kind).buf."""
-    return weight_image(w, kind).buf
-
-
-def weight_image(w, kind: str, pair: bool = False, separate: bool = False) -> "_WeightImage":
-    """The limb image of a weight operand as the right operand B [N, K] of relgnn_limb_gemm_xf32 (pair: of relgnn_limb16_gemm_xf32:
-    two fp16 limbs, .wmax = the device float its scale comes from); .buf is the flat 16-bit buffer.  w: a matrix, a
-    [L, ., .] stack or a sequence of matrices (laid side by side along k):
-      WEIGHT_NN  w_l [K_l, N]:  [x_0 | x_1 | ..] @ [w_0; w_1; ..] = sum_l x_l @ w_l     (Dense forward; gnns/rgcn.py:96-98 summed over
-                                                                                          the edge types in one product)
-      WEIGHT_NT  w_l [N, K_l]:  [g_0 | g_1 | ..] @ [w_0 | w_1 | ..]^T = sum_l g_l @ w_l^T   (the input gradients of the same)
-    separate: one image PER matrix, one behind the other in the buffer (matrix l at element l * relgnn_limb_elements(N, K); every
-    matrix the same shape, N % 128 == 0) — the per-edge-type operands of relgnn_limb_gemm_sel_xf32 (round 6: the typed transforms
-    and the D = 128 Dense layers no longer re-split their weights in front of every product).
-    Valid until the next weights_changed() / in-place write to a matrix; on the current stream."""
-    from . import _lib
-    lib = _lib.load_library()
-    ws = _weight_matrices(w)
-    if separate:
-        rows, cols = _weight_image_shape(ws[:1], kind)
-        per = int(lib.relgnn_limb_elements(rows, cols))
-        elements = per * len(ws)
-    else:
-        rows, cols = _weight_image_shape(ws, kind)
-        elements = int(lib.relgnn_limb16_elements(rows, cols) if pair else lib.relgnn_limb_elements(rows, cols))
-    dev = ws[0].device
-
-    def make_items(buf):
-        if not separate:
-            return _weight_image_items(ws, kind, buf)
-        return [(m.data_ptr(), m.stride(0), m.shape[0], m.shape[1], 1 if kind == WEIGHT_NN else 0, buf.data_ptr() + 2 * per * l, 0,
-                 cols // 16) for l, m in enumerate(ws)]
-
-    if torch.cuda.is_current_stream_capturing() or _cfg.weight_limb_cache != "1":
-        # Under stream capture nothing outlives the capture — but WITHIN one captured training step the weights change once, at
-        # its end (the optimizer's update calls weights_changed()): an image split for the forward serves the backward too
-        # (capture_image_cache(): Sparse_Graph_Model.capture_train_step opens it around the capture).
-        ckey = None
-        if _CAPTURE_IMAGES["on"] and _cfg.weight_limb_cache == "1":
-            ckey = (kind, pair, separate, torch.cuda.current_stream(dev).cuda_stream) + tuple(
-                (m.data_ptr(), m.shape[0], m.shape[1], m.stride(0)) for m in ws)
-            hit = _CAPTURE_IMAGES["images"].get(ckey)
-            if hit is not None:
-                return hit
-        im = _WeightImage()
-        im.pair, im.wmax = pair, None
-        im.buf = torch.empty(elements, dtype=torch.bfloat16, device=dev)
-        im.items = make_items(im.buf)
-        _split_weight_images([im])
-        if ckey is not None:
-            im.refs = list(ws)                      # (keeps the addresses of the key alive for the duration of the capture)
-            _CAPTURE_IMAGES["images"][ckey] = im
-        return im
-    import weakref
-    skey = (dev, torch.cuda.current_stream(dev).cuda_stream)
-    table = _WEIGHT_LIMBS.lookup(skey)
-    if table is None:
-        table = _WEIGHT_LIMBS.store(skey, {})
-    key = (kind, pair, separate) + tuple((m.data_ptr(), m.shape[0], m.shape[1], m.stride(0)) for m in ws)
-    gen = _WEIGHT_GEN[0]
-    im = table.get(key)
-    bases = [m._base if m._base is not None else m for m in ws]
-    if im is not None and any(r() is not b for r, b in zip(im.refs, bases)):
-        im = None                                        # another tensor lives at that address now
-    if im is not None and im.gen == gen and im.versions == [m._version for m in ws]:
-        im.used_gen = gen
-        return im
-    if im is None:
-        im = table[key] = _WeightImage()
-        im.refs, im.gen, im.versions, im.used_gen = [weakref.ref(b) for b in bases], -1, None, gen
-        im.pair, im.wmax = pair, None
-        im.buf = torch.empty(elements, dtype=torch.bfloat16, device=dev)
-        im.items = make_items(im.buf)
-    todo = [im]
-    for k, other in list(table.items()):
-        if other is im:
-            continue
-        alive = [r() for r in other.refs]
-        if any(b is None for b in alive) or other.used_gen < gen - 1:       # gone, or not part of the last step: forget it
-            del table[k]
-        elif other.gen != gen or other.versions != [b._version for b in alive]:
-            todo.append(other)
-    _split_weight_images(todo)
-    for t in todo:
-        t.gen, t.versions = gen, [r()._version for r in t.refs]
-    im.used_gen = gen
-    return im
-
-
 def limb_gemm_weight(a: torch.Tensor, w, kind: str, bias: torch.Tensor = None, act: int = 0,
                      out: torch.Tensor = None, xmax: torch.Tensor = None, xgroups: int = 0, dact: int = 0,
                      dy: torch.Tensor = None) -> torch.Tensor:
@@ -812,61 +570,6 @@ def _limb_ws(device, need: int) -> torch.Tensor:
     if ws is None or ws.numel() < need:
         ws = _LIMB_WS.store(key, torch.empty(max(need, 1 << 20), dtype=torch.bfloat16, device=device))
     return ws
-
-
-_SEL_CACHE = True          # (scripts flip this for A/B runs of the cached panel-product images; not a route switch)
-
-
-def sel_weights_cacheable(ws, layout: int) -> bool:
-    """May the 128-column panel product take its weights from the step's limb-image cache (weight_image(separate=True))?  ws: the
-    weight matrices as the caller holds them (parameters or views of parameters: something whose storage outlives the product and
-    whose version moves when it is written) — all the same shape, N % 128 == 0, K % 16 == 0."""
-    ws = _weight_matrices(ws)
-    kind = WEIGHT_NN if layout == GEMM_NN else WEIGHT_NT
-    n, k = (ws[0].shape[1], ws[0].shape[0]) if layout == GEMM_NN else (ws[0].shape[0], ws[0].shape[1])
-    return (_SEL_CACHE and _cfg.weight_limb_cache == "1" and n % 128 == 0 and k % 16 == 0 and all(m.shape == ws[0].shape for m in ws)
-            and weight_image_ok(ws[:1], kind) and all(weight_image_ok([m], kind) for m in ws[1:]))
-
-
-_FAST_IMAGES = {}
-
-
-def sel_image(ws, layout: int):
-    """The cached limb images of the weight matrices `ws` (one image per matrix, one behind the other) for the 128-column panel
-    products, or None when they cannot come from the cache (shapes, switches).  Looked up by the IDENTITY of the weight tensors
-    first — a training step asks for the same parameters' images five or six times per layer, and the general lookup
-    (weight_image: addresses, shapes, strides, bases of every matrix) costs more host time than the split launch it saves when a
-    layer has 23 of them (measured, round 6: C5 31.2 -> 32.7 ms with the general lookup alone, eager)."""
-    if not (_SEL_CACHE and _cfg.weight_limb_cache == "1"):
-        return None
-    from . import _lib
-    ws = _weight_matrices(ws)
-    if not ws[0].is_cuda:
-        return None
-    kind = WEIGHT_NN if layout == GEMM_NN else WEIGHT_NT
-    capturing = torch.cuda.is_current_stream_capturing()
-    key = None
-    if not capturing:
-        key = (kind, _lib.current_stream()) + tuple(map(id, ws))
-        ent = _FAST_IMAGES.get(key)
-        if ent is not None:
-            im, refs = ent
-            if im.gen == _WEIGHT_GEN[0]:
-                for w, r, v in zip(ws, refs, im.versions):
-                    if r() is not w or w._version != v:
-                        break
-                else:
-                    im.used_gen = im.gen
-                    return im
-    if not sel_weights_cacheable(ws, layout):
-        return None
-    im = weight_image(ws, kind, separate=True)
-    if key is not None and all(w._base is None for w in ws):
-        import weakref
-        if len(_FAST_IMAGES) > 512:
-            _FAST_IMAGES.clear()
-        _FAST_IMAGES[key] = (im, [weakref.ref(w) for w in ws])
-    return im
 
 
 def limb_dense_sel(layout: int, a: torch.Tensor, b, bias: torch.Tensor = None, act: int = 0, *,
