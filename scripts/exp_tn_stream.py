@@ -3,7 +3,7 @@ split-K path; checks the result against float64."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
-from tf_gnn_samples_amd import dense as D
+from tf_gnn_samples_amd import config, dense as D
 dev = torch.device("cuda:0")
 g = torch.Generator(device=dev).manual_seed(0)
 r = lambda *s: torch.rand(s, device=dev, generator=g) * 2 - 1
@@ -24,10 +24,8 @@ for V in (36411, 30011, 1000003, 777):
         got = D.tn_stream_gemm(a, b)
         err = (got.double() - want).abs().max().item() / max(1.0, want.abs().max().item())
         ts = t(lambda: D.tn_stream_gemm(a, b))
-        tl = t(lambda: D.matmul_tn_splitk(a, b))
-        own = ""
-        D._OWN_GEMM = True
-        D._OWN_GEMM = False
+        with config.override(gemm="lib", tn="lib"):
+            tl = t(lambda: D.matmul_tn_splitk(a, b))
         fl = 2.0 * V * M * N
-        print("  [V,%3d]^T@[V,%3d]  stream %7.1f us %6.1f TF (rel err %.1e) | library split-K %7.1f us %6.1f TF %s"
-              % (M, N, ts, fl / ts / 1e6, err, tl, fl / tl / 1e6, own))
+        print("  [V,%3d]^T@[V,%3d]  stream %7.1f us %6.1f TF (rel err %.1e) | library split-K %7.1f us %6.1f TF"
+              % (M, N, ts, fl / ts / 1e6, err, tl, fl / tl / 1e6))

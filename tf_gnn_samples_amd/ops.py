@@ -727,7 +727,7 @@ class _TypedLinearPanel(torch.autograd.Function):
 def _typed_limb_ok(k: int, n: int) -> bool:
     """The limb route (relgnn_limb_dense_sel_f32) for a typed product with reduction length k and n output columns."""
     from . import dense
-    return _cfg.limb_gemm and n % 128 == 0 and k % 16 == 0 and 16 <= k <= dense._LIMB_MAX_K
+    return _cfg.limb_gemm and dense.limb_shape_ok(None, n, k, 128)          # (rows: gathered per (node, type), any number)
 
 
 def _typed_panel_ok(H, side, weights) -> bool:
@@ -1113,8 +1113,7 @@ def _pair_products(X, rowptr, stride, V, k, n, kernels, kind) -> bool:
     """The two-fp16-limb form for this gather + product pair (dense.RELGNN_LIMB=pair): the gather can write the per-bucket
     magnitudes and the product takes the limb route."""
     from . import dense as DN
-    if not (_cfg.limb_pair and X.is_cuda and V >= DN._LIMB_MIN_ROWS and n % 256 == 0 and k % 16 == 0
-            and 16 <= k <= DN._LIMB_MAX_K):
+    if not (_cfg.limb_pair and X.is_cuda and DN.limb_shape_ok(V, n, k)):
         return False
     if not _cfg.pair_part(kind):                         # (diagnostics: which products take the form)
         return False
@@ -1170,10 +1169,10 @@ def raise_on_handover(value: int):
 
 def _fused_layer_ok(H, graph, w, kernels) -> bool:
     """relgnn_rgcn_fused_fwd applies: switch on, exact-split limb route, 256 -> 256, no hub plan on the by-target buckets."""
-    from .dense import WEIGHT_NN, _rows_ok, weight_image_ok
+    from .dense import WEIGHT_NN, rows_aligned, weight_image_ok
     if _cfg.rgcn_fused != "1" or not _cfg.limb_gemm or aggregate_acc64():
         return False
-    if not (H.is_cuda and _rows_ok(H) and kernels[0].shape == (256, 256) and H.shape[1] == 256 and weight_image_ok(kernels, WEIGHT_NN)):
+    if not (H.is_cuda and rows_aligned(H) and kernels[0].shape == (256, 256) and H.shape[1] == 256 and weight_image_ok(kernels, WEIGHT_NN)):
         return False
     split = getattr(graph.rowptr_t, "_relgnn_split", None)
     if (split is not None and 1 in split) or graph.V <= 0 or len(kernels) > 64:
@@ -1305,7 +1304,7 @@ class _AggregateThenTransform(torch.autograd.Function):
 
 
 def aggregate_then_transform(H, W, graph, w, aggregation: str, activation: Optional[str], sole_reader: bool = False):
-    """sole_reader: this call is the only reader of H (dense.py, "activation gradients folded into the product that feeds them")."""
+    """sole_reader: this call is the only reader of H (activation_tags.py, "activation gradients folded into the product that feeds them")."""
     mode, act = aggregation_mode_id(aggregation), activation_id(activation)
     if mode == _lib.AGG_MAX or act not in _FUSABLE_ACTS:
         raise ValueError("aggregate_then_transform: max aggregation / %r do not apply" % activation)
