@@ -527,6 +527,34 @@ int relgnn_sigmoid_ce_bwd(const float* logits, const float* labels, int64_t n, c
 int relgnn_sigmoid_ce_bwd_padded(const float* logits, const float* labels, int64_t rows, int32_t cols, const float* g_mean,
                                  float mean_scale, const float* g_total, float* glogits, int32_t ldg, void* stream);
 
+/*
+ * Citation-network output head in one pass (tasks/citation_network_task.py:133-148: tf.nn.sparse_softmax_cross_entropy_with_logits,
+ * the two masked tf.reduce_sum, tf.argmax + tf.equal + tf.cast, and the two divisions by tf.reduce_sum(mask)):
+ *   logits [rows, cols] float32, row stride ld >= cols;  labels int32 [rows];  mask float32 [rows]
+ *   stats[0] = sum_v mask_v * (logsumexp(logits_v) - logits_v[label_v])         (total_loss; summed in double, fixed order)
+ *   stats[1] = sum_v mask_v                                                     (num_masked_preds)
+ *   stats[2] = sum_v mask_v * [argmax(logits_v) == label_v]                     (argmax = the LOWEST index among equal maxima)
+ *   stats[3] = stats[0] / stats[1]  (loss)      stats[4] = stats[2] / stats[1]  (accuracy)     float32 quotients, 0 / 0 = NaN
+ * rows >= 0, cols >= 1 of any length; no atomics: the same inputs give the same bits.  rows == 0 launches only the finalising
+ * kernel.  A label outside [0, cols) is never used as an index (its row's loss is unspecified).  stats has 5 floats.
+ * Columns of -inf count as exp(-inf) = 0 (a row of nothing but -inf: a tie at index 0, loss log(cols)); +inf and NaN logits give
+ * what IEEE arithmetic gives.
+ */
+size_t relgnn_softmax_ce_stats_workspace_bytes(void);
+int relgnn_softmax_ce_stats(const float* logits, int64_t ld, const int32_t* labels, const float* mask, int64_t rows, int32_t cols,
+                            float* stats, void* workspace, size_t workspace_bytes, void* stream);
+/*
+ * The loss gradient of the same head (tf.gradients through tasks/citation_network_task.py:134-145):
+ *   glogits[v, c] = mask_v * (softmax(logits_v)_c - [c == label_v]) * (g_total[0] + g_loss[0] / stats[1])
+ * written into rows of ldg >= cols floats, the columns behind `cols` as zeros (ldg a multiple of 16: the left operand of the head's
+ * input-gradient MatMul on the limb route, as relgnn_sigmoid_ce_bwd_padded); rows with mask 0 are exactly zero.  stats = the
+ * forward's block; g_loss / g_total = device scalars with the incoming gradients of stats[3] / stats[0] (either may be NULL = 0,
+ * not both): nothing is read back to the host.  logits / labels / mask / rows / cols / ld as in the forward.
+ */
+int relgnn_softmax_ce_bwd(const float* logits, int64_t ld, const int32_t* labels, const float* mask, int64_t rows, int32_t cols,
+                          const float* stats, const float* g_loss, const float* g_total, float* glogits, int64_t ldg,
+                          void* stream);
+
 /* ========================================================================== *
  * 8. GRU cell elementwise halves (node-side; gnns/ggnn.py:92 via utils/utils.py:15-16)
  * ========================================================================== */

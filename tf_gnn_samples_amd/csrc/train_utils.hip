@@ -2,6 +2,7 @@
 // launch-bound once the gather/segment kernels and GEMMs are fast:
 //   * multi-tensor per-variable clip_by_norm + TF-style Adam   models/sparse_graph_model.py:227-260
 //   * PPI output head loss + micro-F1 counts in one pass        tasks/ppi_task.py:181-191, utils/utils.py:61-74
+//   * citation head: masked softmax cross-entropy + accuracy     tasks/citation_network_task.py:133-148
 // Deterministic (no float atomics): fixed-shape tree reductions only.
 #include "common.h"
 
@@ -221,6 +222,158 @@ __global__ __launch_bounds__(256) void sigmoid_ce_bwd_padded_kernel(const float*
   }
 }
 
+// ---- citation head: masked sparse softmax cross-entropy + accuracy (tasks/citation_network_task.py:133-148) -----------
+// stats = {sum_v loss_v mask_v, sum_v mask_v, sum_v [argmax_v == label_v] mask_v, stats[0] / stats[1], stats[2] / stats[1]}
+// One row of logits belongs to a GROUP of W lanes (W = 1, 16 or 64, chosen from cols by the host: the datasets have 3-7 classes,
+// a wave then takes 64 rows at once instead of one); lane j of the group walks columns j, j + W, ... with a running
+// (maximum, sum of exp(x - maximum) over the other columns, index of the first maximum), and the W partial triples are merged by a butterfly.
+struct RowLse {
+  float m, t;      // running maximum; sum of exp(x - m) over the columns seen so far WITHOUT the 1 of the maximum itself: a confident
+                   // row has a loss of log(1 + t) with t << 1, which log1pf keeps to 1e-7 relative and logf(1 + t) does not
+  int idx;         // lowest column holding m
+};
+
+__device__ __forceinline__ void lse_push(RowLse& a, float x, int c) {
+  // (columns arrive in ascending order per lane: a tie keeps the earlier index; a lane's first column is always taken, -inf too)
+  if (x > a.m || a.idx == 0x7fffffff) {
+    a.t = a.m == -INFINITY ? 0.f : (a.t + 1.f) * expf(a.m - x);
+    a.m = x;
+    a.idx = c;
+  } else {
+    // an equal maximum adds its own 1 (said without the subtraction: -inf next to -inf is a tie, not exp(NaN) — a row whose first
+    // columns are -inf keeps a finite loss as soon as one column is finite, as the max-subtracted form of TF does)
+    a.t += x == a.m ? 1.f : expf(x - a.m);
+  }
+}
+
+__device__ __forceinline__ void lse_merge(RowLse& a, float m2, float t2, int i2) {
+  if (i2 == 0x7fffffff) return;                    // the other lane had no column (cols < W)
+  if (a.idx == 0x7fffffff) { a.m = m2; a.t = t2; a.idx = i2; return; }
+  float t;
+  if (a.m == m2) t = (a.t + t2) + 1.f;
+  else if (a.m > m2) t = a.t + (t2 + 1.f) * expf(m2 - a.m);
+  else t = t2 + (a.t + 1.f) * expf(a.m - m2);
+  a.idx = a.m > m2 ? a.idx : (m2 > a.m ? i2 : min(a.idx, i2));
+  a.m = fmaxf(a.m, m2);
+  a.t = t;
+}
+
+template <int W>
+__device__ __forceinline__ RowLse row_lse(const float* __restrict__ row, int cols, int j) {
+  RowLse a = {-INFINITY, 0.f, 0x7fffffff};
+  for (int c = j; c < cols; c += W) lse_push(a, row[c], c);
+#pragma unroll
+  for (int off = W >> 1; off >= 1; off >>= 1) {
+    const float m2 = __shfl_xor(a.m, off), t2 = __shfl_xor(a.t, off);
+    const int i2 = __shfl_xor(a.idx, off);
+    lse_merge(a, m2, t2, i2);
+  }
+  return a;        // the same triple in every lane of the group
+}
+
+// grid-strided over groups of rows; every lane of a wave runs the same number of iterations (the butterfly needs all lanes), a
+// lane past the last row walks zero columns.  partial[block * 3 + {0, 1, 2}] = the block's sums in double.
+template <int W>
+__global__ __launch_bounds__(256) void softmax_ce_stats_kernel(const float* __restrict__ logits, long long ld,
+                                                               const int* __restrict__ labels, const float* __restrict__ mask,
+                                                               long long rows, int cols, double* __restrict__ partial) {
+  __shared__ double red[16];
+  constexpr int kRowsPerBlock = 256 / W;
+  const int j = threadIdx.x % W, g = threadIdx.x / W;
+  double loss = 0.0, msum = 0.0, correct = 0.0;
+  for (long long base = (long long)blockIdx.x * kRowsPerBlock; base < rows; base += (long long)gridDim.x * kRowsPerBlock) {
+    const long long r = base + g;
+    const bool valid = r < rows;
+    const float* row = logits + (valid ? r : 0) * ld;
+    const RowLse a = row_lse<W>(row, valid ? cols : 0, j);
+    if (valid && j == 0) {
+      const int label = labels[r];
+      const float mk = mask[r];
+      const float xl = (label >= 0 && label < cols) ? row[label] : a.m;      // (a label outside the row: no access, loss unspecified)
+      // log-sum-exp in fp32 as TF's kernel; the (max - x_label) part and everything summed over rows in double
+      const double l = (double)log1pf(a.t) + (xl == a.m ? 0.0 : (double)a.m - (double)xl);      // (equal: also -inf next to -inf)
+      loss += l * (double)mk;
+      msum += (double)mk;
+      correct += a.idx == label ? (double)mk : 0.0;
+    }
+  }
+  double s;
+  s = block_sum_1024(loss, red);    if (threadIdx.x == 0) partial[blockIdx.x * 3 + 0] = s;
+  s = block_sum_1024(msum, red);    if (threadIdx.x == 0) partial[blockIdx.x * 3 + 1] = s;
+  s = block_sum_1024(correct, red); if (threadIdx.x == 0) partial[blockIdx.x * 3 + 2] = s;
+}
+
+// 256 threads: thread b holds the three partial sums of block b (nblk may be 0: no rows); fixed-shape tree reduction
+__global__ __launch_bounds__(256) void softmax_ce_stats_final_kernel(const double* __restrict__ partial, int nblk,
+                                                                     float* __restrict__ stats) {
+  __shared__ double red[4][3];
+  const int b = threadIdx.x;
+  double v[3];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) v[k] = b < nblk ? partial[b * 3 + k] : 0.0;
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) v[k] += __shfl_xor(v[k], off);
+  }
+  const int wave = b >> 6, lane = b & 63;
+  if (lane == 0) {
+#pragma unroll
+    for (int k = 0; k < 3; ++k) red[wave][k] = v[k];
+  }
+  __syncthreads();
+  if (b == 0) {
+    float t[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) t[k] = stats[k] = (float)((red[0][k] + red[1][k]) + (red[2][k] + red[3][k]));
+    // float32 quotients of the float32 sums, as the reference's graph forms them (:141, :145); 0 / 0 stays NaN
+    stats[3] = t[0] / t[1];
+    stats[4] = t[2] / t[1];
+  }
+}
+
+// glogits[v, c] = mask_v * (softmax(logits_v)_c - [c == label_v]) * (g_total[0] + g_loss[0] / stats[1]) for c < cols, 0 for
+// cols <= c < ldg; a row with mask 0 is written as zeros whatever its logits hold.  Either gradient pointer may be null.
+template <int W>
+__global__ __launch_bounds__(256) void softmax_ce_bwd_kernel(const float* __restrict__ logits, long long ld,
+                                                             const int* __restrict__ labels, const float* __restrict__ mask,
+                                                             long long rows, int cols, const float* __restrict__ stats,
+                                                             const float* __restrict__ g_loss, const float* __restrict__ g_total,
+                                                             float* __restrict__ gl, long long ldg) {
+  constexpr int kRowsPerBlock = 256 / W;
+  const int j = threadIdx.x % W, g = threadIdx.x / W;
+  float gs = 0.f;
+  if (g_loss) gs = g_loss[0] / stats[1];
+  if (g_total) gs = g_loss ? gs + g_total[0] : g_total[0];
+  for (long long base = (long long)blockIdx.x * kRowsPerBlock; base < rows; base += (long long)gridDim.x * kRowsPerBlock) {
+    const long long r = base + g;
+    const bool valid = r < rows;
+    const float* row = logits + (valid ? r : 0) * ld;
+    const RowLse a = row_lse<W>(row, valid ? cols : 0, j);
+    if (!valid) continue;
+    const float mk = mask[r];
+    const int label = labels[r];
+    const float scale = mk * gs, inv = 1.f / (1.f + a.t);
+    float* out = gl + r * ldg;
+    for (int c = j; c < (int)ldg; c += W) {
+      float v = 0.f;
+      if (c < cols && mk != 0.f) v = scale * (expf(row[c] - a.m) * inv - (c == label ? 1.f : 0.f));
+      out[c] = v;
+    }
+  }
+}
+
+constexpr int kSoftmaxBlocks = 256;
+
+// lanes per row: a lane walks a short row alone, 16 lanes share a row of up to 128 columns, a wave anything longer
+static inline int softmax_group_width(int cols) { return cols <= 8 ? 1 : (cols <= 128 ? 16 : 64); }
+
+static inline int softmax_grid(long long rows, int w) {
+  const long long per_block = 256 / w;
+  long long g = (rows + per_block - 1) / per_block;
+  return (int)(g < 1 ? 1 : (g > kSoftmaxBlocks ? kSoftmaxBlocks : g));
+}
+
 constexpr int kStatsBlocks = 256;
 
 }  // namespace
@@ -322,6 +475,43 @@ int relgnn_sigmoid_ce_bwd_padded(const float* logits, const float* labels, int64
   if (!logits || !labels || (!g_mean && !g_total) || !glogits) return RELGNN_EINVAL;
   sigmoid_ce_bwd_padded_kernel<<<flat_grid(rows * ldg, 256), 256, 0, as_stream(stream)>>>(logits, labels, rows, cols, ldg, g_mean,
                                                                                           mean_scale, g_total, glogits);
+  return launch_status();
+}
+
+size_t relgnn_softmax_ce_stats_workspace_bytes(void) { return (size_t)kSoftmaxBlocks * 3 * sizeof(double); }
+
+int relgnn_softmax_ce_stats(const float* logits, int64_t ld, const int32_t* labels, const float* mask, int64_t rows, int32_t cols,
+                            float* stats, void* workspace, size_t workspace_bytes, void* stream) {
+  if (rows < 0 || cols < 1 || ld < cols || !stats) return RELGNN_EINVAL;
+  if (!workspace || workspace_bytes < relgnn_softmax_ce_stats_workspace_bytes()) return RELGNN_ENOSPC;
+  if (rows > 0 && (!logits || !labels || !mask)) return RELGNN_EINVAL;
+  hipStream_t st = as_stream(stream);
+  double* partial = static_cast<double*>(workspace);
+  int nblk = 0;
+  if (rows > 0) {
+    const int w = softmax_group_width(cols);
+    nblk = softmax_grid(rows, w);
+    if (w == 1) softmax_ce_stats_kernel<1><<<nblk, 256, 0, st>>>(logits, ld, labels, mask, rows, cols, partial);
+    else if (w == 16) softmax_ce_stats_kernel<16><<<nblk, 256, 0, st>>>(logits, ld, labels, mask, rows, cols, partial);
+    else softmax_ce_stats_kernel<64><<<nblk, 256, 0, st>>>(logits, ld, labels, mask, rows, cols, partial);
+  }
+  softmax_ce_stats_final_kernel<<<1, 256, 0, st>>>(partial, nblk, stats);
+  return launch_status();
+}
+
+int relgnn_softmax_ce_bwd(const float* logits, int64_t ld, const int32_t* labels, const float* mask, int64_t rows, int32_t cols,
+                          const float* stats, const float* g_loss, const float* g_total, float* glogits, int64_t ldg,
+                          void* stream) {
+  if (rows < 0 || cols < 1 || ld < cols || ldg < cols || ldg > INT32_MAX) return RELGNN_EINVAL;
+  if (rows == 0) return RELGNN_OK;
+  if (!logits || !labels || !mask || !stats || (!g_loss && !g_total) || !glogits) return RELGNN_EINVAL;
+  hipStream_t st = as_stream(stream);
+  const int w = softmax_group_width(cols);
+  const int64_t per_block = 256 / w;
+  const unsigned nblk = flat_grid((rows + per_block - 1) / per_block * 256, 256);       // one block per 256 / w rows, capped
+  if (w == 1) softmax_ce_bwd_kernel<1><<<nblk, 256, 0, st>>>(logits, ld, labels, mask, rows, cols, stats, g_loss, g_total, glogits, ldg);
+  else if (w == 16) softmax_ce_bwd_kernel<16><<<nblk, 256, 0, st>>>(logits, ld, labels, mask, rows, cols, stats, g_loss, g_total, glogits, ldg);
+  else softmax_ce_bwd_kernel<64><<<nblk, 256, 0, st>>>(logits, ld, labels, mask, rows, cols, stats, g_loss, g_total, glogits, ldg);
   return launch_status();
 }
 

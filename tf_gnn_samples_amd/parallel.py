@@ -32,6 +32,14 @@ def shard_graphs_by_edges(edge_counts: Sequence[int], world_size: int) -> List[L
     return [sorted(s) for s in shards]
 
 
+def refuse_single_graph_task(task_name: str) -> None:
+    """Data parallelism here is BY GRAPH; a task whose fold is one graph that is always the whole batch (the citation networks)
+    has nothing to split.  Its batch iterators call this: under a process group of more than one rank it raises."""
+    if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+        raise RuntimeError("the %s task trains on ONE graph that is the whole batch: it cannot be split by graph across %d ranks; "
+                           "run it on a single GPU" % (task_name, dist.get_world_size()))
+
+
 def effective_cpu_count() -> int:
     """CPUs this process may actually keep busy: the cgroup CPU quota (v2 cpu.max, v1 cfs quota) and the affinity
     mask, whichever is smaller.  os.cpu_count() reports the host's hardware threads (256 on the MI355X boxes) even when

@@ -1,13 +1,20 @@
 from .sparse_graph_task import DataFold, DeviceBatch, MinibatchData, Sparse_Graph_Task
 from .ppi_task import PPI_Task
 from .qm9_task import QM9_Task
+from .citation_network_task import Citation_Network_Task
 
-TASK_CLASSES = {"ppi": PPI_Task, "qm9": QM9_Task}   # utils/model_utils.py:12-29 (VarMisuse / citation tasks: out of scope)
+# utils/model_utils.py:12-29: name -> (class, extra task parameters)  (the VarMisuse task: out of scope)
+TASK_CLASSES = {"ppi": (PPI_Task, {}), "qm9": (QM9_Task, {}),
+                "cora": (Citation_Network_Task, {"data_kind": "cora"}),
+                "citeseer": (Citation_Network_Task, {"data_kind": "citeseer"}),
+                "pubmed": (Citation_Network_Task, {"data_kind": "pubmed"}),
+                "citationnetwork": (Citation_Network_Task, {})}
 
 
 def name_to_task_class(name: str):
-    """-> (class, extra task parameters), utils/model_utils.py:12-29 (the citation / VarMisuse names are unknown here)."""
+    """-> (class, extra task parameters), utils/model_utils.py:12-29 (the VarMisuse name is unknown here)."""
     key = name.lower()
     if key not in TASK_CLASSES:
         raise ValueError("Unknown task type '%s'" % key)
-    return TASK_CLASSES[key], {}
+    task_class, extra = TASK_CLASSES[key]
+    return task_class, dict(extra)

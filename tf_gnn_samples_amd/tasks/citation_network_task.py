@@ -1,0 +1,347 @@
+"""Citation-network task mirror (tasks/citation_network_task.py, utils/citation_network_utils.py): full-graph masked node
+classification on Cora / CiteSeer / PubMed in the Planetoid file layout.
+
+ONE graph is always the whole batch: the three folds share the graph and the row-normalised features and differ in the per-node
+class labels and the 0/1 node mask.  The output head is a bias-free Dense followed by a masked sparse softmax cross-entropy and an
+accuracy count; on the GPU that is one kernel pair (csrc/train_utils.hip: relgnn_softmax_ce_stats / relgnn_softmax_ce_bwd).
+Without the datasets `load_synthetic` fills the folds with a Cora-shaped graph.
+"""
+import os
+import pickle
+import weakref
+from typing import Any, Dict, Iterator, List, NamedTuple, Optional
+
+import numpy as np
+import torch
+
+from .. import config as _cfg
+from ..dense import dense
+from .sparse_graph_task import DataFold, MinibatchData, Sparse_Graph_Task
+
+
+class CitationData(NamedTuple):
+    """One fold = the whole graph (the reference's CitationData, :12, under the attribute names tasks/batcher.py flattens)."""
+    adjacency_lists: List[np.ndarray]                      # [self loops, both directions of every (node, neighbour)], int32 [E_l, 2]
+    type_to_node_to_num_incoming_edges: np.ndarray         # int32 [2, V]
+    node_features: np.ndarray                              # float32 [V, F], row-normalised
+    labels: np.ndarray                                     # int32 [V]
+    mask: np.ndarray                                       # float32 [V], 1 = the node counts in this fold
+
+
+class _SoftmaxCEStats(torch.autograd.Function):
+    """(loss, total_loss, accuracy, [total_loss, sum of mask, masked correct count]) of the whole graph in one pass over the logits
+    (csrc/train_utils.hip).  log_softmax, gather, mul, sum, argmax, eq, sum, div and their autograd mirrors would be a dozen ~5 us
+    launches around a step that is launch-bound by construction (a few thousand nodes); see _SigmoidCEStats in ppi_task.py."""
+
+    @staticmethod
+    def forward(ctx, logits, labels, mask):
+        from .. import _lib
+        lib = _lib.load_library()
+        if logits.dim() != 2 or logits.stride(1) != 1:
+            logits = logits.contiguous()
+        labels, mask = labels.contiguous(), mask.contiguous()
+        rows, cols = logits.shape
+        stats = torch.empty(5, dtype=torch.float32, device=logits.device)
+        nbytes = lib.relgnn_softmax_ce_stats_workspace_bytes()
+        ws = torch.empty(nbytes // 8, dtype=torch.float64, device=logits.device)
+        _lib.check(lib.relgnn_softmax_ce_stats(_lib.ptr(logits, rows_strided=True), logits.stride(0) if rows > 1 else cols,
+                                               _lib.ptr(labels), _lib.ptr(mask), rows, cols, _lib.ptr(stats), _lib.ptr(ws), nbytes,
+                                               _lib.current_stream()), "relgnn_softmax_ce_stats")
+        ctx.save_for_backward(logits, labels, mask, stats)
+        ctx.set_materialize_grads(False)          # an unused output's gradient arrives as None, not as a zero tensor
+        loss, total, accuracy = stats[3], stats[0], stats[4]
+        counts = stats[0:3]                       # total_loss, sum of mask, masked correct count
+        ctx.mark_non_differentiable(accuracy, counts)
+        return loss, total, accuracy, counts
+
+    @staticmethod
+    def backward(ctx, g_loss, g_total, g_accuracy, g_counts):
+        from .. import _lib
+        lib = _lib.load_library()
+        logits, labels, mask, stats = ctx.saved_tensors
+        if g_loss is None and g_total is None:
+            return None, None, None
+
+        def scalar(g):                            # the incoming gradients stay on the device: the kernel reads them (and sum of mask)
+            return None if g is None else g.reshape(1).to(torch.float32).contiguous()
+        g_loss, g_total = scalar(g_loss), scalar(g_total)
+        rows, cols = logits.shape
+        ld = logits.stride(0) if rows > 1 else cols
+        if cols % 16 and _cfg.settings.limb_gemm and _cfg.settings.head_pad == "1":
+            # rows of the next multiple of 16 floats, zeros behind the classes: the head's input-gradient product then runs on the limb
+            # route with the activation gradient of the last GNN layer's Dense in its epilogue (dense.mark_zero_padded), as PPI's
+            from ..dense import mark_zero_padded
+            ldg = (cols + 15) // 16 * 16
+            buf = torch.empty((rows, ldg), dtype=torch.float32, device=logits.device)
+            _lib.check(lib.relgnn_softmax_ce_bwd(_lib.ptr(logits, rows_strided=True), ld, _lib.ptr(labels), _lib.ptr(mask), rows, cols,
+                                                 _lib.ptr(stats), _lib.ptr(g_loss), _lib.ptr(g_total), _lib.ptr(buf), ldg,
+                                                 _lib.current_stream()), "relgnn_softmax_ce_bwd")
+            return mark_zero_padded(buf[:, :cols], ldg), None, None
+        gl = torch.empty((rows, cols), dtype=torch.float32, device=logits.device)
+        _lib.check(lib.relgnn_softmax_ce_bwd(_lib.ptr(logits, rows_strided=True), ld, _lib.ptr(labels), _lib.ptr(mask), rows, cols,
+                                             _lib.ptr(stats), _lib.ptr(g_loss), _lib.ptr(g_total), _lib.ptr(gl), cols,
+                                             _lib.current_stream()), "relgnn_softmax_ce_bwd")
+        return gl, None, None
+
+
+def softmax_ce_stats(logits: torch.Tensor, labels: torch.Tensor, mask: torch.Tensor):
+    """-> (loss, total_loss, accuracy, counts) of float32 device logits [V, C], int32 labels [V], float32 mask [V]."""
+    return _SoftmaxCEStats.apply(logits, labels, mask)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# Planetoid files (utils/citation_network_utils.py:25-90, :114-121)
+# ---------------------------------------------------------------------------------------------------------------------------------
+def load_planetoid(directory: str, data_kind: str):
+    """ind.<kind>.{x,y,tx,ty,allx,ally,graph} + ind.<kind>.test.index -> (graph dict, feature matrix (scipy LIL), the three
+    one-hot label tables restricted to their fold, the three boolean node masks), utils/citation_network_utils.py:25-90.
+
+    The test rows are stored in the order of the sorted test ids and put where test.index says; the train fold is the first len(y)
+    nodes, the validation fold the next 500.  CiteSeer's test ids have holes (isolated nodes the files leave out): those become
+    all-zero feature rows and all-zero label rows."""
+    import scipy.sparse as sp           # (the pickles hold scipy matrices; nothing else in the package needs scipy)
+    loaded = {}
+    for part in ("x", "y", "tx", "ty", "allx", "ally", "graph"):
+        with open(os.path.join(directory, "ind.%s.%s" % (data_kind, part)), "rb") as f:
+            loaded[part] = pickle.load(f, encoding="latin1")
+    with open(os.path.join(directory, "ind.%s.test.index" % data_kind)) as f:
+        test_ids = [int(line.strip()) for line in f]
+    test_sorted = np.sort(test_ids)
+    tx, ty = loaded["tx"], loaded["ty"]
+    if data_kind == "citeseer":
+        first, span = min(test_ids), max(test_ids) - min(test_ids) + 1
+        tx_full = sp.lil_matrix((span, loaded["x"].shape[1]))
+        tx_full[test_sorted - first, :] = tx
+        ty_full = np.zeros((span, loaded["y"].shape[1]))
+        ty_full[test_sorted - first, :] = ty
+        tx, ty = tx_full, ty_full
+    features = sp.vstack((loaded["allx"], tx)).tolil()
+    features[test_ids, :] = features[test_sorted, :]
+    labels = np.vstack((loaded["ally"], ty))
+    labels[test_ids, :] = labels[test_sorted, :]
+    num_nodes, num_train = labels.shape[0], len(loaded["y"])
+    folds = (np.arange(num_train), np.arange(num_train, num_train + 500), test_sorted)
+    masks, tables = [], []
+    for ids in folds:
+        m = np.zeros(num_nodes, dtype=bool)
+        m[ids] = True
+        t = np.zeros(labels.shape)
+        t[m, :] = labels[m, :]
+        masks.append(m)
+        tables.append(t)
+    return loaded["graph"], features, tables, masks
+
+
+def row_normalise(features) -> np.ndarray:
+    """utils/citation_network_utils.py:114-121: every row divided by its sum, in the matrix's own dtype; the reciprocal of a zero
+    row sum counts as 0 (the row stays zero).  Returns the dense array."""
+    import scipy.sparse as sp
+    row_sum = np.array(features.sum(1))
+    with np.errstate(divide="ignore"):
+        reciprocal = np.power(row_sum, -1).flatten()
+    reciprocal[np.isinf(reciprocal)] = 0.
+    return sp.diags(reciprocal).dot(features).toarray()
+
+
+def graph_to_edge_lists(graph: Dict[int, List[int]]):
+    """:90-109.  Type 0: one self loop per node, in the dict's iteration order.  Type 1: for every (node, neighbour) of the dict in
+    iteration order the rows (node, neighbour) and (neighbour, node); duplicates stay (the segment sums follow this order).
+    -> ([self loops, edges] as int32 [E, 2], in-degree table int32 [2, V] = [ones, counts])."""
+    num_nodes = len(graph)
+    nodes = np.fromiter(graph.keys(), dtype=np.int64, count=num_nodes)
+    lengths = np.fromiter((len(v) for v in graph.values()), dtype=np.int64, count=num_nodes)
+    src = np.repeat(nodes, lengths)
+    dst = np.fromiter((n for v in graph.values() for n in v), dtype=np.int64, count=int(lengths.sum()))
+    edges = np.empty((2 * len(src), 2), dtype=np.int32)
+    edges[0::2, 0], edges[0::2, 1] = src, dst
+    edges[1::2, 0], edges[1::2, 1] = dst, src
+    self_loops = np.stack([nodes, nodes], axis=1).astype(np.int32)
+    counts = np.bincount(edges[:, 1], minlength=num_nodes).astype(np.int32)       # every pair adds one to either end
+    return [self_loops, edges], np.stack([np.ones_like(counts), counts])
+
+
+class Citation_Network_Task(Sparse_Graph_Task):
+    @classmethod
+    def default_params(cls):
+        # :16-25
+        params = super().default_params()
+        params.update({
+            'add_self_loop_edges': True,
+            'use_graph': True,
+            'activation_function': "tanh",
+            'out_layer_dropout_keep_prob': 1.0,
+        })
+        return params
+
+    @staticmethod
+    def name() -> str:
+        return "CitationNetwork"
+
+    @staticmethod
+    def default_data_path() -> str:
+        return "data/citation-networks"
+
+    def __init__(self, params: Dict[str, Any]):
+        super().__init__(params)
+        self._resident_batches = weakref.WeakKeyDictionary()      # resident fold -> its one assembled batch (released with the fold)
+        self.__num_edge_types = 2
+        self.__initial_node_feature_size = 0
+        self.__num_output_classes = 0
+
+    def get_metadata(self) -> Dict[str, Any]:
+        metadata = {'params': self.params}          # (the reference's base class stores the task parameters here, sparse_graph_task.py:46-59)
+        metadata['initial_node_feature_size'] = self.__initial_node_feature_size
+        metadata['num_output_classes'] = self.__num_output_classes
+        return metadata
+
+    def restore_from_metadata(self, metadata: Dict[str, Any]) -> None:
+        self.params = metadata.get('params', self.params)
+        self.__initial_node_feature_size = metadata['initial_node_feature_size']
+        self.__num_output_classes = metadata['num_output_classes']
+
+    @property
+    def num_edge_types(self) -> int:
+        return self.__num_edge_types
+
+    @property
+    def initial_node_feature_size(self) -> int:
+        return self.__initial_node_feature_size
+
+    @property
+    def num_output_classes(self) -> int:
+        return self.__num_output_classes
+
+    # -------------------- Data (:63-109) --------------------
+    def load_data(self, path: str) -> None:
+        train, valid, _ = self._load_folds(path)
+        self._loaded_data[DataFold.TRAIN] = train
+        self._loaded_data[DataFold.VALIDATION] = valid
+
+    def load_eval_data_from_path(self, path: str):
+        return self._load_folds(path)[2]
+
+    def _load_folds(self, path):
+        data_path = getattr(path, "path", path)                       # (a RichPath-like object or a plain string)
+        print(" Loading CitationNetwork data from %s." % (data_path,))
+        graph, features, label_tables, masks = load_planetoid(data_path, self.params['data_kind'])
+        self.__initial_node_feature_size = features.shape[1]
+        self.__num_output_classes = label_tables[0].shape[1]
+        # the reference feeds its array into a float32 placeholder: the cast happens once, here
+        features = np.ascontiguousarray(row_normalise(features), dtype=np.float32)
+        adjacency, degrees = graph_to_edge_lists(graph)
+        return tuple([self._fold(adjacency, degrees, features, np.argmax(table, axis=1), mask)]
+                     for table, mask in zip(label_tables, masks))
+
+    @staticmethod
+    def _fold(adjacency, degrees, features, labels, mask) -> CitationData:
+        # (the reference feeds a bool mask into a float32 placeholder, :117)
+        return CitationData(adjacency_lists=adjacency, type_to_node_to_num_incoming_edges=degrees, node_features=features,
+                            labels=np.ascontiguousarray(labels, dtype=np.int32), mask=np.ascontiguousarray(mask, dtype=np.float32))
+
+    def load_synthetic(self, num_nodes: int = 2708, num_features: int = 1433, num_classes: int = 7, num_train: int = 140,
+                       num_valid: int = 500, num_test: int = 1000, neighbours_per_node: float = 2.0, feature_density: float = 0.0127,
+                       seed: int = 0) -> None:
+        """Cora-shaped stand-in for load_data (no dataset on the machines): 2708 nodes, 1433 binary bag-of-words features at Cora's
+        density, row-normalised, 7 classes, ~5.4 k neighbour-list entries = 10.8 k directed edges + self loops; folds of
+        140 / 500 / 1000 nodes laid out as Planetoid's (first, next, last).  The test fold is kept as `synthetic_test_data`."""
+        rng = np.random.default_rng(seed)
+        graph = {}
+        lengths = rng.poisson(neighbours_per_node, size=num_nodes)
+        for node in range(num_nodes):
+            graph[node] = rng.integers(0, num_nodes, size=int(lengths[node])).tolist()
+        bag = (rng.random((num_nodes, num_features)) < feature_density).astype(np.float32)
+        row_sum = bag.sum(1, keepdims=True)
+        features = np.divide(bag, row_sum, out=np.zeros_like(bag), where=row_sum > 0)
+        labels = rng.integers(0, num_classes, size=num_nodes)
+        adjacency, degrees = graph_to_edge_lists(graph)
+        self.__initial_node_feature_size, self.__num_output_classes = num_features, num_classes
+        folds = []
+        for ids in (np.arange(num_train), np.arange(num_train, num_train + num_valid), np.arange(num_nodes - num_test, num_nodes)):
+            mask = np.zeros(num_nodes, dtype=bool)
+            mask[ids] = True
+            folds.append([self._fold(adjacency, degrees, features, np.where(mask, labels, 0), mask)])
+        self._loaded_data[DataFold.TRAIN], self._loaded_data[DataFold.VALIDATION], self.synthetic_test_data = folds
+
+    # -------------------- Output head (:112-148) --------------------
+    def output_variable_scope(self, model_has_input_projection: bool) -> str:
+        # :127-131: a NAMED Keras Dense made outside the model's variable scope: its variable sits at the graph's root whatever the
+        # model built before it
+        return "OutputDenseLayer"
+
+    def output_variables(self, hidden_size: int):
+        return {"kernel": ((hidden_size, self.__num_output_classes), "glorot_uniform")}
+
+    def compute_task_metrics(self, final_node_representations: torch.Tensor, batch, weights) -> Dict[str, torch.Tensor]:
+        labels, mask = batch.extra['labels'], batch.extra['mask']
+        keep = float(batch.extra.get('out_layer_dropout_keep_prob', 1.0))
+        if keep < 1.0:                                                                    # :123-125
+            final_node_representations = torch.nn.functional.dropout(final_node_representations, p=1.0 - keep, training=True)
+        logits = dense(final_node_representations, weights["kernel"])                     # :126-131, [V, classes]
+        if logits.is_cuda:
+            if labels.dtype != torch.int32:           # (the numpy iterator's DeviceBatch widens integer arrays; the native one keeps int32)
+                labels = labels.to(torch.int32)
+            loss, total_loss, accuracy, _ = softmax_ce_stats(logits, labels, mask)
+            return {'loss': loss, 'total_loss': total_loss, 'accuracy': accuracy}
+        # :133-148 in torch
+        num_masked = mask.sum()
+        losses = torch.nn.functional.cross_entropy(logits, labels.long(), reduction='none')
+        total_loss = (losses * mask).sum()
+        top = logits.detach().max(dim=1, keepdim=True).values
+        columns = torch.arange(logits.shape[1], device=logits.device).expand_as(logits)
+        first_max = torch.where(logits.detach() == top, columns, logits.shape[1]).min(dim=1).values   # the first of equal maxima, as tf.argmax
+        accuracy = ((first_max == labels.long()).to(torch.float32) * mask).sum() / num_masked
+        return {'loss': total_loss / num_masked, 'total_loss': total_loss, 'accuracy': accuracy}
+
+    NODE_PAYLOADS = {"initial_node_features": ("node_features", np.float32), "labels": ("labels", np.int32),
+                     "mask": ("mask", np.float32)}
+
+    # -------------------- Minibatching (:151-177) --------------------
+    def _out_keep(self, data_fold: DataFold) -> float:
+        return self.params['out_layer_dropout_keep_prob'] if data_fold == DataFold.TRAIN else 1.0
+
+    def make_minibatch_iterator(self, data, data_fold: DataFold, max_nodes_per_batch: int,
+                                rng: Optional[np.random.RandomState] = None) -> Iterator[MinibatchData]:
+        """Exactly one minibatch per epoch, the whole graph; max_nodes_per_batch is not consulted (:157-177)."""
+        from ..parallel import refuse_single_graph_task
+        refuse_single_graph_task(self.name())
+        fold = next(iter(data))
+        feed = {
+            'initial_node_features': fold.node_features,
+            'adjacency_lists': list(fold.adjacency_lists),
+            'type_to_num_incoming_edges': fold.type_to_node_to_num_incoming_edges,
+            'num_graphs': 1,
+            'labels': fold.labels,
+            'mask': fold.mask,
+            'out_layer_dropout_keep_prob': self._out_keep(data_fold),
+        }
+        yield MinibatchData(feed_dict=feed, num_graphs=1, num_nodes=fold.node_features.shape[0],
+                            num_edges=sum(len(a) for a in fold.adjacency_lists))
+
+    def make_native_minibatch_iterator(self, batcher, data_fold: DataFold, max_nodes_per_batch: int,
+                                       rng: Optional[np.random.RandomState] = None):
+        """The same single batch from the flattened fold.  The packer's rule (graphs are taken while the node count stays BELOW
+        max_nodes_per_batch) is not asked: the graph is the batch whatever its size.  A resident fold (tasks/resident.py) was
+        bucketed once when it was made; its one assembled batch is kept and handed out again every epoch."""
+        from ..parallel import refuse_single_graph_task
+        refuse_single_graph_task(self.name())
+        if batcher.store.num_graphs != 1:
+            raise ValueError("a citation-network fold is ONE graph; got %d" % batcher.store.num_graphs)
+        keep = self._out_keep(data_fold)
+        batcher.constants['out_layer_dropout_keep_prob'] = keep
+        ids = np.zeros(1, dtype=np.int64)
+        from .resident import ResidentDataset
+        if isinstance(batcher, ResidentDataset):
+            batch = self._resident_batches.get(batcher)
+            if batch is None:
+                batch = self._resident_batches[batcher] = batcher.assemble(ids)
+            batch.extra['out_layer_dropout_keep_prob'] = keep
+        else:
+            batch = batcher.pack(ids)
+        yield batch
+
+    def early_stopping_metric(self, task_metric_results: List[Dict[str, Any]], num_graphs: int) -> float:
+        # :179-181: average loss
+        return float(np.sum([float(m['total_loss']) for m in task_metric_results]) / num_graphs)
+
+    def pretty_print_epoch_task_metrics(self, task_metric_results: List[Dict[str, Any]], num_graphs: int) -> str:
+        return "Acc: %.2f%%" % (float(task_metric_results[0]['accuracy']) * 100,)
