@@ -555,6 +555,67 @@ int relgnn_softmax_ce_bwd(const float* logits, int64_t ld, const int32_t* labels
                           const float* stats, const float* g_loss, const float* g_total, float* glogits, int64_t ldg,
                           void* stream);
 
+/*
+ * VarMisuse input model (tasks/varmisuse_task.py:317-367): the 2-layer character CNN over node labels,
+ *   one_hot(chars, 68) -> Conv1D(16, kernel 5, leaky_relu 0.2) -> MaxPool1D(5, stride 1) -> Conv1D(out_dim, kernel C - 8, leaky_relu)
+ *   -> squeeze -> gather by label_of_node;  padding "valid", cross-correlations, Keras kernels [k, in, out]:
+ *   W1 [5, 68, 16], b1 [16], W2 [C - 8, 16, out_dim], b2 [out_dim];  chars uint8 [num_labels, C]  (0 = PAD, a live column; 1 = UNK;
+ *   codes >= 68 are outside the one-hot depth and contribute nothing, :341-343).
+ * The one-hot product is a table lookup (conv1[u, t, f] = b1[f] + sum_j W1[j, c[u, t + j], f]); [U, C, 68] is never materialised.
+ *   fwd : out [num_nodes, out_dim] dense.  label_of_node int32 [num_nodes] or NULL (= identity, num_nodes == num_labels); with a
+ *         map the label representations go to `workspace` (relgnn_charcnn_fwd_workspace_bytes) and are gathered; a map entry
+ *         outside [0, num_labels) writes a zero row and ORs RELGNN_ERRFLAG_INDEX_OUT_OF_RANGE into *err_flag (nullable).
+ *         A label's arithmetic depends on neither its row number nor num_labels: equal labels give equal bits.
+ *   bwd : g_labels [num_labels, out_dim] = the gradient of the LABEL representations (with a map: the deterministic segment sum of
+ *         the node gradient by label, relgnn_seg_reduce_fwd, which is the gather's gradient).  The forward is recomputed from the
+ *         characters.  dW1 / db1: every workgroup owns a fixed label range (relgnn_charcnn_range_labels(1) labels or more, at most
+ *         512 ranges) and a partial table of its own, in which one thread is the only writer of an entry; the partials are added in
+ *         range order in double.  dW2 = pooled^T @ G2 by relgnn_gemm_tn_stream_f32 over the materialised pooled table, db2 by
+ *         relgnn_column_sum.  Max-pool ties go to the first maximum.  No atomics: the same inputs give the same bits.
+ * Supported (relgnn_charcnn_supported): C in 9 .. 32, out_dim a multiple of 16 up to 128; anything else RELGNN_EUNSUPPORTED.
+ * relgnn_charcnn_range_labels(backward): labels per workgroup step of the forward (0) / smallest label range of the backward (1).
+ */
+int relgnn_charcnn_supported(int32_t num_chars, int32_t out_dim);
+int64_t relgnn_charcnn_range_labels(int32_t backward);
+size_t relgnn_charcnn_fwd_workspace_bytes(int64_t num_labels, int32_t out_dim, int32_t has_map);
+int relgnn_charcnn_fwd(const uint8_t* chars, int64_t num_labels, int32_t num_chars, const int32_t* label_of_node, int64_t num_nodes,
+                       const float* W1, const float* b1, const float* W2, const float* b2, int32_t out_dim, float* out,
+                       void* workspace, size_t workspace_bytes, uint32_t* err_flag, void* stream);
+size_t relgnn_charcnn_bwd_workspace_bytes(int64_t num_labels, int32_t num_chars, int32_t out_dim);
+int relgnn_charcnn_bwd(const uint8_t* chars, int64_t num_labels, int32_t num_chars, const float* W1, const float* b1, const float* W2,
+                       const float* b2, int32_t out_dim, const float* g_labels, float* dW1, float* db1, float* dW2, float* db2,
+                       void* workspace, size_t workspace_bytes, void* stream);
+
+/*
+ * VarMisuse output head (tasks/varmisuse_task.py:389-448), one wave per graph: tf.gather of the slot row and the num_candidates
+ * candidate rows of states [num_nodes, hidden] (row stride ld), the einsum 'sd,scd->sc', the optional bias-free Dense
+ * `slot_score_linear_layer` over [candidate | slot | inner product] (w [2 * hidden + 1], NULL = the inner product is the logit),
+ * logits += (1 - mask) * -1e7 in float32, sparse softmax cross-entropy against class 0, argmax of the softmax (first of equal
+ * maxima) compared with 0.
+ *   slot_ids int32 [G], cand_ids int32 [G, num_candidates], cand_mask float32 [G, num_candidates];
+ *   first_node int32 [G] or NULL: ids are graph-local and first_node[g] is added, or absolute.  An id outside [0, num_nodes) ORs
+ *   RELGNN_ERRFLAG_INDEX_OUT_OF_RANGE into *err_flag (nullable); that graph gets zero logits and counts for nothing.
+ *   fwd : logits [G, num_candidates];  stats = [total_loss, num_correct, total_loss / G, num_correct / G], the per-graph terms
+ *         added in a fixed order in double.
+ *   bwd : g_loss / g_total = device scalars with the incoming gradients of stats[2] / stats[0] (either may be NULL, not both).
+ *         d_states [num_nodes, hidden] (row stride ldg) is zero-filled, then every graph's wave writes that graph's slot and
+ *         candidate rows; rows that coincide inside a graph (padded candidates point at the graph's node 0) are added in candidate
+ *         order, then the slot.  Rows of different graphs must not coincide.  dw [2 * hidden + 1] (NULL iff w is NULL): per-workgroup
+ *         partials in double, added in workgroup order.
+ * Supported (relgnn_varmisuse_head_supported): num_candidates 1 .. 8, hidden a multiple of 64 up to 256.
+ * workspace: relgnn_varmisuse_head_workspace_bytes(G, hidden), for either direction.
+ */
+int relgnn_varmisuse_head_supported(int32_t num_candidates, int32_t hidden);
+size_t relgnn_varmisuse_head_workspace_bytes(int64_t num_graphs, int32_t hidden);
+int relgnn_varmisuse_head_fwd(const float* states, int64_t ld, int64_t num_nodes, int32_t hidden, const int32_t* slot_ids,
+                              const int32_t* cand_ids, const float* cand_mask, const int32_t* first_node, int64_t num_graphs,
+                              int32_t num_candidates, const float* w, float* logits, float* stats, void* workspace,
+                              size_t workspace_bytes, uint32_t* err_flag, void* stream);
+int relgnn_varmisuse_head_bwd(const float* states, int64_t ld, int64_t num_nodes, int32_t hidden, const int32_t* slot_ids,
+                              const int32_t* cand_ids, const float* cand_mask, const int32_t* first_node, int64_t num_graphs,
+                              int32_t num_candidates, const float* w, const float* g_loss, const float* g_total, float* d_states,
+                              int64_t ldg, float* dw, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ========================================================================== *
  * 8. GRU cell elementwise halves (node-side; gnns/ggnn.py:92 via utils/utils.py:15-16)
  * ========================================================================== */

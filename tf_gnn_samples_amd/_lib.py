@@ -76,6 +76,20 @@ _SIGNATURES = {
     "relgnn_softmax_ce_stats_workspace_bytes": (ctypes.c_size_t, []),
     "relgnn_softmax_ce_stats": (ctypes.c_int, [_ptr, _c_i64, _ptr, _ptr, _c_i64, _c_i32, _ptr, _ptr, ctypes.c_size_t, _ptr]),
     "relgnn_softmax_ce_bwd": (ctypes.c_int, [_ptr, _c_i64, _ptr, _ptr, _c_i64, _c_i32, _ptr, _ptr, _ptr, _ptr, _c_i64, _ptr]),
+    "relgnn_charcnn_supported": (ctypes.c_int, [_c_i32, _c_i32]),
+    "relgnn_charcnn_range_labels": (_c_i64, [_c_i32]),
+    "relgnn_charcnn_fwd_workspace_bytes": (ctypes.c_size_t, [_c_i64, _c_i32, _c_i32]),
+    "relgnn_charcnn_fwd": (ctypes.c_int, [_ptr, _c_i64, _c_i32, _ptr, _c_i64, _ptr, _ptr, _ptr, _ptr, _c_i32, _ptr, _ptr, ctypes.c_size_t,
+                                          _ptr, _ptr]),
+    "relgnn_charcnn_bwd_workspace_bytes": (ctypes.c_size_t, [_c_i64, _c_i32, _c_i32]),
+    "relgnn_charcnn_bwd": (ctypes.c_int, [_ptr, _c_i64, _c_i32, _ptr, _ptr, _ptr, _ptr, _c_i32, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr,
+                                          ctypes.c_size_t, _ptr]),
+    "relgnn_varmisuse_head_supported": (ctypes.c_int, [_c_i32, _c_i32]),
+    "relgnn_varmisuse_head_workspace_bytes": (ctypes.c_size_t, [_c_i64, _c_i32]),
+    "relgnn_varmisuse_head_fwd": (ctypes.c_int, [_ptr, _c_i64, _c_i64, _c_i32, _ptr, _ptr, _ptr, _ptr, _c_i64, _c_i32, _ptr, _ptr, _ptr, _ptr,
+                                                 ctypes.c_size_t, _ptr, _ptr]),
+    "relgnn_varmisuse_head_bwd": (ctypes.c_int, [_ptr, _c_i64, _c_i64, _c_i32, _ptr, _ptr, _ptr, _ptr, _c_i64, _c_i32, _ptr, _ptr, _ptr, _ptr,
+                                                 _c_i64, _ptr, _ptr, ctypes.c_size_t, _ptr]),
     "relgnn_gru_gates_fwd": (ctypes.c_int, [_ptr, _ptr, _ptr, _c_i64, _c_i32, _ptr, _ptr, _ptr, _ptr]),
     "relgnn_gru_cell_fwd_supported": (ctypes.c_int, [_c_i32, _c_i32, _c_i32]),
     "relgnn_gru_cell_fwd_xf32": (ctypes.c_int, [_ptr, _c_i64, _ptr, _c_i64, _ptr, _ptr, _ptr, _c_i32, _ptr, _ptr, _ptr, _ptr, _ptr,

@@ -788,7 +788,8 @@ def check_pending_graph_errors():
     flags = torch.cat([f for f, _ in pending])
     bad = torch.nonzero(flags).flatten().tolist()          # one host sync for all pending graphs
     if bad:
-        raise ValueError("adjacency list holds a node id outside [0, %d)" % pending[bad[0]][1])
+        what = pending[bad[0]][1]          # a node count, or the message of another producer's index check (tasks/varmisuse_task.py)
+        raise ValueError(what if isinstance(what, str) else "adjacency list holds a node id outside [0, %d)" % what)
 
 
 def as_rel_graph(adjacency_lists, num_nodes: int, validate=True) -> RelGraph:

@@ -38,12 +38,14 @@ def restore(saved_model_path: str, result_dir: str, run_id: str = None, device=N
     import os
     import pickle
     import time
-    from ..tasks import name_to_task_class
+    from ..tasks import CHECKPOINT_TASK_CLASSES, name_to_task_class
     print("Loading model from file %s." % saved_model_path)
     with open(saved_model_path, 'rb') as in_file:
         data_to_load = pickle.load(in_file)
     model_cls, _ = name_to_model_class(data_to_load['model_class'])
-    task_cls, _ = name_to_task_class(data_to_load['task_class'])
+    task_cls = CHECKPOINT_TASK_CLASSES.get(data_to_load['task_class'])
+    if task_cls is None:
+        task_cls, _ = name_to_task_class(data_to_load['task_class'])
     if run_id is None:
         run_id = "_".join([task_cls.name(), model_cls.name(data_to_load['model_params']), time.strftime("%Y-%m-%d-%H-%M-%S"),
                            str(os.getpid())])

@@ -434,6 +434,7 @@ class Sparse_Graph_Model(ABC):
         p = self.params
         h_dim = p['hidden_size']
         vs = self.variables
+        vs.create_all("", self.task.input_variables())            # :138 make_task_input_model runs before the propagation model
         if self.task.initial_node_feature_size != h_dim:          # :165-170, unnamed Keras Dense
             vs.create("graph_model/dense/kernel", (self.task.initial_node_feature_size, h_dim))
         self._inter_norm_name = []
@@ -540,7 +541,8 @@ class Sparse_Graph_Model(ABC):
         # a batch from the input pipeline may carry its bucketing, built on a side stream (tasks/batcher.py)
         graph = getattr(batch, "graph", None)
         final = self.compute_final_node_representations(
-            batch.initial_node_features, graph if graph is not None else batch.adjacency_lists,
+            self.task.compute_initial_node_features(batch, self.variables.scope("")),
+            graph if graph is not None else batch.adjacency_lists,
             batch.type_to_num_incoming_edges, keep)
         return self.task.compute_task_metrics(final, batch, self.variables.scope(self._task_scope))
 

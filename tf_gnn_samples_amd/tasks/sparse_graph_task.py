@@ -39,7 +39,8 @@ class DeviceBatch:
                 t = t.pin_memory()
             return t.to(device, non_blocking=pin)
 
-        self.initial_node_features = put(fd['initial_node_features'], torch.float32)
+        # (a task with an input model of its own, tasks/varmisuse_task.py, feeds what that model reads instead)
+        self.initial_node_features = put(fd['initial_node_features'], torch.float32) if 'initial_node_features' in fd else None
         self.adjacency_lists = [put(np.asarray(a).reshape(-1, 2), torch.int32) for a in fd['adjacency_lists']]
         self.type_to_num_incoming_edges = put(fd['type_to_num_incoming_edges'], torch.float32)
         self.graph_nodes_list = put(fd['graph_nodes_list'], torch.int32) if fd.get('graph_nodes_list') is not None else None
@@ -123,6 +124,15 @@ class Sparse_Graph_Task:
     def output_variable_scope(self, model_has_input_projection: bool) -> str:
         """Absolute TF variable scope of the task's output variables ("" = the graph's root scope)."""
         return ""
+
+    # ---- a task-owned input model (make_task_input_model, tasks/sparse_graph_task.py:139-149; only VarMisuse has variables there) ----
+    def input_variables(self) -> Dict[str, tuple]:
+        """Variable specs (absolute names, the graph's root scope) of the task's input model, created BEFORE graph_model/..."""
+        return {}
+
+    def compute_initial_node_features(self, batch: "DeviceBatch", weights) -> torch.Tensor:
+        """model_ops['initial_node_features'] of one batch; `weights` maps the names of input_variables() to the parameters."""
+        return batch.initial_node_features
 
     # ---- native batching (tasks/batcher.py); tasks override the payload tables / post-processing ----
     NODE_PAYLOADS = {"initial_node_features": ("node_features", np.float32)}

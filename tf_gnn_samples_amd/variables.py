@@ -28,6 +28,8 @@ def _init_tensor(shape, init: str, generator: torch.Generator) -> torch.Tensor:
         # Keras / tf.get_variable default for these layers: U(-l, l), l = sqrt(6/(fan_in+fan_out))
         if len(shape) == 1:
             fan_in = fan_out = shape[0]
+        elif len(shape) == 3:               # Conv1D kernel [k, in, out]: the receptive field multiplies both fans
+            fan_in, fan_out = shape[0] * shape[1], shape[0] * shape[2]
         else:
             fan_in, fan_out = shape[0], shape[1]
         limit = math.sqrt(6.0 / (fan_in + fan_out))
