@@ -1067,6 +1067,23 @@ int relgnn_limb_gemm_sel_pc_supported(int32_t M, int32_t N, int32_t K, int32_t r
 int relgnn_limb_gemm_sel_pc_xf32(const float* A, int64_t lda, const int32_t* a_rows, const uint16_t* B_limbs, int32_t num_b,
                                  const int32_t* b_select, int32_t rows_per_select, const void* zeros, float* C, int64_t ldc,
                                  int32_t M, int32_t N, int32_t K, int32_t* status, void* stream);
+/* The first per-edge product of an edge MLP with >= 1 hidden layer (gnns/gnn_edge_mlp.py:95-102, gnns/rgin.py:114-119;
+ * utils/utils.py:120-126 per edge type) with its left operand formed in flight (csrc/edge_mlp_fused.hip):
+ *     C[m, :] = out_act( in_act( P[row_src[m], :] + (Q ? Q[row_tgt[m], :] : 0) ) @ W_{type(m)} )        m in [0, M)
+ * i.e. relgnn_pair_materialize followed by relgnn_limb_gemm_sel_xf32 per type block, bit for bit, without the [M, K] tensor between
+ * them.  P, Q (nullable): fp32 [*, K] tables with row strides ldp / ldq; row_src / row_tgt: their row per message, in the type-major
+ * message order (range checked when the graph was built, not here); W_limbs: num_w limb images of [N, K] operands one behind the
+ * other (relgnn_limb_elements(N, K) elements each); panels: device int32 [num_panels][4] = {first message, rows (1..128), weight
+ * index, 0} — a panel holds messages of ONE edge type, every message sits in exactly one panel (an entry that does not fit M or
+ * num_w is skipped); C: fp32 [M, N], row stride ldc.  in_act: any RELGNN_ACT_*, evaluated as the edge kernels evaluate it; out_act:
+ * any RELGNN_ACT_*, as the epilogue of relgnn_limb_gemm_sel_xf32.
+ * RELGNN_EUNSUPPORTED unless K % 16 == 0, 16 <= K <= 1024, N % 128 == 0 (relgnn_edge_mlp_fwd_supported), every row stride % 4 == 0
+ * and >= the row, 16-byte aligned bases; M == 0 or num_panels == 0: RELGNN_OK, nothing launched. */
+int relgnn_edge_mlp_fwd_supported(int32_t in_act, int32_t out_act, int32_t N, int32_t K);
+int relgnn_edge_mlp_fwd_xf32(int32_t in_act, int32_t out_act, const float* P, int64_t ldp, const float* Q, int64_t ldq,
+                             const int32_t* row_src, const int32_t* row_tgt, const uint16_t* W_limbs, int32_t num_w,
+                             const int32_t* panels, int32_t num_panels, float* C, int64_t ldc, int64_t M, int32_t N, int32_t K,
+                             void* stream);
 /* Weight gradients dW = A^T @ G (A [V, J] = the saved layer input, G [V, C] = the output gradient; tf.gradients of the Dense
  * products above) on the same limb arithmetic: both operands fp32 row-major, split AND transposed in flight (the reduction index is
  * the row of both).  The kernel takes the first V - V % 32 rows, cut into relgnn_limb_gemm_tn_chunks(V, J, C) chunks; chunk z writes

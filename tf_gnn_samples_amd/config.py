@@ -72,6 +72,11 @@ _SPEC: Dict[str, Tuple[str, str, Tuple[str, ...], str]] = {
                  "by-source pass re-gathers (auto: emit on compact pair tables or D <= 128)"),
     "edge_sign_mask": ("RELGNN_EDGE_SIGN_MASK", "0", ("0", "1"),
                        "FiLM regather backward: pass A leaves one sign bit per message and feature for pass B"),
+    "edge_mlp": ("RELGNN_EDGE_MLP", "materialize", ("materialize", "fused"),
+                 "edge MLPs with >= 1 hidden layer (GNN-Edge-MLP, RGIN with an edge MLP), first hidden layer: the [M, Dh] hidden "
+                 "tensor written by the gather kernel, read by one product per edge type and kept for the backward | gather, "
+                 "activation and the per-type product in ONE kernel (csrc/edge_mlp_fused.hip: exact-split arithmetic on the cached "
+                 "weight images, D = 128 and 256; needs gemm=limb); the hidden tensor is recomputed in the backward"),
     "typed": ("RELGNN_TYPED", "panel", ("panel", "bmm"),
               "per-(node, type) transforms of many-type graphs: one gathered-row MFMA launch | index_select + torch.bmm"),
     "typed_tn": ("RELGNN_TYPED_TN", "auto", ("auto", "limb", "panel"),

@@ -11,7 +11,8 @@ from typing import Mapping, Optional
 import torch
 
 from .. import _lib, ops
-from ..dense import dense
+from ..config import settings as _cfg
+from ..dense import GEMM_NN, dense, rows_aligned, sel_weights_cacheable
 from ..utils import apply_activation, get_activation
 
 
@@ -39,6 +40,23 @@ def split_first_layer(kernel: torch.Tensor, in_dim: int):
     return kernel[:in_dim], kernel[in_dim:]
 
 
+def _edge_mlp_fused_ok(p: torch.Tensor, q: Optional[torch.Tensor], kernels, in_act: int, out_act: int) -> bool:
+    """THE route rule of the fused first product (config edge_mlp = fused; ops.edge_mlp_first_product, csrc/edge_mlp_fused.hip):
+    the switch and the limb route are on, the tables are fp32 device matrices with 16-byte aligned rows, the kernel takes the
+    shape and the activations, and the layer-1 kernels' limb images can come from the step's cache.  Anything else: the
+    materialised route, silently."""
+    if _cfg.edge_mlp != "fused" or not _cfg.limb_gemm:
+        return False
+    if not (rows_aligned(p) and (q is None or (rows_aligned(q) and q.shape == p.shape))):
+        return False
+    k, n = kernels[0].shape
+    if k != p.shape[1] or out_act not in ops._FUSABLE_ACTS:
+        return False
+    if not _lib.load_library().relgnn_edge_mlp_fwd_supported(in_act, out_act, n, k):
+        return False
+    return all(w.is_cuda for w in kernels) and sel_weights_cacheable(kernels, GEMM_NN)
+
+
 def edge_mlp_messages(cur: torch.Tensor, graph, weights: Mapping[str, torch.Tensor], mlp_name_pattern: str,
                       num_hidden_layers: int, hidden_activation: Optional[str], use_target_state_as_input: bool,
                       ) -> torch.Tensor:
@@ -58,11 +76,22 @@ def edge_mlp_messages(cur: torch.Tensor, graph, weights: Mapping[str, torch.Tens
     if use_target_state_as_input:
         w_tgt = torch.cat([k[d_in:] for k in k0], dim=1)
         q = dense(cur, w_tgt).view(V * L, dh)
-    hidden = ops.pair_materialize(p, q, graph, hidden_activation)                     # [M, Dh]
     act_fn = get_activation(hidden_activation)
     offs = graph.type_offsets
-    h = hidden
-    for i in range(1, num_hidden_layers + 1):
+    k1 = [weights["%s/%s/kernel" % (mlp_name_pattern % l, names[1])] for l in range(L)]
+    act_id = ops.activation_id(hidden_activation)
+    # (the activation behind the first product rides in its epilogue when its gradient follows from the output; gelu stays outside)
+    epilogue = num_hidden_layers > 1 and act_id in ops._FUSABLE_ACTS
+    first = 1
+    if _edge_mlp_fused_ok(p, q, k1, act_id, act_id if epilogue else _lib.ACT_LINEAR):
+        # gather + add + activation + the first per-type product in one launch: the [M, Dh] hidden tensor is never written
+        h = ops.edge_mlp_first_product(p, q, graph, hidden_activation, k1, hidden_activation if epilogue else None)
+        if num_hidden_layers > 1 and not epilogue:
+            h = apply_activation(act_fn, h)
+        first = 2
+    else:
+        h = ops.pair_materialize(p, q, graph, hidden_activation)                      # [M, Dh]
+    for i in range(first, num_hidden_layers + 1):
         # one per-edge GEMM per edge type on its contiguous [E_l, D] block, written in place of a concat
         h = ops.blocked_linear(h, offs, [weights["%s/%s/kernel" % (mlp_name_pattern % l, names[i])] for l in range(L)])
         if i < num_hidden_layers:

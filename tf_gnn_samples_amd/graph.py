@@ -531,6 +531,42 @@ class RelGraph:
             offs.append(offs[-1] + e)
         return offs
 
+    def edge_mlp_panels(self) -> torch.Tensor:
+        """edge_mlp_panel_table(type_offsets) on the device (int32 [panels, 4]): the row panels of relgnn_edge_mlp_fwd_xf32.
+        Built on the host from python ints and uploaded once per graph — before a step is captured, the eager warm-up steps
+        have put it here."""
+        if "edge_mlp_panels" not in self._plans:
+            table = edge_mlp_panel_table(self.type_offsets)
+            self._plans["edge_mlp_panels"] = (_upload(table, self.device) if len(table)
+                                              else torch.empty((0, 4), dtype=torch.int32, device=self.device))
+        return self._plans["edge_mlp_panels"]
+
+
+EDGE_MLP_PANEL_ROWS = 128
+
+
+def edge_mlp_panel_table(type_offsets):
+    """The 128-row panels of the type-major message list, as csrc/edge_mlp_fused.hip reads them: int32 [panels, 4] rows
+    {first message, rows (1..128), weight index = edge type, 0}.  A panel never crosses a type boundary, every message is in
+    exactly one panel, an empty type has none (type blocks are no multiples of 128: the last panel of a block is short)."""
+    import numpy as np
+    offs = [int(o) for o in type_offsets]
+    parts = []
+    for l in range(len(offs) - 1):
+        a, b = offs[l], offs[l + 1]
+        if b < a:
+            raise ValueError("type_offsets must not decrease")
+        if b == a:
+            continue
+        first = np.arange(a, b, EDGE_MLP_PANEL_ROWS, dtype=np.int64)
+        rows = np.minimum(b - first, EDGE_MLP_PANEL_ROWS)
+        parts.append(np.stack([first, rows, np.full_like(first, l), np.zeros_like(first)], axis=1))
+    if not parts:
+        return np.zeros((0, 4), dtype=np.int32)
+    if offs[-1] > 2 ** 31 - 1:
+        raise ValueError("more than 2^31 - 1 messages")
+    return np.ascontiguousarray(np.concatenate(parts).astype(np.int32))
+
 
 # rows per GEMM batch entry of the compact tables; every type's row block is padded to a multiple
 PAIR_CHUNK = 512

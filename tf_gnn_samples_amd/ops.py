@@ -776,35 +776,42 @@ class _PairMaterialize(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, ghidden):
-        lib = _lib.load_library()
-        graph, act = ctx.graph, ctx.act
         P, Q = ctx.saved_tensors
-        M, D = graph.M, P.shape[1]
-        ghidden = ghidden.contiguous()
-        S = graph.V * graph.L
-        if (ctx.has_q and _cfg.edge_bwd != "emit" and D % 4 == 0 and 128 < D <= 1024
-                and M * (D // 4) < 2 ** 32 and S > 0):
-            # No [M, D] gradient of the pre-activation is written and re-read twice: the by-(source,type) pass of the pair
-            # kernels sums g_m * act'(P[r] + Q[f_m]) per bucket r straight from ghidden's rows (its "target gradient row" is
-            # the message's own row here), once over the by-source buckets for gP and once over the by-target buckets with
-            # the roles of P and Q swapped for gQ.  C2 shape, elu: 959 + 2 x 423 us -> 2 x ~500 us per layer.
-            gP, gQ = torch.empty_like(P), torch.empty_like(Q)
-            st = _lib.current_stream()
-            _lib.check(lib.relgnn_pair_bwd_p(act, _lib.ptr(P), D, _lib.ptr(Q), D, D, _lib.ptr(graph.rowptr_s), S,
-                                             _lib.ptr(graph.perm_s), _lib.ptr(graph.frow_s), None, _lib.ptr(ghidden), D,
-                                             _lib.ptr(gP), D, st), "relgnn_pair_bwd_p")
-            _lib.check(lib.relgnn_pair_bwd_p(act, _lib.ptr(Q), D, _lib.ptr(P), D, D, _lib.ptr(graph.rowptr_t), S,
-                                             _lib.ptr(graph.perm_t), _lib.ptr(graph.col_t), None, _lib.ptr(ghidden), D,
-                                             _lib.ptr(gQ), D, st), "relgnn_pair_bwd_p")
-            return gP, gQ, None, None
-        gpre = torch.empty_like(ghidden)
-        _lib.check(lib.relgnn_pair_materialize(act, _lib.ptr(P), D, _lib.ptr(Q), D, D, _lib.ptr(graph.key_by_source),
-                                               _lib.ptr(graph.key_by_target), M, _lib.ptr(ghidden), _lib.ptr(gpre), D,
-                                               _lib.current_stream()), "relgnn_pair_materialize")
-        # gP[r] = sum of gpre over the messages whose source row is r; gQ[f] likewise by target row
-        gP = _seg_reduce_raw(_lib.AGG_SUM, gpre, graph.rowptr_s, 1, graph.perm_s, None, S)
-        gQ = _seg_reduce_raw(_lib.AGG_SUM, gpre, graph.rowptr_t, 1, graph.perm_t, None, S) if ctx.has_q else None
+        gP, gQ = _pair_hidden_backward(P, Q if ctx.has_q else None, ctx.graph, ctx.act, ghidden)
         return gP, gQ, None, None
+
+
+def _pair_hidden_backward(P, Q, graph, act: int, ghidden):
+    """(gP, gQ) from the gradient of hidden[m] = act(P[src_m*L+l_m] + Q[tgt_m*L+l_m]) (Q may be None: gQ is None then) — the
+    backward of _PairMaterialize and the tail of _EdgeMlpFirstProduct's."""
+    lib = _lib.load_library()
+    has_q = Q is not None
+    M, D = graph.M, P.shape[1]
+    ghidden = ghidden.contiguous()
+    S = graph.V * graph.L
+    if (has_q and _cfg.edge_bwd != "emit" and D % 4 == 0 and 128 < D <= 1024
+            and M * (D // 4) < 2 ** 32 and S > 0):
+        # No [M, D] gradient of the pre-activation is written and re-read twice: the by-(source,type) pass of the pair
+        # kernels sums g_m * act'(P[r] + Q[f_m]) per bucket r straight from ghidden's rows (its "target gradient row" is
+        # the message's own row here), once over the by-source buckets for gP and once over the by-target buckets with
+        # the roles of P and Q swapped for gQ.  C2 shape, elu: 959 + 2 x 423 us -> 2 x ~500 us per layer.
+        gP, gQ = torch.empty_like(P), torch.empty_like(Q)
+        st = _lib.current_stream()
+        _lib.check(lib.relgnn_pair_bwd_p(act, _lib.ptr(P), D, _lib.ptr(Q), D, D, _lib.ptr(graph.rowptr_s), S,
+                                         _lib.ptr(graph.perm_s), _lib.ptr(graph.frow_s), None, _lib.ptr(ghidden), D,
+                                         _lib.ptr(gP), D, st), "relgnn_pair_bwd_p")
+        _lib.check(lib.relgnn_pair_bwd_p(act, _lib.ptr(Q), D, _lib.ptr(P), D, D, _lib.ptr(graph.rowptr_t), S,
+                                         _lib.ptr(graph.perm_t), _lib.ptr(graph.col_t), None, _lib.ptr(ghidden), D,
+                                         _lib.ptr(gQ), D, st), "relgnn_pair_bwd_p")
+        return gP, gQ
+    gpre = torch.empty_like(ghidden)
+    _lib.check(lib.relgnn_pair_materialize(act, _lib.ptr(P), D, _lib.ptr(Q), D, D, _lib.ptr(graph.key_by_source),
+                                           _lib.ptr(graph.key_by_target), M, _lib.ptr(ghidden), _lib.ptr(gpre), D,
+                                           _lib.current_stream()), "relgnn_pair_materialize")
+    # gP[r] = sum of gpre over the messages whose source row is r; gQ[f] likewise by target row
+    gP = _seg_reduce_raw(_lib.AGG_SUM, gpre, graph.rowptr_s, 1, graph.perm_s, None, S)
+    gQ = _seg_reduce_raw(_lib.AGG_SUM, gpre, graph.rowptr_t, 1, graph.perm_t, None, S) if has_q else None
+    return gP, gQ
 
 
 def _pad_columns(X, pad: int):
@@ -820,6 +827,87 @@ def pair_materialize(P, Q, graph, activation: Optional[str]):
     if pad:
         return _PairMaterialize.apply(_pad_columns(P, pad), _pad_columns(Q, pad), graph, activation_id(activation))[:, :D]
     return _PairMaterialize.apply(P, Q, graph, activation_id(activation))
+
+
+class _EdgeMlpFirstProduct(torch.autograd.Function):
+    """C[m] = out_act(in_act(P[src_m*L+l_m] + Q[tgt_m*L+l_m]) @ W_{l_m}) in ONE launch (csrc/edge_mlp_fused.hip): pair_materialize
+    and the first blocked_linear of an edge MLP without the [M, Dh] hidden tensor between them — neither written in the forward
+    nor kept for the backward, which recomputes it into a transient buffer (relgnn_pair_materialize) for the weight gradients.
+      backward  gC *= out_act'(C)                      (when out_act was fused: act_bwd_from_output)
+                hidden = in_act(P[..] + Q[..])          transient
+                gH[a:b] = gC[a:b] @ W_l^T, gW_l = hidden[a:b]^T @ gC[a:b]      per non-empty type block (as _BlockedLinear)
+                gP, gQ from gH                          (_pair_hidden_backward: as _PairMaterialize)"""
+
+    @staticmethod
+    def forward(ctx, P, Q, graph, in_act: int, out_act: int, *weights):
+        from .dense import GEMM_NN, sel_image
+        lib = _lib.load_library()
+        P = P.contiguous()
+        Q = Q.contiguous() if Q is not None else None
+        M, (K, N) = graph.M, weights[0].shape
+        im = sel_image(weights, GEMM_NN)
+        if im is None:
+            raise ValueError("edge_mlp_first_product: the weights have no cached limb image (dense.sel_weights_cacheable)")
+        panels = graph.edge_mlp_panels()
+        C = torch.empty((M, N), dtype=torch.float32, device=P.device)
+        _lib.check(lib.relgnn_edge_mlp_fwd_xf32(in_act, out_act, _lib.ptr(P), P.stride(0), _lib.ptr(Q), Q.stride(0) if Q is not None else 0,
+                                                _lib.ptr(graph.key_by_source), _lib.ptr(graph.key_by_target), im.buf.data_ptr(),
+                                                len(weights), _lib.ptr(panels), panels.shape[0], _lib.ptr(C), N, M, N, K,
+                                                _lib.current_stream()), "relgnn_edge_mlp_fwd_xf32")
+        ctx.graph, ctx.acts, ctx.has_q = graph, (in_act, out_act), Q is not None
+        ctx.save_for_backward(P, Q, C if out_act != _lib.ACT_LINEAR else None, *weights)
+        return C
+
+    @staticmethod
+    def backward(ctx, gC):
+        from .dense import GEMM_NT, act_bwd_from_output, matmul_tn_splitk, mm_into
+        lib = _lib.load_library()
+        P, Q, C, *weights = ctx.saved_tensors
+        graph, (in_act, out_act) = ctx.graph, ctx.acts
+        M, K = graph.M, P.shape[1]
+        gC = gC.contiguous()
+        if C is not None:
+            gC = act_bwd_from_output(out_act, C, gC)
+        need_w = ctx.needs_input_grad[5:]
+        need_h = ctx.needs_input_grad[0] or ctx.needs_input_grad[1]
+        offsets = graph.type_offsets
+        hidden = None
+        if any(need_w) and M > 0:
+            # (the one pass through HBM that a gathered-operand weight-gradient kernel would remove: everything below reads
+            #  `hidden` as the left operand of a TN product only)
+            hidden = torch.empty((M, K), dtype=torch.float32, device=P.device)
+            _lib.check(lib.relgnn_pair_materialize(in_act, _lib.ptr(P), K, _lib.ptr(Q), K, K, _lib.ptr(graph.key_by_source),
+                                                   _lib.ptr(graph.key_by_target), M, None, _lib.ptr(hidden), K,
+                                                   _lib.current_stream()), "relgnn_pair_materialize")
+        gH = torch.empty((M, K), dtype=torch.float32, device=P.device) if need_h else None
+        gW = []
+        for l, W in enumerate(weights):
+            a, b = offsets[l], offsets[l + 1]
+            if b > a:
+                if gH is not None:
+                    mm_into(GEMM_NT, gC[a:b], W, gH[a:b])
+                gW.append(matmul_tn_splitk(hidden[a:b], gC[a:b]) if need_w[l] else None)
+            else:
+                gW.append(torch.zeros_like(W) if need_w[l] else None)
+        del hidden
+        gP = gQ = None
+        if need_h:
+            gP, gQ = _pair_hidden_backward(P, Q if ctx.has_q else None, graph, in_act, gH)
+        return (gP, gQ, None, None, None, *gW)
+
+
+def edge_mlp_first_product(P, Q, graph, in_activation: Optional[str], weights, out_activation: Optional[str] = None):
+    """out_act(in_act(P[src_m*L+l_m] + Q[tgt_m*L+l_m]) @ weights[l_m]) for every message m, [M, N] in the type-major message
+    order: ops.pair_materialize + ops.blocked_linear (+ the activation) in one launch, bit for bit.  P, Q ([V*L, K]; Q may be
+    None), weights: one [K, N] kernel per edge type whose limb images the step's cache holds (dense.sel_weights_cacheable).
+    out_activation must be one whose gradient follows from the output (anything but gelu): apply another one outside.
+    Raises where relgnn_edge_mlp_fwd_xf32 does not take the operands — gnns/pair.py asks first (_edge_mlp_fused_ok)."""
+    _check_f32(P, "P")
+    out_act = activation_id(out_activation)
+    if out_act not in _FUSABLE_ACTS:
+        raise ValueError("edge_mlp_first_product: out_activation %r cannot be fused (its gradient needs the pre-activation)"
+                         % out_activation)
+    return _EdgeMlpFirstProduct.apply(P, Q, graph, activation_id(in_activation), out_act, *list(weights))
 
 
 # ---- RGAT (csrc/rgat_fast.hip, generic fallback csrc/rgat.hip) -------------------------------------
