@@ -1,0 +1,59 @@
+"""weight_grad_stream.fork without a GPU: what it decides and marks when nothing can go aside."""
+import pytest
+import torch
+
+from tf_gnn_samples_amd import ops, weight_grad_stream as wgs
+
+
+@pytest.fixture(autouse=True)
+def _clean_pass():
+    yield
+    wgs.join_deferred()
+
+
+def _never():
+    raise AssertionError("run() belongs to the caller when fork() answers None")
+
+
+def test_ops_re_exports_the_protocol_objects():
+    for name in ("_SIDE_STREAMS", "_DEFER", "deferred_weight_gradient_join", "_accumulator_keeps_the_tensor", "deferred_targets_ok",
+                 "wait_if_in_flight", "hand_over_deferred", "join_deferred", "_side_stream"):
+        assert getattr(ops, name) is getattr(wgs, name), name
+
+
+@pytest.mark.parametrize("join_in_backward", [True, False])
+@pytest.mark.parametrize("deferred", [True, False])
+def test_cpu_operands_stay_on_this_stream(join_in_backward, deferred):
+    x, p = torch.ones(4, 3), torch.ones(3, 2, requires_grad=True)
+    streams = dict(wgs._SIDE_STREAMS)
+    if deferred:
+        with wgs.deferred_weight_gradient_join():
+            aside = wgs.fork(_never, (x, x), (p,), want=True, join_in_backward=join_in_backward, contributes=True)
+    else:
+        aside = wgs.fork(_never, (x, x), (p,), want=True, join_in_backward=join_in_backward, contributes=True)
+    assert aside is None and wgs._SIDE_STREAMS == streams and not wgs._DEFER["pending"] and not wgs._DEFER["handed"]
+
+
+def test_a_contribution_on_this_stream_marks_its_leaf_parameters_for_the_pass():
+    x = torch.ones(4, 3)
+    p, q = torch.ones(3, 2, requires_grad=True), torch.ones(2, requires_grad=True)
+    with wgs.deferred_weight_gradient_join():
+        assert wgs.fork(_never, (x,), (p, q), want=True, join_in_backward=True, contributes=True) is None
+        assert wgs._DEFER["targets"] == {id(p), id(q)}
+    assert wgs._DEFER["targets"] == {id(p), id(q)}                  # the pass lasts until its join
+    wgs.join_deferred()
+    assert not wgs._DEFER["targets"]
+    # nothing is marked: without parameters (a view's or a non-leaf's gradient), without a contribution, outside a deferred pass
+    with wgs.deferred_weight_gradient_join():
+        assert wgs.fork(_never, (x,), None, want=True, join_in_backward=True, contributes=True) is None
+        assert wgs.fork(_never, (x,), (p, q), want=False, join_in_backward=True, contributes=False) is None
+        assert not wgs._DEFER["targets"]
+    assert wgs.fork(_never, (x,), (p, q), want=True, join_in_backward=True, contributes=True) is None
+    assert not wgs._DEFER["targets"]
+
+
+def test_the_new_module_stands_below_its_users():
+    import ast
+    import inspect
+    froms = [n for n in ast.walk(ast.parse(inspect.getsource(wgs))) if isinstance(n, ast.ImportFrom)]
+    assert not ({n.module for n in froms} | {a.name for n in froms for a in n.names}) & {"ops", "dense", "utils"}

@@ -54,6 +54,7 @@ from .dense_kernels import (_LIMB_MAX_K, _LIMB_MIN_ROWS, _LIMB_WS, _WORKSPACE, _
 from .weight_images import (GEMM_NN, GEMM_NT, GEMM_TN, WEIGHT_NN, WEIGHT_NT, _PerStream, _weight_image_items, _weight_image_shape,
                             _weight_matrices, capture_image_cache, clear as _clear_weight_images, sel_image, sel_weights_cacheable,
                             weight_image, weight_image_ok, weight_limbs, weights_changed)
+from .weight_grad_stream import fork
 
 _WARNED_UNSUPPORTED = False
 
@@ -353,35 +354,6 @@ def _leaf_params(kernel, bias):
     return params if all(p.is_leaf and p.requires_grad for p in params) else None
 
 
-def _on_side_stream(run, operands, params, want=True):
-    """A Dense layer's weight and bias gradient on the weight-gradient side stream (ops._side_stream) — only while train_step defers
-    the joins behind the whole backward (ops.deferred_weight_gradient_join): the gradients then leave the main stream's critical
-    path and run under the next layer's gather (C2 step 1.826 -> 1.807 ms).  With the join inside backward() the same move was measured and lost (both
-    products are matrix-pipe kernels: 2.02 vs 1.94 ms per C2 step), so outside train_step everything stays on one stream.
-    `params`: the leaf parameters the gradients go to (ops.deferred_targets_ok: only a parameter that has no gradient yet takes its
-    gradient tensor without launching anything on the main stream), or None.  Returns run()'s result, or None when not applicable."""
-    from . import ops
-    if not (want and ops._DEFER["on"] and _cfg.bwd_overlap_on and all(t.is_cuda for t in operands)):
-        if operands[0].is_cuda:
-            ops.wait_if_in_flight(params, operands[0].device)     # (no-op unless an earlier use of these parameters went aside)
-        return None
-    if not ops.deferred_targets_ok(params, operands[0].device):
-        return None
-    device = operands[0].device
-    side = ops._side_stream(device)
-    cur = torch.cuda.current_stream(device)
-    side.wait_stream(cur)
-    with torch.cuda.stream(side):
-        out = run()
-    for t in operands:
-        t.record_stream(side)
-    for t in out:
-        if t is not None:
-            t.record_stream(cur)
-    ops.hand_over_deferred(device, side, params, out)
-    return out
-
-
 class _DenseFn(torch.autograd.Function):
     """act(x @ kernel (+ bias)) for act in {linear, tanh, relu, leaky_relu, elu, selu} — the activation in the product's epilogue where
     the route has one, differentiated from the saved OUTPUT — with a split-K weight gradient.
@@ -413,13 +385,14 @@ class _DenseFn(torch.autograd.Function):
             gb = column_sum(g) if ctx.has_bias and ctx.needs_input_grad[2] else None
             return gk, gb
 
-        aside = _on_side_stream(weight_side, (x, g), ctx.leaf_params, want=ctx.needs_input_grad[0] and ctx.needs_input_grad[1])
+        aside = fork(weight_side, (x, g), ctx.leaf_params, want=ctx.needs_input_grad[0] and ctx.needs_input_grad[1],
+                     join_in_backward=False, contributes=x.is_cuda)
         if ctx.needs_input_grad[0]:
             if ctx.x_act and premask_ok(x, g.shape[0], kernel.shape[0]):
                 gx = mark_premasked(lib_gemm(GEMM_NT, g, kernel, weight=True, premask=(ctx.x_act, x)), x, ctx.x_act)
             else:
                 gx = lib_gemm(GEMM_NT, g, kernel, weight=True)
-        gk, gb = aside if aside is not None else weight_side()
+        gk, gb = aside.join() if aside is not None else weight_side()
         return gx, gk, gb, None, None
 
 
@@ -452,12 +425,13 @@ class _DenseMultiFn(torch.autograd.Function):
                 return tuple(tn_stream_blocks(x, g, L).unbind(0))
             return tuple(matmul_tn_splitk(x, g[:, l * N:(l + 1) * N]) if ctx.needs_input_grad[1 + l] else None for l in range(L))
 
-        aside = _on_side_stream(weight_side, (x, g), ctx.leaf_params, want=ctx.needs_input_grad[0] and any(ctx.needs_input_grad[1:]))
+        aside = fork(weight_side, (x, g), ctx.leaf_params, want=ctx.needs_input_grad[0] and any(ctx.needs_input_grad[1:]),
+                     join_in_backward=False, contributes=x.is_cuda)
         if ctx.needs_input_grad[0]:
             # gx = sum_l g[:, block l] @ k_l^T: the kernels side by side along the reduction (WEIGHT_NT image), 128 output columns
             im = weight_image(kernels, WEIGHT_NT)                        # B [K, L*N] = [k_0 | k_1 | ..] as stored
             gx = _sel_with_image(g, im, K, L * N)
-        gks = aside if aside is not None else (weight_side() if any(ctx.needs_input_grad[1:]) else (None,) * L)
+        gks = aside.join() if aside is not None else (weight_side() if any(ctx.needs_input_grad[1:]) else (None,) * L)
         return (gx,) + tuple(gks)
 
 

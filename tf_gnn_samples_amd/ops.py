@@ -12,6 +12,8 @@ import torch
 from . import _lib
 from .config import settings as _cfg
 from .graph import GatherReducePlan, build_segment_plan
+from .weight_grad_stream import (_DEFER, _SIDE_STREAMS, _accumulator_keeps_the_tensor, _side_stream, deferred_targets_ok,  # noqa: F401
+                                 deferred_weight_gradient_join, fork, hand_over_deferred, join_deferred, wait_if_in_flight)
 
 _MODE_IDS = {
     "sum": _lib.AGG_SUM, "unsorted_segment_sum": _lib.AGG_SUM,
@@ -538,6 +540,42 @@ def _typed_weight_gradient(H, gY, side, L: int, Din: int, Dout: int):
     return _seg_reduce_raw(_lib.AGG_SUM, part.view(-1, sub), rowptr, 1, col, None, L * K).view(L, Din, Dout)
 
 
+def _typed_product(H, side, weights):
+    """(Y [P, Dout], W): Y = gather(H) @ W_type over the pair table `side`, one launch.  The limb images of the per-type weights come
+    from the step's cache where they can (round 6, dense.weight_image(separate=True): neither a stacked [L, Din, Dout] copy nor a
+    split launch in front of the product) and W is None; else W is the stacked copy the product read — split into the scratch limbs,
+    or on the exact-fp32 panel kernel — for the backward to keep."""
+    from .dense import GEMM_NN, limb_dense_sel, panel_gemm, sel_image
+    Din, Dout = weights[0].shape
+    node32, tile_type = side.panel_indices()
+    im = sel_image(weights, GEMM_NN) if (_typed_limb_ok(Din, Dout) and _typed_limb_ok(Dout, Din)) else None
+    if im is not None:
+        return limb_dense_sel(GEMM_NN, H, weights, a_rows=node32, num_rows=side.P, b_select=tile_type,
+                              rows_per_select=side.chunk, image=im), None
+    W = torch.stack(weights)
+    if _typed_limb_ok(Din, Dout):
+        return limb_dense_sel(GEMM_NN, H, W, a_rows=node32, num_rows=side.P, b_select=tile_type, rows_per_select=side.chunk), W
+    return panel_gemm(GEMM_NN, H, W, a_rows=node32, num_rows=side.P, b_select=tile_type, rows_per_select=side.chunk), W
+
+
+def _typed_input_gradient(gY, side, weights, W, out=None):
+    """dX [P, Din] = dY @ W_type^T per row of the pair table `side`, one launch, into `out` when given.  `weights`: the per-type
+    kernels when the forward read their cached images (W is None), else W is the forward's stacked copy."""
+    from .dense import GEMM_NT, limb_dense_sel, panel_gemm, sel_image
+    Din, Dout = (weights[0] if W is None else W[0]).shape
+    _, tile_type = side.panel_indices()
+    if W is None:
+        im = sel_image(weights, GEMM_NT)
+        if im is not None:
+            return limb_dense_sel(GEMM_NT, gY, weights, b_select=tile_type, rows_per_select=side.chunk, image=im, out=out)
+        W = torch.stack(weights)                                 # (switched off between forward and backward)
+    if _typed_limb_ok(Dout, Din):
+        gX = limb_dense_sel(GEMM_NT, gY, W, b_select=tile_type, rows_per_select=side.chunk)
+    else:
+        gX = panel_gemm(GEMM_NT, gY, W, b_select=tile_type, rows_per_select=side.chunk, dims=(side.P, Din, Dout))
+    return gX if out is None else out.copy_(gX)
+
+
 class _TypedLinearPair(torch.autograd.Function):
     """The two per-(node, type) transforms of a GNN-FiLM layer (gnns/gnn_film.py:92-106: messages h_u W_l over the by-source pair
     table, FiLM weights h_v F_l over the by-target one) as ONE autograd node: the forward is the two products of
@@ -547,69 +585,36 @@ class _TypedLinearPair(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, H, pairs, leaves, La: int, *weights):
-        from .dense import GEMM_NN, limb_dense_sel, sel_image
-        wa, wb = weights[:La], weights[La:]
         ctx.leaf_params, ctx.pairs, ctx.La = leaves, pairs, La
-        outs = []
-        for side, ws in ((pairs.src, wa), (pairs.tgt, wb)):
-            node32, tile_type = side.panel_indices()
-            outs.append(limb_dense_sel(GEMM_NN, H, ws, a_rows=node32, num_rows=side.P, b_select=tile_type,
-                                       rows_per_select=side.chunk, image=sel_image(ws, GEMM_NN)))
         ctx.save_for_backward(H, *weights)
-        return outs[0], outs[1]
+        return tuple(_typed_product(H, side, ws)[0] for side, ws in ((pairs.src, weights[:La]), (pairs.tgt, weights[La:])))
 
     @staticmethod
     def backward(ctx, gYa, gYb):
-        from .dense import GEMM_NT, limb_dense_sel, sel_image
         H, *weights = ctx.saved_tensors
         pairs, La = ctx.pairs, ctx.La
-        wa, wb = weights[:La], weights[La:]
-        sides = ((pairs.src, wa, gYa.contiguous()), (pairs.tgt, wb, gYb.contiguous()))
-        Din = wa[0].shape[0]
-        gH, gWs = None, None
-        want_w = any(ctx.needs_input_grad[4:])
+        sides = ((pairs.src, weights[:La], gYa.contiguous()), (pairs.tgt, weights[La:], gYb.contiguous()))
+        Din = weights[0].shape[0]
+        need = ctx.needs_input_grad[4:]
+        want_w = any(need)
 
-        def weight_gradients():
-            return tuple(_typed_weight_gradient(H, g, side, len(ws), Din, ws[0].shape[1]) for side, ws, g in sides)
+        def weight_side():
+            flat = sum((_typed_weight_gradient(H, g, side, len(ws), Din, ws[0].shape[1]).unbind(0) for side, ws, g in sides), ())
+            return tuple(g if n else None for g, n in zip(flat, need))
 
-        side_stream = None
-        if (want_w and ctx.needs_input_grad[0] and _cfg.bwd_overlap_on and H.is_cuda
-                and (not _DEFER["on"] or deferred_targets_ok(ctx.leaf_params, H.device))):
-            side_stream = _side_stream(H.device)
-            cur = torch.cuda.current_stream(H.device)
-            side_stream.wait_stream(cur)
-            with torch.cuda.stream(side_stream):
-                gWs = weight_gradients()
-            for t in (H, sides[0][2], sides[1][2]):
-                t.record_stream(side_stream)
+        aside = fork(weight_side, (H, sides[0][2], sides[1][2]), ctx.leaf_params, want=want_w and ctx.needs_input_grad[0],
+                     join_in_backward=True, contributes=want_w)
+        gH = None
         if ctx.needs_input_grad[0]:
-            Pa, Pb = pairs.src.P, pairs.tgt.P
-            gX = torch.empty((Pa + Pb, Din), dtype=torch.float32, device=H.device)
+            gX = torch.empty((pairs.src.P + pairs.tgt.P, Din), dtype=torch.float32, device=H.device)
             at = 0
-            images = [sel_image(ws, GEMM_NT) for _, ws, _ in sides]
-            for (side, ws, g), im in zip(sides, images):
-                _, tile_type = side.panel_indices()
-                if im is not None:
-                    limb_dense_sel(GEMM_NT, g, ws, b_select=tile_type, rows_per_select=side.chunk, image=im, out=gX[at:at + side.P])
-                else:                                                   # (switched off between forward and backward)
-                    gX[at:at + side.P] = limb_dense_sel(GEMM_NT, g, torch.stack(ws), b_select=tile_type, rows_per_select=side.chunk)
+            for side, ws, g in sides:
+                _typed_input_gradient(g, side, ws, None, out=gX[at:at + side.P])
                 at += side.P
             rowptr, col = pairs.node_csr_both()
             gH = _seg_reduce_raw(_lib.AGG_SUM, gX, rowptr, 1, col, None, H.shape[0])
-        if side_stream is not None:
-            flat = gWs[0].unbind(0) + gWs[1].unbind(0)
-            if _DEFER["on"]:
-                hand_over_deferred(H.device, side_stream, ctx.leaf_params, flat)
-            else:
-                torch.cuda.current_stream(H.device).wait_stream(side_stream)
-            for g in gWs:
-                g.record_stream(torch.cuda.current_stream(H.device))
-        elif want_w:
-            wait_if_in_flight(ctx.leaf_params, H.device)
-            gWs = weight_gradients()
-        need = ctx.needs_input_grad[4:]
-        grads = (gWs[0].unbind(0) + gWs[1].unbind(0)) if gWs is not None else (None,) * len(weights)
-        return (gH, None, None, None) + tuple(g if n else None for g, n in zip(grads, need))
+        gWs = aside.join() if aside is not None else (weight_side() if want_w else (None,) * len(weights))
+        return (gH, None, None, None) + gWs
 
 
 def typed_linear_pair(H, pairs, weights_src, weights_tgt):
@@ -645,24 +650,10 @@ class _TypedLinearPanel(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, H, side, leaves, *weights):
-        from .dense import GEMM_NN, GEMM_NT, limb_dense_sel, panel_gemm, sel_image
         ctx.leaf_params = leaves            # the per-type weights themselves, when every one is a leaf parameter
-        L, (Din, Dout) = len(weights), weights[0].shape
-        node32, tile_type = side.panel_indices()
-        # round 6: the limb images of the per-type weights come from the step's cache (dense.weight_image(separate=True)): neither a
-        # stacked [L, Din, Dout] copy nor a split launch in front of the product
-        im = sel_image(weights, GEMM_NN) if (_typed_limb_ok(Din, Dout) and _typed_limb_ok(Dout, Din)) else None
-        cached = im is not None
-        W = None if cached else torch.stack(weights)
-        if cached:
-            Y = limb_dense_sel(GEMM_NN, H, weights, a_rows=node32, num_rows=side.P, b_select=tile_type,
-                               rows_per_select=side.chunk, image=im)
-        elif _typed_limb_ok(Din, Dout):
-            Y = limb_dense_sel(GEMM_NN, H, W, a_rows=node32, num_rows=side.P, b_select=tile_type, rows_per_select=side.chunk)
-        else:
-            Y = panel_gemm(GEMM_NN, H, W, a_rows=node32, num_rows=side.P, b_select=tile_type, rows_per_select=side.chunk)
-        ctx.side, ctx.shape, ctx.cached = side, (L, Din, Dout), cached
-        if cached:
+        Y, W = _typed_product(H, side, weights)
+        ctx.side, ctx.shape, ctx.cached = side, (len(weights), *weights[0].shape), W is None
+        if ctx.cached:
             ctx.save_for_backward(H, *weights)
         else:
             ctx.save_for_backward(H, W)
@@ -670,58 +661,28 @@ class _TypedLinearPanel(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, gY):
-        from .dense import GEMM_NT, GEMM_TN, limb_dense_sel, panel_gemm
         H, *saved = ctx.saved_tensors
-        W = None if ctx.cached else saved[0]
         side = ctx.side
         L, Din, Dout = ctx.shape
         gY = gY.contiguous()
-        node32, tile_type = side.panel_indices()
-        gH = gW = None
+        need = ctx.needs_input_grad[3:]
+        want_w = any(need)
 
-        def weight_gradient():
-            return _typed_weight_gradient(H, gY, side, L, Din, Dout)
+        def weight_side():
+            return tuple(g if n else None for g, n in zip(_typed_weight_gradient(H, gY, side, L, Din, Dout).unbind(0), need))
 
         # The weight gradient (exact-fp32 matrix pipe, ~0.25-0.5 ms per product on a 23-type batch) depends on nothing the input
         # gradient computes: it runs on the side stream of the aggregate-first layer's weight gradient, under the memory-bound
         # kernels that follow on the main stream (the other typed product's row sums, the next layer's fused edge backward); the
-        # join is deferred behind the whole backward inside train_step (deferred_weight_gradient_join above).
-        side_stream = None
-        want_w = any(ctx.needs_input_grad[3:])
-        if (want_w and ctx.needs_input_grad[0] and _cfg.bwd_overlap_on and gY.is_cuda
-                and (not _DEFER["on"] or deferred_targets_ok(ctx.leaf_params, gY.device))):
-            side_stream = _side_stream(gY.device)
-            cur = torch.cuda.current_stream(gY.device)
-            side_stream.wait_stream(cur)
-            with torch.cuda.stream(side_stream):
-                gW = weight_gradient()
-            for t in (H, gY):
-                t.record_stream(side_stream)
+        # join is deferred behind the whole backward inside train_step (weight_grad_stream.deferred_weight_gradient_join).
+        aside = fork(weight_side, (H, gY), ctx.leaf_params, want=want_w and ctx.needs_input_grad[0],
+                     join_in_backward=True, contributes=want_w)
+        gH = None
         if ctx.needs_input_grad[0]:
-            im = None
-            if ctx.cached:
-                from .dense import sel_image
-                im = sel_image(saved, GEMM_NT)
-                if im is None:                       # (switched off between forward and backward)
-                    W = torch.stack(saved)
-            if im is not None:
-                gX = limb_dense_sel(GEMM_NT, gY, saved, b_select=tile_type, rows_per_select=side.chunk, image=im)
-            elif _typed_limb_ok(Dout, Din):
-                gX = limb_dense_sel(GEMM_NT, gY, W, b_select=tile_type, rows_per_select=side.chunk)
-            else:
-                gX = panel_gemm(GEMM_NT, gY, W, b_select=tile_type, rows_per_select=side.chunk, dims=(side.P, Din, Dout))
+            gX = _typed_input_gradient(gY, side, saved, None) if ctx.cached else _typed_input_gradient(gY, side, None, saved[0])
             gH = _seg_reduce_raw(_lib.AGG_SUM, gX, side.node_rowptr, 1, side.node_col, None, H.shape[0])
-        if side_stream is not None:
-            if _DEFER["on"]:
-                hand_over_deferred(gY.device, side_stream, ctx.leaf_params, gW.unbind(0))
-            else:
-                torch.cuda.current_stream(gY.device).wait_stream(side_stream)
-            gW.record_stream(torch.cuda.current_stream(gY.device))
-        elif want_w:
-            wait_if_in_flight(ctx.leaf_params, gY.device)     # (no-op unless an earlier use of these weights went aside)
-            gW = weight_gradient()
-        need = ctx.needs_input_grad[3:]
-        return (gH, None, None) + (tuple(g if n else None for g, n in zip(gW.unbind(0), need)) if gW is not None else (None,) * L)
+        gWs = aside.join() if aside is not None else (weight_side() if want_w else (None,) * L)
+        return (gH, None, None) + gWs
 
 
 def _typed_limb_ok(k: int, n: int) -> bool:
@@ -1053,133 +1014,6 @@ def aggregate_acc64() -> bool:
     return _cfg.agg_acc == "f64"
 
 
-# config.settings.bwd_overlap (RELGNN_BWD_OVERLAP; auto = on with the limb route): the weight gradient of the aggregate-first RGCN layer on a side stream next to the input gradient's
-# gather.  Measured on the C2 step, alternated twice in one process group: 2.006 / 2.014 ms without, 1.955 / 1.955 ms with (round 2
-# measured the opposite, 3.08 vs 2.94 ms, with the library's split-K GEMM in that place: it wanted the same CUs and the same L2 as the
-# gather; the limb kernel is one 147 KB-LDS workgroup per CU that leaves registers and the L2 path to the gather's waves).
-# With the exact-fp32 routes (RELGNN_GEMM=lib / panel) the default is off: 2.45 vs 2.22 ms.
-_SIDE_STREAMS = {}
-
-
-# The join of the side stream (main stream waits for the weight gradient) normally sits at the end of the layer's backward: whatever
-# reads the gradient next finds it complete.  A training step that owns the whole backward can do better: nothing reads a weight
-# gradient before the optimizer, and next to the gather the side stream's workgroups starve (the gather's 27 k four-wave workgroups
-# hold every wave slot and register), so its kernels really start at the gather's tail and finish AFTER the input-gradient product
-# — the main stream then idled at every layer's join.  deferred_weight_gradient_join() (models/sparse_graph_model.py: train_step)
-# moves the joins to join_deferred(), called once behind the backward.
-_DEFER = {"on": False, "pending": [], "targets": set(), "handed": []}
-
-
-class deferred_weight_gradient_join:
-    def __enter__(self):
-        self._old = _DEFER["on"]
-        _DEFER["on"] = True
-        return self
-
-    def __exit__(self, exc_type, exc, tb):
-        _DEFER["on"] = self._old
-        if exc_type is not None:
-            # the backward raised (out of memory, a check inside a Function): nobody will call join_deferred() for this pass.  Wait
-            # for the side streams and forget the pass — stale `handed` entries would hold the parameters alive and make the NEXT
-            # step's join verify gradients that belong to this one
-            pending, _DEFER["pending"] = _DEFER["pending"], []
-            _DEFER["handed"] = []
-            _DEFER["targets"].clear()
-            for device, side in pending:
-                try:
-                    torch.cuda.current_stream(device).wait_stream(side)
-                except Exception:
-                    pass
-        return False
-
-
-def _accumulator_keeps_the_tensor(p) -> bool:
-    """Will autograd's AccumulateGrad take the gradient tensor of leaf `p` as it is, launching nothing on the main stream?  It
-    copies (reads the tensor at once) when a tensor hook sits on the parameter (the gradient passes through Python and gains a
-    reference), when the layouts differ, and under create_graph (grad mode on inside the backward); anomaly mode inspects every
-    gradient; a post-accumulate hook reads p.grad right behind the accumulation."""
-    return (p.is_leaf and p.requires_grad and p.grad is None and p.is_contiguous()
-            and not getattr(p, "_backward_hooks", None) and not getattr(p, "_post_accumulate_grad_hooks", None))
-
-
-def deferred_targets_ok(params, device) -> bool:
-    """May a weight gradient be left in flight on the side stream until join_deferred()?  Only if nothing on the main stream reads
-    it before: every target must be a LEAF that has no gradient yet and has not been a target in this backward pass — autograd's
-    accumulator then keeps the tensor itself and launches nothing (_accumulator_keeps_the_tensor lists what else makes it copy;
-    join_deferred() verifies afterwards that it did keep it).  A parameter used twice in the graph (the timesteps of a GGNN
-    layer share their weights) has its contributions SUMMED on the main stream (in the engine's input buffer, or `grad += new`),
-    which would read tensors that are still being written: on the second sight of a parameter the main stream is made to wait for
-    the side stream here and the caller computes on one stream."""
-    seen = _DEFER["targets"]
-    if (params is not None and not torch.is_grad_enabled() and not torch.is_anomaly_enabled()
-            and all(_accumulator_keeps_the_tensor(p) and id(p) not in seen for p in params)):
-        seen.update(id(p) for p in params)
-        return True
-    wait_if_in_flight(params, device)
-    return False
-
-
-def wait_if_in_flight(params, device) -> None:
-    """A contribution to `params` is about to be produced on the main stream.  If an earlier one of this backward went aside,
-    autograd will sum the two on the main stream: it waits for the side stream first.  The parameters are marked as seen either
-    way — a LATER contribution must not go aside either (the engine would add it, still in flight, to the one buffered here).
-    Called on every sight of a parameter that does not go aside itself, whatever else the caller computes.  (A view's or a
-    non-leaf's gradient never goes aside and is consumed by the view's backward at once: params is None for those.)"""
-    if params is None:
-        return
-    seen = _DEFER["targets"]
-    if any(id(p) in seen for p in params):
-        side = _SIDE_STREAMS.get(device)
-        if side is not None:
-            torch.cuda.current_stream(device).wait_stream(side)
-        # their first contributions are complete as far as the main stream is concerned from here on: summing into them is safe and
-        # join_deferred() has nothing left to verify for these parameters
-        mine = {id(p) for p in params}
-        _DEFER["handed"] = [h for h in _DEFER["handed"] if id(h[0]) not in mine]
-    if _DEFER["on"]:
-        seen.update(id(p) for p in params)
-
-
-def hand_over_deferred(device, side, params, grads) -> None:
-    """Record that `grads` (in flight on `side`) are being returned to autograd as the gradients of the leaves `params`."""
-    _DEFER["pending"].append((device, side))
-    for p, g in zip(params, grads):
-        if g is not None:
-            _DEFER["handed"].append((p, g.data_ptr(), g._version))
-
-
-def join_deferred() -> None:
-    """Make the current stream wait for every side stream whose join was deferred (no host synchronisation), then check that
-    autograd did what the deferral relies on: every parameter's .grad IS the tensor that was handed over (same storage, never
-    written in place since).  Anything else means the main stream read or wrote a gradient that was still being produced — raised
-    here rather than left as a silently wrong update."""
-    pending, _DEFER["pending"] = _DEFER["pending"], []
-    handed, _DEFER["handed"] = _DEFER["handed"], []
-    _DEFER["targets"].clear()
-    done = set()
-    for device, side in pending:
-        if id(side) not in done:
-            torch.cuda.current_stream(device).wait_stream(side)
-            done.add(id(side))
-    for p, ptr, version in handed:
-        g = p.grad
-        if g is None or g.data_ptr() != ptr or g._version != version:
-            raise RuntimeError(
-                "deferred weight-gradient join: the gradient of a %s parameter was %s on the main stream while its producer was "
-                "still in flight on the side stream (a second use of the parameter outside this package's layers, a hook, or a "
-                "copying accumulator); run the backward without ops.deferred_weight_gradient_join() or set bwd_overlap=0"
-                % (tuple(p.shape), "dropped" if g is None else "copied" if g.data_ptr() != ptr else "accumulated into in place"))
-
-
-def _side_stream(device):
-    st = _SIDE_STREAMS.get(device)
-    if st is None:
-        # (a high-priority queue changes nothing here: measured 1.810 / 1.813 ms on C2, 32.5 / 33.0 ms on C5 — the side stream's
-        #  large workgroups still become resident only where the main stream's small ones leave room)
-        st = _SIDE_STREAMS[device] = torch.cuda.Stream(device=device)
-    return st
-
-
 def _weight_gradient(agg, gsc, amax, L: int):
     """agg^T @ gsc (agg [V, L*Din]: the bucket sums, gsc [V, Dout]).  On the two-fp16-limb route (RELGNN_LIMB=pair: `amax`, the
     forward gather's per-bucket magnitudes [V*L], says the layer took it) the operands go behind exact power-of-two scales that
@@ -1346,23 +1180,21 @@ class _AggregateThenTransform(torch.autograd.Function):
         gout = gout.contiguous()
         if act != _lib.ACT_LINEAR and not premasked:
             gout = act_bwd_from_output(act, out, gout)
-        gH = gW = None
-        want_w = any(ctx.needs_input_grad[7:])
+        need = ctx.needs_input_grad[7:]
+        want_w = any(need)
+
+        def weight_side():
+            f = _mode_factor(graph, mode)               # agg holds the raw sums: the factor multiplies dOut
+            gsc = gout if f is None else gout * f.unsqueeze(1)
+            gW = _weight_gradient(agg, gsc, amax, L)    # dW_l = A_l^T @ dOut: row block l of [L*Din, Dout]
+            return tuple(gW[l * d_in:(l + 1) * d_in] if need[l] else None for l in range(L))
+
         # The weight gradient (matrix-pipe bound, one workgroup per CU, 147 KB of LDS, no L2 pressure) does not depend on the input
         # gradient's gather (L2-latency bound, no LDS, few registers): it runs on a side stream next to it (fork / join by events,
         # capturable in a hipGraph; the result is the same bits, the kernels are the same).
-        side = None
-        if (want_w and ctx.needs_input_grad[0] and _cfg.bwd_overlap_on and gout.is_cuda
-                and (not _DEFER["on"] or deferred_targets_ok(ctx.leaf_params, gout.device))):
-            side = _side_stream(gout.device)
-            cur = torch.cuda.current_stream(gout.device)
-            side.wait_stream(cur)
-            with torch.cuda.stream(side):
-                f = _mode_factor(graph, mode)
-                gsc = gout if f is None else gout * f.unsqueeze(1)
-                gW = _weight_gradient(agg, gsc, amax, L)
-            for t in (agg, gout, gsc) + ((amax,) if amax is not None else ()):
-                t.record_stream(side)
+        aside = fork(weight_side, (gout, agg) + ((amax,) if amax is not None else ()), ctx.leaf_params,
+                     want=want_w and ctx.needs_input_grad[0], join_in_backward=True, contributes=want_w)
+        gH = None
         if ctx.needs_input_grad[0]:
             plan = graph.plan_transformed(w)            # by-source buckets; weights carry the mean / sqrt_n factor
             gmax = None
@@ -1375,19 +1207,7 @@ class _AggregateThenTransform(torch.autograd.Function):
                 gH = mark_premasked(grouped_nt_gemm(gT, kernels, xmax=gmax, xgroups=L, premask=(ctx.h_act, H_in)), H_in, ctx.h_act)
             else:
                 gH = grouped_nt_gemm(gT, kernels, xmax=gmax, xgroups=L)
-        if side is not None:
-            if not _DEFER["on"]:
-                torch.cuda.current_stream(gout.device).wait_stream(side)
-            gW.record_stream(torch.cuda.current_stream(gout.device))
-        elif want_w:
-            wait_if_in_flight(ctx.leaf_params, gout.device)     # (no-op unless an earlier use of these kernels went aside)
-            f = _mode_factor(graph, mode)               # agg holds the raw sums: the factor multiplies dOut
-            gsc = gout if f is None else gout * f.unsqueeze(1)
-            gW = _weight_gradient(agg, gsc, amax, L)
-        gWs = tuple(gW[l * d_in:(l + 1) * d_in] if ctx.needs_input_grad[7 + l] else None for l in range(L)) \
-            if gW is not None else (None,) * L           # dW_l = A_l^T @ dOut: row block l of [L*Din, Dout]
-        if side is not None and _DEFER["on"]:
-            hand_over_deferred(gout.device, side, kernels, gWs)
+        gWs = aside.join() if aside is not None else (weight_side() if want_w else (None,) * L)
         return (gH, None, None, None, None, None, None) + gWs
 
 

@@ -18,6 +18,7 @@ import torch
 
 from . import ops
 from .dense import dense, dense_relu
+from .weight_grad_stream import fork
 
 BIG_NUMBER = 1e7
 SMALL_NUMBER = 1e-7
@@ -194,7 +195,7 @@ class _GRUCellFn(torch.autograd.Function):
     Same kernels and the same arithmetic as the composition of dense() / _FusedGRU it replaces (round 6); what goes away is what
     autograd wrapped around the two column views of the recurrent kernel — per cell and step two zero-fills, two copies and an add
     for the views' gradients, a copy of U[:, 2u:] — because the recurrent kernel's gradient is written block by block into ONE
-    [u, 3u] tensor (dense.tn_stream_into).  The weight gradients go to the side stream like a Dense layer's (dense._on_side_stream)."""
+    [u, 3u] tensor (dense.tn_stream_into).  The weight gradients go to the side stream like a Dense layer's (weight_grad_stream.fork)."""
 
     @staticmethod
     def forward(ctx, x, h, K, U, b, act: int):
@@ -241,7 +242,7 @@ class _GRUCellFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, gout):
         from . import _lib
-        from .dense import GEMM_NT, _on_side_stream, column_sum, lib_gemm, matmul_tn_splitk, tn_stream_into
+        from .dense import GEMM_NT, column_sum, lib_gemm, matmul_tn_splitk, tn_stream_into
         lib = _lib.load_library()
         st = _lib.current_stream()
         x, h, K, U, z, r, rh, hh = ctx.saved_tensors
@@ -292,15 +293,15 @@ class _GRUCellFn(torch.autograd.Function):
             gb = column_sum(gxk) if ctx.needs_input_grad[4] else None
             return gK, gU, gb
 
-        aside = _on_side_stream(weight_side, (x, h, rh, gxk, gq), ctx.leaf_params,
-                                want=(ctx.needs_input_grad[0] or ctx.needs_input_grad[1]) and any(ctx.needs_input_grad[2:5]))
+        aside = fork(weight_side, (x, h, rh, gxk, gq), ctx.leaf_params, join_in_backward=False, contributes=x.is_cuda,
+                     want=(ctx.needs_input_grad[0] or ctx.needs_input_grad[1]) and any(ctx.needs_input_grad[2:5]))
         if not fused:
             gx = lib_gemm(GEMM_NT, gxk, K, weight=True) if ctx.needs_input_grad[0] else None
             if ctx.needs_input_grad[1]:
                 gh = gh.add_(lib_gemm(GEMM_NT, grec, U[:, :2 * u], weight=True))
             else:
                 gh = None
-        gK, gU, gb = aside if aside is not None else weight_side()
+        gK, gU, gb = aside.join() if aside is not None else weight_side()
         return gx, gh, gK, gU, gb, None
 
 
