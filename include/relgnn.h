@@ -505,6 +505,22 @@ int relgnn_adam_step_size(float* d_state, float lr, float beta1, float beta2, vo
 int relgnn_mt_adam_clip_devlr(float* const* h_params, const float* const* h_grads, float* const* h_m,
                               float* const* h_v, const int64_t* h_sizes, int32_t n, const float* norms,
                               float clip, const float* d_lr_t, float beta1, float beta2, float eps, void* stream);
+/*
+ * The other two optimizers of :239-249 with the same clip and the same conventions (tf.train.RMSPropOptimizer, not centered, and
+ * tf.train.GradientDescentOptimizer) [TF-internal update rules, in the operation order of ApplyRMSProp / ApplyGradientDescent]:
+ *   g' = g * (clip / max(||g||_2, clip))           (exactly g where nothing is clipped, an all-zero gradient included)
+ *   RMSProp:  ms += (g'*g' - ms) * (1 - decay);  mom = mom*momentum + lr*g'/sqrt(ms + eps);  p -= mom
+ *             (1 - decay is formed in float32; a zero gradient still decays ms and mom and moves p by mom)
+ *   SGD:      p -= lr*g'
+ * Every product and sum is rounded on its own: an element's new bits depend on its own (p, g, ms, mom) and the scalars only,
+ * not on its position in the tensor or on the tensor's alignment (16-byte accesses are used where all pointers of a tensor
+ * allow them).  lr is a launch scalar: these rules have no step-dependent factor, so a captured step needs no device state.
+ */
+int relgnn_mt_rmsprop_clip(float* const* h_params, const float* const* h_grads, float* const* h_ms,
+                           float* const* h_mom, const int64_t* h_sizes, int32_t n, const float* norms,
+                           float clip, float lr, float decay, float momentum, float eps, void* stream);
+int relgnn_mt_sgd_clip(float* const* h_params, const float* const* h_grads, const int64_t* h_sizes, int32_t n,
+                       const float* norms, float clip, float lr, void* stream);
 
 /*
  * PPI output head in one pass (tasks/ppi_task.py:181-191 + utils/utils.py:61-74):

@@ -69,6 +69,8 @@ _SIGNATURES = {
     "relgnn_mt_adam_clip": (ctypes.c_int, [_ptr, _ptr, _ptr, _ptr, _ptr, _c_i32, _ptr, _c_f32, _c_f32, _c_f32, _c_f32, _c_f32, _ptr]),
     "relgnn_adam_step_size": (ctypes.c_int, [_ptr, _c_f32, _c_f32, _c_f32, _ptr]),
     "relgnn_mt_adam_clip_devlr": (ctypes.c_int, [_ptr, _ptr, _ptr, _ptr, _ptr, _c_i32, _ptr, _c_f32, _ptr, _c_f32, _c_f32, _c_f32, _ptr]),
+    "relgnn_mt_rmsprop_clip": (ctypes.c_int, [_ptr, _ptr, _ptr, _ptr, _ptr, _c_i32, _ptr, _c_f32, _c_f32, _c_f32, _c_f32, _c_f32, _ptr]),
+    "relgnn_mt_sgd_clip": (ctypes.c_int, [_ptr, _ptr, _ptr, _c_i32, _ptr, _c_f32, _c_f32, _ptr]),
     "relgnn_sigmoid_ce_stats_workspace_bytes": (ctypes.c_size_t, []),
     "relgnn_sigmoid_ce_stats": (ctypes.c_int, [_ptr, _ptr, _c_i64, _c_f32, _ptr, _ptr, ctypes.c_size_t, _ptr]),
     "relgnn_sigmoid_ce_bwd": (ctypes.c_int, [_ptr, _ptr, _c_i64, _ptr, _c_f32, _ptr, _ptr, _ptr]),

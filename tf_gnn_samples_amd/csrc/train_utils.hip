@@ -1,6 +1,6 @@
 // Training-step plumbing AROUND the hot path, fused so that the step is not
 // launch-bound once the gather/segment kernels and GEMMs are fast:
-//   * multi-tensor per-variable clip_by_norm + TF-style Adam   models/sparse_graph_model.py:227-260
+//   * multi-tensor per-variable clip_by_norm + TF-style Adam, RMSProp, SGD   models/sparse_graph_model.py:227-260
 //   * PPI output head loss + micro-F1 counts in one pass        tasks/ppi_task.py:181-191, utils/utils.py:61-74
 //   * citation head: masked softmax cross-entropy + accuracy     tasks/citation_network_task.py:133-148
 // Deterministic (no float atomics): fixed-shape tree reductions only.
@@ -105,6 +105,106 @@ __global__ __launch_bounds__(256) void mt_adam_clip_kernel(MtArgs a, const float
     m[i] = mi;
     v[i] = vi;
     p[i] = p[i] - lr_t * mi / (sqrtf(vi) + eps);
+  }
+}
+
+// ---- RMSProp and SGD: the same grid (chunks of 4096 elements, tensors) and the same clip scale as the Adam kernel ------------
+struct SgdArgs {
+  float* p[RELGNN_MT_MAX];
+  const float* g[RELGNN_MT_MAX];
+  long long n[RELGNN_MT_MAX];
+};
+
+// g' = g * scale, then TF1 ApplyRMSProp in the operation order of oracle/optim.py:
+//   ms += (g'*g' - ms) * (1 - decay);  mom = mom*momentum + lr*g'/sqrt(ms + eps);  p -= mom
+// THE element rule: every product and sum is rounded on its own (no contraction, whatever the compile flags say), so an element's
+// new bits depend on its own (p, g, ms, mom) and the scalars only — not on its position, the tensor's length, or which loop ran it.
+__device__ __forceinline__ void rmsprop_element(float& p, float g, float& ms, float& mom, float scale, float lr,
+                                                float one_minus_decay, float momentum, float eps) {
+#pragma clang fp contract(off)
+  const float gi = g * scale;
+  const float d = gi * gi - ms;
+  ms = ms + d * one_minus_decay;
+  const float num = lr * gi;
+  mom = mom * momentum + num / sqrtf(ms + eps);
+  p = p - mom;
+}
+
+// g' = g * scale, then ApplyGradientDescent: p -= lr*g'
+__device__ __forceinline__ void sgd_element(float& p, float g, float scale, float lr) {
+#pragma clang fp contract(off)
+  const float gi = g * scale;
+  p = p - lr * gi;
+}
+
+__device__ __forceinline__ float clip_scale(const float* __restrict__ norms, int t, float clip) {
+  return clip > 0.f ? clip / fmaxf(norms[t], clip) : 1.f;      // exactly 1 where nothing is clipped (norm 0 included)
+}
+
+__device__ __forceinline__ bool aligned16(const void* a, const void* b, const void* c = nullptr, const void* d = nullptr) {
+  return ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b) | reinterpret_cast<uintptr_t>(c) |
+           reinterpret_cast<uintptr_t>(d)) & 15) == 0;
+}
+
+__global__ __launch_bounds__(256) void mt_rmsprop_clip_kernel(MtArgs a, const float* __restrict__ norms, float clip, float lr,
+                                                              float decay, float momentum, float eps) {
+  const int t = blockIdx.y;
+  const long long n = a.n[t];
+  const long long beg = (long long)blockIdx.x * 4096;
+  if (beg >= n) return;
+  const int len = (int)min(n - beg, 4096LL);
+  const float scale = clip_scale(norms, t, clip);
+  const float omd = 1.f - decay;
+  float* p = a.p[t] + beg;                 // (m, v of MtArgs: the mean-square and the momentum slot)
+  const float* g = a.g[t] + beg;
+  float* ms = a.m[t] + beg;
+  float* mom = a.v[t] + beg;
+  // 16-byte loads and stores over the body when all four tensors allow them (beg is a multiple of 4096 elements: the bases decide;
+  // a parameter may be a view that starts at a 4-byte offset), scalar code otherwise and for the tail
+  const int n4 = aligned16(p, g, ms, mom) ? len / 4 : 0;
+  for (int i = threadIdx.x; i < n4; i += blockDim.x) {
+    float4 pv = reinterpret_cast<float4*>(p)[i], sv = reinterpret_cast<float4*>(ms)[i], mv = reinterpret_cast<float4*>(mom)[i];
+    const float4 gv = reinterpret_cast<const float4*>(g)[i];
+    rmsprop_element(pv.x, gv.x, sv.x, mv.x, scale, lr, omd, momentum, eps);
+    rmsprop_element(pv.y, gv.y, sv.y, mv.y, scale, lr, omd, momentum, eps);
+    rmsprop_element(pv.z, gv.z, sv.z, mv.z, scale, lr, omd, momentum, eps);
+    rmsprop_element(pv.w, gv.w, sv.w, mv.w, scale, lr, omd, momentum, eps);
+    reinterpret_cast<float4*>(ms)[i] = sv;
+    reinterpret_cast<float4*>(mom)[i] = mv;
+    reinterpret_cast<float4*>(p)[i] = pv;
+  }
+  for (int i = 4 * n4 + threadIdx.x; i < len; i += blockDim.x) {
+    float pi = p[i], si = ms[i], mi = mom[i];
+    rmsprop_element(pi, g[i], si, mi, scale, lr, omd, momentum, eps);
+    ms[i] = si;
+    mom[i] = mi;
+    p[i] = pi;
+  }
+}
+
+__global__ __launch_bounds__(256) void mt_sgd_clip_kernel(SgdArgs a, const float* __restrict__ norms, float clip, float lr) {
+  const int t = blockIdx.y;
+  const long long n = a.n[t];
+  const long long beg = (long long)blockIdx.x * 4096;
+  if (beg >= n) return;
+  const int len = (int)min(n - beg, 4096LL);
+  const float scale = clip_scale(norms, t, clip);
+  float* p = a.p[t] + beg;
+  const float* g = a.g[t] + beg;
+  const int n4 = aligned16(p, g) ? len / 4 : 0;
+  for (int i = threadIdx.x; i < n4; i += blockDim.x) {
+    float4 pv = reinterpret_cast<float4*>(p)[i];
+    const float4 gv = reinterpret_cast<const float4*>(g)[i];
+    sgd_element(pv.x, gv.x, scale, lr);
+    sgd_element(pv.y, gv.y, scale, lr);
+    sgd_element(pv.z, gv.z, scale, lr);
+    sgd_element(pv.w, gv.w, scale, lr);
+    reinterpret_cast<float4*>(p)[i] = pv;
+  }
+  for (int i = 4 * n4 + threadIdx.x; i < len; i += blockDim.x) {
+    float pi = p[i];
+    sgd_element(pi, g[i], scale, lr);
+    p[i] = pi;
   }
 }
 
@@ -439,6 +539,43 @@ static int mt_adam_clip_impl(float* const* h_params, const float* const* h_grads
   if (maxn == 0) return RELGNN_OK;
   dim3 grid((unsigned)((maxn + 4095) / 4096), (unsigned)n);
   mt_adam_clip_kernel<<<grid, 256, 0, as_stream(stream)>>>(a, norms, clip, lr_t, d_lr_t, beta1, beta2, eps);
+  return launch_status();
+}
+
+int relgnn_mt_rmsprop_clip(float* const* h_params, const float* const* h_grads, float* const* h_ms, float* const* h_mom,
+                           const int64_t* h_sizes, int32_t n, const float* norms, float clip, float lr, float decay,
+                           float momentum, float eps, void* stream) {
+  if (n < 0 || n > RELGNN_MT_MAX) return RELGNN_EINVAL;
+  if (n == 0) return RELGNN_OK;
+  if (!h_params || !h_grads || !h_ms || !h_mom || !h_sizes || (clip > 0.f && !norms)) return RELGNN_EINVAL;
+  MtArgs a;
+  long long maxn = 0;
+  for (int i = 0; i < n; ++i) {
+    if (h_sizes[i] < 0 || (h_sizes[i] > 0 && (!h_params[i] || !h_grads[i] || !h_ms[i] || !h_mom[i]))) return RELGNN_EINVAL;
+    a.p[i] = h_params[i]; a.g[i] = h_grads[i]; a.m[i] = h_ms[i]; a.v[i] = h_mom[i]; a.n[i] = h_sizes[i];
+    if (h_sizes[i] > maxn) maxn = h_sizes[i];
+  }
+  if (maxn == 0) return RELGNN_OK;
+  dim3 grid((unsigned)((maxn + 4095) / 4096), (unsigned)n);
+  mt_rmsprop_clip_kernel<<<grid, 256, 0, as_stream(stream)>>>(a, norms, clip, lr, decay, momentum, eps);
+  return launch_status();
+}
+
+int relgnn_mt_sgd_clip(float* const* h_params, const float* const* h_grads, const int64_t* h_sizes, int32_t n,
+                       const float* norms, float clip, float lr, void* stream) {
+  if (n < 0 || n > RELGNN_MT_MAX) return RELGNN_EINVAL;
+  if (n == 0) return RELGNN_OK;
+  if (!h_params || !h_grads || !h_sizes || (clip > 0.f && !norms)) return RELGNN_EINVAL;
+  SgdArgs a;
+  long long maxn = 0;
+  for (int i = 0; i < n; ++i) {
+    if (h_sizes[i] < 0 || (h_sizes[i] > 0 && (!h_params[i] || !h_grads[i]))) return RELGNN_EINVAL;
+    a.p[i] = h_params[i]; a.g[i] = h_grads[i]; a.n[i] = h_sizes[i];
+    if (h_sizes[i] > maxn) maxn = h_sizes[i];
+  }
+  if (maxn == 0) return RELGNN_OK;
+  dim3 grid((unsigned)((maxn + 4095) / 4096), (unsigned)n);
+  mt_sgd_clip_kernel<<<grid, 256, 0, as_stream(stream)>>>(a, norms, clip, lr);
   return launch_status();
 }
 

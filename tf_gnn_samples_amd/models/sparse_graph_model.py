@@ -49,18 +49,20 @@ class TFStyleOptimizer:
             self.ms = [torch.ones_like(p) for p in self.params]
             self.mom = [torch.zeros_like(p) for p in self.params]
 
-    def _fused_adam_available(self):
-        return self.name == 'adam' and len(self.params) > 0 and all(p.is_cuda for p in self.params)
+    def _fused_update_available(self):
+        return len(self.params) > 0 and all(p.is_cuda for p in self.params)
 
     @torch.no_grad()
     def clip_and_step(self, lr_scale: float = 1.0, device_step_count: bool = False):
-        """clip_by_norm per variable + update.  Adam on the GPU: two fused multi-tensor HIP launches
-        (relgnn_mt_l2norm, relgnn_mt_adam_clip) instead of ~30 elementwise kernels.
-        device_step_count=True (hipGraph capture): the step count and lr_t live in device memory
-        (relgnn_adam_step_size / relgnn_mt_adam_clip_devlr); the caller keeps self.t in step."""
-        if not self._fused_adam_available():
+        """clip_by_norm per variable + update.  On the GPU, for all three optimizers: two fused multi-tensor HIP launches per
+        48 variables (relgnn_mt_l2norm, then relgnn_mt_adam_clip / relgnn_mt_rmsprop_clip / relgnn_mt_sgd_clip) instead of the
+        ~15-30 elementwise kernels of clip_gradients() + step(), which stay as the un-fused restatement (and the CPU path).
+        device_step_count=True (hipGraph capture): the caller keeps self.t in step.  Adam's step count and lr_t then live in
+        device memory (relgnn_adam_step_size / relgnn_mt_adam_clip_devlr); RMSProp and SGD have no step-dependent factor:
+        their lr = self.lr * lr_scale is a launch scalar, frozen into a captured graph."""
+        if not self._fused_update_available():
             if device_step_count:
-                raise RuntimeError("a captured training step needs the fused device-side Adam update")
+                raise RuntimeError("a captured training step needs the fused update: every parameter on the GPU")
             self.clip_gradients()
             self.step(lr_scale)
             return
@@ -72,13 +74,14 @@ class TFStyleOptimizer:
         if not idx:
             return
         b1, b2, eps = 0.9, 0.999, 1e-8
+        lr = self.lr * lr_scale
         dev_state = None
-        if device_step_count:
+        if device_step_count and self.name == 'adam':
             dev_state = self._device_state()
-            _lib.check(lib.relgnn_adam_step_size(_lib.ptr(dev_state), self.lr * lr_scale, b1, b2, st), "relgnn_adam_step_size")
-        else:
+            _lib.check(lib.relgnn_adam_step_size(_lib.ptr(dev_state), lr, b1, b2, st), "relgnn_adam_step_size")
+        elif not device_step_count:
             self.t += 1
-            lr_t = self.lr * lr_scale * (1 - b2 ** self.t) ** 0.5 / (1 - b1 ** self.t)
+            lr_t = lr * (1 - b2 ** self.t) ** 0.5 / (1 - b1 ** self.t)
         for c0 in range(0, len(idx), _lib.MT_MAX):
             chunk = idx[c0:c0 + _lib.MT_MAX]
             n = len(chunk)
@@ -87,19 +90,24 @@ class TFStyleOptimizer:
             arr = ctypes.c_void_p * n
             h_g = arr(*[g.data_ptr() for g in grads])
             h_p = arr(*[self.params[i].data_ptr() for i in chunk])
-            h_m = arr(*[self.m[i].data_ptr() for i in chunk])
-            h_v = arr(*[self.v[i].data_ptr() for i in chunk])
             h_n = (ctypes.c_int64 * n)(*[self.params[i].numel() for i in chunk])
             norms = torch.empty(n, dtype=torch.float32, device=self.params[chunk[0]].device)
             ws_bytes = lib.relgnn_mt_l2norm_workspace_bytes()
             ws = torch.empty(ws_bytes, dtype=torch.uint8, device=norms.device)
             _lib.check(lib.relgnn_mt_l2norm(h_g, h_n, n, _lib.ptr(norms), _lib.ptr(ws), ws_bytes, st), "relgnn_mt_l2norm")
-            if dev_state is not None:
-                _lib.check(lib.relgnn_mt_adam_clip_devlr(h_p, h_g, h_m, h_v, h_n, n, _lib.ptr(norms), float(self.clip),
-                                                         dev_state[1:].data_ptr(), b1, b2, eps, st), "relgnn_mt_adam_clip_devlr")
+            h_s = [arr(*[t[i].data_ptr() for i in chunk]) for _, t in self._slots()]      # Adam: m, v; RMSProp: ms, mom; SGD: none
+            d_norms, clip = _lib.ptr(norms), float(self.clip)
+            if self.name == 'sgd':
+                what, rc = "relgnn_mt_sgd_clip", lib.relgnn_mt_sgd_clip(h_p, h_g, h_n, n, d_norms, clip, lr, st)
+            elif self.name == 'rmsprop':
+                what, rc = "relgnn_mt_rmsprop_clip", lib.relgnn_mt_rmsprop_clip(
+                    h_p, h_g, *h_s, h_n, n, d_norms, clip, lr, float(self.decay), float(self.momentum), 1e-10, st)
+            elif dev_state is not None:
+                what, rc = "relgnn_mt_adam_clip_devlr", lib.relgnn_mt_adam_clip_devlr(
+                    h_p, h_g, *h_s, h_n, n, d_norms, clip, dev_state[1:].data_ptr(), b1, b2, eps, st)
             else:
-                _lib.check(lib.relgnn_mt_adam_clip(h_p, h_g, h_m, h_v, h_n, n, _lib.ptr(norms), float(self.clip), lr_t,
-                                                   b1, b2, eps, st), "relgnn_mt_adam_clip")
+                what, rc = "relgnn_mt_adam_clip", lib.relgnn_mt_adam_clip(h_p, h_g, *h_s, h_n, n, d_norms, clip, lr_t, b1, b2, eps, st)
+            _lib.check(rc, what)
         from ..dense import weights_changed
         weights_changed()                  # (written through raw pointers: the tensors' version counters did not move)
 
@@ -298,7 +306,9 @@ class MetricsReadback:
 
 
 class CapturedTrainStep:
-    """A training step recorded as a hipGraph on one fixed batch (Sparse_Graph_Model.capture_train_step)."""
+    """A training step recorded as a hipGraph on one fixed batch (Sparse_Graph_Model.capture_train_step), with any of the
+    three optimizers.  Adam's step count is device state that every replay advances; the learning rate of an RMSProp or SGD
+    step is a launch scalar of the recorded update."""
 
     def __init__(self, model, graph, metrics, batch):
         self.model, self.graph, self.metrics, self.batch = model, graph, metrics, batch
@@ -306,8 +316,9 @@ class CapturedTrainStep:
 
     def replay(self) -> Dict[str, torch.Tensor]:
         """One more training step: a single graph launch.  The returned tensors are overwritten by the next replay.
-        The graph reads the Adam step count from device memory; if the host count moved since the last replay (an eager
-        train_step(), load_weights()), the device copy is re-seeded first, so lr_t never comes from a stale count.
+        With Adam the graph reads the step count from device memory; if the host count moved since the last replay (an eager
+        train_step(), load_weights()), the device copy is re-seeded first, so lr_t never comes from a stale count.  RMSProp and
+        SGD keep no device state (the re-seeding is a no-op): their update does not depend on the step count.
         (lr_t of a replayed step is computed in float32 on the device, of an eager step in double on the host: the two
         agree to ~1e-7 relative, not bit for bit.)"""
         opt = self.model.optimizer
@@ -547,13 +558,16 @@ class Sparse_Graph_Model(ABC):
         return self.task.compute_task_metrics(final, batch, self.variables.scope(self._task_scope))
 
     def capture_train_step(self, batch: DeviceBatch, warmup_steps: int = 3):
-        """One full training step on a FIXED batch as a hipGraph (forward, backward, clip, Adam: ~150 launches replayed
-        with one host call).  For workloads whose step is host-enqueue bound (C3: 153 k messages per batch) and whose
-        batch shapes repeat.  Runs `warmup_steps` real steps first (allocator / plan caches), then captures; returns a
-        CapturedTrainStep whose replay() performs exactly one more step and returns the (static) metric tensors."""
+        """One full training step on a FIXED batch as a hipGraph (forward, backward, clip, update with Adam, RMSProp or SGD:
+        ~150 launches replayed with one host call).  For workloads whose step is host-enqueue bound (C3: 153 k messages per
+        batch) and whose batch shapes repeat.  Runs `warmup_steps` real steps first (allocator / plan caches), then captures;
+        returns a CapturedTrainStep whose replay() performs exactly one more step and returns the (static) metric tensors.
+        The learning rate of a captured RMSProp or SGD step is a launch scalar.  With lr_for_num_graphs_per_batch set it is
+        learning_rate * num_graphs / lr_for_num_graphs_per_batch of THIS batch: constant for the fixed batch, so freezing it
+        into the graph is correct (Adam's lr_t changes per step and is computed on the device instead)."""
         from ..graph import as_rel_graph as _as_graph
-        if self.device.type != "cuda" or self.optimizer.name != 'adam':
-            raise RuntimeError("capture_train_step needs a GPU model trained with Adam")
+        if self.device.type != "cuda":
+            raise RuntimeError("capture_train_step needs a model on the GPU (a hipGraph records GPU work)")
         batch.wait_ready()
         if getattr(batch, "graph", None) is None:           # the bucketing is part of the fixed batch, not of the step
             batch.graph = _as_graph(batch.adjacency_lists, batch.num_nodes, validate=True)
