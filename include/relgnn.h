@@ -44,6 +44,7 @@ extern "C" {
 
 /* bits OR-ed into *err_flag by device-side validation */
 #define RELGNN_ERRFLAG_INDEX_OUT_OF_RANGE 1u /* TF: InvalidArgumentError for gather / segment ids */
+#define RELGNN_ERRFLAG_NOT_SORTED 2u         /* a list that a kernel needs non-decreasing holds ids[v] < ids[v - 1] */
 
 /* ---- aggregation modes: utils/utils.py:23-33 (get_aggregation_function) -- */
 #define RELGNN_AGG_SUM 0    /* tf.unsorted_segment_sum                      */
@@ -631,6 +632,46 @@ int relgnn_varmisuse_head_bwd(const float* states, int64_t ld, int64_t num_nodes
                               const int32_t* cand_ids, const float* cand_mask, const int32_t* first_node, int64_t num_graphs,
                               int32_t num_candidates, const float* w, const float* g_loss, const float* g_total, float* d_states,
                               int64_t ldg, float* dw, void* workspace, size_t workspace_bytes, void* stream);
+
+/*
+ * QM9 readout head (tasks/qm9_task.py:163-197), all num_tasks regression tasks of a batch in one call.  For node v and task t:
+ * out = x_v . w_reg[t] + b_reg[t], gate = sigmoid([x_v | a_v] . w_gate[t] + b_gate[t]) with x_v the row of states
+ * [num_nodes, hidden] (row stride ld, a multiple of 4; 16-byte aligned) and a_v the row of features [num_nodes, annotation_size]
+ * (row stride ldf); the [V, hidden + annotation_size] concatenation is never built and every state row is read once for all tasks.
+ * y[t, g] = sum of gate * out over the nodes of graph g (tf.unsorted_segment_sum: an empty graph gives 0), e = y - targets.
+ *   w_reg / b_reg / w_gate / b_gate: HOST arrays of num_tasks DEVICE pointers (w_reg[t] [hidden], w_gate[t] [hidden +
+ *   annotation_size], both 16-byte aligned; the biases [1]).  They are passed on to the kernels by value: nothing is stacked or
+ *   uploaded, the call can be captured into a hipGraph.
+ *   graph_nodes_list int32 [num_nodes] must be non-decreasing; each graph's node range is found by binary search, one wave per graph.
+ *   Every probe of the search lies inside the list, so ANY contents are memory-safe.  Independently of the search every adjacent
+ *   pair is checked: an id outside [0, num_graphs) ORs RELGNN_ERRFLAG_INDEX_OUT_OF_RANGE, ids[v] < ids[v - 1] ORs
+ *   RELGNN_ERRFLAG_NOT_SORTED into *err_flag (nullable).  A node outside the range found for its id counts for nothing, in both
+ *   directions.
+ *   fwd : y [num_tasks, G]; node_range int32 [G, 2] = first node and one past the last node of every graph (for the backward);
+ *         stats [num_tasks + 2] = [abs_err[t] = sum_g |e|, ..., loss = sum_t mean_g 0.5 e^2, total_loss = loss * G], the per-graph
+ *         terms added in a fixed order in double.  No workspace.
+ *   bwd : g_loss / g_total = device scalars with the incoming gradients of loss / total_loss (either may be NULL, not both); out and
+ *         gate are computed again, nothing of size [V, hidden] is kept.  d_states [num_nodes, hidden] (row stride ldg): every row is
+ *         written (zeros for a node that counts for nothing), no zero-fill pass.  d_features [num_nodes, annotation_size] or NULL.
+ *         d_w_reg / d_b_reg / d_w_gate / d_b_gate: host arrays of num_tasks device pointers, one buffer per variable; workgroup b
+ *         owns the nodes [256 b, 256 b + 256) and adds its share in node order in double, the shares are added in workgroup order.
+ * No float atomics; the same graph gives the same bits at any place of the batch, the same task at any place of the list.
+ * Supported (relgnn_qm9_head_supported): num_tasks 1 .. 16, hidden a multiple of 4 up to 512, annotation_size 1 .. 64; anything
+ * else RELGNN_EUNSUPPORTED.  num_graphs >= 1.
+ * workspace: relgnn_qm9_head_workspace_bytes(num_nodes, num_tasks, hidden, annotation_size), for the backward.
+ */
+int relgnn_qm9_head_supported(int32_t num_tasks, int32_t hidden, int32_t annotation_size);
+size_t relgnn_qm9_head_workspace_bytes(int64_t num_nodes, int32_t num_tasks, int32_t hidden, int32_t annotation_size);
+int relgnn_qm9_head_fwd(const float* states, int64_t ld, const float* features, int64_t ldf, const int32_t* graph_nodes_list,
+                        int64_t num_nodes, int64_t num_graphs, int32_t hidden, int32_t annotation_size, int32_t num_tasks,
+                        const float* const* w_reg, const float* const* b_reg, const float* const* w_gate, const float* const* b_gate,
+                        const float* targets, float* y, int32_t* node_range, float* stats, uint32_t* err_flag, void* stream);
+int relgnn_qm9_head_bwd(const float* states, int64_t ld, const float* features, int64_t ldf, const int32_t* graph_nodes_list,
+                        int64_t num_nodes, int64_t num_graphs, int32_t hidden, int32_t annotation_size, int32_t num_tasks,
+                        const float* const* w_reg, const float* const* b_reg, const float* const* w_gate, const float* const* b_gate,
+                        const float* targets, const float* y, const int32_t* node_range, const float* g_loss, const float* g_total,
+                        float* d_states, int64_t ldg, float* d_features, float* const* d_w_reg, float* const* d_b_reg,
+                        float* const* d_w_gate, float* const* d_b_gate, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ========================================================================== *
  * 8. GRU cell elementwise halves (node-side; gnns/ggnn.py:92 via utils/utils.py:15-16)

@@ -15,6 +15,7 @@ LIB_PATH = _PKG_DIR / "librelgnn.so"
 
 OK, EINVAL, ENOSPC, EHIP, EUNSUPPORTED = 0, 1, 2, 3, 4
 ERRFLAG_INDEX_OUT_OF_RANGE = 1
+ERRFLAG_NOT_SORTED = 2
 
 AGG_SUM, AGG_MEAN, AGG_SQRT_N, AGG_MAX = 0, 1, 2, 3
 MT_MAX = 48
@@ -92,6 +93,13 @@ _SIGNATURES = {
                                                  ctypes.c_size_t, _ptr, _ptr]),
     "relgnn_varmisuse_head_bwd": (ctypes.c_int, [_ptr, _c_i64, _c_i64, _c_i32, _ptr, _ptr, _ptr, _ptr, _c_i64, _c_i32, _ptr, _ptr, _ptr, _ptr,
                                                  _c_i64, _ptr, _ptr, ctypes.c_size_t, _ptr]),
+    "relgnn_qm9_head_supported": (ctypes.c_int, [_c_i32, _c_i32, _c_i32]),
+    "relgnn_qm9_head_workspace_bytes": (ctypes.c_size_t, [_c_i64, _c_i32, _c_i32, _c_i32]),
+    "relgnn_qm9_head_fwd": (ctypes.c_int, [_ptr, _c_i64, _ptr, _c_i64, _ptr, _c_i64, _c_i64, _c_i32, _c_i32, _c_i32, _ptr, _ptr, _ptr, _ptr,
+                                           _ptr, _ptr, _ptr, _ptr, _ptr, _ptr]),
+    "relgnn_qm9_head_bwd": (ctypes.c_int, [_ptr, _c_i64, _ptr, _c_i64, _ptr, _c_i64, _c_i64, _c_i32, _c_i32, _c_i32, _ptr, _ptr, _ptr, _ptr,
+                                           _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _c_i64, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, ctypes.c_size_t,
+                                           _ptr]),
     "relgnn_gru_gates_fwd": (ctypes.c_int, [_ptr, _ptr, _ptr, _c_i64, _c_i32, _ptr, _ptr, _ptr, _ptr]),
     "relgnn_gru_cell_fwd_supported": (ctypes.c_int, [_c_i32, _c_i32, _c_i32]),
     "relgnn_gru_cell_fwd_xf32": (ctypes.c_int, [_ptr, _c_i64, _ptr, _c_i64, _ptr, _ptr, _ptr, _c_i32, _ptr, _ptr, _ptr, _ptr, _ptr,

@@ -77,6 +77,11 @@ _SPEC: Dict[str, Tuple[str, str, Tuple[str, ...], str]] = {
                  "tensor written by the gather kernel, read by one product per edge type and kept for the backward | gather, "
                  "activation and the per-type product in ONE kernel (csrc/edge_mlp_fused.hip: exact-split arithmetic on the cached "
                  "weight images, D = 128 and 256; needs gemm=limb); the hidden tensor is recomputed in the backward"),
+    "qm9_head": ("RELGNN_QM9_HEAD", "compose", ("compose", "fused"),
+                 "QM9 readout head: the reference's op chain once per task id (two Dense products, concat, sigmoid, segment sum, "
+                 "loss terms) | ONE kernel pair for all task ids of the batch (csrc/qm9_head.hip: every state row read once, no "
+                 "[V, hidden + A] concatenation, fixed-order sums; GPU tensors, up to 16 tasks, hidden a multiple of 4 up to 512, "
+                 "up to 64 initial features; anything else takes the op chain).  The last bits differ from the composition"),
     "typed": ("RELGNN_TYPED", "panel", ("panel", "bmm"),
               "per-(node, type) transforms of many-type graphs: one gathered-row MFMA launch | index_select + torch.bmm"),
     "typed_tn": ("RELGNN_TYPED_TN", "auto", ("auto", "limb", "panel"),

@@ -825,6 +825,9 @@ def check_pending_graph_errors():
     bad = torch.nonzero(flags).flatten().tolist()          # one host sync for all pending graphs
     if bad:
         what = pending[bad[0]][1]          # a node count, or the message of another producer's index check (tasks/varmisuse_task.py)
+        if isinstance(what, dict):         # one message per flag bit (tasks/qm9_task.py)
+            bits = int(flags[bad[0]])
+            what = "; ".join(msg for bit, msg in what.items() if bits & bit)
         raise ValueError(what if isinstance(what, str) else "adjacency list holds a node id outside [0, %d)" % what)
 
 

@@ -3,7 +3,11 @@ gated-regression head with per-graph unsorted_segment_sum pooling (:150-197) —
 segment-sum kernel in the reference.
 
 Edge types (defaults add_self_loop_edges=True, tie_fwd_bkwd_edges=True): type 0 = self loops, types 1..4 = bond
-types with both directions in one list (:114-133); each graph's adjacency lists are SORTED (:135)."""
+types with both directions in one list (:114-133); each graph's adjacency lists are SORTED (:135).
+
+The head has two routes (config.settings.qm9_head): `compose`, the reference's op chain per task id (any device, any shape), and
+`fused`, one HIP kernel pair for all task ids of the batch (csrc/qm9_head.hip) on GPU tensors of a shape the kernels take; ROUTES
+says which one the last call took."""
 import gzip
 import json
 from typing import Any, Dict, Iterator, List, NamedTuple, Optional
@@ -11,7 +15,7 @@ from typing import Any, Dict, Iterator, List, NamedTuple, Optional
 import numpy as np
 import torch
 
-from .. import ops
+from .. import config, ops
 from ..dense import dense
 from .sparse_graph_task import DataFold, MinibatchData, Sparse_Graph_Task
 
@@ -21,6 +25,114 @@ class QM9GraphSample(NamedTuple):
     type_to_node_to_num_incoming_edges: np.ndarray
     node_features: List[List[float]]
     target_values: List[float]
+
+
+ROUTES = {"head": None}                                 # which implementation the last call took: "hip" or "composition"
+
+_NOT_SORTED = "graph_nodes_list is not non-decreasing (a node's graph id is smaller than its predecessor's)"
+
+
+def _err_flag(device, num_graphs: int) -> torch.Tensor:
+    """A fresh device word for the kernel's check of graph_nodes_list, read back with the graphs' own at the next metric fetch."""
+    from .. import _lib
+    from ..graph import _PENDING_CHECKS
+    flag = torch.zeros(1, dtype=torch.int32, device=device)
+    _PENDING_CHECKS.append((flag, {_lib.ERRFLAG_INDEX_OUT_OF_RANGE: "graph_nodes_list holds a graph id outside [0, %d)" % num_graphs,
+                                   _lib.ERRFLAG_NOT_SORTED: _NOT_SORTED}))
+    return flag
+
+
+def _pointer_table(tensors):
+    """Host array of device pointers (the C ABI hands them to the kernel by value)."""
+    import ctypes
+    from .. import _lib
+    return (ctypes.c_void_p * len(tensors))(*[_lib.ptr(t) for t in tensors])
+
+
+def _aligned(t: torch.Tensor) -> torch.Tensor:
+    t = t.detach().reshape(-1).contiguous()
+    return t if t.data_ptr() % 16 == 0 else t.clone()
+
+
+class _Head(torch.autograd.Function):
+    """(loss, total_loss, abs_err [T], y [T, G]) of one batch for all T tasks: csrc/qm9_head.hip, one wave per graph.
+    loss and total_loss are differentiable.  abs_err and y are marked non-differentiable: nothing in the package back-propagates
+    through them (the reference's train step differentiates `loss` alone), and a gradient asked of them is an error instead of a
+    silent zero.  variables = w_reg, b_reg, w_gate, b_gate of task 0, then of task 1, ..."""
+
+    @staticmethod
+    def forward(ctx, states, features, graph_nodes_list, targets, num_graphs, *variables):
+        from .. import _lib
+        lib = _lib.load_library()
+        num_tasks = len(variables) // 4
+        if states.stride(1) != 1 or states.stride(0) % 4 != 0 or states.data_ptr() % 16 != 0:
+            states = states.contiguous()
+        if features.stride(1) != 1:
+            features = features.contiguous()
+        num_nodes, hidden = states.shape
+        annotation_size = features.shape[1]
+        ld = states.stride(0) if num_nodes > 1 else hidden
+        ldf = features.stride(0) if num_nodes > 1 else annotation_size
+        flat = [_aligned(v) for v in variables]
+        tables = [_pointer_table(flat[k::4]) for k in range(4)]
+        targets = targets.contiguous()
+        device = states.device
+        y = torch.empty((num_tasks, num_graphs), dtype=torch.float32, device=device)
+        node_range = torch.empty((num_graphs, 2), dtype=torch.int32, device=device)
+        stats = torch.empty(num_tasks + 2, dtype=torch.float32, device=device)
+        _lib.check(lib.relgnn_qm9_head_fwd(_lib.ptr(states, rows_strided=True), ld, _lib.ptr(features, rows_strided=True), ldf,
+                                           _lib.ptr(graph_nodes_list), num_nodes, num_graphs, hidden, annotation_size, num_tasks,
+                                           *tables, _lib.ptr(targets), _lib.ptr(y), _lib.ptr(node_range), _lib.ptr(stats),
+                                           _lib.ptr(_err_flag(device, num_graphs)), _lib.current_stream()), "relgnn_qm9_head_fwd")
+        ctx.save_for_backward(states, features, graph_nodes_list, targets, y, node_range, *flat)
+        ctx.shapes = [tuple(v.shape) for v in variables]
+        ctx.num_graphs = num_graphs
+        ctx.set_materialize_grads(False)
+        loss, total_loss, abs_err = stats[num_tasks], stats[num_tasks + 1], stats[:num_tasks]
+        ctx.mark_non_differentiable(abs_err, y)
+        return loss, total_loss, abs_err, y
+
+    @staticmethod
+    def backward(ctx, g_loss, g_total, g_abs_err, g_y):
+        from .. import _lib
+        lib = _lib.load_library()
+        states, features, graph_nodes_list, targets, y, node_range, *flat = ctx.saved_tensors
+        num_tasks = len(flat) // 4
+        if g_loss is None and g_total is None:
+            return (None,) * (5 + len(flat))
+
+        def scalar(g):                                  # the incoming gradients stay on the device: the kernel reads them
+            return None if g is None else g.reshape(1).to(torch.float32).contiguous()
+        g_loss, g_total = scalar(g_loss), scalar(g_total)
+        num_nodes, hidden = states.shape
+        annotation_size = features.shape[1]
+        ld = states.stride(0) if num_nodes > 1 else hidden
+        ldf = features.stride(0) if num_nodes > 1 else annotation_size
+        device = states.device
+        d_states = torch.empty((num_nodes, hidden), dtype=torch.float32, device=device)
+        d_features = torch.empty((num_nodes, annotation_size), dtype=torch.float32, device=device) if ctx.needs_input_grad[1] else None
+        grads = [torch.empty_like(v) for v in flat]     # one buffer per variable: the kernel writes each gradient where it stays
+        nbytes = lib.relgnn_qm9_head_workspace_bytes(num_nodes, num_tasks, hidden, annotation_size)
+        ws = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=device)
+        _lib.check(lib.relgnn_qm9_head_bwd(_lib.ptr(states, rows_strided=True), ld, _lib.ptr(features, rows_strided=True), ldf,
+                                           _lib.ptr(graph_nodes_list), num_nodes, ctx.num_graphs, hidden, annotation_size, num_tasks,
+                                           *[_pointer_table(flat[k::4]) for k in range(4)], _lib.ptr(targets), _lib.ptr(y),
+                                           _lib.ptr(node_range), _lib.ptr(g_loss), _lib.ptr(g_total), _lib.ptr(d_states), hidden,
+                                           _lib.ptr(d_features), *[_pointer_table(grads[k::4]) for k in range(4)], _lib.ptr(ws), nbytes,
+                                           _lib.current_stream()), "relgnn_qm9_head_bwd")
+        return (d_states, d_features, None, None, None) + tuple(g.reshape(s) for g, s in zip(grads, ctx.shapes))
+
+
+def head_supported(num_tasks: int, hidden: int, annotation_size: int) -> bool:
+    from .. import _lib
+    return bool(_lib.load_library().relgnn_qm9_head_supported(int(num_tasks), int(hidden), int(annotation_size)))
+
+
+def qm9_head(states: torch.Tensor, features: torch.Tensor, graph_nodes_list: torch.Tensor, targets: torch.Tensor, num_graphs: int,
+             variables):
+    """-> (loss, total_loss, abs_err [T], y [T, G]) on the HIP route: float32 device states [V, hidden] and features [V, A], int32
+    non-decreasing graph_nodes_list [V], float32 targets [T, G]; variables = [(w_reg, b_reg, w_gate, b_gate), ...] per task."""
+    return _Head.apply(states, features, graph_nodes_list, targets, int(num_graphs), *[v for task in variables for v in task])
 
 
 class QM9_Task(Sparse_Graph_Task):
@@ -154,6 +266,27 @@ class QM9_Task(Sparse_Graph_Task):
         losses = []
         num_graphs = batch.num_graphs
         targets = batch.extra['target_values']                                   # [tasks, G]
+        task_ids = self.params['task_ids']
+        features = batch.initial_node_features
+        use_hip = (config.settings.qm9_head == "fused" and final_node_representations.is_cuda and features.is_cuda
+                   and final_node_representations.dtype == torch.float32 and features.dtype == torch.float32
+                   and torch.is_tensor(targets) and targets.dtype == torch.float32
+                   and batch.graph_nodes_list.dtype == torch.int32 and num_graphs >= 1 and final_node_representations.dim() == 2
+                   and head_supported(len(task_ids), final_node_representations.shape[1], features.shape[1]))
+        ROUTES["head"] = "hip" if use_hip else "composition"
+        if use_hip:
+            variables = []
+            for task_id in task_ids:
+                w = weights.scope("out_layer_task%i" % task_id) if hasattr(weights, "scope") else weights
+                variables.append((w["regression/dense/kernel"], w["regression/dense/bias"],
+                                  w["regression_gate/dense/kernel"], w["regression_gate/dense/bias"]))
+            loss, total_loss, abs_err, _ = qm9_head(final_node_representations, features, batch.graph_nodes_list, targets, num_graphs,
+                                                    variables)
+            for internal_id, task_id in enumerate(task_ids):
+                metrics['abs_err_task%i' % task_id] = abs_err[internal_id]
+            metrics['loss'] = loss
+            metrics['total_loss'] = total_loss
+            return metrics
         for internal_id, task_id in enumerate(self.params['task_ids']):
             w = weights.scope("out_layer_task%i" % task_id) if hasattr(weights, "scope") else weights
             # (dense(): the [hidden, 1] weight gradients go through the streaming kernel — as plain `@` autograd handed
