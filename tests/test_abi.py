@@ -33,6 +33,42 @@ def test_python_binding_covers_header():
     assert sorted(_lib.exported_signatures()) == declared_functions()
 
 
+_C_TYPES = {"int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64, "float": ctypes.c_float, "size_t": ctypes.c_size_t, "int": ctypes.c_int}
+
+
+def _c_type(text, returned=False):
+    """The ctypes type of one C parameter (or return) type as the header writes it: any pointer is c_void_p (a returned
+    const char* c_char_p), the scalar types map to their ctypes."""
+    if "*" in text:
+        return ctypes.c_char_p if returned and re.fullmatch(r"const\s+char\s*\*", text.strip()) else ctypes.c_void_p
+    words = [w for w in text.split() if w != "const"]
+    return _C_TYPES[words[0]]            # (a parameter's name, when it has one, is the second word)
+
+
+def declared_signatures():
+    """name -> (restype, [argtypes]) for every function include/relgnn.h declares, read from the text with its comments stripped."""
+    text = (ROOT / "include" / "relgnn.h").read_text()
+    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    text = re.sub(r"//[^\n]*", "", text)
+    out = {}
+    for ret, name, params in re.findall(r"^\s*((?:const\s+)?\w+\s*\**)\s*\b(relgnn_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", text, flags=re.M):
+        params = " ".join(params.split())
+        args = [] if params in ("", "void") else [_c_type(a) for a in params.split(",")]
+        out[name] = (_c_type(ret, returned=True), args)
+    return out
+
+
+def test_python_binding_types_every_argument_as_the_header_declares_it():
+    """restype and argtypes of _lib's table against the header, element for element: a c_int32 where the header says int64_t is a
+    silently wrong value for any argument passed on the stack, and most entries have more than six."""
+    from tf_gnn_samples_amd import _lib
+    declared, bound = declared_signatures(), _lib.exported_signatures()
+    assert sorted(declared) == declared_functions() and len(declared) == 126
+    assert sorted(bound) == sorted(declared)
+    wrong = {n: (bound[n], declared[n]) for n in declared if (bound[n][0], list(bound[n][1])) != declared[n]}
+    assert not wrong, "bound (restype, argtypes) vs the header's: %s" % wrong
+
+
 def test_loader_types_every_symbol_and_reports_version():
     from tf_gnn_samples_amd import _build, _lib
     if not _lib.LIB_PATH.exists():

@@ -87,7 +87,7 @@ def test_a_backward_that_raises_leaves_no_deferred_join_state_behind():
 
 def test_combined_node_csr_of_both_pair_tables_sums_what_the_two_reductions_sum():
     """graph.PairTables.node_csr_both: one CSR node -> (its by-source table rows, then its by-target table rows + P_s) — the
-    single reduction of ops._TypedLinearPair — gives every node the sum of the two separate reductions, the by-source rows first."""
+    single reduction of ops._TypedLinearPanel over both tables — gives every node the sum of the two separate reductions, the by-source rows first."""
     import types
     from tf_gnn_samples_amd.graph import PairTables
     g = torch.Generator().manual_seed(0)

@@ -15,17 +15,17 @@ pytestmark = pytest.mark.gpu
 U = 128
 
 
-def _weights(dev, seed, scale=0.15):
+def _weights(dev, seed, scale=0.15, U=U, D=U):
     g = torch.Generator(device="cpu").manual_seed(seed)
-    K = ((torch.rand((U, 3 * U), generator=g) * 2 - 1) * scale).to(dev)
+    K = ((torch.rand((D, 3 * U), generator=g) * 2 - 1) * scale).to(dev)
     R = ((torch.rand((U, 3 * U), generator=g) * 2 - 1) * scale).to(dev)
     b = ((torch.rand((3 * U,), generator=g) * 2 - 1) * 0.3).to(dev)
     return K, R, b
 
 
-def _states(dev, V, seed):
+def _states(dev, V, seed, U=U, D=U):
     g = torch.Generator(device="cpu").manual_seed(seed)
-    return (torch.randn((V, U), generator=g) * 1.5).to(dev), (torch.rand((V, U), generator=g) * 2 - 1).to(dev)
+    return (torch.randn((V, D), generator=g) * 1.5).to(dev), (torch.rand((V, U), generator=g) * 2 - 1).to(dev)
 
 
 def _cell64(x, h, K, R, b, act):
@@ -127,7 +127,7 @@ def test_rows_with_non_finite_values_spoil_their_own_rows_only(gpu_device):
     assert torch.equal(torch.isfinite(got[40]), torch.isfinite(ref40[0]))
 
 
-def _cell_backward64(x, h, K, R, z, r, hh, g, act):
+def _cell_backward64(x, h, K, R, z, r, hh, g, act, U=U):
     """The cell's gradients in float64 from the float32 forward's own z, r and candidate — the derivative of hard_sigmoid / ReLU
     is a step, and a gate that float32 put ON the step (z == 1.0f where float64 has 1 - 1e-9) would make an autograd reference
     differ by a whole term."""
@@ -272,3 +272,39 @@ def test_cell_kernels_that_give_up_on_a_hand_over_say_so_and_end(gpu_device):
     utils._GRUCellFn.apply(*clean, _lib.ACT_TANH).backward(gout)
     torch.cuda.synchronize()
     assert ops.handover_status() == 0 and all(bool(torch.isfinite(t.grad).all()) for t in clean)
+
+
+@pytest.mark.parametrize("V", [300, 4608])
+def test_cells_the_one_node_form_refuses_take_the_composition_route(gpu_device, V):
+    """A GGNN cell of 192 units over 128-wide inputs: 2 u^2 = 73 728 recurrent-kernel gradient entries per block are past the size
+    class utils._gru_cell_fused_ok admits (256^2), so the gated unit runs dense() + utils._FusedGRU — gru.hip's two kernel pairs
+    around the inner product, with the surrounding Dense nodes' weight gradients.  Forward against the oracle's cell at the bound
+    of test_cell_kernel_against_the_oracle_cell; the gradients of inputs, state and the three variables against the float64
+    restatement of test_cell_backward_kernel_against_float64 (on the forward's own gates and candidate), at that test's bound."""
+    from oracle import tf_ops
+    from tf_gnn_samples_amd import utils
+    dev = gpu_device
+    u, D = 192, 128
+    K, R, b = _weights(dev, 61, U=u, D=D)
+    x, h = _states(dev, V, V + 7, U=u, D=D)
+    assert not utils._gru_cell_fused_ok(x, h, K, R, b, u)
+    g = torch.Generator(device="cpu").manual_seed(V)
+    gout = torch.randn((V, u), generator=g).to(dev)
+    leaves = [t.clone().requires_grad_(True) for t in (x, h, K, R, b)]
+    cell = utils.get_gated_unit(u, "gru", "tanh", {"kernel": leaves[2], "recurrent_kernel": leaves[3], "bias": leaves[4]})
+    out, _ = cell(leaves[0], [leaves[1]])
+    assert type(out.grad_fn).__name__ == "_FusedGRUBackward"
+    z, r, _, _, hh, _ = out.grad_fn.saved_tensors
+    want = tf_ops.gru_cell(x.cpu().numpy(), h.cpu().numpy(), K.cpu().numpy(), R.cpu().numpy(), b.cpu().numpy(), np.tanh)
+    err = float(np.abs(out.detach().cpu().numpy().astype(np.float64) - want.astype(np.float64)).max())
+    print("forward |route - oracle| V=%d: %.3e" % (V, err))
+    assert err <= 1e-5
+    out.backward(gout)
+    torch.cuda.synchronize()
+    want = _cell_backward64(x, h, K, R, z, r, hh, gout, "tanh", U=u)
+    errs = []
+    for name, got, w in zip(("x", "h", "kernel", "recurrent_kernel", "bias"), leaves, want):
+        scale = max(1.0, float(w.abs().max()))
+        errs.append((name, float((got.grad.double() - w).abs().max()), 4e-6 * scale * max(1.0, float(np.sqrt(V)) / 30)))
+        print("backward V=%d %s: error %.3e, bound %.3e" % ((V,) + errs[-1]))
+    assert all(e <= bound for _, e, bound in errs), (V, errs)

@@ -51,7 +51,7 @@ def test_typed_linear_pair_is_the_same_bits_in_every_mode(gpu_device):
         Hd = H.clone().requires_grad_(True)
         Wd = [w.clone().requires_grad_(True) for w in Ws]
         Ya, Yb = ops.typed_linear_pair(Hd, pairs, Wd[:L], Wd[L:])
-        assert type(Ya.grad_fn).__name__ == "_TypedLinearPairBackward" and Yb.grad_fn is Ya.grad_fn
+        assert type(Ya.grad_fn).__name__ == "_TypedLinearPanelBackward" and Yb.grad_fn is Ya.grad_fn
         if gYs is None:
             gYs = [torch.as_tensor(rng.standard_normal(tuple(Y.shape)).astype(np.float32), device=gpu_device) for Y in (Ya, Yb)]
         pending = _backward([Ya, Yb], gYs, overlap, deferred)

@@ -249,3 +249,14 @@ def current_stream():
     if _raw_stream is not None:
         return _raw_stream(torch.cuda.current_device())
     return torch.cuda.current_stream().cuda_stream
+
+
+def launch(name: str, *args) -> None:
+    """librelgnn's `name`(*args, the current stream); raises on a status other than OK."""
+    check(getattr(load_library(), name)(*args, current_stream()), name)
+
+
+def scratch(nbytes: int, device) -> torch.Tensor:
+    """Workspace of at least `nbytes` bytes for one launch (the kernels take a pointer and a byte count; the caching allocator's
+    alignment exceeds every element type they keep there).  A plain torch.empty: on the current stream, capturable."""
+    return torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=device)

@@ -14,11 +14,6 @@ from .weight_images import (GEMM_NN, GEMM_NT, GEMM_TN, WEIGHT_NN, WEIGHT_NT, _Pe
 _LIMB_MIN_ROWS, _LIMB_MAX_K = 4096, 1024
 
 
-def _launch(name: str, *args) -> None:
-    """librelgnn's `name`(*args, the current stream); raises on a status other than OK."""
-    _lib.check(getattr(_lib.load_library(), name)(*args, _lib.current_stream()), name)
-
-
 # ---- what an operand must look like: one predicate per question ---------------------------------------------------------------------
 def rows_aligned(t: torch.Tensor) -> bool:
     """fp32 device matrix, unit column stride, rows that do not overlap, every row 16-byte aligned: the limb and panel kernels
@@ -85,17 +80,13 @@ def _zeros(device) -> torch.Tensor:
     return z
 
 
-def _float_scratch(nbytes: int, device) -> torch.Tensor:
-    return torch.empty(max(nbytes // 4, 1), dtype=torch.float32, device=device)
-
-
 # ---- passes -------------------------------------------------------------------------------------------------------------------------
 def act_bwd_from_output(act: int, y: torch.Tensor, g: torch.Tensor, out: torch.Tensor = None) -> torch.Tensor:
     """g * act'(y) with the derivative taken from the activation's output (relgnn_act_bwd_from_output); out may be g itself."""
     g = g if g.is_contiguous() else g.contiguous()
     if out is None:
         out = torch.empty_like(g)
-    _launch("relgnn_act_bwd_from_output", act, _lib.ptr(y), _lib.ptr(g), g.numel(), _lib.ptr(out))
+    _lib.launch("relgnn_act_bwd_from_output", act, _lib.ptr(y), _lib.ptr(g), g.numel(), _lib.ptr(out))
     return out
 
 
@@ -107,8 +98,8 @@ def column_sum(g: torch.Tensor) -> torch.Tensor:
     V, N = g.shape
     out = torch.empty(N, dtype=torch.float32, device=g.device)
     nbytes = _lib.load_library().relgnn_column_sum_workspace_bytes(V, N)
-    ws = torch.empty(nbytes // 4, dtype=torch.float32, device=g.device)
-    _launch("relgnn_column_sum", _lib.ptr(g, rows_strided=True), V, N, g.stride(0), _lib.ptr(out), _lib.ptr(ws), nbytes)
+    ws = _lib.scratch(nbytes, g.device)
+    _lib.launch("relgnn_column_sum", _lib.ptr(g, rows_strided=True), V, N, g.stride(0), _lib.ptr(out), _lib.ptr(ws), nbytes)
     return out
 
 
@@ -123,8 +114,8 @@ def col_absmax(x: torch.Tensor) -> torch.Tensor:
         x = x.contiguous()
     out = torch.empty(cols, dtype=torch.float32, device=x.device)
     nbytes = int(_lib.load_library().relgnn_col_absmax_workspace_bytes(x.shape[0], cols))
-    ws = torch.empty(nbytes // 4, dtype=torch.int32, device=x.device) if nbytes else None
-    _launch("relgnn_col_absmax_f32", _lib.ptr(x, rows_strided=True), x.stride(0) if x.shape[0] > 1 else cols, x.shape[0], cols,
+    ws = _lib.scratch(nbytes, x.device) if nbytes else None
+    _lib.launch("relgnn_col_absmax_f32", _lib.ptr(x, rows_strided=True), x.stride(0) if x.shape[0] > 1 else cols, x.shape[0], cols,
             out.data_ptr(), _lib.ptr(ws), nbytes)
     return out
 
@@ -133,7 +124,7 @@ def absmax(x: torch.Tensor) -> torch.Tensor:
     """[1] float32 on the device: max |x| over the finite elements (relgnn_absmax_f32; no host round trip)."""
     x = x if x.is_contiguous() else x.contiguous()
     out = torch.empty(1, dtype=torch.float32, device=x.device)
-    _launch("relgnn_absmax_f32", _lib.ptr(x), x.numel(), out.data_ptr())
+    _lib.launch("relgnn_absmax_f32", _lib.ptr(x), x.numel(), out.data_ptr())
     return out
 
 
@@ -177,7 +168,7 @@ def panel_gemm(layout: int, a: torch.Tensor, b: torch.Tensor, bias: torch.Tensor
     if out is None:
         out = torch.empty((batch, M, N) if batch > 1 else (M, N), dtype=torch.float32, device=a.device)
     ldc = out.stride(-2)
-    _launch("relgnn_panel_gemm_f32", layout, act, a.data_ptr(), a.stride(-2), _lib.ptr(a_rows), b.data_ptr(), b.stride(-2),
+    _lib.launch("relgnn_panel_gemm_f32", layout, act, a.data_ptr(), a.stride(-2), _lib.ptr(a_rows), b.data_ptr(), b.stride(-2),
             _lib.ptr(b_select), int(rows_per_select), b.stride(0) if b_select is not None else 0, _lib.ptr(bias),
             _lib.ptr(_zeros(a.device)), out.data_ptr(), ldc, M, N, K, batch, strides[0], strides[1],
             strides[2] if batch > 1 and strides[2] else (M * ldc if batch > 1 else 0), int(split_k_rows))
@@ -210,7 +201,7 @@ def limb_split(x: torch.Tensor, transpose: bool = False, out: "Limbs" = None) ->
         out = Limbs(torch.empty(int(_lib.load_library().relgnn_limb_elements(rows, cols)), dtype=torch.bfloat16, device=x.device), rows, cols)
     elif (out.rows, out.cols) != (rows, cols):
         raise ValueError("limb_split: out holds a [%d, %d] matrix, not [%d, %d]" % (out.rows, out.cols, rows, cols))
-    _launch("relgnn_limb_split_f32", x.data_ptr(), x.stride(0), R, C, 1 if transpose else 0, out.data.data_ptr())
+    _lib.launch("relgnn_limb_split_f32", x.data_ptr(), x.stride(0), R, C, 1 if transpose else 0, out.data.data_ptr())
     return out
 
 
@@ -222,7 +213,7 @@ def limb_gemm(a: "Limbs", b: "Limbs", bias: torch.Tensor = None, act: int = 0, o
     dev = a.data.device
     if out is None:
         out = torch.empty((a.rows, b.rows), dtype=torch.float32, device=dev)
-    _launch("relgnn_limb_gemm_f32", act, a.data.data_ptr(), b.data.data_ptr(), _lib.ptr(bias), _lib.ptr(_zeros(dev)), out.data_ptr(),
+    _lib.launch("relgnn_limb_gemm_f32", act, a.data.data_ptr(), b.data.data_ptr(), _lib.ptr(bias), _lib.ptr(_zeros(dev)), out.data_ptr(),
             out.stride(0), a.rows, b.rows, a.cols)
     return out
 
@@ -236,7 +227,7 @@ def limb_gemm_xf32(a: torch.Tensor, b: "Limbs", bias: torch.Tensor = None, act: 
         raise ValueError("limb_gemm_xf32: reduction lengths differ (%d, %d)" % (K, b.cols))
     if out is None:
         out = torch.empty((M, b.rows), dtype=torch.float32, device=a.device)
-    _launch("relgnn_limb_gemm_xf32", act, a.data_ptr(), a.stride(0), b.data.data_ptr(), _lib.ptr(bias), _lib.ptr(_zeros(a.device)),
+    _lib.launch("relgnn_limb_gemm_xf32", act, a.data_ptr(), a.stride(0), b.data.data_ptr(), _lib.ptr(bias), _lib.ptr(_zeros(a.device)),
             out.data_ptr(), out.stride(0), M, b.rows, K)
     return out
 
@@ -270,15 +261,15 @@ def limb_gemm_weight(a: torch.Tensor, w, kind: str, bias: torch.Tensor = None, a
         if xmax.numel() != M * xgroups or xmax.dtype != torch.float32 or not xmax.is_contiguous():
             raise ValueError("limb_gemm_weight: xmax must be a contiguous float32 [%d * %d]" % (M, xgroups))
         im = weight_image(w, kind, pair=True)
-        _launch("relgnn_limb16_gemm_xf32_dact" if factor else "relgnn_limb16_gemm_xf32", *left, xmax.data_ptr(), int(xgroups),
+        _lib.launch("relgnn_limb16_gemm_xf32_dact" if factor else "relgnn_limb16_gemm_xf32", *left, xmax.data_ptr(), int(xgroups),
                 im.buf.data_ptr(), im.wmax.data_ptr(), _lib.ptr(bias), _lib.ptr(_zeros(a.device)), *factor, *result)
         return out
     buf = weight_limbs(w, kind)
     if _limb_pc_ok(a, n, k, bias, act, dy, out, kind):
-        _launch("relgnn_limb_gemm_xf32_pc", *left, buf.data_ptr(), _lib.ptr(bias), *(factor or (int(dact), None, 0)), *result,
+        _lib.launch("relgnn_limb_gemm_xf32_pc", *left, buf.data_ptr(), _lib.ptr(bias), *(factor or (int(dact), None, 0)), *result,
                 _handover(a.device))
     else:
-        _launch("relgnn_limb_gemm_xf32_dact" if factor else "relgnn_limb_gemm_xf32", *left, buf.data_ptr(), _lib.ptr(bias),
+        _lib.launch("relgnn_limb_gemm_xf32_dact" if factor else "relgnn_limb_gemm_xf32", *left, buf.data_ptr(), _lib.ptr(bias),
                 _lib.ptr(_zeros(a.device)), *factor, *result)
     return out
 
@@ -310,7 +301,7 @@ def limb_dense(layout: int, a: torch.Tensor, b: torch.Tensor, bias: torch.Tensor
     ws = _limb_ws(a.device, int(_lib.load_library().relgnn_limb_elements(N, K)))
     if out is None:
         out = torch.empty((M, N), dtype=torch.float32, device=a.device)
-    _launch("relgnn_limb_dense_f32", layout, act, a.data_ptr(), a.stride(0), b.data_ptr(), b.stride(0), _lib.ptr(bias),
+    _lib.launch("relgnn_limb_dense_f32", layout, act, a.data_ptr(), a.stride(0), b.data_ptr(), b.stride(0), _lib.ptr(bias),
             _lib.ptr(_zeros(a.device)), ws.data_ptr(), ws.numel(), out.data_ptr(), out.stride(0), M, N, K)
     return out
 
@@ -345,7 +336,7 @@ def limb_dense_sel(layout: int, a: torch.Tensor, b, bias: torch.Tensor = None, a
     N = b.shape[-1] if layout == GEMM_NN else b.shape[-2]
     ws = _limb_ws(a.device, int(lib.relgnn_limb_elements((N + 127) // 128 * 128, K)) * num_b)
     out = torch.empty((M, N), dtype=torch.float32, device=a.device)
-    _launch("relgnn_limb_dense_sel_f32", layout, act, a.data_ptr(), a.stride(0), _lib.ptr(a_rows), b.data_ptr(), b.stride(-2), num_b,
+    _lib.launch("relgnn_limb_dense_sel_f32", layout, act, a.data_ptr(), a.stride(0), _lib.ptr(a_rows), b.data_ptr(), b.stride(-2), num_b,
             b.stride(0) if b.dim() == 3 else 0, _lib.ptr(b_select), int(rows_per_select), _lib.ptr(bias), _lib.ptr(_zeros(a.device)),
             ws.data_ptr(), ws.numel(), out.data_ptr(), out.stride(0), M, N, K)
     return out
@@ -362,9 +353,9 @@ def _sel_with_image(a: torch.Tensor, im, n: int, k: int, act: int = 0, bias: tor
     left = (a.data_ptr(), a.stride(0), _lib.ptr(a_rows), im.buf.data_ptr(), count, _lib.ptr(b_select), int(rows_per_select))
     result = (_lib.ptr(_zeros(a.device)), out.data_ptr(), out.stride(0), m, n, k)
     if roles:
-        _launch("relgnn_limb_gemm_sel_pc_xf32", *left, *result, _handover(a.device))
+        _lib.launch("relgnn_limb_gemm_sel_pc_xf32", *left, *result, _handover(a.device))
     else:
-        _launch("relgnn_limb_gemm_sel_xf32", act, *left, _lib.ptr(bias), *result)
+        _lib.launch("relgnn_limb_gemm_sel_xf32", act, *left, _lib.ptr(bias), *result)
     return out
 
 
@@ -390,9 +381,9 @@ def limb_gemm_tn(a: torch.Tensor, b: torch.Tensor, amax: torch.Tensor = None, bm
         na, nb = amax.numel(), bmax.numel()
         if na < 1 or nb < 1 or J % na or C % nb or amax.dtype != torch.float32 or bmax.dtype != torch.float32:
             raise ValueError("limb_gemm_tn: the magnitude counts (%d, %d) must divide the operand widths (%d, %d)" % (na, nb, J, C))
-        _launch("relgnn_limb16_gemm_tn_f32", *operands, amax.data_ptr(), J // na, bmax.data_ptr(), C // nb, parts.data_ptr(), V, J, C)
+        _lib.launch("relgnn_limb16_gemm_tn_f32", *operands, amax.data_ptr(), J // na, bmax.data_ptr(), C // nb, parts.data_ptr(), V, J, C)
     else:
-        _launch("relgnn_limb_gemm_tn_f32", *operands, parts.data_ptr(), V, J, C)
+        _lib.launch("relgnn_limb_gemm_tn_f32", *operands, parts.data_ptr(), V, J, C)
     return sum_slabs_tail(parts, a, b, V - V % 32)
 
 
@@ -403,7 +394,7 @@ def sum_slabs_tail(parts: torch.Tensor, a: torch.Tensor, b: torch.Tensor, head: 
     Z, M, N = parts.shape
     R = a.shape[0] - head
     out = torch.empty((M, N), dtype=torch.float32, device=a.device)
-    _launch("relgnn_sum_slabs_tail_f32", _lib.ptr(parts), Z, M, N, a[head:].data_ptr() if R else None, a.stride(0),
+    _lib.launch("relgnn_sum_slabs_tail_f32", _lib.ptr(parts), Z, M, N, a[head:].data_ptr() if R else None, a.stride(0),
             b[head:].data_ptr() if R else None, b.stride(0), R, _lib.ptr(out))
     return out
 
@@ -422,7 +413,7 @@ def limb_gemm_tn_tiles(a: torch.Tensor, g: torch.Tensor, a_rows: torch.Tensor, r
     P, C = g.shape
     J = a.shape[1]
     part = torch.empty((P // rows_per_tile, J, C), dtype=torch.float32, device=g.device)
-    _launch("relgnn_limb_gemm_tn_tiles_f32", a.data_ptr(), a.stride(0), a_rows.data_ptr(), g.data_ptr(), g.stride(0),
+    _lib.launch("relgnn_limb_gemm_tn_tiles_f32", a.data_ptr(), a.stride(0), a_rows.data_ptr(), g.data_ptr(), g.stride(0),
             _lib.ptr(_zeros(g.device)), part.data_ptr(), P, int(rows_per_tile), J, C)
     return part
 
@@ -436,8 +427,8 @@ def _tn_stream(name: str, a: torch.Tensor, b: torch.Tensor, *result) -> None:
     V, M = a.shape
     N = b.shape[1]
     nbytes = _lib.load_library().relgnn_gemm_tn_stream_workspace_bytes(M, N, V)
-    ws = _float_scratch(nbytes, a.device)
-    _launch(name, _lib.ptr(a, rows_strided=True), a.stride(0), _lib.ptr(b, rows_strided=True), b.stride(0), *result, _lib.ptr(ws), nbytes)
+    ws = _lib.scratch(nbytes, a.device)
+    _lib.launch(name, _lib.ptr(a, rows_strided=True), a.stride(0), _lib.ptr(b, rows_strided=True), b.stride(0), *result, _lib.ptr(ws), nbytes)
 
 
 def tn_stream_gemm(a: torch.Tensor, b: torch.Tensor, out: torch.Tensor = None) -> torch.Tensor:
@@ -499,6 +490,6 @@ def tn_stream_group(products, colsum: torch.Tensor = None) -> None:
     M = i32(*[a.shape[1] for a, _, _ in products])
     N = i32(*[b.shape[1] for _, b, _ in products])
     nbytes = _lib.load_library().relgnn_gemm_tn_stream_group_workspace_bytes(n, M, N, V, 1 if colsum is not None else 0)
-    ws = _float_scratch(nbytes, products[0][0].device)
+    ws = _lib.scratch(nbytes, products[0][0].device)
     per_operand = [arg for i in range(3) for arg in (vp(*[p[i].data_ptr() for p in products]), i64(*[p[i].stride(0) for p in products]))]
-    _launch("relgnn_gemm_tn_stream_group_f32", n, *per_operand, M, N, V, _lib.ptr(colsum), _lib.ptr(ws), nbytes)
+    _lib.launch("relgnn_gemm_tn_stream_group_f32", n, *per_operand, M, N, V, _lib.ptr(colsum), _lib.ptr(ws), nbytes)

@@ -25,11 +25,8 @@ def pair_messages_reduce(p: torch.Tensor, q: torch.Tensor, graph, w: Optional[to
     more than ops.LONG_SEGMENT messages in one bucket) takes the materialised route instead, whose reduction is the gather-reduce
     kernel with chunked virtual rows (ops.SplitPlan) — slower per message, but no wave walks 1e4+ messages alone."""
     if ops.aggregation_mode_id(aggregation) == _lib.AGG_MAX or graph.has_long_buckets:
-        msgs = ops.pair_materialize(p, q, graph, None)                 # [M, D] type-major order
-        if w is not None:
-            msgs = graph.w_original_order(w).unsqueeze(1) * msgs
-        msgs = apply_activation(get_activation(message_activation), msgs)
-        out = ops.seg_gather_reduce(msgs, graph.plan_messages(), aggregation, None)
+        # ([M, D] in the type-major order; message_act_reduce takes its own materialised route under the same two conditions)
+        out = ops.message_act_reduce(ops.pair_materialize(p, q, graph, None), graph, w, aggregation, message_activation)
     else:
         out = ops.pair_messages_reduce_fused(p, q, graph, w, aggregation, message_activation)
     return apply_activation(get_activation(output_activation), out)

@@ -62,8 +62,6 @@ class GatherReducePlan:
         w_b[q] = w[p(q)] * f(n_segment(p(q))), f = 1, 1/max(n,1), 1/sqrt(max(n,1))."""
         if mode in self._w_bwd:
             return self._w_bwd[mode]
-        lib = _lib.load_library()
-        st = _lib.current_stream()
         M = self.num_messages
         if self.w is None and mode == _lib.AGG_SUM:
             res = None
@@ -74,12 +72,10 @@ class GatherReducePlan:
                 scale_f = self.w
             else:
                 scale_f = torch.empty(M, dtype=torch.float32, device=self.rowptr.device)
-                _lib.check(lib.relgnn_segment_counts_scale(
-                    _lib.ptr(self.rowptr), self.num_out, self.stride, mode, _lib.ptr(self.w),
-                    _lib.ptr(scale_f), st), "relgnn_segment_counts_scale")
+                _lib.launch("relgnn_segment_counts_scale", _lib.ptr(self.rowptr), self.num_out, self.stride, mode, _lib.ptr(self.w),
+                            _lib.ptr(scale_f))
             res = torch.empty(M, dtype=torch.float32, device=self.rowptr.device)
-            _lib.check(lib.relgnn_gather_f32(_lib.ptr(scale_f), _lib.ptr(self.pos_b), M,
-                                             _lib.ptr(res), st), "relgnn_gather_f32")
+            _lib.launch("relgnn_gather_f32", _lib.ptr(scale_f), _lib.ptr(self.pos_b), M, _lib.ptr(res))
         self._w_bwd[mode] = res
         return res
 
@@ -93,10 +89,9 @@ def build_segment_plan(keys: torch.Tensor, num_segments: int, want_sorted_keys: 
     perm = _i32(M, dev)
     sorted_keys = _i32(M, dev) if want_sorted_keys else None
     ws_bytes = lib.relgnn_segment_plan_workspace_bytes(M, num_segments)
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-    _lib.check(lib.relgnn_segment_plan(_lib.ptr(keys), M, num_segments, _lib.ptr(rowptr),
-                                       _lib.ptr(perm), _lib.ptr(sorted_keys), _lib.ptr(ws), ws_bytes,
-                                       _lib.current_stream()), "relgnn_segment_plan")
+    ws = _lib.scratch(ws_bytes, dev)
+    _lib.launch("relgnn_segment_plan", _lib.ptr(keys), M, num_segments, _lib.ptr(rowptr), _lib.ptr(perm), _lib.ptr(sorted_keys),
+                _lib.ptr(ws), ws_bytes)
     return rowptr, perm, sorted_keys
 
 
@@ -128,35 +123,31 @@ class RelGraph:
         self.device = dev
         if V * L >= 2 ** 31 - 1 or M >= 2 ** 31 - 1:
             raise ValueError("graph too large for int32 indices")
-        st = _lib.current_stream()
 
         key_t, key_s = _i32(M, dev), _i32(M, dev)
         node_t, node_s = _i32(M, dev), _i32(M, dev)
         err = torch.zeros(1, dtype=torch.int32, device=dev)
         h_adj = (ctypes.c_void_p * L)(*[_lib.ptr(a) if a.shape[0] else None for a in adj])    # refuses host tensors
         h_cnt = (ctypes.c_int64 * L)(*self.edge_counts)
-        _lib.check(lib.relgnn_relational_keys_all(h_adj, h_cnt, L, V, _lib.ptr(key_t), _lib.ptr(key_s), _lib.ptr(node_t),
-                                                  _lib.ptr(node_s), _lib.ptr(err), st), "relgnn_relational_keys_all")
+        _lib.launch("relgnn_relational_keys_all", h_adj, h_cnt, L, V, _lib.ptr(key_t), _lib.ptr(key_s), _lib.ptr(node_t), _lib.ptr(node_s),
+                    _lib.ptr(err))
         self._key_t, self._key_s = key_t, key_s
 
         S = V * L
         ws_bytes = lib.relgnn_relational_plan_workspace_bytes(M, V)
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        ws = _lib.scratch(ws_bytes, dev)
         # by (target, type): position p -> original message perm_t[p]; gathers row col_t[p] = src*L + l
         self.rowptr_t, self.perm_t, self.col_t = _i32(S + 1, dev), _i32(M, dev), _i32(M, dev)
         inv_t = _i32(M, dev)
-        _lib.check(lib.relgnn_relational_plan(_lib.ptr(node_t), _lib.ptr(key_t), _lib.ptr(key_s), M, V, L,
-                                              _lib.ptr(self.rowptr_t), _lib.ptr(self.perm_t), _lib.ptr(self.col_t), None,
-                                              _lib.ptr(inv_t), None, None, _lib.ptr(ws), ws_bytes, st),
-                   "relgnn_relational_plan")
+        _lib.launch("relgnn_relational_plan", _lib.ptr(node_t), _lib.ptr(key_t), _lib.ptr(key_s), M, V, L, _lib.ptr(self.rowptr_t),
+                    _lib.ptr(self.perm_t), _lib.ptr(self.col_t), None, _lib.ptr(inv_t), None, None, _lib.ptr(ws), ws_bytes)
         # by (source, type): position q -> original message perm_s[q]; (target, type) row frow_s[q] = tgt*L + l,
         # target node tgt_s[q]; pos_t_of_s[q] = by-target position of the same message
         self.rowptr_s, self.perm_s = _i32(S + 1, dev), _i32(M, dev)
         self.frow_s, self.tgt_s, self.pos_t_of_s = _i32(M, dev), _i32(M, dev), _i32(M, dev)
-        _lib.check(lib.relgnn_relational_plan(_lib.ptr(node_s), _lib.ptr(key_s), _lib.ptr(key_t), M, V, L,
-                                              _lib.ptr(self.rowptr_s), _lib.ptr(self.perm_s), _lib.ptr(self.frow_s),
-                                              _lib.ptr(self.tgt_s), None, _lib.ptr(inv_t), _lib.ptr(self.pos_t_of_s),
-                                              _lib.ptr(ws), ws_bytes, st), "relgnn_relational_plan")
+        _lib.launch("relgnn_relational_plan", _lib.ptr(node_s), _lib.ptr(key_s), _lib.ptr(key_t), M, V, L, _lib.ptr(self.rowptr_s),
+                    _lib.ptr(self.perm_s), _lib.ptr(self.frow_s), _lib.ptr(self.tgt_s), None, _lib.ptr(inv_t), _lib.ptr(self.pos_t_of_s),
+                    _lib.ptr(ws), ws_bytes)
         self.inv_perm_t = inv_t
         self._src_t = None
         self._plans = {}
@@ -234,15 +225,13 @@ class RelGraph:
 
     def _ensure_keys(self):
         if self._key_t is None:
-            lib = _lib.load_library()
             L, M, dev = self.L, self.M, self.device
             key_t, key_s, node_t, node_s = _i32(M, dev), _i32(M, dev), _i32(M, dev), _i32(M, dev)
             err = torch.zeros(1, dtype=torch.int32, device=dev)
             h_adj = (ctypes.c_void_p * L)(*[_lib.ptr(a) if a.shape[0] else None for a in self.adjacency_lists])
             h_cnt = (ctypes.c_int64 * L)(*self.edge_counts)
-            _lib.check(lib.relgnn_relational_keys_all(h_adj, h_cnt, L, self.V, _lib.ptr(key_t), _lib.ptr(key_s),
-                                                      _lib.ptr(node_t), _lib.ptr(node_s), _lib.ptr(err),
-                                                      _lib.current_stream()), "relgnn_relational_keys_all")
+            _lib.launch("relgnn_relational_keys_all", h_adj, h_cnt, L, self.V, _lib.ptr(key_t), _lib.ptr(key_s), _lib.ptr(node_t),
+                        _lib.ptr(node_s), _lib.ptr(err))
             self._key_t, self._key_s = key_t, key_s
 
     @property
@@ -351,11 +340,8 @@ class RelGraph:
     def src_t(self):
         """source NODE of each by-target position (row into an untransformed [V, D] table)."""
         if self._src_t is None:
-            lib = _lib.load_library()
             self._src_t = _i32(self.M, self.device)
-            _lib.check(lib.relgnn_gather_div_i32(_lib.ptr(self.key_by_source), _lib.ptr(self.perm_t),
-                                                 self.M, self.L, _lib.ptr(self._src_t),
-                                                 _lib.current_stream()), "relgnn_gather_div_i32")
+            _lib.launch("relgnn_gather_div_i32", _lib.ptr(self.key_by_source), _lib.ptr(self.perm_t), self.M, self.L, _lib.ptr(self._src_t))
         return self._src_t
 
     def degree_scale(self, type_to_num_incoming_edges: torch.Tensor) -> torch.Tensor:
@@ -370,10 +356,8 @@ class RelGraph:
             raise ValueError("type_to_num_incoming_edges must have shape [%d, %d]" % (self.L, self.V))
         tt = t.to(torch.float32).contiguous()
         w = torch.empty(self.M, dtype=torch.float32, device=self.device)
-        lib = _lib.load_library()
         if self.M > 0:           # an edge-free batch has no message to scale
-            _lib.check(lib.relgnn_degree_scale(_lib.ptr(tt), _lib.ptr(self.rowptr_t), self.L, self.V, 1e-7,
-                                           _lib.ptr(w), _lib.current_stream()), "relgnn_degree_scale")
+            _lib.launch("relgnn_degree_scale", _lib.ptr(tt), _lib.ptr(self.rowptr_t), self.L, self.V, 1e-7, _lib.ptr(w))
         self._scales[key] = (t, w)  # keep `t` alive so the data_ptr key cannot be recycled
         while len(self._scales) > 4:
             self._scales.popitem(last=False)
@@ -385,10 +369,8 @@ class RelGraph:
             return None
         key = ("w_s", w.data_ptr())
         if key not in self._plans:
-            lib = _lib.load_library()
             ws = torch.empty_like(w)
-            _lib.check(lib.relgnn_gather_f32(_lib.ptr(w), _lib.ptr(self.pos_t_of_s), self.M, _lib.ptr(ws),
-                                             _lib.current_stream()), "relgnn_gather_f32")
+            _lib.launch("relgnn_gather_f32", _lib.ptr(w), _lib.ptr(self.pos_t_of_s), self.M, _lib.ptr(ws))
             self._plans[key] = (w, ws)
         return self._plans[key][1]
 
@@ -396,10 +378,8 @@ class RelGraph:
         """per-message weights in the reference's type-major message order."""
         key = ("w_o", w.data_ptr())
         if key not in self._plans:
-            lib = _lib.load_library()
             wo = torch.empty_like(w)
-            _lib.check(lib.relgnn_gather_f32(_lib.ptr(w), _lib.ptr(self.inv_perm_t), self.M, _lib.ptr(wo),
-                                             _lib.current_stream()), "relgnn_gather_f32")
+            _lib.launch("relgnn_gather_f32", _lib.ptr(w), _lib.ptr(self.inv_perm_t), self.M, _lib.ptr(wo))
             self._plans[key] = (w, wo)
         return self._plans[key][1]
 
@@ -423,10 +403,8 @@ class RelGraph:
     def tgt_t(self):
         """target NODE of each by-target position."""
         if "tgt_t" not in self._plans:
-            lib = _lib.load_library()
             t = _i32(self.M, self.device)
-            _lib.check(lib.relgnn_gather_div_i32(_lib.ptr(self.key_by_target), _lib.ptr(self.perm_t), self.M, self.L,
-                                                 _lib.ptr(t), _lib.current_stream()), "relgnn_gather_div_i32")
+            _lib.launch("relgnn_gather_div_i32", _lib.ptr(self.key_by_target), _lib.ptr(self.perm_t), self.M, self.L, _lib.ptr(t))
             self._plans["tgt_t"] = t
         return self._plans["tgt_t"]
 
@@ -478,11 +456,9 @@ class RelGraph:
         if key not in self._plans:
             dev = self.device
             if "tgt_orig" not in self._plans:
-                lib = _lib.load_library()
                 t = _i32(self.M, dev)
                 ident = torch.arange(self.M, dtype=torch.int32, device=dev)
-                _lib.check(lib.relgnn_gather_div_i32(_lib.ptr(self.key_by_target), _lib.ptr(ident), self.M, self.L,
-                                                     _lib.ptr(t), _lib.current_stream()), "relgnn_gather_div_i32")
+                _lib.launch("relgnn_gather_div_i32", _lib.ptr(self.key_by_target), _lib.ptr(ident), self.M, self.L, _lib.ptr(t))
                 self._plans["tgt_orig"] = t
             self._plans[key] = (None, GatherReducePlan(
                 rowptr=self.rowptr_t, stride=self.L, col=self.perm_t, w=None, num_out=self.V, num_rows_x=self.M,
@@ -756,7 +732,7 @@ class PairTables:
     def node_csr_both(self):
         """(rowptr [V+1], col [num_pairs_src + num_pairs_tgt]) int32: node -> its rows in the by-source table FOLLOWED by its rows in
         the by-target table, the latter numbered behind the former (row + P_s) — the CSR of ONE reduction that sums the per-row
-        input gradients of both typed transforms of a layer into the nodes (ops._TypedLinearPair)."""
+        input gradients of both typed transforms of a layer into the nodes (ops._TypedLinearPanel over both tables)."""
         both = getattr(self, "_both", None)
         if both is None:
             a, b = self.src, self.tgt
@@ -783,15 +759,11 @@ class PairTables:
         whose output rows ARE the compact rows (the table is type-major, the by-source order of RelGraph node-major)."""
         if self._by_row is None:
             g = self._graph
-            lib = _lib.load_library()
-            st = _lib.current_stream()
             keys = self.src.bucket_row[g.key_by_source.long()].contiguous()            # row of every original message
             rowptr, perm, _ = build_segment_plan(keys, self.P_s)
             tgt, pos_t = _i32(g.M, g.device), _i32(g.M, g.device)
-            _lib.check(lib.relgnn_gather_div_i32(_lib.ptr(g.key_by_target), _lib.ptr(perm), g.M, g.L, _lib.ptr(tgt), st),
-                       "relgnn_gather_div_i32")
-            _lib.check(lib.relgnn_gather_i32(_lib.ptr(g.inv_perm_t), _lib.ptr(perm), g.M, _lib.ptr(pos_t), st),
-                       "relgnn_gather_i32")
+            _lib.launch("relgnn_gather_div_i32", _lib.ptr(g.key_by_target), _lib.ptr(perm), g.M, g.L, _lib.ptr(tgt))
+            _lib.launch("relgnn_gather_i32", _lib.ptr(g.inv_perm_t), _lib.ptr(perm), g.M, _lib.ptr(pos_t))
             self._by_row = (rowptr, tgt, pos_t)
         return self._by_row
 

@@ -69,7 +69,6 @@ class TFStyleOptimizer:
         import ctypes
         from .. import _lib
         lib = _lib.load_library()
-        st = _lib.current_stream()
         idx = [i for i, p in enumerate(self.params) if p.grad is not None]
         if not idx:
             return
@@ -78,7 +77,7 @@ class TFStyleOptimizer:
         dev_state = None
         if device_step_count and self.name == 'adam':
             dev_state = self._device_state()
-            _lib.check(lib.relgnn_adam_step_size(_lib.ptr(dev_state), lr, b1, b2, st), "relgnn_adam_step_size")
+            _lib.launch("relgnn_adam_step_size", _lib.ptr(dev_state), lr, b1, b2)
         elif not device_step_count:
             self.t += 1
             lr_t = lr * (1 - b2 ** self.t) ** 0.5 / (1 - b1 ** self.t)
@@ -93,21 +92,19 @@ class TFStyleOptimizer:
             h_n = (ctypes.c_int64 * n)(*[self.params[i].numel() for i in chunk])
             norms = torch.empty(n, dtype=torch.float32, device=self.params[chunk[0]].device)
             ws_bytes = lib.relgnn_mt_l2norm_workspace_bytes()
-            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=norms.device)
-            _lib.check(lib.relgnn_mt_l2norm(h_g, h_n, n, _lib.ptr(norms), _lib.ptr(ws), ws_bytes, st), "relgnn_mt_l2norm")
+            ws = _lib.scratch(ws_bytes, norms.device)
+            _lib.launch("relgnn_mt_l2norm", h_g, h_n, n, _lib.ptr(norms), _lib.ptr(ws), ws_bytes)
             h_s = [arr(*[t[i].data_ptr() for i in chunk]) for _, t in self._slots()]      # Adam: m, v; RMSProp: ms, mom; SGD: none
             d_norms, clip = _lib.ptr(norms), float(self.clip)
             if self.name == 'sgd':
-                what, rc = "relgnn_mt_sgd_clip", lib.relgnn_mt_sgd_clip(h_p, h_g, h_n, n, d_norms, clip, lr, st)
+                _lib.launch("relgnn_mt_sgd_clip", h_p, h_g, h_n, n, d_norms, clip, lr)
             elif self.name == 'rmsprop':
-                what, rc = "relgnn_mt_rmsprop_clip", lib.relgnn_mt_rmsprop_clip(
-                    h_p, h_g, *h_s, h_n, n, d_norms, clip, lr, float(self.decay), float(self.momentum), 1e-10, st)
+                _lib.launch("relgnn_mt_rmsprop_clip", h_p, h_g, *h_s, h_n, n, d_norms, clip, lr, float(self.decay), float(self.momentum),
+                            1e-10)
             elif dev_state is not None:
-                what, rc = "relgnn_mt_adam_clip_devlr", lib.relgnn_mt_adam_clip_devlr(
-                    h_p, h_g, *h_s, h_n, n, d_norms, clip, dev_state[1:].data_ptr(), b1, b2, eps, st)
+                _lib.launch("relgnn_mt_adam_clip_devlr", h_p, h_g, *h_s, h_n, n, d_norms, clip, dev_state[1:].data_ptr(), b1, b2, eps)
             else:
-                what, rc = "relgnn_mt_adam_clip", lib.relgnn_mt_adam_clip(h_p, h_g, *h_s, h_n, n, d_norms, clip, lr_t, b1, b2, eps, st)
-            _lib.check(rc, what)
+                _lib.launch("relgnn_mt_adam_clip", h_p, h_g, *h_s, h_n, n, d_norms, clip, lr_t, b1, b2, eps)
         from ..dense import weights_changed
         weights_changed()                  # (written through raw pointers: the tensors' version counters did not move)
 

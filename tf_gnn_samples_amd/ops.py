@@ -117,24 +117,16 @@ def _seg_reduce_raw(mode, X, rowptr, stride, col, w, num_out, act=_lib.ACT_LINEA
     split = getattr(rowptr, "_relgnn_split", None)
     if split is not None and stride in split:
         return _seg_reduce_split(mode, X, split[stride], col, w, num_out, act)
-    lib = _lib.load_library()
     D = X.shape[1]
     out = torch.empty((num_out, D), dtype=torch.float32, device=X.device)
+    args = (mode, _lib.ptr(X, rows_strided=True), X.shape[0], X.stride(0), D, _lib.ptr(rowptr), num_out, stride, _lib.ptr(col), _lib.ptr(w),
+            act, _lib.ptr(out), D)
     if rowmax is not None:
-        _lib.check(lib.relgnn_seg_reduce_fwd_rowmax(
-            mode, _lib.ptr(X, rows_strided=True), X.shape[0], X.stride(0), D, _lib.ptr(rowptr), num_out, stride,
-            _lib.ptr(col), _lib.ptr(w), act, _lib.ptr(out), D, _lib.ptr(rowmax), _lib.current_stream()),
-            "relgnn_seg_reduce_fwd_rowmax")
-        return out
-    if acc64 and mode != _lib.AGG_MAX and acc64_supported(D) and X.stride(0) % 4 == 0 and X.data_ptr() % 16 == 0:
-        _lib.check(lib.relgnn_seg_reduce_acc64_fwd(
-            mode, _lib.ptr(X, rows_strided=True), X.shape[0], X.stride(0), D, _lib.ptr(rowptr), num_out, stride,
-            _lib.ptr(col), _lib.ptr(w), act, _lib.ptr(out), D, _lib.current_stream()), "relgnn_seg_reduce_acc64_fwd")
-        return out
-    _lib.check(lib.relgnn_seg_reduce_fwd(
-        mode, _lib.ptr(X, rows_strided=True), X.shape[0], X.stride(0), D, _lib.ptr(rowptr), num_out, stride,
-        _lib.ptr(col), _lib.ptr(w), act, _lib.ptr(out), D, _lib.current_stream()),
-        "relgnn_seg_reduce_fwd")
+        _lib.launch("relgnn_seg_reduce_fwd_rowmax", *args, _lib.ptr(rowmax))
+    elif acc64 and mode != _lib.AGG_MAX and acc64_supported(D) and X.stride(0) % 4 == 0 and X.data_ptr() % 16 == 0:
+        _lib.launch("relgnn_seg_reduce_acc64_fwd", *args)
+    else:
+        _lib.launch("relgnn_seg_reduce_fwd", *args)
     return out
 
 
@@ -155,30 +147,22 @@ class _SegGatherReduce(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, gout):
-        lib = _lib.load_library()
-        st = _lib.current_stream()
+        from .dense import act_bwd_from_output
         plan, mode, act = ctx.plan, ctx.mode, ctx.act
         X, out = ctx.saved_tensors
         gout = gout.contiguous()
         D = gout.shape[1]
         if act != _lib.ACT_LINEAR:
-            g = torch.empty_like(gout)
-            _lib.check(lib.relgnn_act_bwd_from_output(act, _lib.ptr(out), _lib.ptr(gout), gout.numel(),
-                                                      _lib.ptr(g), st), "relgnn_act_bwd_from_output")
-            gout = g
+            gout = act_bwd_from_output(act, out, gout)
         if mode == _lib.AGG_MAX:
             if act != _lib.ACT_LINEAR:
                 raise RuntimeError("max aggregation is never fused with an activation epilogue")
             gsel = torch.empty_like(gout)
-            _lib.check(lib.relgnn_seg_max_count(
-                _lib.ptr(X), X.stride(0), D, _lib.ptr(plan.rowptr), plan.num_out, plan.stride,
-                _lib.ptr(plan.col), _lib.ptr(plan.w), _lib.ptr(out), _lib.ptr(gout), D, _lib.ptr(gsel), st),
-                "relgnn_seg_max_count")
+            _lib.launch("relgnn_seg_max_count", _lib.ptr(X), X.stride(0), D, _lib.ptr(plan.rowptr), plan.num_out, plan.stride,
+                        _lib.ptr(plan.col), _lib.ptr(plan.w), _lib.ptr(out), _lib.ptr(gout), D, _lib.ptr(gsel))
             gX = torch.empty((plan.num_rows_x, D), dtype=torch.float32, device=gout.device)
-            _lib.check(lib.relgnn_seg_max_bwd(
-                _lib.ptr(X), X.stride(0), D, _lib.ptr(plan.rowptr_b), plan.num_rows_x, plan.stride_b,
-                _lib.ptr(plan.col_b), _lib.ptr(plan.w_bwd(_lib.AGG_SUM)), _lib.ptr(out), _lib.ptr(gsel), D,
-                _lib.ptr(gX), D, st), "relgnn_seg_max_bwd")
+            _lib.launch("relgnn_seg_max_bwd", _lib.ptr(X), X.stride(0), D, _lib.ptr(plan.rowptr_b), plan.num_rows_x, plan.stride_b,
+                        _lib.ptr(plan.col_b), _lib.ptr(plan.w_bwd(_lib.AGG_SUM)), _lib.ptr(out), _lib.ptr(gsel), D, _lib.ptr(gX), D)
             return gX, None, None, None
         # sum / mean / sqrt_n: the gradient is the same gather-reduce over the transposed buckets
         gX = _seg_reduce_raw(_lib.AGG_SUM, gout, plan.rowptr_b, plan.stride_b, plan.col_b,
@@ -228,10 +212,8 @@ class SegmentPlanCache:
                 segments += 1
         num_segments = segments
         rowptr, perm, _ = build_segment_plan(ids, num_segments)
-        lib = _lib.load_library()
         inv = torch.empty_like(perm)
-        _lib.check(lib.relgnn_invert_perm(_lib.ptr(perm), M, _lib.ptr(inv), _lib.current_stream()),
-                   "relgnn_invert_perm")
+        _lib.launch("relgnn_invert_perm", _lib.ptr(perm), M, _lib.ptr(inv))
         plan = GatherReducePlan(
             rowptr=rowptr, stride=1, col=perm, w=None, num_out=num_segments, num_rows_x=M,
             rowptr_b=torch.arange(M + 1, dtype=torch.int32, device=ids.device), stride_b=1, col_b=ids,
@@ -292,7 +274,6 @@ class _FusedEdgeMessages(torch.autograd.Function):
     @staticmethod
     def forward(ctx, T, A, graph, w, mode: int, act: int, kind: str, pairs=None):
         """pairs (graph.PairTables, FiLM only): T / A hold rows for the non-empty (node,type) buckets only."""
-        lib = _lib.load_library()
         _check_f32(T, "T"); _check_f32(A, "A")
         T, A = T.contiguous(), A.contiguous()
         V, L = graph.V, graph.L
@@ -306,21 +287,17 @@ class _FusedEdgeMessages(torch.autograd.Function):
         if kind == "film":
             col = graph.col_t if pairs is None else pairs.col_t
             brow = None if pairs is None else pairs.tgt.bucket_row
-            _lib.check(lib.relgnn_film_fwd(mode, act, _lib.ptr(T), D, _lib.ptr(A), A.shape[1], D, _lib.ptr(graph.rowptr_t),
-                                           V, L, _lib.ptr(col), _lib.ptr(w), _lib.ptr(out), D, _lib.ptr(brow),
-                                           _lib.current_stream()), "relgnn_film_fwd")
+            _lib.launch("relgnn_film_fwd", mode, act, _lib.ptr(T), D, _lib.ptr(A), A.shape[1], D, _lib.ptr(graph.rowptr_t), V, L,
+                        _lib.ptr(col), _lib.ptr(w), _lib.ptr(out), D, _lib.ptr(brow))
         else:
-            _lib.check(lib.relgnn_pair_fwd(mode, act, _lib.ptr(T), D, _lib.ptr(A), A.shape[1], D, _lib.ptr(graph.rowptr_t),
-                                           V, L, _lib.ptr(graph.col_t), _lib.ptr(w), _lib.ptr(out), D,
-                                           _lib.current_stream()), "relgnn_pair_fwd")
+            _lib.launch("relgnn_pair_fwd", mode, act, _lib.ptr(T), D, _lib.ptr(A), A.shape[1], D, _lib.ptr(graph.rowptr_t), V, L,
+                        _lib.ptr(graph.col_t), _lib.ptr(w), _lib.ptr(out), D)
         ctx.graph, ctx.w, ctx.mode, ctx.act, ctx.kind, ctx.pairs = graph, w, mode, act, kind, pairs
         ctx.save_for_backward(T, A)
         return out
 
     @staticmethod
     def backward(ctx, gout):
-        lib = _lib.load_library()
-        st = _lib.current_stream()
         graph, w, mode, act, kind, pairs = ctx.graph, ctx.w, ctx.mode, ctx.act, ctx.kind, ctx.pairs
         if mode == _lib.AGG_MAX:
             raise RuntimeError("fused %s messages have no max-aggregation backward; the layer uses the unfused path" % kind)
@@ -357,14 +334,12 @@ class _FusedEdgeMessages(torch.autograd.Function):
         if kind == "film":
             col = graph.col_t if pairs is None else pairs.col_t
             brow_t = None if pairs is None else pairs.tgt.bucket_row
-            _lib.check(lib.relgnn_film_bwd_film(act, _lib.ptr(T), D, _lib.ptr(A), A.shape[1], D, _lib.ptr(graph.rowptr_t),
-                                                V, L, _lib.ptr(col), _lib.ptr(w), _lib.ptr(gagg), D,
-                                                _lib.ptr(gA), A.shape[1], _lib.ptr(brow_t), _lib.ptr(dmsg), _lib.ptr(smask), st),
-                       "relgnn_film_bwd_film")
+            _lib.launch("relgnn_film_bwd_film", act, _lib.ptr(T), D, _lib.ptr(A), A.shape[1], D, _lib.ptr(graph.rowptr_t), V, L,
+                        _lib.ptr(col), _lib.ptr(w), _lib.ptr(gagg), D, _lib.ptr(gA), A.shape[1], _lib.ptr(brow_t), _lib.ptr(dmsg),
+                        _lib.ptr(smask))
         else:
-            _lib.check(lib.relgnn_pair_bwd_q(act, _lib.ptr(T), D, _lib.ptr(A), D, D, _lib.ptr(graph.rowptr_t), V, L,
-                                             _lib.ptr(graph.col_t), _lib.ptr(w), _lib.ptr(gagg), D, _lib.ptr(gA), D,
-                                             _lib.ptr(dmsg), st), "relgnn_pair_bwd_q")
+            _lib.launch("relgnn_pair_bwd_q", act, _lib.ptr(T), D, _lib.ptr(A), D, D, _lib.ptr(graph.rowptr_t), V, L, _lib.ptr(graph.col_t),
+                        _lib.ptr(w), _lib.ptr(gagg), D, _lib.ptr(gA), D, _lib.ptr(dmsg))
         if emit:
             if pairs is None:
                 gT = _seg_reduce_raw(_lib.AGG_SUM, dmsg, graph.rowptr_s, 1, graph.pos_t_of_s, None, V * L)
@@ -373,40 +348,30 @@ class _FusedEdgeMessages(torch.autograd.Function):
                 gT = _seg_reduce_raw(_lib.AGG_SUM, dmsg, rowptr_c, 1, pos_c, None, pairs.P_s)   # padding rows: zero
         elif smask is not None:
             gT = torch.empty_like(T)
-            _lib.check(lib.relgnn_film_bwd_msg_masked(act, _lib.ptr(A), A.shape[1], D, _lib.ptr(graph.rowptr_s), V * L,
-                                                      _lib.ptr(graph.tgt_s), _lib.ptr(graph.frow_s),
-                                                      _lib.ptr(graph.w_by_source(w)), _lib.ptr(graph.pos_t_of_s),
-                                                      _lib.ptr(smask), _lib.ptr(gagg), D, _lib.ptr(gT), D, st),
-                       "relgnn_film_bwd_msg_masked")
+            _lib.launch("relgnn_film_bwd_msg_masked", act, _lib.ptr(A), A.shape[1], D, _lib.ptr(graph.rowptr_s), V * L,
+                        _lib.ptr(graph.tgt_s), _lib.ptr(graph.frow_s), _lib.ptr(graph.w_by_source(w)), _lib.ptr(graph.pos_t_of_s),
+                        _lib.ptr(smask), _lib.ptr(gagg), D, _lib.ptr(gT), D)
         elif kind == "film":
             gT = torch.empty_like(T)
             if pairs is not None:
                 _fill_rows(gT, pairs.src.pad_rows, 0.0)
             frow = graph.frow_s if pairs is None else pairs.frow_s
             brow_s = None if pairs is None else pairs.src.bucket_row
-            _lib.check(lib.relgnn_film_bwd_msg(act, _lib.ptr(T), D, _lib.ptr(A), A.shape[1], D, _lib.ptr(graph.rowptr_s),
-                                               V * L, _lib.ptr(graph.tgt_s), _lib.ptr(frow),
-                                               _lib.ptr(graph.w_by_source(w)), _lib.ptr(gagg), D, _lib.ptr(gT), D,
-                                               _lib.ptr(brow_s), st), "relgnn_film_bwd_msg")
+            _lib.launch("relgnn_film_bwd_msg", act, _lib.ptr(T), D, _lib.ptr(A), A.shape[1], D, _lib.ptr(graph.rowptr_s), V * L,
+                        _lib.ptr(graph.tgt_s), _lib.ptr(frow), _lib.ptr(graph.w_by_source(w)), _lib.ptr(gagg), D, _lib.ptr(gT), D,
+                        _lib.ptr(brow_s))
         else:
             gT = torch.empty_like(T)
-            _lib.check(lib.relgnn_pair_bwd_p(act, _lib.ptr(T), D, _lib.ptr(A), D, D, _lib.ptr(graph.rowptr_s), V * L,
-                                             _lib.ptr(graph.tgt_s), _lib.ptr(graph.frow_s), _lib.ptr(graph.w_by_source(w)),
-                                             _lib.ptr(gagg), D, _lib.ptr(gT), D, st), "relgnn_pair_bwd_p")
+            _lib.launch("relgnn_pair_bwd_p", act, _lib.ptr(T), D, _lib.ptr(A), D, D, _lib.ptr(graph.rowptr_s), V * L, _lib.ptr(graph.tgt_s),
+                        _lib.ptr(graph.frow_s), _lib.ptr(graph.w_by_source(w)), _lib.ptr(gagg), D, _lib.ptr(gT), D)
         return gT, gA, None, None, None, None, None, None
 
 
 def film_messages_reduce(T, film, graph, w, aggregation: str, activation: Optional[str], pairs=None):
     """gnns/gnn_film.py:92-116 in one kernel (sum / mean / sqrt_n; max forward only).  With `pairs`
     (graph.PairTables) T is [P_s, D] and film [P_t, 2D]: rows for the non-empty (node,type) buckets only."""
-    D = T.shape[1]
-    pad = (-D) % 4
-    if pad:                                       # [gamma | beta] halves padded separately (see _pad_columns)
-        film = torch.nn.functional.pad(film.reshape(film.shape[0], 2, D), (0, pad)).reshape(film.shape[0], 2 * (D + pad))
-        return _FusedEdgeMessages.apply(_pad_columns(T, pad), film, graph, w, aggregation_mode_id(aggregation),
-                                        activation_id(activation), "film", pairs)[:, :D]
-    return _FusedEdgeMessages.apply(T, film, graph, w, aggregation_mode_id(aggregation), activation_id(activation),
-                                    "film", pairs)
+    return _on_padded_columns(_FusedEdgeMessages, (T, film), graph, w, aggregation_mode_id(aggregation), activation_id(activation),
+                              "film", pairs)
 
 
 class _TypedLinear(torch.autograd.Function):
@@ -485,21 +450,27 @@ class _BlockedLinear(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, gY):
-        from .dense import GEMM_NT, matmul_tn_splitk, mm_into
         X, *weights = ctx.saved_tensors
-        offsets = ctx.offsets
-        gY = gY.contiguous()
-        gX = torch.empty_like(X) if ctx.needs_input_grad[0] else None
-        gW = []
-        for l, W in enumerate(weights):
-            a, b = offsets[l], offsets[l + 1]
-            if b > a:
-                if gX is not None:
-                    mm_into(GEMM_NT, gY[a:b], W, gX[a:b])
-                gW.append(matmul_tn_splitk(X[a:b], gY[a:b]) if ctx.needs_input_grad[2 + l] else None)
-            else:
-                gW.append(torch.zeros_like(W) if ctx.needs_input_grad[2 + l] else None)
+        gX, gW = _blocked_backward(X, gY.contiguous(), ctx.offsets, weights, ctx.needs_input_grad[0], ctx.needs_input_grad[2:])
         return (gX, None, *gW)
+
+
+def _blocked_backward(left, gY, offsets, weights, need_x: bool, need_w):
+    """(gX, [gW_l]) of Y[a_l:b_l] = left[a_l:b_l] @ W_l: per non-empty row block gX[a:b] = gY[a:b] @ W_l^T written in place and
+    gW_l = left[a:b]^T @ gY[a:b] (split-K over the block's rows); an empty block's weight gradient is zero.  need_w: one flag per
+    block; `left` is read for the weight gradients only."""
+    from .dense import GEMM_NT, matmul_tn_splitk, mm_into
+    gX = torch.empty((gY.shape[0], weights[0].shape[0]), dtype=torch.float32, device=gY.device) if need_x else None
+    gW = []
+    for l, W in enumerate(weights):
+        a, b = offsets[l], offsets[l + 1]
+        if b > a:
+            if need_x:
+                mm_into(GEMM_NT, gY[a:b], W, gX[a:b])
+            gW.append(matmul_tn_splitk(left[a:b], gY[a:b]) if need_w[l] else None)
+        else:
+            gW.append(torch.zeros_like(W) if need_w[l] else None)
+    return gX, gW
 
 
 def blocked_linear(X, offsets, weights):
@@ -515,8 +486,7 @@ def _fill_rows(X: torch.Tensor, rows: torch.Tensor, value: float) -> None:
     if not (X.is_cuda and X.dtype == torch.float32 and X.dim() == 2 and X.stride(1) == 1 and rows.dtype == torch.int64 and rows.is_contiguous()):
         X.index_fill_(0, rows, value)
         return
-    _lib.check(_lib.load_library().relgnn_fill_rows_f32(X.data_ptr(), X.stride(0), X.shape[1], rows.data_ptr(), rows.numel(), float(value),
-                                                        _lib.current_stream()), "relgnn_fill_rows_f32")
+    _lib.launch("relgnn_fill_rows_f32", X.data_ptr(), X.stride(0), X.shape[1], rows.data_ptr(), rows.numel(), float(value))
 
 
 def _typed_weight_gradient(H, gY, side, L: int, Din: int, Dout: int):
@@ -576,50 +546,83 @@ def _typed_input_gradient(gY, side, weights, W, out=None):
     return gX if out is None else out.copy_(gX)
 
 
-class _TypedLinearPair(torch.autograd.Function):
-    """The two per-(node, type) transforms of a GNN-FiLM layer (gnns/gnn_film.py:92-106: messages h_u W_l over the by-source pair
-    table, FiLM weights h_v F_l over the by-target one) as ONE autograd node: the forward is the two products of
-    _TypedLinearPanel; the backward sums BOTH tables' per-row input gradients into the nodes with one gather-reduce over a
-    combined node -> rows CSR (graph.PairTables.node_csr_both) instead of two reductions and an addition of their [V, D] results
-    (round 6: one launch and ~0.1 ms less per layer of the C5 step).  Cached limb images only (dense.sel_image)."""
+class _TypedLinearPanel(torch.autograd.Function):
+    """_TypedLinear on the row-panel MFMA kernels, for one pair table or several over the same node states H: the gather H[node[r]]
+    and the per-tile kernel selection happen in the kernel's load addresses.  Nothing [P, Din] (the gathered rows) and nothing
+    [tiles, Din, Dout] (a per-tile copy of the kernels) is materialised, forward or backward.  Per table:
+      forward   Y  = gather(H) @ W_type            one launch (NN, gathered rows, per-tile B)
+      backward  dX = dY @ W_type^T                 one launch (NT with the kernels as stored)
+                dW = per-tile gather(H)^T @ dY     one launch (TN, gathered reduction rows, one product per tile), the per-tile
+                                                   partials summed per type by the gather-reduce kernel (tile order)
+    and ONE gather-reduce sums the stacked dX rows of all tables into the nodes over `node_csr` (ascending type order).  The two
+    per-(node, type) transforms of a GNN-FiLM layer (gnns/gnn_film.py:92-106: messages h_u W_l over the by-source table, FiLM
+    weights h_v F_l over the by-target one) are one node over graph.PairTables.node_csr_both instead of two reductions and an
+    addition of their [V, D] results (round 6: one launch and ~0.1 ms less per layer of the C5 step).
+      tables    ((side, L), ..): graph.SidePairs and how many of *weights, in order, are its per-type kernels
+      node_csr  () -> (rowptr, col): the node -> rows CSR over the tables' rows one behind the other
+      leaves    the weights themselves, when every one is a leaf parameter"""
 
     @staticmethod
-    def forward(ctx, H, pairs, leaves, La: int, *weights):
-        ctx.leaf_params, ctx.pairs, ctx.La = leaves, pairs, La
-        ctx.save_for_backward(H, *weights)
-        return tuple(_typed_product(H, side, ws)[0] for side, ws in ((pairs.src, weights[:La]), (pairs.tgt, weights[La:])))
+    def forward(ctx, H, tables, node_csr, leaves, *weights):
+        ctx.leaf_params, ctx.node_csr = leaves, node_csr
+        outs, kept, saved, at = [], [], [H], 0
+        for side, L in tables:
+            ws = weights[at:at + L]
+            at += L
+            Y, W = _typed_product(H, side, ws)
+            outs.append(Y)
+            # the per-type kernels where the product read their cached images (W is None), else the stacked copy it read
+            kept.append((side, (L, *ws[0].shape), W is None, L if W is None else 1))
+            saved.extend(ws if W is None else (W,))
+        ctx.tables = kept
+        ctx.save_for_backward(*saved)
+        return tuple(outs)
 
     @staticmethod
-    def backward(ctx, gYa, gYb):
-        H, *weights = ctx.saved_tensors
-        pairs, La = ctx.pairs, ctx.La
-        sides = ((pairs.src, weights[:La], gYa.contiguous()), (pairs.tgt, weights[La:], gYb.contiguous()))
-        Din = weights[0].shape[0]
+    def backward(ctx, *gYs):
+        H, *saved = ctx.saved_tensors
+        gYs = [g.contiguous() for g in gYs]
         need = ctx.needs_input_grad[4:]
         want_w = any(need)
 
         def weight_side():
-            flat = sum((_typed_weight_gradient(H, g, side, len(ws), Din, ws[0].shape[1]).unbind(0) for side, ws, g in sides), ())
+            flat = sum((_typed_weight_gradient(H, g, side, *shape).unbind(0) for (side, shape, _, _), g in zip(ctx.tables, gYs)), ())
             return tuple(g if n else None for g, n in zip(flat, need))
 
-        aside = fork(weight_side, (H, sides[0][2], sides[1][2]), ctx.leaf_params, want=want_w and ctx.needs_input_grad[0],
+        # The weight gradients (exact-fp32 matrix pipe, ~0.25-0.5 ms per product on a 23-type batch) depend on nothing the input
+        # gradient computes: they run on the side stream of the aggregate-first layer's weight gradient, under the memory-bound
+        # kernels that follow on the main stream (the row sums, the next layer's fused edge backward); the join is deferred behind
+        # the whole backward inside train_step (weight_grad_stream.deferred_weight_gradient_join).
+        aside = fork(weight_side, (H, *gYs), ctx.leaf_params, want=want_w and ctx.needs_input_grad[0],
                      join_in_backward=True, contributes=want_w)
         gH = None
         if ctx.needs_input_grad[0]:
-            gX = torch.empty((pairs.src.P + pairs.tgt.P, Din), dtype=torch.float32, device=H.device)
-            at = 0
-            for side, ws, g in sides:
-                _typed_input_gradient(g, side, ws, None, out=gX[at:at + side.P])
-                at += side.P
-            rowptr, col = pairs.node_csr_both()
-            gH = _seg_reduce_raw(_lib.AGG_SUM, gX, rowptr, 1, col, None, H.shape[0])
-        gWs = aside.join() if aside is not None else (weight_side() if want_w else (None,) * len(weights))
+            # (one table: its rows need no stacking, the product's own output is reduced)
+            stacked = None if len(gYs) == 1 else torch.empty((sum(t[0].P for t in ctx.tables), H.shape[1]), dtype=torch.float32,
+                                                             device=H.device)
+            at = row = 0
+            for (side, _, cached, count), g in zip(ctx.tables, gYs):
+                kept = saved[at:at + count]
+                out = None if stacked is None else stacked[row:row + side.P]
+                gX = _typed_input_gradient(g, side, kept if cached else None, None if cached else kept[0], out=out)
+                at, row = at + count, row + side.P
+            rowptr, col = ctx.node_csr()
+            gH = _seg_reduce_raw(_lib.AGG_SUM, gX if stacked is None else stacked, rowptr, 1, col, None, H.shape[0])
+        gWs = aside.join() if aside is not None else (weight_side() if want_w else (None,) * len(need))
         return (gH, None, None, None) + gWs
+
+
+def _typed_panel(H, tables, node_csr):
+    """_TypedLinearPanel over tables ((side, weights), ..): one [P, Dout] table each."""
+    allw = [w for _, ws in tables for w in ws]
+    leaves = tuple(allw) if all(w.is_leaf and w.requires_grad for w in allw) else None
+    return _TypedLinearPanel.apply(H, tuple((side, len(ws)) for side, ws in tables), node_csr, leaves, *allw)
 
 
 def typed_linear_pair(H, pairs, weights_src, weights_tgt):
     """(typed_linear(H, pairs.src, weights_src), typed_linear(H, pairs.tgt, weights_tgt)) with ONE reduction of both input
-    gradients into the nodes (_TypedLinearPair) where the cached limb route applies; else the two separate calls."""
+    gradients into the nodes (one _TypedLinearPanel over both tables) where the cached limb route applies; else the two separate
+    calls."""
     from .dense import GEMM_NN, GEMM_NT, sel_image
     weights_src, weights_tgt = list(weights_src), list(weights_tgt)
     _check_f32(H, "H")
@@ -633,56 +636,7 @@ def typed_linear_pair(H, pairs, weights_src, weights_tgt):
                 and sel_image(ws, GEMM_NT) is not None
     if not ok:
         return typed_linear(H, pairs.src, weights_src), typed_linear(H, pairs.tgt, weights_tgt)
-    allw = weights_src + weights_tgt
-    leaves = tuple(allw) if all(w.is_leaf and w.requires_grad for w in allw) else None
-    return _TypedLinearPair.apply(H, pairs, leaves, len(weights_src), *allw)
-
-
-class _TypedLinearPanel(torch.autograd.Function):
-    """_TypedLinear on the row-panel MFMA kernel (csrc/panel_gemm.hip): the gather H[node[r]] and the per-tile kernel
-    selection happen in the kernel's load addresses.  Nothing [P, Din] (the gathered rows) and nothing [tiles, Din, Dout] (a
-    per-tile copy of the kernels) is materialised, forward or backward:
-      forward   Y  = gather(H) @ W_type            one launch (NN, gathered rows, per-tile B)
-      backward  dX = dY @ W_type^T                 one launch (NT with the kernels as stored), summed into nodes over the
-                                                   node -> rows CSR by the gather-reduce kernel (ascending type order)
-                dW = per-tile gather(H)^T @ dY     one launch (TN, gathered reduction rows, one product per tile), the per-tile
-                                                   partials summed per type by the gather-reduce kernel (tile order)"""
-
-    @staticmethod
-    def forward(ctx, H, side, leaves, *weights):
-        ctx.leaf_params = leaves            # the per-type weights themselves, when every one is a leaf parameter
-        Y, W = _typed_product(H, side, weights)
-        ctx.side, ctx.shape, ctx.cached = side, (len(weights), *weights[0].shape), W is None
-        if ctx.cached:
-            ctx.save_for_backward(H, *weights)
-        else:
-            ctx.save_for_backward(H, W)
-        return Y
-
-    @staticmethod
-    def backward(ctx, gY):
-        H, *saved = ctx.saved_tensors
-        side = ctx.side
-        L, Din, Dout = ctx.shape
-        gY = gY.contiguous()
-        need = ctx.needs_input_grad[3:]
-        want_w = any(need)
-
-        def weight_side():
-            return tuple(g if n else None for g, n in zip(_typed_weight_gradient(H, gY, side, L, Din, Dout).unbind(0), need))
-
-        # The weight gradient (exact-fp32 matrix pipe, ~0.25-0.5 ms per product on a 23-type batch) depends on nothing the input
-        # gradient computes: it runs on the side stream of the aggregate-first layer's weight gradient, under the memory-bound
-        # kernels that follow on the main stream (the other typed product's row sums, the next layer's fused edge backward); the
-        # join is deferred behind the whole backward inside train_step (weight_grad_stream.deferred_weight_gradient_join).
-        aside = fork(weight_side, (H, gY), ctx.leaf_params, want=want_w and ctx.needs_input_grad[0],
-                     join_in_backward=True, contributes=want_w)
-        gH = None
-        if ctx.needs_input_grad[0]:
-            gX = _typed_input_gradient(gY, side, saved, None) if ctx.cached else _typed_input_gradient(gY, side, None, saved[0])
-            gH = _seg_reduce_raw(_lib.AGG_SUM, gX, side.node_rowptr, 1, side.node_col, None, H.shape[0])
-        gWs = aside.join() if aside is not None else (weight_side() if want_w else (None,) * L)
-        return (gH, None, None) + gWs
+    return _typed_panel(H, ((pairs.src, weights_src), (pairs.tgt, weights_tgt)), pairs.node_csr_both)
 
 
 def _typed_limb_ok(k: int, n: int) -> bool:
@@ -703,19 +657,12 @@ def typed_linear(H, side, weights):
     _check_f32(H, "H")
     H = H.contiguous()
     if _typed_panel_ok(H, side, weights):
-        weights = list(weights)
-        leaves = tuple(weights) if all(w.is_leaf and w.requires_grad for w in weights) else None
-        return _TypedLinearPanel.apply(H, side, leaves, *weights)
+        return _typed_panel(H, ((side, list(weights)),), lambda: (side.node_rowptr, side.node_col))[0]
     return _TypedLinear.apply(H, side, *weights)
 
 
 def pair_messages_reduce_fused(P, Q, graph, w, aggregation: str, activation: Optional[str]):
-    D = P.shape[1]
-    pad = (-D) % 4
-    if pad:
-        return _FusedEdgeMessages.apply(_pad_columns(P, pad), _pad_columns(Q, pad), graph, w, aggregation_mode_id(aggregation),
-                                        activation_id(activation), "pair")[:, :D]
-    return _FusedEdgeMessages.apply(P, Q, graph, w, aggregation_mode_id(aggregation), activation_id(activation), "pair")
+    return _on_padded_columns(_FusedEdgeMessages, (P, Q), graph, w, aggregation_mode_id(aggregation), activation_id(activation), "pair")
 
 
 class _PairMaterialize(torch.autograd.Function):
@@ -723,14 +670,12 @@ class _PairMaterialize(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, P, Q, graph, act: int):
-        lib = _lib.load_library()
         P = P.contiguous()
         Q = Q.contiguous() if Q is not None else None
         M, D = graph.M, P.shape[1]
         out = torch.empty((M, D), dtype=torch.float32, device=P.device)
-        _lib.check(lib.relgnn_pair_materialize(act, _lib.ptr(P), D, _lib.ptr(Q), D, D, _lib.ptr(graph.key_by_source),
-                                               _lib.ptr(graph.key_by_target), M, None, _lib.ptr(out), D,
-                                               _lib.current_stream()), "relgnn_pair_materialize")
+        _lib.launch("relgnn_pair_materialize", act, _lib.ptr(P), D, _lib.ptr(Q), D, D, _lib.ptr(graph.key_by_source),
+                    _lib.ptr(graph.key_by_target), M, None, _lib.ptr(out), D)
         ctx.graph, ctx.act, ctx.has_q = graph, act, Q is not None
         ctx.save_for_backward(P, Q)
         return out
@@ -745,7 +690,6 @@ class _PairMaterialize(torch.autograd.Function):
 def _pair_hidden_backward(P, Q, graph, act: int, ghidden):
     """(gP, gQ) from the gradient of hidden[m] = act(P[src_m*L+l_m] + Q[tgt_m*L+l_m]) (Q may be None: gQ is None then) — the
     backward of _PairMaterialize and the tail of _EdgeMlpFirstProduct's."""
-    lib = _lib.load_library()
     has_q = Q is not None
     M, D = graph.M, P.shape[1]
     ghidden = ghidden.contiguous()
@@ -757,37 +701,40 @@ def _pair_hidden_backward(P, Q, graph, act: int, ghidden):
         # the message's own row here), once over the by-source buckets for gP and once over the by-target buckets with
         # the roles of P and Q swapped for gQ.  C2 shape, elu: 959 + 2 x 423 us -> 2 x ~500 us per layer.
         gP, gQ = torch.empty_like(P), torch.empty_like(Q)
-        st = _lib.current_stream()
-        _lib.check(lib.relgnn_pair_bwd_p(act, _lib.ptr(P), D, _lib.ptr(Q), D, D, _lib.ptr(graph.rowptr_s), S,
-                                         _lib.ptr(graph.perm_s), _lib.ptr(graph.frow_s), None, _lib.ptr(ghidden), D,
-                                         _lib.ptr(gP), D, st), "relgnn_pair_bwd_p")
-        _lib.check(lib.relgnn_pair_bwd_p(act, _lib.ptr(Q), D, _lib.ptr(P), D, D, _lib.ptr(graph.rowptr_t), S,
-                                         _lib.ptr(graph.perm_t), _lib.ptr(graph.col_t), None, _lib.ptr(ghidden), D,
-                                         _lib.ptr(gQ), D, st), "relgnn_pair_bwd_p")
+        _lib.launch("relgnn_pair_bwd_p", act, _lib.ptr(P), D, _lib.ptr(Q), D, D, _lib.ptr(graph.rowptr_s), S, _lib.ptr(graph.perm_s),
+                    _lib.ptr(graph.frow_s), None, _lib.ptr(ghidden), D, _lib.ptr(gP), D)
+        _lib.launch("relgnn_pair_bwd_p", act, _lib.ptr(Q), D, _lib.ptr(P), D, D, _lib.ptr(graph.rowptr_t), S, _lib.ptr(graph.perm_t),
+                    _lib.ptr(graph.col_t), None, _lib.ptr(ghidden), D, _lib.ptr(gQ), D)
         return gP, gQ
     gpre = torch.empty_like(ghidden)
-    _lib.check(lib.relgnn_pair_materialize(act, _lib.ptr(P), D, _lib.ptr(Q), D, D, _lib.ptr(graph.key_by_source),
-                                           _lib.ptr(graph.key_by_target), M, _lib.ptr(ghidden), _lib.ptr(gpre), D,
-                                           _lib.current_stream()), "relgnn_pair_materialize")
+    _lib.launch("relgnn_pair_materialize", act, _lib.ptr(P), D, _lib.ptr(Q), D, D, _lib.ptr(graph.key_by_source),
+                _lib.ptr(graph.key_by_target), M, _lib.ptr(ghidden), _lib.ptr(gpre), D)
     # gP[r] = sum of gpre over the messages whose source row is r; gQ[f] likewise by target row
     gP = _seg_reduce_raw(_lib.AGG_SUM, gpre, graph.rowptr_s, 1, graph.perm_s, None, S)
     gQ = _seg_reduce_raw(_lib.AGG_SUM, gpre, graph.rowptr_t, 1, graph.perm_t, None, S) if has_q else None
     return gP, gQ
 
 
-def _pad_columns(X, pad: int):
-    """[rows, D] -> [rows, D + pad] with zero columns: the edge kernels move 16-byte pieces of a row (D % 4 == 0).  A width the
-    reference accepts and they do not (hidden_size 15) runs on padded tables: every message activation maps 0 to 0, so the padded
-    columns stay 0 through product, scale, activation and every aggregation, and are cut off again (differentiable: F.pad / slice)."""
-    return torch.nn.functional.pad(X, (0, pad)) if X is not None else None
+def _on_padded_columns(node, tables, *rest):
+    """node.apply(*tables, *rest) for tables [rows, D] (or [rows, k * D]: k blocks of D columns, FiLM's [gamma | beta]; or None).  The
+    edge kernels move 16-byte pieces of a row (D % 4 == 0).  A width the reference accepts and they do not (hidden_size 15) runs on
+    tables whose every block has zero columns behind it: every message activation maps 0 to 0, so the padded columns stay 0 through
+    product, scale, activation and every aggregation, and are cut off again (differentiable: F.pad / slice)."""
+    D = tables[0].shape[1]
+    pad = (-D) % 4
+    if not pad:
+        return node.apply(*tables, *rest)
+
+    def padded(X):
+        if X is None or X.shape[1] == D:
+            return torch.nn.functional.pad(X, (0, pad)) if X is not None else None
+        return torch.nn.functional.pad(X.reshape(X.shape[0], -1, D), (0, pad)).reshape(X.shape[0], -1)
+
+    return node.apply(*map(padded, tables), *rest)[:, :D]
 
 
 def pair_materialize(P, Q, graph, activation: Optional[str]):
-    D = P.shape[1]
-    pad = (-D) % 4
-    if pad:
-        return _PairMaterialize.apply(_pad_columns(P, pad), _pad_columns(Q, pad), graph, activation_id(activation))[:, :D]
-    return _PairMaterialize.apply(P, Q, graph, activation_id(activation))
+    return _on_padded_columns(_PairMaterialize, (P, Q), graph, activation_id(activation))
 
 
 class _EdgeMlpFirstProduct(torch.autograd.Function):
@@ -802,7 +749,6 @@ class _EdgeMlpFirstProduct(torch.autograd.Function):
     @staticmethod
     def forward(ctx, P, Q, graph, in_act: int, out_act: int, *weights):
         from .dense import GEMM_NN, sel_image
-        lib = _lib.load_library()
         P = P.contiguous()
         Q = Q.contiguous() if Q is not None else None
         M, (K, N) = graph.M, weights[0].shape
@@ -811,18 +757,16 @@ class _EdgeMlpFirstProduct(torch.autograd.Function):
             raise ValueError("edge_mlp_first_product: the weights have no cached limb image (dense.sel_weights_cacheable)")
         panels = graph.edge_mlp_panels()
         C = torch.empty((M, N), dtype=torch.float32, device=P.device)
-        _lib.check(lib.relgnn_edge_mlp_fwd_xf32(in_act, out_act, _lib.ptr(P), P.stride(0), _lib.ptr(Q), Q.stride(0) if Q is not None else 0,
-                                                _lib.ptr(graph.key_by_source), _lib.ptr(graph.key_by_target), im.buf.data_ptr(),
-                                                len(weights), _lib.ptr(panels), panels.shape[0], _lib.ptr(C), N, M, N, K,
-                                                _lib.current_stream()), "relgnn_edge_mlp_fwd_xf32")
+        _lib.launch("relgnn_edge_mlp_fwd_xf32", in_act, out_act, _lib.ptr(P), P.stride(0), _lib.ptr(Q), Q.stride(0) if Q is not None else 0,
+                    _lib.ptr(graph.key_by_source), _lib.ptr(graph.key_by_target), im.buf.data_ptr(), len(weights), _lib.ptr(panels),
+                    panels.shape[0], _lib.ptr(C), N, M, N, K)
         ctx.graph, ctx.acts, ctx.has_q = graph, (in_act, out_act), Q is not None
         ctx.save_for_backward(P, Q, C if out_act != _lib.ACT_LINEAR else None, *weights)
         return C
 
     @staticmethod
     def backward(ctx, gC):
-        from .dense import GEMM_NT, act_bwd_from_output, matmul_tn_splitk, mm_into
-        lib = _lib.load_library()
+        from .dense import act_bwd_from_output
         P, Q, C, *weights = ctx.saved_tensors
         graph, (in_act, out_act) = ctx.graph, ctx.acts
         M, K = graph.M, P.shape[1]
@@ -831,25 +775,14 @@ class _EdgeMlpFirstProduct(torch.autograd.Function):
             gC = act_bwd_from_output(out_act, C, gC)
         need_w = ctx.needs_input_grad[5:]
         need_h = ctx.needs_input_grad[0] or ctx.needs_input_grad[1]
-        offsets = graph.type_offsets
         hidden = None
         if any(need_w) and M > 0:
             # (the one pass through HBM that a gathered-operand weight-gradient kernel would remove: everything below reads
             #  `hidden` as the left operand of a TN product only)
             hidden = torch.empty((M, K), dtype=torch.float32, device=P.device)
-            _lib.check(lib.relgnn_pair_materialize(in_act, _lib.ptr(P), K, _lib.ptr(Q), K, K, _lib.ptr(graph.key_by_source),
-                                                   _lib.ptr(graph.key_by_target), M, None, _lib.ptr(hidden), K,
-                                                   _lib.current_stream()), "relgnn_pair_materialize")
-        gH = torch.empty((M, K), dtype=torch.float32, device=P.device) if need_h else None
-        gW = []
-        for l, W in enumerate(weights):
-            a, b = offsets[l], offsets[l + 1]
-            if b > a:
-                if gH is not None:
-                    mm_into(GEMM_NT, gC[a:b], W, gH[a:b])
-                gW.append(matmul_tn_splitk(hidden[a:b], gC[a:b]) if need_w[l] else None)
-            else:
-                gW.append(torch.zeros_like(W) if need_w[l] else None)
+            _lib.launch("relgnn_pair_materialize", in_act, _lib.ptr(P), K, _lib.ptr(Q), K, K, _lib.ptr(graph.key_by_source),
+                        _lib.ptr(graph.key_by_target), M, None, _lib.ptr(hidden), K)
+        gH, gW = _blocked_backward(hidden, gC, graph.type_offsets, weights, need_h, need_w)
         del hidden
         gP = gQ = None
         if need_h:
@@ -884,8 +817,6 @@ def _rgat_dz_fast_ok(D: int, K: int) -> bool:
 class _RgatAttention(torch.autograd.Function):
     @staticmethod
     def forward(ctx, T, s_src, s_tgt, graph, num_heads: int, slope: float):
-        lib = _lib.load_library()
-        st = _lib.current_stream()
         T, s_src, s_tgt = T.contiguous(), s_src.contiguous(), s_tgt.contiguous()
         V, L, M = graph.V, graph.L, graph.M
         D = T.shape[1]
@@ -893,23 +824,19 @@ class _RgatAttention(torch.autograd.Function):
         alpha = torch.empty((M, num_heads), dtype=torch.float32, device=T.device)
         fast = _rgat_fast_ok(D, num_heads)
         if fast:
-            _lib.check(lib.relgnn_rgat_alpha(_lib.ptr(s_src), _lib.ptr(s_tgt), num_heads, _lib.ptr(graph.rowptr_t), V, L,
-                                             _lib.ptr(graph.col_t), slope, _lib.ptr(alpha), st), "relgnn_rgat_alpha")
-            _lib.check(lib.relgnn_headw_reduce(_lib.ptr(T), V * L, D, D, num_heads, _lib.ptr(graph.rowptr_t), V, L,
-                                               _lib.ptr(graph.col_t), _lib.ptr(alpha), None, _lib.ptr(out), D, None, None, st),
-                       "relgnn_headw_reduce")
+            _lib.launch("relgnn_rgat_alpha", _lib.ptr(s_src), _lib.ptr(s_tgt), num_heads, _lib.ptr(graph.rowptr_t), V, L,
+                        _lib.ptr(graph.col_t), slope, _lib.ptr(alpha))
+            _lib.launch("relgnn_headw_reduce", _lib.ptr(T), V * L, D, D, num_heads, _lib.ptr(graph.rowptr_t), V, L, _lib.ptr(graph.col_t),
+                        _lib.ptr(alpha), None, _lib.ptr(out), D, None, None)
         else:
-            _lib.check(lib.relgnn_rgat_fwd(_lib.ptr(T), D, D, num_heads, _lib.ptr(s_src), _lib.ptr(s_tgt),
-                                           _lib.ptr(graph.rowptr_t), V, L, _lib.ptr(graph.col_t), slope, _lib.ptr(out), D,
-                                           _lib.ptr(alpha), st), "relgnn_rgat_fwd")
+            _lib.launch("relgnn_rgat_fwd", _lib.ptr(T), D, D, num_heads, _lib.ptr(s_src), _lib.ptr(s_tgt), _lib.ptr(graph.rowptr_t), V, L,
+                        _lib.ptr(graph.col_t), slope, _lib.ptr(out), D, _lib.ptr(alpha))
         ctx.graph, ctx.K, ctx.slope, ctx.fast = graph, num_heads, slope, fast
         ctx.save_for_backward(T, s_src, s_tgt, alpha, out)
         return out
 
     @staticmethod
     def backward(ctx, gout):
-        lib = _lib.load_library()
-        st = _lib.current_stream()
         graph, K, slope = ctx.graph, ctx.K, ctx.slope
         T, s_src, s_tgt, alpha, out = ctx.saved_tensors
         V, L, M = graph.V, graph.L, graph.M
@@ -923,32 +850,26 @@ class _RgatAttention(torch.autograd.Function):
         if ctx.fast and _rgat_dz_fast_ok(D, K):
             fuse_t = fuse and L * K <= 64
             gs_tgt = torch.empty((V * L, K), dtype=torch.float32, device=T.device) if fuse_t else None
-            _lib.check(lib.relgnn_rgat_dz(_lib.ptr(T), V * L, D, D, K, _lib.ptr(s_src), _lib.ptr(s_tgt),
-                                          _lib.ptr(graph.rowptr_t), V, L, _lib.ptr(graph.col_t), slope, _lib.ptr(alpha),
-                                          _lib.ptr(out), _lib.ptr(gout), D, _lib.ptr(dz), _lib.ptr(gs_tgt), st), "relgnn_rgat_dz")
+            _lib.launch("relgnn_rgat_dz", _lib.ptr(T), V * L, D, D, K, _lib.ptr(s_src), _lib.ptr(s_tgt), _lib.ptr(graph.rowptr_t), V, L,
+                        _lib.ptr(graph.col_t), slope, _lib.ptr(alpha), _lib.ptr(out), _lib.ptr(gout), D, _lib.ptr(dz), _lib.ptr(gs_tgt))
             if not fuse_t:
                 gs_tgt = _seg_reduce_raw(_lib.AGG_SUM, dz, graph.rowptr_t, 1, graph.iota, None, V * L)
         else:
             gs_tgt = torch.empty((V * L, K), dtype=torch.float32, device=T.device)
-            _lib.check(lib.relgnn_rgat_bwd_logits(_lib.ptr(T), D, D, K, _lib.ptr(s_src), _lib.ptr(s_tgt),
-                                                  _lib.ptr(graph.rowptr_t), V, L, _lib.ptr(graph.col_t), slope,
-                                                  _lib.ptr(alpha), _lib.ptr(out), _lib.ptr(gout), D, _lib.ptr(dz),
-                                                  _lib.ptr(gs_tgt), st), "relgnn_rgat_bwd_logits")
+            _lib.launch("relgnn_rgat_bwd_logits", _lib.ptr(T), D, D, K, _lib.ptr(s_src), _lib.ptr(s_tgt), _lib.ptr(graph.rowptr_t), V, L,
+                        _lib.ptr(graph.col_t), slope, _lib.ptr(alpha), _lib.ptr(out), _lib.ptr(gout), D, _lib.ptr(dz), _lib.ptr(gs_tgt))
         if ctx.fast:
             gT = torch.empty_like(T)
             gs_src = torch.empty((V * L, K), dtype=torch.float32, device=T.device) if fuse else None
-            _lib.check(lib.relgnn_headw_reduce(_lib.ptr(gout), V, D, D, K, _lib.ptr(graph.rowptr_s), V * L, 1,
-                                               _lib.ptr(graph.tgt_s), _lib.ptr(alpha), _lib.ptr(graph.pos_t_of_s),
-                                               _lib.ptr(gT), D, _lib.ptr(dz) if fuse else None, _lib.ptr(gs_src), st),
-                       "relgnn_headw_reduce")
+            _lib.launch("relgnn_headw_reduce", _lib.ptr(gout), V, D, D, K, _lib.ptr(graph.rowptr_s), V * L, 1, _lib.ptr(graph.tgt_s),
+                        _lib.ptr(alpha), _lib.ptr(graph.pos_t_of_s), _lib.ptr(gT), D, _lib.ptr(dz) if fuse else None, _lib.ptr(gs_src))
             if not fuse:
                 gs_src = _seg_reduce_raw(_lib.AGG_SUM, dz, graph.rowptr_s, 1, graph.pos_t_of_s, None, V * L)
         else:
             gT = torch.empty_like(T)
             gs_src = torch.empty((V * L, K), dtype=torch.float32, device=T.device)
-            _lib.check(lib.relgnn_rgat_bwd_msg(D, K, _lib.ptr(graph.rowptr_s), V * L, _lib.ptr(graph.tgt_s),
-                                               _lib.ptr(graph.pos_t_of_s), _lib.ptr(alpha), _lib.ptr(dz), _lib.ptr(gout), D,
-                                               _lib.ptr(gT), D, _lib.ptr(gs_src), st), "relgnn_rgat_bwd_msg")
+            _lib.launch("relgnn_rgat_bwd_msg", D, K, _lib.ptr(graph.rowptr_s), V * L, _lib.ptr(graph.tgt_s), _lib.ptr(graph.pos_t_of_s),
+                        _lib.ptr(alpha), _lib.ptr(dz), _lib.ptr(gout), D, _lib.ptr(gT), D, _lib.ptr(gs_src))
         return gT, gs_src, gs_tgt, None, None, None
 
 
@@ -964,15 +885,12 @@ class _RgatLayerAttention(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, T, att, graph, num_heads: int, slope: float):
-        lib = _lib.load_library()
-        st = _lib.current_stream()
         T, att = T.contiguous(), att.contiguous()
         V, L = graph.V, graph.L
         D = T.shape[1]
         s_src = torch.empty((V * L, num_heads), dtype=torch.float32, device=T.device)
         s_tgt = torch.empty_like(s_src)
-        _lib.check(lib.relgnn_rgat_scores_fwd(_lib.ptr(T), D, D, num_heads, _lib.ptr(att), L, V, _lib.ptr(s_src),
-                                              _lib.ptr(s_tgt), st), "relgnn_rgat_scores_fwd")
+        _lib.launch("relgnn_rgat_scores_fwd", _lib.ptr(T), D, D, num_heads, _lib.ptr(att), L, V, _lib.ptr(s_src), _lib.ptr(s_tgt))
         out = _RgatAttention.forward(ctx, T, s_src, s_tgt, graph, num_heads, slope)   # saves T, s_*, alpha, out
         ctx.att = att
         return out
@@ -980,17 +898,15 @@ class _RgatLayerAttention(torch.autograd.Function):
     @staticmethod
     def backward(ctx, gout):
         from .dense import column_sum
-        lib = _lib.load_library()
         T = ctx.saved_tensors[0]
         att, graph, K = ctx.att, ctx.graph, ctx.K
         V, L = graph.V, graph.L
         D = T.shape[1]
         gT, gs_src, gs_tgt = _RgatAttention.backward(ctx, gout)[:3]
-        groups = int(lib.relgnn_rgat_scores_groups(V))
+        groups = int(_lib.load_library().relgnn_rgat_scores_groups(V))
         partial = torch.empty((groups, L * 2 * D), dtype=torch.float32, device=T.device)
-        _lib.check(lib.relgnn_rgat_scores_bwd(_lib.ptr(T), D, D, K, _lib.ptr(att), L, V, _lib.ptr(gs_src), _lib.ptr(gs_tgt),
-                                              _lib.ptr(gT), D, _lib.ptr(partial), groups, _lib.current_stream()),
-                   "relgnn_rgat_scores_bwd")
+        _lib.launch("relgnn_rgat_scores_bwd", _lib.ptr(T), D, D, K, _lib.ptr(att), L, V, _lib.ptr(gs_src), _lib.ptr(gs_tgt), _lib.ptr(gT),
+                    D, _lib.ptr(partial), groups)
         gatt = column_sum(partial).view(L, 2 * D)
         return gT, gatt, None, None, None
 
@@ -1104,15 +1020,13 @@ def _fused_layer_ok(H, graph, w, kernels) -> bool:
 
 def _rgcn_fused(H, graph, w, kernels, relu: bool, want_sums: bool):
     from .dense import WEIGHT_NN, weight_limbs
-    lib = _lib.load_library()
     V, L = graph.V, len(kernels)
     out = torch.empty((V, 256), dtype=torch.float32, device=H.device)
     agg = torch.empty((V, L * 256), dtype=torch.float32, device=H.device) if want_sums else None
     buf = weight_limbs(list(kernels), WEIGHT_NN)
-    _lib.check(lib.relgnn_rgcn_fused_fwd(_lib.ptr(H, rows_strided=True), H.shape[0], H.stride(0), _lib.ptr(graph.rowptr_t), V, L,
-                                         _lib.ptr(graph.src_t), _lib.ptr(w), buf.data_ptr(), None,
-                                         _lib.ACT_RELU if relu else _lib.ACT_LINEAR, _lib.ptr(agg), L * 256, _lib.ptr(out), 256,
-                                         256, 256, handover_word(H.device).data_ptr(), _lib.current_stream()), "relgnn_rgcn_fused_fwd")
+    _lib.launch("relgnn_rgcn_fused_fwd", _lib.ptr(H, rows_strided=True), H.shape[0], H.stride(0), _lib.ptr(graph.rowptr_t), V, L,
+                _lib.ptr(graph.src_t), _lib.ptr(w), buf.data_ptr(), None, _lib.ACT_RELU if relu else _lib.ACT_LINEAR, _lib.ptr(agg),
+                L * 256, _lib.ptr(out), 256, 256, 256, handover_word(H.device).data_ptr())
     return agg, out
 
 
@@ -1231,39 +1145,33 @@ class _RgdcnApply(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, A, P, graph, C: int, K: int, mode: int, weight_act: int, out_act: int, channel_major: bool):
-        lib = _lib.load_library()
         A, P = A.contiguous(), P.contiguous()
         V, L = graph.V, graph.L
         KK = K * K
         strides = (L * KK, KK, V * L * KK) if channel_major else (L * C * KK, C * KK, KK)
         out = torch.empty((V, C * K), dtype=torch.float32, device=A.device)
-        _lib.check(lib.relgnn_rgdcn_apply_fwd(mode, weight_act, out_act, _lib.ptr(A), _lib.ptr(P), *strides, V, L, C, K,
-                                              _lib.ptr(graph.rowptr_t), _lib.ptr(out), _lib.current_stream()),
-                   "relgnn_rgdcn_apply_fwd")
+        _lib.launch("relgnn_rgdcn_apply_fwd", mode, weight_act, out_act, _lib.ptr(A), _lib.ptr(P), *strides, V, L, C, K,
+                    _lib.ptr(graph.rowptr_t), _lib.ptr(out))
         ctx.graph, ctx.geom, ctx.strides = graph, (C, K, mode, weight_act, out_act), strides
         ctx.save_for_backward(A, P, out if out_act != _lib.ACT_LINEAR else None)
         return out
 
     @staticmethod
     def backward(ctx, gout):
-        lib = _lib.load_library()
-        st = _lib.current_stream()
+        from .dense import act_bwd_from_output
         A, P, out = ctx.saved_tensors
         graph = ctx.graph
         C, K, mode, weight_act, out_act = ctx.geom
         V, L = graph.V, graph.L
         g = gout.contiguous()
         if out_act != _lib.ACT_LINEAR:
-            g2 = torch.empty_like(g)
-            _lib.check(lib.relgnn_act_bwd_from_output(out_act, _lib.ptr(out), _lib.ptr(g), g.numel(), _lib.ptr(g2), st),
-                       "relgnn_act_bwd_from_output")
-            g = g2
+            g = act_bwd_from_output(out_act, out, g)
         f = _mode_factor(graph, mode)
         if f is not None:
             g = (g * f.unsqueeze(1)).contiguous()
         gA, gP = torch.empty_like(A), torch.empty_like(P)
-        _lib.check(lib.relgnn_rgdcn_apply_bwd(weight_act, _lib.ptr(A), _lib.ptr(P), *ctx.strides, V, L, C, K, _lib.ptr(g),
-                                              _lib.ptr(gA), _lib.ptr(gP), st), "relgnn_rgdcn_apply_bwd")
+        _lib.launch("relgnn_rgdcn_apply_bwd", weight_act, _lib.ptr(A), _lib.ptr(P), *ctx.strides, V, L, C, K, _lib.ptr(g), _lib.ptr(gA),
+                    _lib.ptr(gP))
         return gA, gP, None, None, None, None, None, None, None
 
 
@@ -1284,21 +1192,18 @@ class _MessageActReduce(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, msgs, graph, w, mode: int, act: int):
-        lib = _lib.load_library()
         msgs = msgs.contiguous()
         M, D = msgs.shape
         plan = graph.plan_messages()
         out = torch.empty((graph.V, D), dtype=torch.float32, device=msgs.device)
-        _lib.check(lib.relgnn_seg_reduce_msgact_fwd(mode, act, _lib.ptr(msgs), M, D, D, _lib.ptr(plan.rowptr), graph.V,
-                                                    plan.stride, _lib.ptr(plan.col), _lib.ptr(w), _lib.ptr(out), D,
-                                                    _lib.current_stream()), "relgnn_seg_reduce_msgact_fwd")
+        _lib.launch("relgnn_seg_reduce_msgact_fwd", mode, act, _lib.ptr(msgs), M, D, D, _lib.ptr(plan.rowptr), graph.V, plan.stride,
+                    _lib.ptr(plan.col), _lib.ptr(w), _lib.ptr(out), D)
         ctx.graph, ctx.w, ctx.mode, ctx.act = graph, w, mode, act
         ctx.save_for_backward(msgs)
         return out
 
     @staticmethod
     def backward(ctx, gout):
-        lib = _lib.load_library()
         graph, w, mode, act = ctx.graph, ctx.w, ctx.mode, ctx.act
         (msgs,) = ctx.saved_tensors
         M, D = msgs.shape
@@ -1307,8 +1212,7 @@ class _MessageActReduce(torch.autograd.Function):
         plan = graph.plan_messages()
         w_orig = graph.w_original_order(w) if w is not None else None
         gX = torch.empty_like(msgs)
-        _lib.check(lib.relgnn_msg_act_bwd(act, _lib.ptr(msgs), D, _lib.ptr(w_orig), _lib.ptr(plan.col_b), _lib.ptr(gagg), M,
-                                          _lib.ptr(gX), _lib.current_stream()), "relgnn_msg_act_bwd")
+        _lib.launch("relgnn_msg_act_bwd", act, _lib.ptr(msgs), D, _lib.ptr(w_orig), _lib.ptr(plan.col_b), _lib.ptr(gagg), M, _lib.ptr(gX))
         return gX, None, None, None, None
 
 

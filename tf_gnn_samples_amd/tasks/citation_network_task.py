@@ -43,10 +43,9 @@ class _SoftmaxCEStats(torch.autograd.Function):
         rows, cols = logits.shape
         stats = torch.empty(5, dtype=torch.float32, device=logits.device)
         nbytes = lib.relgnn_softmax_ce_stats_workspace_bytes()
-        ws = torch.empty(nbytes // 8, dtype=torch.float64, device=logits.device)
-        _lib.check(lib.relgnn_softmax_ce_stats(_lib.ptr(logits, rows_strided=True), logits.stride(0) if rows > 1 else cols,
-                                               _lib.ptr(labels), _lib.ptr(mask), rows, cols, _lib.ptr(stats), _lib.ptr(ws), nbytes,
-                                               _lib.current_stream()), "relgnn_softmax_ce_stats")
+        ws = _lib.scratch(nbytes, logits.device)
+        _lib.launch("relgnn_softmax_ce_stats", _lib.ptr(logits, rows_strided=True), logits.stride(0) if rows > 1 else cols,
+                    _lib.ptr(labels), _lib.ptr(mask), rows, cols, _lib.ptr(stats), _lib.ptr(ws), nbytes)
         ctx.save_for_backward(logits, labels, mask, stats)
         ctx.set_materialize_grads(False)          # an unused output's gradient arrives as None, not as a zero tensor
         loss, total, accuracy = stats[3], stats[0], stats[4]
@@ -57,7 +56,6 @@ class _SoftmaxCEStats(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g_loss, g_total, g_accuracy, g_counts):
         from .. import _lib
-        lib = _lib.load_library()
         logits, labels, mask, stats = ctx.saved_tensors
         if g_loss is None and g_total is None:
             return None, None, None
@@ -73,14 +71,12 @@ class _SoftmaxCEStats(torch.autograd.Function):
             from ..dense import mark_zero_padded
             ldg = (cols + 15) // 16 * 16
             buf = torch.empty((rows, ldg), dtype=torch.float32, device=logits.device)
-            _lib.check(lib.relgnn_softmax_ce_bwd(_lib.ptr(logits, rows_strided=True), ld, _lib.ptr(labels), _lib.ptr(mask), rows, cols,
-                                                 _lib.ptr(stats), _lib.ptr(g_loss), _lib.ptr(g_total), _lib.ptr(buf), ldg,
-                                                 _lib.current_stream()), "relgnn_softmax_ce_bwd")
+            _lib.launch("relgnn_softmax_ce_bwd", _lib.ptr(logits, rows_strided=True), ld, _lib.ptr(labels), _lib.ptr(mask), rows, cols,
+                        _lib.ptr(stats), _lib.ptr(g_loss), _lib.ptr(g_total), _lib.ptr(buf), ldg)
             return mark_zero_padded(buf[:, :cols], ldg), None, None
         gl = torch.empty((rows, cols), dtype=torch.float32, device=logits.device)
-        _lib.check(lib.relgnn_softmax_ce_bwd(_lib.ptr(logits, rows_strided=True), ld, _lib.ptr(labels), _lib.ptr(mask), rows, cols,
-                                             _lib.ptr(stats), _lib.ptr(g_loss), _lib.ptr(g_total), _lib.ptr(gl), cols,
-                                             _lib.current_stream()), "relgnn_softmax_ce_bwd")
+        _lib.launch("relgnn_softmax_ce_bwd", _lib.ptr(logits, rows_strided=True), ld, _lib.ptr(labels), _lib.ptr(mask), rows, cols,
+                    _lib.ptr(stats), _lib.ptr(g_loss), _lib.ptr(g_total), _lib.ptr(gl), cols)
         return gl, None, None
 
 

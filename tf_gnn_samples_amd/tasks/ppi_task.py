@@ -31,10 +31,9 @@ class _SigmoidCEStats(torch.autograd.Function):
         logits, labels = logits.contiguous(), labels.contiguous()
         stats = torch.empty(6, dtype=torch.float32, device=logits.device)
         nbytes = lib.relgnn_sigmoid_ce_stats_workspace_bytes()
-        ws = torch.empty(nbytes // 8, dtype=torch.float64, device=logits.device)
-        _lib.check(lib.relgnn_sigmoid_ce_stats(_lib.ptr(logits), _lib.ptr(labels), logits.numel(), float(inv_n),
-                                               _lib.ptr(stats), _lib.ptr(ws), nbytes, _lib.current_stream()),
-                   "relgnn_sigmoid_ce_stats")
+        ws = _lib.scratch(nbytes, logits.device)
+        _lib.launch("relgnn_sigmoid_ce_stats", _lib.ptr(logits), _lib.ptr(labels), logits.numel(), float(inv_n), _lib.ptr(stats),
+                    _lib.ptr(ws), nbytes)
         ctx.save_for_backward(logits, labels)
         ctx.inv_n = float(inv_n)
         ctx.set_materialize_grads(False)          # an unused output's gradient arrives as None, not as a zero tensor
@@ -46,7 +45,6 @@ class _SigmoidCEStats(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g_mean, g_total, g_f1, g_counts):
         from .. import _lib
-        lib = _lib.load_library()
         logits, labels = ctx.saved_tensors
         if g_mean is None and g_total is None:
             return None, None, None
@@ -62,13 +60,12 @@ class _SigmoidCEStats(torch.autograd.Function):
             from ..dense import mark_zero_padded
             ld = (cols + 15) // 16 * 16
             buf = torch.empty((rows, ld), dtype=torch.float32, device=logits.device)
-            _lib.check(lib.relgnn_sigmoid_ce_bwd_padded(_lib.ptr(logits), _lib.ptr(labels), rows, cols, _lib.ptr(g_mean), ctx.inv_n,
-                                                        _lib.ptr(g_total), _lib.ptr(buf), ld, _lib.current_stream()),
-                       "relgnn_sigmoid_ce_bwd_padded")
+            _lib.launch("relgnn_sigmoid_ce_bwd_padded", _lib.ptr(logits), _lib.ptr(labels), rows, cols, _lib.ptr(g_mean), ctx.inv_n,
+                        _lib.ptr(g_total), _lib.ptr(buf), ld)
             return mark_zero_padded(buf[:, :cols], ld), None, None
         gl = torch.empty_like(logits)
-        _lib.check(lib.relgnn_sigmoid_ce_bwd(_lib.ptr(logits), _lib.ptr(labels), logits.numel(), _lib.ptr(g_mean), ctx.inv_n,
-                                             _lib.ptr(g_total), _lib.ptr(gl), _lib.current_stream()), "relgnn_sigmoid_ce_bwd")
+        _lib.launch("relgnn_sigmoid_ce_bwd", _lib.ptr(logits), _lib.ptr(labels), logits.numel(), _lib.ptr(g_mean), ctx.inv_n,
+                    _lib.ptr(g_total), _lib.ptr(gl))
         return gl, None, None
 
 

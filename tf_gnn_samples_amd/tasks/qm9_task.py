@@ -63,7 +63,6 @@ class _Head(torch.autograd.Function):
     @staticmethod
     def forward(ctx, states, features, graph_nodes_list, targets, num_graphs, *variables):
         from .. import _lib
-        lib = _lib.load_library()
         num_tasks = len(variables) // 4
         if states.stride(1) != 1 or states.stride(0) % 4 != 0 or states.data_ptr() % 16 != 0:
             states = states.contiguous()
@@ -80,10 +79,9 @@ class _Head(torch.autograd.Function):
         y = torch.empty((num_tasks, num_graphs), dtype=torch.float32, device=device)
         node_range = torch.empty((num_graphs, 2), dtype=torch.int32, device=device)
         stats = torch.empty(num_tasks + 2, dtype=torch.float32, device=device)
-        _lib.check(lib.relgnn_qm9_head_fwd(_lib.ptr(states, rows_strided=True), ld, _lib.ptr(features, rows_strided=True), ldf,
-                                           _lib.ptr(graph_nodes_list), num_nodes, num_graphs, hidden, annotation_size, num_tasks,
-                                           *tables, _lib.ptr(targets), _lib.ptr(y), _lib.ptr(node_range), _lib.ptr(stats),
-                                           _lib.ptr(_err_flag(device, num_graphs)), _lib.current_stream()), "relgnn_qm9_head_fwd")
+        _lib.launch("relgnn_qm9_head_fwd", _lib.ptr(states, rows_strided=True), ld, _lib.ptr(features, rows_strided=True), ldf,
+                    _lib.ptr(graph_nodes_list), num_nodes, num_graphs, hidden, annotation_size, num_tasks, *tables, _lib.ptr(targets),
+                    _lib.ptr(y), _lib.ptr(node_range), _lib.ptr(stats), _lib.ptr(_err_flag(device, num_graphs)))
         ctx.save_for_backward(states, features, graph_nodes_list, targets, y, node_range, *flat)
         ctx.shapes = [tuple(v.shape) for v in variables]
         ctx.num_graphs = num_graphs
@@ -113,13 +111,12 @@ class _Head(torch.autograd.Function):
         d_features = torch.empty((num_nodes, annotation_size), dtype=torch.float32, device=device) if ctx.needs_input_grad[1] else None
         grads = [torch.empty_like(v) for v in flat]     # one buffer per variable: the kernel writes each gradient where it stays
         nbytes = lib.relgnn_qm9_head_workspace_bytes(num_nodes, num_tasks, hidden, annotation_size)
-        ws = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=device)
-        _lib.check(lib.relgnn_qm9_head_bwd(_lib.ptr(states, rows_strided=True), ld, _lib.ptr(features, rows_strided=True), ldf,
-                                           _lib.ptr(graph_nodes_list), num_nodes, ctx.num_graphs, hidden, annotation_size, num_tasks,
-                                           *[_pointer_table(flat[k::4]) for k in range(4)], _lib.ptr(targets), _lib.ptr(y),
-                                           _lib.ptr(node_range), _lib.ptr(g_loss), _lib.ptr(g_total), _lib.ptr(d_states), hidden,
-                                           _lib.ptr(d_features), *[_pointer_table(grads[k::4]) for k in range(4)], _lib.ptr(ws), nbytes,
-                                           _lib.current_stream()), "relgnn_qm9_head_bwd")
+        ws = _lib.scratch(nbytes, device)
+        _lib.launch("relgnn_qm9_head_bwd", _lib.ptr(states, rows_strided=True), ld, _lib.ptr(features, rows_strided=True), ldf,
+                    _lib.ptr(graph_nodes_list), num_nodes, ctx.num_graphs, hidden, annotation_size, num_tasks,
+                    *[_pointer_table(flat[k::4]) for k in range(4)], _lib.ptr(targets), _lib.ptr(y), _lib.ptr(node_range), _lib.ptr(g_loss),
+                    _lib.ptr(g_total), _lib.ptr(d_states), hidden, _lib.ptr(d_features), *[_pointer_table(grads[k::4]) for k in range(4)],
+                    _lib.ptr(ws), nbytes)
         return (d_states, d_features, None, None, None) + tuple(g.reshape(s) for g, s in zip(grads, ctx.shapes))
 
 

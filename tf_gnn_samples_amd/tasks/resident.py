@@ -113,8 +113,6 @@ class ResidentDataset:
         permutation-type arrays of the bucketing (RelGraph._LAZY_ARRAYS) are gathered on their first read, from the same
         offset tables (the RGCN / GGNN sum paths never read them).  lean=False produces everything at once."""
         import ctypes
-        lib = _lib.load_library()
-        st = _lib.current_stream()
         dev, L, G = self.device, self.store.num_edge_types, self.store.num_graphs
         ids = np.ascontiguousarray(np.asarray(graph_ids, dtype=np.int64))
         K = len(ids)
@@ -157,14 +155,12 @@ class ResidentDataset:
         arr = ctypes.c_void_p * max(nf, 1)
 
         def gather(n_payloads, with_node_tables, adj_flat):
-            _lib.check(lib.relgnn_batch_gather(
-                _lib.ptr(ids_d), K, L, G, _lib.ptr(node_off_bd), _lib.ptr(edge_off_bd), _lib.ptr(type_off_bd),
-                _lib.ptr(self.node_off_d), _lib.ptr(self.edge_off_d), _lib.ptr(self.type_off_d), V, M, self._num_nodes_fold,
-                n_payloads, arr(*[self.payload_d[i].data_ptr() for i in self._fast]),
-                (ctypes.c_int32 * max(nf, 1))(*self._fast_cols), arr(*[t.data_ptr() for t in out_fast]),
-                _lib.ptr(self.deg_d), _lib.ptr(deg) if with_node_tables else None, _lib.ptr(self.adj_flat_d),
-                _lib.ptr(adj_flat), _lib.ptr(n2g) if with_node_tables else None, _lib.current_stream()),
-                "relgnn_batch_gather")
+            _lib.launch("relgnn_batch_gather", _lib.ptr(ids_d), K, L, G, _lib.ptr(node_off_bd), _lib.ptr(edge_off_bd),
+                        _lib.ptr(type_off_bd), _lib.ptr(self.node_off_d), _lib.ptr(self.edge_off_d), _lib.ptr(self.type_off_d), V, M,
+                        self._num_nodes_fold, n_payloads, arr(*[self.payload_d[i].data_ptr() for i in self._fast]),
+                        (ctypes.c_int32 * max(nf, 1))(*self._fast_cols), arr(*[t.data_ptr() for t in out_fast]), _lib.ptr(self.deg_d),
+                        _lib.ptr(deg) if with_node_tables else None, _lib.ptr(self.adj_flat_d), _lib.ptr(adj_flat),
+                        _lib.ptr(n2g) if with_node_tables else None)
 
         def split_types(adj_flat):
             return [adj_flat[type_off[l]:type_off[l + 1]] for l in range(L)]
@@ -190,16 +186,14 @@ class ResidentDataset:
             """full=False: row pointers, src_t, tgt_s, scales.  full=True: additionally the six permutation-type arrays
             (the lean outputs are rewritten with the same values)."""
             six = {k: (i32(M) if full else None) for k in RelGraph._LAZY_ARRAYS}
-            _lib.check(lib.relgnn_plan_assemble(
-                _lib.ptr(ids_d), K, L, G, _lib.ptr(node_off_bd), _lib.ptr(msg_off_bd), _lib.ptr(edge_off_bd),
-                _lib.ptr(type_off_bd), _lib.ptr(self.node_off_d), _lib.ptr(self.msg_off_d), _lib.ptr(self.edge_off_d),
-                _lib.ptr(self.type_off_d), V, M,
-                _lib.ptr(d["rowptr_t"]), _lib.ptr(d["perm_t"]), _lib.ptr(d["col_t"]), _lib.ptr(d["rowptr_s"]),
-                _lib.ptr(d["perm_s"]), _lib.ptr(d["frow_s"]), _lib.ptr(d["pos_t_of_s"]),
-                _lib.ptr(rowptr_t), _lib.ptr(six["perm_t"]), _lib.ptr(six["col_t"]), _lib.ptr(six["inv_perm_t"]),
-                _lib.ptr(rowptr_s), _lib.ptr(six["perm_s"]), _lib.ptr(six["frow_s"]), _lib.ptr(tgt_s),
-                _lib.ptr(six["pos_t_of_s"]), _lib.ptr(self.w_t_d), _lib.ptr(self.w_s_d), _lib.ptr(src_t), _lib.ptr(w_t),
-                _lib.ptr(w_s), _lib.current_stream()), "relgnn_plan_assemble")
+            _lib.launch("relgnn_plan_assemble", _lib.ptr(ids_d), K, L, G, _lib.ptr(node_off_bd), _lib.ptr(msg_off_bd),
+                        _lib.ptr(edge_off_bd), _lib.ptr(type_off_bd), _lib.ptr(self.node_off_d), _lib.ptr(self.msg_off_d),
+                        _lib.ptr(self.edge_off_d), _lib.ptr(self.type_off_d), V, M, _lib.ptr(d["rowptr_t"]), _lib.ptr(d["perm_t"]),
+                        _lib.ptr(d["col_t"]), _lib.ptr(d["rowptr_s"]), _lib.ptr(d["perm_s"]), _lib.ptr(d["frow_s"]),
+                        _lib.ptr(d["pos_t_of_s"]), _lib.ptr(rowptr_t), _lib.ptr(six["perm_t"]), _lib.ptr(six["col_t"]),
+                        _lib.ptr(six["inv_perm_t"]), _lib.ptr(rowptr_s), _lib.ptr(six["perm_s"]), _lib.ptr(six["frow_s"]), _lib.ptr(tgt_s),
+                        _lib.ptr(six["pos_t_of_s"]), _lib.ptr(self.w_t_d), _lib.ptr(self.w_s_d), _lib.ptr(src_t), _lib.ptr(w_t),
+                        _lib.ptr(w_s))
             return six
 
         state = {"adj": None if lean else split_types(adj_flat)}

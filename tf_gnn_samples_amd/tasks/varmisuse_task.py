@@ -279,11 +279,10 @@ class _CharCNN(torch.autograd.Function):
         num_nodes = num_labels if label_of_node is None else label_of_node.shape[0]
         out = torch.empty((num_nodes, out_dim), dtype=torch.float32, device=chars.device)
         nbytes = lib.relgnn_charcnn_fwd_workspace_bytes(num_labels, out_dim, 0 if label_of_node is None else 1)
-        ws = torch.empty(max(nbytes, 4) // 4, dtype=torch.float32, device=chars.device)
+        ws = _lib.scratch(nbytes, chars.device)
         flag = None if label_of_node is None else _err_flag(chars.device, "node_labels_to_unique_labels holds an id outside [0, %d)" % num_labels)
-        _lib.check(lib.relgnn_charcnn_fwd(_lib.ptr(chars), num_labels, num_chars, _lib.ptr(label_of_node), num_nodes, _lib.ptr(w1c),
-                                          _lib.ptr(b1c), _lib.ptr(w2c), _lib.ptr(b2c), out_dim, _lib.ptr(out), _lib.ptr(ws), nbytes,
-                                          _lib.ptr(flag), _lib.current_stream()), "relgnn_charcnn_fwd")
+        _lib.launch("relgnn_charcnn_fwd", _lib.ptr(chars), num_labels, num_chars, _lib.ptr(label_of_node), num_nodes, _lib.ptr(w1c),
+                    _lib.ptr(b1c), _lib.ptr(w2c), _lib.ptr(b2c), out_dim, _lib.ptr(out), _lib.ptr(ws), nbytes, _lib.ptr(flag))
         ctx.save_for_backward(chars, label_of_node, w1c, b1c, w2c, b2c)
         return out
 
@@ -299,10 +298,9 @@ class _CharCNN(torch.autograd.Function):
             g = ops.unsorted_segment_sum(g, label_of_node, num_labels).contiguous()
         dw1, db1, dw2, db2 = (torch.empty_like(t) for t in (w1, b1, w2, b2))
         nbytes = lib.relgnn_charcnn_bwd_workspace_bytes(num_labels, num_chars, out_dim)
-        ws = torch.empty(max(nbytes, 8) // 8, dtype=torch.float64, device=chars.device)
-        _lib.check(lib.relgnn_charcnn_bwd(_lib.ptr(chars), num_labels, num_chars, _lib.ptr(w1), _lib.ptr(b1), _lib.ptr(w2), _lib.ptr(b2),
-                                          out_dim, _lib.ptr(g), _lib.ptr(dw1), _lib.ptr(db1), _lib.ptr(dw2), _lib.ptr(db2),
-                                          _lib.ptr(ws), nbytes, _lib.current_stream()), "relgnn_charcnn_bwd")
+        ws = _lib.scratch(nbytes, chars.device)
+        _lib.launch("relgnn_charcnn_bwd", _lib.ptr(chars), num_labels, num_chars, _lib.ptr(w1), _lib.ptr(b1), _lib.ptr(w2), _lib.ptr(b2),
+                    out_dim, _lib.ptr(g), _lib.ptr(dw1), _lib.ptr(db1), _lib.ptr(dw2), _lib.ptr(db2), _lib.ptr(ws), nbytes)
         return None, None, dw1, db1, dw2, db2
 
 
@@ -341,13 +339,12 @@ class _Head(torch.autograd.Function):
         logits = torch.empty((num_graphs, num_cands), dtype=torch.float32, device=states.device)
         stats = torch.empty(4, dtype=torch.float32, device=states.device)
         nbytes = lib.relgnn_varmisuse_head_workspace_bytes(num_graphs, hidden)
-        ws = torch.empty(nbytes // 8, dtype=torch.float64, device=states.device)
+        ws = _lib.scratch(nbytes, states.device)
         ld = states.stride(0) if num_nodes > 1 else hidden
-        _lib.check(lib.relgnn_varmisuse_head_fwd(_lib.ptr(states, rows_strided=True), ld, num_nodes, hidden, _lib.ptr(slot_ids),
-                                                 _lib.ptr(cand_ids), _lib.ptr(mask), _lib.ptr(first_node), num_graphs, num_cands,
-                                                 _lib.ptr(wv), _lib.ptr(logits), _lib.ptr(stats), _lib.ptr(ws), nbytes,
-                                                 _lib.ptr(_err_flag(states.device, "a slot or candidate node id lies outside [0, %d)" % num_nodes)),
-                                                 _lib.current_stream()), "relgnn_varmisuse_head_fwd")
+        _lib.launch("relgnn_varmisuse_head_fwd", _lib.ptr(states, rows_strided=True), ld, num_nodes, hidden, _lib.ptr(slot_ids),
+                    _lib.ptr(cand_ids), _lib.ptr(mask), _lib.ptr(first_node), num_graphs, num_cands, _lib.ptr(wv), _lib.ptr(logits),
+                    _lib.ptr(stats), _lib.ptr(ws), nbytes,
+                    _lib.ptr(_err_flag(states.device, "a slot or candidate node id lies outside [0, %d)" % num_nodes)))
         ctx.save_for_backward(states, slot_ids, cand_ids, mask, first_node, wv)
         ctx.w_shape = None if w is None else tuple(w.shape)
         ctx.set_materialize_grads(False)
@@ -371,12 +368,11 @@ class _Head(torch.autograd.Function):
         d_states = torch.empty((num_nodes, hidden), dtype=torch.float32, device=states.device)
         dw = None if wv is None else torch.empty_like(wv)
         nbytes = lib.relgnn_varmisuse_head_workspace_bytes(num_graphs, hidden)
-        ws = torch.empty(nbytes // 8, dtype=torch.float64, device=states.device)
+        ws = _lib.scratch(nbytes, states.device)
         ld = states.stride(0) if num_nodes > 1 else hidden
-        _lib.check(lib.relgnn_varmisuse_head_bwd(_lib.ptr(states, rows_strided=True), ld, num_nodes, hidden, _lib.ptr(slot_ids),
-                                                 _lib.ptr(cand_ids), _lib.ptr(mask), _lib.ptr(first_node), num_graphs, num_cands,
-                                                 _lib.ptr(wv), _lib.ptr(g_loss), _lib.ptr(g_total), _lib.ptr(d_states), hidden,
-                                                 _lib.ptr(dw), _lib.ptr(ws), nbytes, _lib.current_stream()), "relgnn_varmisuse_head_bwd")
+        _lib.launch("relgnn_varmisuse_head_bwd", _lib.ptr(states, rows_strided=True), ld, num_nodes, hidden, _lib.ptr(slot_ids),
+                    _lib.ptr(cand_ids), _lib.ptr(mask), _lib.ptr(first_node), num_graphs, num_cands, _lib.ptr(wv), _lib.ptr(g_loss),
+                    _lib.ptr(g_total), _lib.ptr(d_states), hidden, _lib.ptr(dw), _lib.ptr(ws), nbytes)
         return d_states, None, None, None, None, (None if dw is None else dw.reshape(ctx.w_shape))
 
 

@@ -84,14 +84,13 @@ class _LayerNormFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, gamma, beta, eps: float):
         from . import _lib
-        lib = _lib.load_library()
         x, gamma, beta = x.contiguous(), gamma.contiguous(), beta.contiguous()
         V, D = x.shape
         y = torch.empty_like(x)
         mean = torch.empty(V, dtype=torch.float32, device=x.device)
         rstd = torch.empty_like(mean)
-        _lib.check(lib.relgnn_layer_norm_fwd(_lib.ptr(x), D, V, D, _lib.ptr(gamma), _lib.ptr(beta), eps, _lib.ptr(y), D,
-                                             _lib.ptr(mean), _lib.ptr(rstd), _lib.current_stream()), "relgnn_layer_norm_fwd")
+        _lib.launch("relgnn_layer_norm_fwd", _lib.ptr(x), D, V, D, _lib.ptr(gamma), _lib.ptr(beta), eps, _lib.ptr(y), D, _lib.ptr(mean),
+                    _lib.ptr(rstd))
         ctx.save_for_backward(x, gamma, mean, rstd)
         return y
 
@@ -108,9 +107,8 @@ class _LayerNormFn(torch.autograd.Function):
             return dx, torch.zeros_like(gamma), torch.zeros_like(gamma), None
         groups = int(lib.relgnn_layer_norm_groups(V, D))
         partial = torch.empty((groups, 2 * D), dtype=torch.float32, device=x.device)
-        _lib.check(lib.relgnn_layer_norm_bwd(_lib.ptr(x), D, _lib.ptr(gy), D, V, D, _lib.ptr(gamma), _lib.ptr(mean),
-                                             _lib.ptr(rstd), _lib.ptr(dx), D, _lib.ptr(partial), groups,
-                                             _lib.current_stream()), "relgnn_layer_norm_bwd")
+        _lib.launch("relgnn_layer_norm_bwd", _lib.ptr(x), D, _lib.ptr(gy), D, V, D, _lib.ptr(gamma), _lib.ptr(mean), _lib.ptr(rstd),
+                    _lib.ptr(dx), D, _lib.ptr(partial), groups)
         gsum = column_sum(partial)
         return dx, gsum[:D], gsum[D:], None
 
@@ -140,51 +138,65 @@ def layer_norm(x, gamma, beta, eps: float = 1e-12):
     return torch.nn.functional.layer_norm(x, (D,), gamma, beta, eps)
 
 
+def _gru_gates_fwd(xk, rec, h):
+    """(z, r, r * h) from xk = x @ K + b [V, 3u], rec = h @ U[:, :2u] and h [V, u] (csrc/gru.hip)."""
+    from . import _lib
+    V, u = h.shape
+    z, r, rh = torch.empty_like(h), torch.empty_like(h), torch.empty_like(h)
+    _lib.launch("relgnn_gru_gates_fwd", _lib.ptr(xk), _lib.ptr(rec), _lib.ptr(h), V, u, _lib.ptr(z), _lib.ptr(r), _lib.ptr(rh))
+    return z, r, rh
+
+
+def _gru_out_fwd(xk, q, z, h, act: int):
+    """(hh, out): the candidate hh = act(xk_h + q), q = (r * h) @ U[:, 2u:], and out = z h + (1 - z) hh."""
+    from . import _lib
+    V, u = h.shape
+    hh, out = torch.empty_like(h), torch.empty_like(h)
+    _lib.launch("relgnn_gru_out_fwd", _lib.ptr(xk), _lib.ptr(q), _lib.ptr(z), _lib.ptr(h), V, u, act, _lib.ptr(hh), _lib.ptr(out))
+    return hh, out
+
+
+def _gru_composition_bwd(gout, z, r, h, hh, u_h, act: int):
+    """(gxk [V, 3u], gq [V, u], gh [V, u]) of the two kernels above around q = (r * h) @ u_h: output backward, gq @ u_h^T, gates
+    backward.  gxk[:, :2u] is also the gradient of rec; gh does not hold the products' share (rec = h @ U[:, :2u]) yet."""
+    from . import _lib
+    from .dense import GEMM_NT, lib_gemm
+    V, u = h.shape
+    gxk = torch.empty((V, 3 * u), dtype=torch.float32, device=h.device)
+    gq, gz, gh = torch.empty_like(h), torch.empty_like(h), torch.empty_like(h)
+    _lib.launch("relgnn_gru_out_bwd", _lib.ptr(gout), _lib.ptr(z), _lib.ptr(h), _lib.ptr(hh), V, u, act, _lib.ptr(gxk), _lib.ptr(gq),
+                _lib.ptr(gz), _lib.ptr(gh))
+    grh = lib_gemm(GEMM_NT, gq, u_h, weight=True)
+    _lib.launch("relgnn_gru_gates_bwd", _lib.ptr(grh), _lib.ptr(gz), _lib.ptr(z), _lib.ptr(r), _lib.ptr(h), V, u, _lib.ptr(gxk), _lib.ptr(gh))
+    return gxk, gq, gh
+
+
 class _FusedGRU(torch.autograd.Function):
     """Keras GRUCell given xk = x@K+b and rec = h@U[:, :2u]: two fused elementwise kernels around the inner GEMM
-    (r*h) @ U_h forward, two backward (csrc/gru.hip) instead of ~40 elementwise launches."""
+    (r*h) @ U_h forward, two backward (csrc/gru.hip) instead of ~40 elementwise launches.  The route of the cells _GRUCellFn does
+    not take (_gru_cell_fused_ok); the weight gradients of K, b and U[:, :2u] are the surrounding dense() nodes'."""
 
     @staticmethod
     def forward(ctx, xk, rec, h, u_h, act: int):
-        from . import _lib
-        lib = _lib.load_library()
-        st = _lib.current_stream()
+        from .dense import GEMM_NN, lib_gemm
         xk, rec, h = xk.contiguous(), rec.contiguous(), h.contiguous()
         # (u_h = recurrent_kernel[:, 2u:] stays the strided view of the parameter it is: the product reads it with its leading
         #  dimension and keeps its limb image with the step's other weights — round 6: no copy, no split launch per cell)
         if not (u_h.dim() == 2 and u_h.stride(1) == 1 and u_h.stride(0) % 4 == 0 and u_h.data_ptr() % 16 == 0):
             u_h = u_h.contiguous()
-        V, u = h.shape
-        z, r, rh = torch.empty_like(h), torch.empty_like(h), torch.empty_like(h)
-        _lib.check(lib.relgnn_gru_gates_fwd(_lib.ptr(xk), _lib.ptr(rec), _lib.ptr(h), V, u, _lib.ptr(z), _lib.ptr(r),
-                                            _lib.ptr(rh), st), "relgnn_gru_gates_fwd")
-        from .dense import GEMM_NN, lib_gemm
-        q = lib_gemm(GEMM_NN, rh, u_h, weight=True)
-        hh, out = torch.empty_like(h), torch.empty_like(h)
-        _lib.check(lib.relgnn_gru_out_fwd(_lib.ptr(xk), _lib.ptr(q), _lib.ptr(z), _lib.ptr(h), V, u, act, _lib.ptr(hh),
-                                          _lib.ptr(out), st), "relgnn_gru_out_fwd")
+        z, r, rh = _gru_gates_fwd(xk, rec, h)
+        hh, out = _gru_out_fwd(xk, lib_gemm(GEMM_NN, rh, u_h, weight=True), z, h, act)
         ctx.act = act
         ctx.save_for_backward(z, r, rh, h, hh, u_h)
         return out
 
     @staticmethod
     def backward(ctx, gout):
-        from . import _lib
         from .dense import matmul_tn_splitk
-        lib = _lib.load_library()
-        st = _lib.current_stream()
         z, r, rh, h, hh, u_h = ctx.saved_tensors
-        V, u = h.shape
-        gout = gout.contiguous()
-        gxk = torch.empty((V, 3 * u), dtype=torch.float32, device=h.device)
-        gq, gz, gh = torch.empty_like(h), torch.empty_like(h), torch.empty_like(h)
-        _lib.check(lib.relgnn_gru_out_bwd(_lib.ptr(gout), _lib.ptr(z), _lib.ptr(h), _lib.ptr(hh), V, u, ctx.act,
-                                          _lib.ptr(gxk), _lib.ptr(gq), _lib.ptr(gz), _lib.ptr(gh), st), "relgnn_gru_out_bwd")
-        from .dense import GEMM_NT, lib_gemm
-        grh = lib_gemm(GEMM_NT, gq, u_h, weight=True)
+        u = h.shape[1]
+        gxk, gq, gh = _gru_composition_bwd(gout.contiguous(), z, r, h, hh, u_h, ctx.act)
         gu_h = matmul_tn_splitk(rh, gq) if ctx.needs_input_grad[3] else None
-        _lib.check(lib.relgnn_gru_gates_bwd(_lib.ptr(grh), _lib.ptr(gz), _lib.ptr(z), _lib.ptr(r), _lib.ptr(h), V, u,
-                                            _lib.ptr(gxk), _lib.ptr(gh), st), "relgnn_gru_gates_bwd")
         return gxk, gxk[:, :2 * u], gh, gu_h, None
 
 
@@ -201,8 +213,6 @@ class _GRUCellFn(torch.autograd.Function):
     def forward(ctx, x, h, K, U, b, act: int):
         from . import _lib
         from .dense import GEMM_NN, lib_gemm
-        lib = _lib.load_library()
-        st = _lib.current_stream()
         x, h = x.contiguous(), h.contiguous()
         V, u = h.shape
         if _gru_cell_kernel_ok(x, h, K, U, b, act):
@@ -215,10 +225,9 @@ class _GRUCellFn(torch.autograd.Function):
             im_h = weight_image([K[:, 2 * u:], U[:, 2 * u:]], WEIGHT_NN)   # B [u, D + u]:  k = [x | r * h]
             z, r, rh, hh = (torch.empty_like(h) for _ in range(4)) if train else (None,) * 4
             out = torch.empty_like(h)
-            _lib.check(lib.relgnn_gru_cell_fwd_xf32(_lib.ptr(x), x.stride(0), _lib.ptr(h), h.stride(0), im_zr.buf.data_ptr(),
-                                                    im_h.buf.data_ptr(), _lib.ptr(b), act, _lib.ptr(z), _lib.ptr(r), _lib.ptr(rh),
-                                                    _lib.ptr(hh), _lib.ptr(out), V, u, x.shape[1],
-                                                    ops.handover_word(h.device).data_ptr(), st), "relgnn_gru_cell_fwd_xf32")
+            _lib.launch("relgnn_gru_cell_fwd_xf32", _lib.ptr(x), x.stride(0), _lib.ptr(h), h.stride(0), im_zr.buf.data_ptr(),
+                        im_h.buf.data_ptr(), _lib.ptr(b), act, _lib.ptr(z), _lib.ptr(r), _lib.ptr(rh), _lib.ptr(hh), _lib.ptr(out), V, u,
+                        x.shape[1], ops.handover_word(h.device).data_ptr())
             ctx.act, ctx.cell_kernel = act, True
             if train:
                 ctx.save_for_backward(x, h, K, U, z, r, rh, hh)
@@ -227,13 +236,8 @@ class _GRUCellFn(torch.autograd.Function):
         ctx.cell_kernel = False
         xk = lib_gemm(GEMM_NN, x, K, b, weight=True)                       # [V, 3u]
         rec = lib_gemm(GEMM_NN, h, U[:, :2 * u], weight=True)              # [V, 2u] (the view read with its leading dimension)
-        z, r, rh = torch.empty_like(h), torch.empty_like(h), torch.empty_like(h)
-        _lib.check(lib.relgnn_gru_gates_fwd(_lib.ptr(xk), _lib.ptr(rec), _lib.ptr(h), V, u, _lib.ptr(z), _lib.ptr(r),
-                                            _lib.ptr(rh), st), "relgnn_gru_gates_fwd")
-        q = lib_gemm(GEMM_NN, rh, U[:, 2 * u:], weight=True)
-        hh, out = torch.empty_like(h), torch.empty_like(h)
-        _lib.check(lib.relgnn_gru_out_fwd(_lib.ptr(xk), _lib.ptr(q), _lib.ptr(z), _lib.ptr(h), V, u, act, _lib.ptr(hh),
-                                          _lib.ptr(out), st), "relgnn_gru_out_fwd")
+        z, r, rh = _gru_gates_fwd(xk, rec, h)
+        hh, out = _gru_out_fwd(xk, lib_gemm(GEMM_NN, rh, U[:, 2 * u:], weight=True), z, h, act)
         ctx.act = act
         ctx.save_for_backward(x, h, K, U, z, r, rh, hh)
         ctx.leaf_params = (K, U, b) if all(p.is_leaf and p.requires_grad for p in (K, U, b)) else None
@@ -243,12 +247,9 @@ class _GRUCellFn(torch.autograd.Function):
     def backward(ctx, gout):
         from . import _lib
         from .dense import GEMM_NT, column_sum, lib_gemm, matmul_tn_splitk, tn_stream_into
-        lib = _lib.load_library()
-        st = _lib.current_stream()
         x, h, K, U, z, r, rh, hh = ctx.saved_tensors
         V, u = h.shape
         gout = gout.contiguous()
-        gxk = torch.empty((V, 3 * u), dtype=torch.float32, device=h.device)
         fused = ctx.cell_kernel and _gru_cell_kernel_ok(x, h, K, U, None, ctx.act)
         if fused:
             # one launch (csrc/gru_cell.hip): the gate / candidate gradients and the three input-gradient products; gxk for the
@@ -257,19 +258,14 @@ class _GRUCellFn(torch.autograd.Function):
             from .dense import WEIGHT_NT, weight_image
             im_h = weight_image([K[:, 2 * u:], U[:, 2 * u:]], WEIGHT_NT, separate=True)
             im_zr = weight_image([K[:, :2 * u], U[:, :2 * u]], WEIGHT_NT, separate=True)
+            gxk = torch.empty((V, 3 * u), dtype=torch.float32, device=h.device)
             gx, gh = torch.empty_like(x), torch.empty_like(h)
-            _lib.check(lib.relgnn_gru_cell_bwd_xf32(_lib.ptr(gout), gout.stride(0), _lib.ptr(z), _lib.ptr(r), _lib.ptr(h), h.stride(0),
-                                                    _lib.ptr(hh), im_h.buf.data_ptr(), im_zr.buf.data_ptr(), ctx.act, _lib.ptr(gxk),
-                                                    _lib.ptr(gx), _lib.ptr(gh), V, u, x.shape[1],
-                                                    ops.handover_word(h.device).data_ptr(), st), "relgnn_gru_cell_bwd_xf32")
+            _lib.launch("relgnn_gru_cell_bwd_xf32", _lib.ptr(gout), gout.stride(0), _lib.ptr(z), _lib.ptr(r), _lib.ptr(h), h.stride(0),
+                        _lib.ptr(hh), im_h.buf.data_ptr(), im_zr.buf.data_ptr(), ctx.act, _lib.ptr(gxk), _lib.ptr(gx), _lib.ptr(gh), V, u,
+                        x.shape[1], ops.handover_word(h.device).data_ptr())
             gq = gxk[:, 2 * u:]
         else:
-            gq, gz, gh = torch.empty_like(h), torch.empty_like(h), torch.empty_like(h)
-            _lib.check(lib.relgnn_gru_out_bwd(_lib.ptr(gout), _lib.ptr(z), _lib.ptr(h), _lib.ptr(hh), V, u, ctx.act,
-                                              _lib.ptr(gxk), _lib.ptr(gq), _lib.ptr(gz), _lib.ptr(gh), st), "relgnn_gru_out_bwd")
-            grh = lib_gemm(GEMM_NT, gq, U[:, 2 * u:], weight=True)
-            _lib.check(lib.relgnn_gru_gates_bwd(_lib.ptr(grh), _lib.ptr(gz), _lib.ptr(z), _lib.ptr(r), _lib.ptr(h), V, u,
-                                                _lib.ptr(gxk), _lib.ptr(gh), st), "relgnn_gru_gates_bwd")
+            gxk, gq, gh = _gru_composition_bwd(gout, z, r, h, hh, U[:, 2 * u:], ctx.act)
         grec = gxk[:, :2 * u]                                              # d loss / d rec = the z, r columns of d loss / d xk
 
         def weight_side():

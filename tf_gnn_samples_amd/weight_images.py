@@ -146,7 +146,6 @@ def _marshal(items):
 
 def _split_weight_images(images, marshalled: dict) -> None:
     """The split launches for `images` of one table.  marshalled: that table's {ids of a set of images: launch arguments}."""
-    lib = _lib.load_library()
     triples = [im for im in images if not im.pair]
     pairs = [im for im in images if im.pair]
     if triples:
@@ -157,15 +156,14 @@ def _split_weight_images(images, marshalled: dict) -> None:
         ent = marshalled.get(key) or _marshal([it for im in triples for it in im.items])
         if len(triples) > 4:                           # (small sets are cheap to marshal and vary more)
             marshalled[key] = ent
-        _lib.check(lib.relgnn_limb_split_multi_f32(*ent, _lib.current_stream()), "relgnn_limb_split_multi_f32")
+        _lib.launch("relgnn_limb_split_multi_f32", *ent)
     if pairs:           # two fp16 limbs: one magnitude per image first (its power-of-two scale), then the limbs — three launches
         wm = torch.empty(len(pairs), dtype=torch.float32, device=pairs[0].buf.device)
         for i, im in enumerate(pairs):
             im.wmax = wm[i:i + 1]
         items = [it for im in pairs for it in im.items]
         image = [i for i, im in enumerate(pairs) for _ in im.items]
-        _lib.check(lib.relgnn_limb16_split_multi_f32(*_marshal(items), (ctypes.c_int32 * len(image))(*image), len(pairs),
-                                                     wm.data_ptr(), _lib.current_stream()), "relgnn_limb16_split_multi_f32")
+        _lib.launch("relgnn_limb16_split_multi_f32", *_marshal(items), (ctypes.c_int32 * len(image))(*image), len(pairs), wm.data_ptr())
 
 
 class _Table:
