@@ -1,4 +1,4 @@
-"""Build librelgnn.so (the C-ABI HIP library, include/relgnn.h) in-tree for gfx950.
+"""Build librelgnn.so (the C-ABI HIP library, include/relgnn.h and include/relgnn_dropout.h) in-tree for gfx950.
 
 hipcc cross-compiles without a GPU, so this runs in the CPU-only build container; the
 resulting tf_gnn_samples_amd/librelgnn.so travels with the repo snapshot to the GPU box.
@@ -11,6 +11,7 @@ from pathlib import Path
 PKG_DIR = Path(__file__).resolve().parent
 CSRC = PKG_DIR / "csrc"
 LIB_PATH = PKG_DIR / "librelgnn.so"
+HEADERS = [PKG_DIR.parent / "include" / "relgnn.h", PKG_DIR.parent / "include" / "relgnn_dropout.h"]      # the C ABI
 HIPCC_FLAGS = [
     "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC",
     # product and add of `scale * row` then `acc + msg` are rounded separately, like the
@@ -35,7 +36,7 @@ def is_stale() -> bool:
     if not LIB_PATH.exists():
         return True
     t = LIB_PATH.stat().st_mtime
-    deps = _sources() + list(CSRC.glob("*.h")) + [PKG_DIR.parent / "include" / "relgnn.h"]
+    deps = _sources() + list(CSRC.glob("*.h")) + HEADERS
     return any(d.stat().st_mtime > t for d in deps)
 
 
@@ -56,7 +57,7 @@ def build_library(force: bool = False, verbose: bool = False) -> Path:
         obj = objdir / (src.stem + ".o")
         objs.append(obj)
         newest_dep = max([src.stat().st_mtime] + [h.stat().st_mtime for h in CSRC.glob("*.h")]
-                         + [(PKG_DIR.parent / "include" / "relgnn.h").stat().st_mtime])
+                         + [h.stat().st_mtime for h in HEADERS])
         if not force and obj.exists() and obj.stat().st_mtime > newest_dep:
             continue
         cmd = [hipcc, *HIPCC_FLAGS, "-c", str(src), "-o", str(obj)]

@@ -1,4 +1,4 @@
-"""ctypes binding of librelgnn.so (C ABI: include/relgnn.h).
+"""ctypes binding of librelgnn.so (C ABI: include/relgnn.h, include/relgnn_dropout.h).
 
 This is the ONLY compute backend of the package.  There is no CPU / eager-PyTorch fallback:
 if the HIP library is missing, or a tensor is not a float32/int32 CUDA(HIP) tensor, the
@@ -23,6 +23,7 @@ ACT_LINEAR, ACT_TANH, ACT_RELU, ACT_LEAKY_RELU, ACT_ELU, ACT_SELU, ACT_GELU = ra
 ACT_NAMES = ("linear", "tanh", "relu", "leaky_relu", "elu", "selu", "gelu")      # utils.get_activation's strings, by id
 
 _c_i32, _c_i64, _c_f32 = ctypes.c_int32, ctypes.c_int64, ctypes.c_float
+_c_u32 = ctypes.c_uint32
 _ptr = ctypes.c_void_p
 
 # name -> (restype, argtypes); must list every function declared in include/relgnn.h
@@ -180,6 +181,15 @@ _SIGNATURES = {
     "relgnn_batch_pack": (ctypes.c_int, [_c_i32, _c_i64, _ptr, _ptr, _ptr, _ptr, _ptr, _c_i32, _ptr, _ptr, _ptr, _ptr, ctypes.c_size_t, _c_i32]),
 }
 
+# include/relgnn_dropout.h (the opt-in layer-input dropout route): typed by load_library() like the table above, kept apart
+# from it because exported_signatures() is the list of include/relgnn.h
+_DROPOUT_SIGNATURES = {
+    "relgnn_dropout_fwd": (ctypes.c_int, [_ptr, _c_i64, _c_i64, _ptr, _c_i32, _c_u32, _c_f32, _ptr, _ptr]),
+    "relgnn_dropout_bwd": (ctypes.c_int, [_ptr, _c_i64, _c_i64, _ptr, _c_i32, _c_u32, _c_f32, _ptr, _ptr]),
+    "relgnn_dropout_residual_fwd": (ctypes.c_int, [_ptr, _ptr, _c_i64, _c_i64, _ptr, _c_i32, _c_u32, _c_f32, _ptr, _ptr, _ptr]),
+    "relgnn_dropout_residual_bwd": (ctypes.c_int, [_ptr, _ptr, _c_i64, _c_i64, _ptr, _c_i32, _c_u32, _c_f32, _ptr, _ptr, _ptr]),
+}
+
 _lib = None
 
 
@@ -197,7 +207,7 @@ def load_library():
             "%s not found: the HIP extension is not built. Run `python -c 'import __graft_entry__ as g; "
             "g.build()'` (needs hipcc). There is no CPU fallback for this path." % LIB_PATH)
     lib = ctypes.CDLL(str(LIB_PATH))
-    for name, (restype, argtypes) in _SIGNATURES.items():
+    for name, (restype, argtypes) in list(_SIGNATURES.items()) + list(_DROPOUT_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the symbol is not exported
         fn.restype = restype
         fn.argtypes = argtypes
@@ -209,6 +219,11 @@ def load_library():
 
 def exported_signatures():
     return dict(_SIGNATURES)
+
+
+def dropout_signatures():
+    """The entry points of include/relgnn_dropout.h (not part of exported_signatures(): that is relgnn.h's list)."""
+    return dict(_DROPOUT_SIGNATURES)
 
 
 def status_string(code: int) -> str:

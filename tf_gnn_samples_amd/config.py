@@ -82,6 +82,13 @@ _SPEC: Dict[str, Tuple[str, str, Tuple[str, ...], str]] = {
                  "loss terms) | ONE kernel pair for all task ids of the batch (csrc/qm9_head.hip: every state row read once, no "
                  "[V, hidden + A] concatenation, fixed-order sums; GPU tensors, up to 16 tasks, hidden a multiple of 4 up to 512, "
                  "up to 64 initial features; anything else takes the op chain).  The last bits differ from the composition"),
+    "layer_dropout": ("RELGNN_LAYER_DROPOUT", "torch", ("torch", "fused"),
+                      "dropout on every layer's input (keep-prob < 1, training): torch.nn.functional.dropout, then an add and a divide "
+                      "at the residual layers, one stored mask per layer | ONE kernel per layer (csrc/dropout.hip: dropout and the "
+                      "residual average in one pass; Philox4x32-10 masks that are a function of (seed, replica, step, layer, element) "
+                      "and are regenerated in the backward, none stored; the step count lives on the device, so a captured step draws "
+                      "new masks on every replay; contiguous fp32 GPU tensors, anything else takes the torch call).  Other random "
+                      "draws than torch's; on the same masks the same bits"),
     "typed": ("RELGNN_TYPED", "panel", ("panel", "bmm"),
               "per-(node, type) transforms of many-type graphs: one gathered-row MFMA launch | index_select + torch.bmm"),
     "typed_tn": ("RELGNN_TYPED_TN", "auto", ("auto", "limb", "panel"),

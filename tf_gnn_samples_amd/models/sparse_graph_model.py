@@ -382,6 +382,12 @@ class Sparse_Graph_Model(ABC):
             # read back with every step's metrics (MetricsReadback) and by handover_status()
             from .. import ops as _ops
             self.handover_word = _ops.handover_word(self.device)
+            # the state block of the fused layer-input dropout (ops.dropout): {seed, replica, step} in HBM, next to the hand-over
+            # word for the same reason (a captured step needs a live pointer).  replica = the data-parallel rank (the drivers form
+            # their process group before they build the model), so that ranks do not share masks
+            import torch.distributed as dist
+            rank = dist.get_rank() if dist.is_available() and dist.is_initialized() else 0
+            self.dropout_state = _ops.dropout_state(self.device, params['random_seed'], rank, 0)
         self.variables = VariableStore(seed=params['random_seed'])
         self.__make_model()
         self.variables.to(self.device)
@@ -471,7 +477,15 @@ class Sparse_Graph_Model(ABC):
     def compute_final_node_representations(self, initial_node_features: torch.Tensor,
                                            adjacency_lists, type_to_num_incoming_edges: torch.Tensor,
                                            dropout_keep_prob: float = 1.0) -> torch.Tensor:
-        """__build_graph_propagation_model, models/sparse_graph_model.py:162-202."""
+        """__build_graph_propagation_model, models/sparse_graph_model.py:162-202.
+
+        Dropout on the layer inputs (keep-prob < 1) is torch.nn.functional.dropout by default.  With
+        config.settings.layer_dropout == "fused" a contiguous fp32 GPU input takes ops.dropout / ops.dropout_residual instead (one
+        kernel per layer, the residual average included; no mask stored): the masks are Philox4x32-10 draws keyed by
+        self.dropout_state = {random_seed, replica, step} with the layer index as the stream.  The step is bumped here, on the
+        device, once per call that drops anything, so every pass (and every replay of a captured step) draws new masks; each pass
+        works on its own 24-byte copy of the state, which its backward reads again.  The step is NOT written to checkpoints (the
+        reference's pickle layout has no place for it): a restored model starts at step 0."""
         p = self.params
         activation_fn = get_activation(p['graph_model_activation_function'])
         w = self.variables.scope("graph_model")
@@ -479,7 +493,7 @@ class Sparse_Graph_Model(ABC):
         # bucketed once, shared by every layer; the index range check is read back at the next fetch
         graph = as_rel_graph(adjacency_lists, num_nodes, validate="deferred")
         from ..dense import dense_act, vouch_sole_consumer
-        from ..ops import activation_id
+        from ..ops import activation_id, dropout as fused_dropout, dropout_residual, dropout_tensor_ok, fused_dropout_on
         act_id = activation_id(p['graph_model_activation_function'])
         num_layers, res_every = p['graph_num_layers'], p['graph_residual_connection_every_num_layers']
 
@@ -501,16 +515,32 @@ class Sparse_Graph_Model(ABC):
         else:
             cur_node_representations = initial_node_features
         last_residual_representations = None          # (the reference's zeros_like is overwritten at layer 0 before any use)
+        pass_state = None
+        if fused_dropout_on(dropout_keep_prob) and getattr(self, "dropout_state", None) is not None:
+            with torch.no_grad():
+                self.dropout_state[2].add_(1)                  # on the device, stream-ordered: every replay of a captured step advances it
+                pass_state = self.dropout_state.clone()        # this pass's 24 bytes: read by its forward kernels and by its backward
         for layer_idx in range(p['graph_num_layers']):
             self._layer_weights = w.scope('gnn_layer_%i' % layer_idx)
-            if dropout_keep_prob < 1.0:
-                cur_node_representations = torch.nn.functional.dropout(
-                    cur_node_representations, p=1.0 - dropout_keep_prob, training=True)
-            if layer_idx % p['graph_residual_connection_every_num_layers'] == 0:
-                t = cur_node_representations
-                if layer_idx > 0:
-                    cur_node_representations = (cur_node_representations + last_residual_representations) / 2
-                last_residual_representations = t
+            residual_step = layer_idx % res_every == 0
+            if pass_state is not None and dropout_tensor_ok(cur_node_representations):
+                # csrc/dropout.hip: one kernel for the whole layer-input stage; the layer index is the Philox stream
+                if residual_step and layer_idx > 0:
+                    last_residual_representations, cur_node_representations = dropout_residual(
+                        cur_node_representations, last_residual_representations, dropout_keep_prob, pass_state, layer_idx)
+                else:
+                    cur_node_representations = fused_dropout(cur_node_representations, dropout_keep_prob, pass_state, layer_idx)
+                    if residual_step:
+                        last_residual_representations = cur_node_representations
+            else:
+                if dropout_keep_prob < 1.0:
+                    cur_node_representations = torch.nn.functional.dropout(
+                        cur_node_representations, p=1.0 - dropout_keep_prob, training=True)
+                if residual_step:
+                    t = cur_node_representations
+                    if layer_idx > 0:
+                        cur_node_representations = (cur_node_representations + last_residual_representations) / 2
+                    last_residual_representations = t
             cur_node_representations = self._apply_gnn_layer(
                 cur_node_representations, graph, type_to_num_incoming_edges, p['graph_num_timesteps_per_layer'])
             if p['graph_inter_layer_norm']:
