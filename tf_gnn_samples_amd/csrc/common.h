@@ -8,6 +8,18 @@
 
 #define RELGNN_WAVE 64
 
+// Cycle stamps of the diagnostic builds: a file defines RELGNN_STAMPS under its own switch (RELGNN_LIMB_TIMING, RELGNN_PCT_TIMING,
+// RELGNN_FUSED_TIMING); TACC adds into the `tacc` array of the kernel that uses it.  Nothing otherwise.
+// RELGNN_STAMPS MUST BE DEFINED IN FRONT OF THE FILE'S FIRST #include: every project header includes this one, and a definition
+// behind any of them leaves the stamps empty without a word from the compiler.
+#ifdef RELGNN_STAMPS
+#define TSTAMP(v) __builtin_amdgcn_sched_barrier(0); const unsigned long long v = __builtin_amdgcn_s_memtime(); __builtin_amdgcn_sched_barrier(0)
+#define TACC(slot, t1, t0) tacc[slot] += (t1) - (t0)
+#else
+#define TSTAMP(v)
+#define TACC(slot, t1, t0)
+#endif
+
 namespace relgnn {
 
 static inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
@@ -75,6 +87,22 @@ __device__ __forceinline__ float act_grad(float x) {
   }
   return 1.f;
 }
+
+// act'(x) as a function of y = act(x), for the activations whose derivative the output determines (the epilogue of an
+// input-gradient product; act_bwd_from_output_kernel, seg_reduce.hip, states the same expressions per compile-time ACT)
+__device__ __forceinline__ float dact_from_output(int act, float yy) {
+  switch (act) {
+    case RELGNN_ACT_TANH: return 1.f - yy * yy;
+    case RELGNN_ACT_RELU: return yy > 0.f ? 1.f : 0.f;
+    case RELGNN_ACT_LEAKY_RELU: return yy > 0.f ? 1.f : 0.2f;
+    case RELGNN_ACT_ELU: return yy > 0.f ? 1.f : yy + 1.f;
+    case RELGNN_ACT_SELU: return yy > 0.f ? 1.0507009873554804934193349852946f : yy + 1.7580993408473768599402175208123f;
+    default: return 1.f;
+  }
+}
+
+// Keras' hard_sigmoid, the recurrent activation of the GRU cell (gru.hip, gru_cell.hip)
+__device__ __forceinline__ float hard_sigmoid(float x) { return fminf(fmaxf(0.2f * x + 0.5f, 0.f), 1.f); }
 
 // ---- per-MESSAGE activations ---------------------------------------------------------------------------------------
 // The edge kernels evaluate the activation once per message and feature (C2 shape: 4.7e8 evaluations per launch).  With

@@ -29,6 +29,7 @@
 // composition (2301 us; profiles/edge_mlp_fused.jsonl).
 #include "common.h"
 #include "lds_dma.h"
+#include "limb_frag.h"
 #include "limb_split.h"
 
 #include <type_traits>
@@ -37,9 +38,6 @@ using namespace relgnn;
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 constexpr int BK = 16;
 constexpr int EM_STAGES = 3;
 
@@ -144,29 +142,13 @@ __global__ __launch_bounds__(512, 2) void edge_mlp_fwd_kernel(const EdgeMlpArgs 
   };
 
   // ---- fragments / products -----------------------------------------------------------------------------------------------
-  struct Limbs { bf16x8 hi, mid, lo; };
-  auto read_blk = [&](int stage, int blk) {
-    const unsigned char* p = lds + stage * STAGE_BYTES + blk * 1024 + 16 * lane;
-    Limbs f;
-    f.hi = *reinterpret_cast<const bf16x8*>(p);
-    f.mid = *reinterpret_cast<const bf16x8*>(p + 1024);
-    f.lo = *reinterpret_cast<const bf16x8*>(p + 2048);
-    return f;
-  };
+  auto read_blk = [&](int stage, int blk) { return read_planes(lds + stage * STAGE_BYTES + blk * 1024 + 16 * lane, 1024); };
   f32x16 acc[TW];
 #pragma unroll
   for (int tm = 0; tm < TW; ++tm)
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[tm][r] = 0.f;
-  auto products = [&](f32x16 c, const Limbs& w, const Limbs& xx) {          // (the order of limb_gemm_sel_kernel)
-    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w.hi, xx.lo, c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w.lo, xx.hi, c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w.mid, xx.mid, c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w.hi, xx.mid, c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w.mid, xx.hi, c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w.hi, xx.hi, c, 0, 0, 0);
-    return c;
-  };
+  auto products = [&](f32x16 c, const Frag& w, const Frag& xx) { return limb_products(c, w, xx); };
 
   // ---- pipeline: k-tile t is multiplied while k-tile t+1 is complete in LDS and k-tile t+2 arrives (W by DMA, the left operand
   // from the register set of its parity, whose next load — k-tile t+4 — follows) ---------------------------------------------------
@@ -183,7 +165,7 @@ __global__ __launch_bounds__(512, 2) void edge_mlp_fwd_kernel(const EdgeMlpArgs 
   wait_w(min(1, ntiles - 1));
   wait_lgkm0();
   __builtin_amdgcn_s_barrier();
-  Limbs w_cur, w_nxt, x0, x1;
+  Frag w_cur, w_nxt, x0, x1;
   w_cur = read_blk(0, PA + 3 * wn);
   x0 = read_blk(0, 3 * (wm * TW));
   auto ktile = [&](int t, auto odd_c) {

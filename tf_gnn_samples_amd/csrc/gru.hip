@@ -10,8 +10,7 @@ using namespace relgnn;
 
 namespace {
 
-__device__ __forceinline__ float hard_sigmoid(float x) { return fminf(fmaxf(0.2f * x + 0.5f, 0.f), 1.f); }
-// derivative of hard_sigmoid evaluated from its OUTPUT y (0 < y < 1 on the linear piece)
+// derivative of hard_sigmoid (common.h) evaluated from its OUTPUT y (0 < y < 1 on the linear piece)
 __device__ __forceinline__ float hard_sigmoid_grad_from_out(float y) { return (y > 0.f && y < 1.f) ? 0.2f : 0.f; }
 
 __device__ __forceinline__ float act_apply(int act, float x) {

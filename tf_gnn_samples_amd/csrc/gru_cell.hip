@@ -27,6 +27,7 @@
 #include "common.h"
 #include "handover.h"
 #include "lds_dma.h"
+#include "limb_frag.h"
 #include "limb_split.h"
 
 #include <stdlib.h>
@@ -36,13 +37,7 @@ using namespace relgnn;
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
-constexpr int PIECE = 528;              // 32 rows x 16 B (8 k of one limb) + 16 B: consecutive pieces start in consecutive bank quads
-constexpr int PLANE = 16 * PIECE;       // the 16 (k-tile, k half) pieces of one limb of a sub-slab (32 rows x 128 k)
-constexpr int SLAB = 3 * PLANE;         // 3 limbs: 25 344 B
+constexpr int PIECE = SubSlab<16>::PIECE, PLANE = SubSlab<16>::PLANE, SLAB = SubSlab<16>::SLAB;   // 32 rows x 128 k (limb_frag.h)
 constexpr int U = 128;                  // units = input width
 
 struct GruArgs {
@@ -58,8 +53,6 @@ struct GruArgs {
   int32_t* status;
 };
 
-struct Frag { bf16x8 hi, mid, lo; };
-
 // store at `base + byte offset`: a uniform base and a 32-bit per-lane byte offset (the global_store form that needs no per-lane
 // 64-bit address)
 __device__ __forceinline__ void st4(float* base, uint32_t boff, f32x4 v) {
@@ -68,8 +61,6 @@ __device__ __forceinline__ void st4(float* base, uint32_t boff, f32x4 v) {
 // the value as the compiler must take it here (an offset it cannot compute ahead of the k-loops: the addresses of every epilogue
 // access, hoisted to the top of a panel, were seventy spilled registers reloaded one round trip at a time)
 __device__ __forceinline__ uint32_t here(uint32_t v) { asm volatile("" : "+v"(v)); return v; }
-
-__device__ __forceinline__ float hard_sigmoid(float x) { return fminf(fmaxf(0.2f * x + 0.5f, 0.f), 1.f); }   // (gru.hip's expression)
 
 // ---------------------------------------------------------------------------------------------------------------------------------
 // The forward.  Four sub-slabs with fixed jobs — 0, 1 the x tiles, 2, 3 the h
@@ -104,19 +95,9 @@ __global__ __launch_bounds__(1024) void gru_cell_fwd_kernel(const GruArgs a) {
   bool dead = false;
   const int spin_limit = handover_limit(a.status);
   auto poll = [&](int* p, int target) {
-    if (dead) return;
-    int spins = 0;
-    while (__builtin_amdgcn_readfirstlane(handover_counter(p)) < target) {
-      __builtin_amdgcn_s_sleep(1);
-      if (++spins > spin_limit) { dead = true; if (lane == 0 && a.status) atomicOr(a.status, 4 + (wave < 8 ? 0 : 4)); break; }
-    }
-    handover_fence();
+    handover_poll(p, target, spin_limit, dead, a.status, wave < 8 ? RELGNN_HANDOVER_PC_MATRIX : RELGNN_HANDOVER_PC_PRODUCER, lane);
   };
-  auto bump = [&](int* p, int by) {                           // (behind the LDS accesses it reports)
-    wait_lgkm0();
-    handover_fence();
-    if (lane == 0) __hip_atomic_fetch_add(p, by, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-  };
+  auto bump = [&](int* p, int by) { handover_signal(p, by); };      // (behind the LDS accesses it reports)
 
   if (wave < 8) {
     // =================================================== matrix waves ===================================================
@@ -136,22 +117,8 @@ __global__ __launch_bounds__(1024) void gru_cell_fwd_kernel(const GruArgs a) {
       f.lo = *reinterpret_cast<const bf16x8*>(p + wlane + 2048);
       if (++wt == wlen) wt = 0;
     };
-    auto products = [&](f32x16 c, const Frag& w, const Frag& x) {        // limb_gemm.hip's order: small terms first
-      c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w.hi, x.lo, c, 0, 0, 0);
-      c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w.lo, x.hi, c, 0, 0, 0);
-      c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w.mid, x.mid, c, 0, 0, 0);
-      c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w.hi, x.mid, c, 0, 0, 0);
-      c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w.mid, x.hi, c, 0, 0, 0);
-      c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w.hi, x.hi, c, 0, 0, 0);
-      return c;
-    };
-    auto xread = [&](const unsigned char* p) {
-      Frag f;
-      f.hi = *reinterpret_cast<const bf16x8*>(p);
-      f.mid = *reinterpret_cast<const bf16x8*>(p + PLANE);
-      f.lo = *reinterpret_cast<const bf16x8*>(p + 2 * PLANE);
-      return f;
-    };
+    auto products = [&](f32x16 c, const Frag& w, const Frag& x) { return limb_products(c, w, x); };
+    auto xread = [&](const unsigned char* p) { return read_planes(p, PLANE); };
     wload(wr[0]); wload(wr[1]); wload(wr[2]);
     const int xlane = h32 * PIECE + i32 * 16;
     unsigned char* const epatch = ex + i32 * EROWB + (cw + 4 * h32) * 4;       // my patch of exchange tile 0 (tile 1: + 32 rows)
@@ -221,17 +188,7 @@ __global__ __launch_bounds__(1024) void gru_cell_fwd_kernel(const GruArgs a) {
   const int pw = wave - 8;
   const int col4 = lane & 31, rsub = lane >> 5;
   auto put4 = [&](unsigned char* slab, int row, f32x4 x) {
-    uint32_t h0, m0_, l0, h1, m1, l1;
-    split_pair(x[0], x[1], h0, m0_, l0);
-    split_pair(x[2], x[3], h1, m1, l1);
-    if (__builtin_expect(max3_abs(max3_abs(x[0], x[1], x[2]), x[3], x[3]) >= __uint_as_float(0x7F7F8000u), 0)) {
-      split_pair_sat(x[0], x[1], h0, m0_, l0);
-      split_pair_sat(x[2], x[3], h1, m1, l1);
-    }
-    unsigned char* o = slab + row * 16 + (col4 >> 1) * PIECE + (col4 & 1) * 8;
-    *reinterpret_cast<uint2*>(o) = make_uint2(h0, h1);
-    *reinterpret_cast<uint2*>(o + PLANE) = make_uint2(m0_, m1);
-    *reinterpret_cast<uint2*>(o + 2 * PLANE) = make_uint2(l0, l1);
+    split4(x, slab + row * 16 + (col4 >> 1) * PIECE + (col4 & 1) * 8, PLANE);
   };
   f32x4 xv[2][2], hv[2][2];
   auto request = [&](int pi) {                                 // x and h of my rows of panel pi (past the end: row 0, zeroed later)
@@ -396,32 +353,12 @@ __global__ __launch_bounds__(1024) void gru_cell_bwd_kernel(const GruBwdArgs a) 
   bool dead = false;
   const int spin_limit = handover_limit(a.status);
   auto poll = [&](int* p, int target) {
-    if (dead) return;
-    int spins = 0;
-    while (__builtin_amdgcn_readfirstlane(handover_counter(p)) < target) {
-      __builtin_amdgcn_s_sleep(1);
-      if (++spins > spin_limit) { dead = true; if (lane == 0 && a.status) atomicOr(a.status, 4 + (wave < 8 ? 0 : 4)); break; }
-    }
-    handover_fence();
+    handover_poll(p, target, spin_limit, dead, a.status, wave < 8 ? RELGNN_HANDOVER_PC_MATRIX : RELGNN_HANDOVER_PC_PRODUCER, lane);
   };
-  auto bump = [&](int* p, int by) {                           // (behind the LDS accesses it reports)
-    wait_lgkm0();
-    handover_fence();
-    if (lane == 0) __hip_atomic_fetch_add(p, by, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-  };
+  auto bump = [&](int* p, int by) { handover_signal(p, by); };      // (behind the LDS accesses it reports)
   // four columns of a row tile as limbs into a sub-slab: 8 bytes per limb at row * 16 + (col4 >> 1) * PIECE + (col4 & 1) * 8
   auto put4 = [&](unsigned char* slab, int row, int col4, f32x4 x) {
-    uint32_t h0, m0_, l0, h1, m1, l1;
-    split_pair(x[0], x[1], h0, m0_, l0);
-    split_pair(x[2], x[3], h1, m1, l1);
-    if (__builtin_expect(max3_abs(max3_abs(x[0], x[1], x[2]), x[3], x[3]) >= __uint_as_float(0x7F7F8000u), 0)) {
-      split_pair_sat(x[0], x[1], h0, m0_, l0);
-      split_pair_sat(x[2], x[3], h1, m1, l1);
-    }
-    unsigned char* o = slab + row * 16 + (col4 >> 1) * PIECE + (col4 & 1) * 8;
-    *reinterpret_cast<uint2*>(o) = make_uint2(h0, h1);
-    *reinterpret_cast<uint2*>(o + PLANE) = make_uint2(m0_, m1);
-    *reinterpret_cast<uint2*>(o + 2 * PLANE) = make_uint2(l0, l1);
+    split4(x, slab + row * 16 + (col4 >> 1) * PIECE + (col4 & 1) * 8, PLANE);
   };
 
   if (wave < 8) {
@@ -446,22 +383,8 @@ __global__ __launch_bounds__(1024) void gru_cell_bwd_kernel(const GruBwdArgs a) 
       f.lo = *reinterpret_cast<const bf16x8*>(p + wlane + 2048);
       if (++wt == 24) wt = 0;
     };
-    auto products = [&](f32x16 c, const Frag& w, const Frag& x) {        // limb_gemm.hip's order: small terms first
-      c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w.hi, x.lo, c, 0, 0, 0);
-      c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w.lo, x.hi, c, 0, 0, 0);
-      c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w.mid, x.mid, c, 0, 0, 0);
-      c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w.hi, x.mid, c, 0, 0, 0);
-      c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w.mid, x.hi, c, 0, 0, 0);
-      c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w.hi, x.hi, c, 0, 0, 0);
-      return c;
-    };
-    auto xread = [&](const unsigned char* p) {
-      Frag f;
-      f.hi = *reinterpret_cast<const bf16x8*>(p);
-      f.mid = *reinterpret_cast<const bf16x8*>(p + PLANE);
-      f.lo = *reinterpret_cast<const bf16x8*>(p + 2 * PLANE);
-      return f;
-    };
+    auto products = [&](f32x16 c, const Frag& w, const Frag& x) { return limb_products(c, w, x); };
+    auto xread = [&](const unsigned char* p) { return read_planes(p, PLANE); };
     wload(wr[0]); wload(wr[1]); wload(wr[2]);
     const int xlane = h32 * PIECE + i32 * 16;
     unsigned char* const epatch = ex + i32 * EROW + (cw + 4 * h32) * 4;        // my patch of exchange tile 0 (tile 1: + 32 rows)

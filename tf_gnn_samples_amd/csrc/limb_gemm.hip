@@ -27,8 +27,12 @@
 // (i = lane & 31, h = lane >> 5) owns row i, k = 8 h .. 8 h + 7, stored at 16 B * lane — conflict-free for the 16-lane groups of gfx950's ds_read_b128 (rows 0-3, 12-15, 20-27 of one k half hit 16
 // different bank quads).  The W limbs are the MFMA's A operand and the X limbs its B operand, so a lane ends up with four
 // consecutive output columns of one output row (one 16-byte store), as in panel_gemm.hip.
+#ifdef RELGNN_LIMB_TIMING
+#define RELGNN_STAMPS
+#endif
 #include "common.h"
 #include "lds_dma.h"
+#include "limb_frag.h"
 #include "limb_split.h"
 
 #include <stdlib.h>
@@ -38,17 +42,11 @@ using namespace relgnn;
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 constexpr int BK = 16;
 constexpr int STAGES = 4;
 #ifdef RELGNN_LIMB_TIMING
 __device__ unsigned long long* g_limb_timing_dev = nullptr;
 unsigned long long* g_limb_timing = nullptr;   // diagnostic build: per-wave cycle totals of the k-loop's segments
-#define TSTAMP(v) __builtin_amdgcn_sched_barrier(0); const unsigned long long v = __builtin_amdgcn_s_memtime(); __builtin_amdgcn_sched_barrier(0)
-#else
-#define TSTAMP(v)
 #endif
 
 struct LimbArgs {
@@ -71,24 +69,11 @@ struct LimbArgs {
 #endif
 };
 
-// act'(x) as a function of y = act(x) — the same expressions, in the same order, as act_bwd_from_output_kernel (seg_reduce.hip)
-__device__ __forceinline__ float dact_from_output(int act, float yy) {
-  switch (act) {
-    case RELGNN_ACT_TANH: return 1.f - yy * yy;
-    case RELGNN_ACT_RELU: return yy > 0.f ? 1.f : 0.f;
-    case RELGNN_ACT_LEAKY_RELU: return yy > 0.f ? 1.f : 0.2f;
-    case RELGNN_ACT_ELU: return yy > 0.f ? 1.f : yy + 1.f;
-    case RELGNN_ACT_SELU: return yy > 0.f ? 1.0507009873554804934193349852946f : yy + 1.7580993408473768599402175208123f;
-    default: return 1.f;
-  }
-}
-
 // ---- fp32 -> two fp16 limbs behind an exact power-of-two scale ----------------------------------------------------------
 // x * s = hi + lo + r with hi = fp16(x s), lo = fp16(x s - hi), |r| <= 2^-22 |x s|; s = 2^j puts the largest magnitude of the
 // row (of the matrix, for weights) into [2^14, 2^15): fp16's mantissa is enough for two limbs, its exponent range is what the
 // scale is for.  Three products per fp32 product (hi hi, hi lo, lo hi: each exact in fp32) instead of the six of the bf16 triple.
 typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 __device__ __forceinline__ uint32_t limb16_scale_bits(float mx) {          // exponent field of s (s = 1 for 0 / denormal / inf / nan)
   const uint32_t e = (__float_as_uint(mx) >> 23) & 0xFFu;
   if (e == 0u || e == 255u) return 127u;
@@ -260,45 +245,15 @@ __global__ __launch_bounds__(512) void limb_gemm_kernel(const LimbArgs a) {
   };
 
   // ---- fragments -----------------------------------------------------------------------------------------------------
-  struct Limbs { bf16x8 hi, mid, lo; };
-  auto read_planes = [&](const unsigned char* p) {          // (NL = 2: hi, lo; `mid` stays unused)
-    Limbs f;
-    f.hi = *reinterpret_cast<const bf16x8*>(p);
-    if constexpr (NL == 3) {
-      f.mid = *reinterpret_cast<const bf16x8*>(p + 1024);
-      f.lo = *reinterpret_cast<const bf16x8*>(p + 2048);
-    } else {
-      f.lo = *reinterpret_cast<const bf16x8*>(p + 1024);
-      f.mid = f.lo;
-    }
-    return f;
-  };
-  auto read_x = [&](int stage, int tm) { return read_planes(lds + stage * STAGE_BYTES + (NL * tm) * 1024 + 16 * lane); };
-  auto read_w = [&](int stage) { return read_planes(lds + stage * STAGE_BYTES + (PA + NL * wave) * 1024 + 16 * lane); };
+  auto planes = [&](const unsigned char* p) { return read_planes<NL>(p, 1024); };      // (NL = 2: hi, lo)
+  auto read_x = [&](int stage, int tm) { return planes(lds + stage * STAGE_BYTES + (NL * tm) * 1024 + 16 * lane); };
+  auto read_w = [&](int stage) { return planes(lds + stage * STAGE_BYTES + (PA + NL * wave) * 1024 + 16 * lane); };
   f32x16 acc[T32];
 #pragma unroll
   for (int tm = 0; tm < T32; ++tm)
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[tm][r] = 0.f;
-  // small terms first: the three 2^-16 products, then the two 2^-8 ones, then the leading one
-  auto products = [&](f32x16 c, const Limbs& w, const Limbs& x) {
-    if constexpr (NL == 2) {
-      const f16x8 wh = __builtin_bit_cast(f16x8, w.hi), wl = __builtin_bit_cast(f16x8, w.lo);
-      const f16x8 xh_ = __builtin_bit_cast(f16x8, x.hi), xl = __builtin_bit_cast(f16x8, x.lo);
-      c = __builtin_amdgcn_mfma_f32_32x32x16_f16(wh, xl, c, 0, 0, 0);
-      c = __builtin_amdgcn_mfma_f32_32x32x16_f16(wl, xh_, c, 0, 0, 0);
-      c = __builtin_amdgcn_mfma_f32_32x32x16_f16(wh, xh_, c, 0, 0, 0);
-      return c;
-    } else {
-      c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w.hi, x.lo, c, 0, 0, 0);
-      c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w.lo, x.hi, c, 0, 0, 0);
-      c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w.mid, x.mid, c, 0, 0, 0);
-      c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w.hi, x.mid, c, 0, 0, 0);
-      c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w.mid, x.hi, c, 0, 0, 0);
-      c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w.hi, x.hi, c, 0, 0, 0);
-      return c;
-    }
-  };
+  auto products = [&](f32x16 c, const Frag& w, const Frag& x) { return limb_products<NL>(c, w, x); };
 
   // ---- pipeline ------------------------------------------------------------------------------------------------------
   // The W limbs of a k-tile stay in registers for the whole tile; the X limbs rotate through two register sets, row tile
@@ -311,7 +266,7 @@ __global__ __launch_bounds__(512) void limb_gemm_kernel(const LimbArgs a) {
   // by then every read of stage t % 4 has been issued, so the barrier releases that stage, and the reads of k-tile t+1 (its W
   // limbs, its first X tile) go out under the last row tile's six MFMAs.  The DMA of k-tile t+3 is issued during k-tile t, a few
   // instructions in front of every row tile but the last (its stage, (t-1) % 4, was released inside k-tile t-1).
-  Limbs w_cur, w_nxt, xs[2];
+  Frag w_cur, w_nxt, xs[2];
   constexpr int SLOTS = T32 > 1 ? T32 - 1 : 1;
   constexpr int PER = (G + SLOTS - 1) / SLOTS;
   constexpr int C1 = PER < G ? PER : G, C2 = 2 * PER < G ? 2 * PER : G, C3 = 3 * PER < G ? 3 * PER : G;
@@ -365,8 +320,8 @@ __global__ __launch_bounds__(512) void limb_gemm_kernel(const LimbArgs a) {
 #endif
 #pragma unroll
     for (int tm = 0; tm < T32; ++tm) {
-      Limbs& xc = xs[(tm + PAR) & 1];
-      Limbs& xn = xs[(tm + PAR + 1) & 1];
+      Frag& xc = xs[(tm + PAR) & 1];
+      Frag& xn = xs[(tm + PAR + 1) & 1];
       if (feed) {                                              // blocks [tm * PER, (tm + 1) * PER) of k-tile t + 3
         if (tm == 0) issue_part(fstage, std::integral_constant<int, 0>{}, std::integral_constant<int, C1>{});
         if (tm == 1 && SLOTS > 1) issue_part(fstage, std::integral_constant<int, C1>{}, std::integral_constant<int, C2>{});
@@ -559,29 +514,13 @@ __global__ __launch_bounds__(512, 2) void limb_gemm_sel_kernel(const LimbSelArgs
   };
 
   // ---- fragments / products -----------------------------------------------------------------------------------------------
-  struct Limbs { bf16x8 hi, mid, lo; };
-  auto read_blk = [&](int stage, int blk) {
-    const unsigned char* p = lds + stage * STAGE_BYTES + blk * 1024 + 16 * lane;
-    Limbs f;
-    f.hi = *reinterpret_cast<const bf16x8*>(p);
-    f.mid = *reinterpret_cast<const bf16x8*>(p + 1024);
-    f.lo = *reinterpret_cast<const bf16x8*>(p + 2048);
-    return f;
-  };
+  auto read_blk = [&](int stage, int blk) { return read_planes(lds + stage * STAGE_BYTES + blk * 1024 + 16 * lane, 1024); };
   f32x16 acc[TW];
 #pragma unroll
   for (int tm = 0; tm < TW; ++tm)
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[tm][r] = 0.f;
-  auto products = [&](f32x16 c, const Limbs& w, const Limbs& xx) {
-    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w.hi, xx.lo, c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w.lo, xx.hi, c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w.mid, xx.mid, c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w.hi, xx.mid, c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w.mid, xx.hi, c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w.hi, xx.hi, c, 0, 0, 0);
-    return c;
-  };
+  auto products = [&](f32x16 c, const Frag& w, const Frag& xx) { return limb_products(c, w, xx); };
 
   // ---- pipeline: k-tile t is multiplied while k-tile t+1 is complete in LDS and k-tile t+2 arrives (W by DMA, X split from the
   // register set of its parity, whose next load — k-tile t+4 — follows) ----------------------------------------------------------
@@ -600,7 +539,7 @@ __global__ __launch_bounds__(512, 2) void limb_gemm_sel_kernel(const LimbSelArgs
     wait_lgkm0();
     __builtin_amdgcn_s_barrier();
   }
-  Limbs w_cur, w_nxt, x0, x1;
+  Frag w_cur, w_nxt, x0, x1;
   if (ntiles > 0) {
     w_cur = read_blk(0, PA + 3 * wn);
     x0 = read_blk(0, 3 * (wm * TW));
@@ -767,14 +706,7 @@ __global__ __launch_bounds__(512) void limb_gemm_tile_kernel(const LimbSelArgs a
     *reinterpret_cast<uint4*>(p + 2048) = l;
   };
 
-  struct Limbs { bf16x8 hi, mid, lo; };
-  auto read3 = [&](const unsigned char* p) {
-    Limbs f;
-    f.hi = *reinterpret_cast<const bf16x8*>(p);
-    f.mid = *reinterpret_cast<const bf16x8*>(p + 1024);
-    f.lo = *reinterpret_cast<const bf16x8*>(p + 2048);
-    return f;
-  };
+  auto read3 = [&](const unsigned char* p) { return read_planes(p, 1024); };
   auto read_w = [&](int kt) { return read3(lds + (kt * WB + 3 * wn) * 1024 + 16 * lane); };
   auto read_x = [&](int kt, int tm) { return read3(ring + (kt % TILE_RING) * STAGE_BYTES + (3 * (wm * TW + tm)) * 1024 + 16 * lane); };
   f32x16 acc[TW];
@@ -851,7 +783,9 @@ __global__ __launch_bounds__(512) void limb_gemm_tile_kernel(const LimbSelArgs a
   // split from its register set into the other two stages — they were read one super-tile ago, before the last barrier — and
   // set j, split one super-tile ago, is reloaded for the next panel (three super-tiles, 48 KB per CU, ahead of its split; a lead of
   // seven super-tiles in eight register sets only lengthened the queues in front of the stores: 259 vs 227 us).
-  auto two = [&](const Limbs& w, const Limbs& xa, const Limbs& xb) {
+  // (limb_products' order (limb_frag.h) per accumulator, written out so that the two chains alternate: as two calls of the shared
+  //  function hipcc schedules the twelve MFMAs and the reads around them differently)
+  auto two = [&](const Frag& w, const Frag& xa, const Frag& xb) {
     acc[0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w.hi, xa.lo, acc[0], 0, 0, 0);
     acc[1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w.hi, xb.lo, acc[1], 0, 0, 0);
     acc[0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w.lo, xa.hi, acc[0], 0, 0, 0);
@@ -873,11 +807,11 @@ __global__ __launch_bounds__(512) void limb_gemm_tile_kernel(const LimbSelArgs a
       constexpr int j = decltype(j_c)::value;
       constexpr int jn = (j + 1) % 4;
       TSTAMP(q0);
-      const Limbs wa = read_w(2 * j), xa0 = read_x(2 * j, 0), xa1 = read_x(2 * j, 1);
+      const Frag wa = read_w(2 * j), xa0 = read_x(2 * j, 0), xa1 = read_x(2 * j, 1);
       x_split(xv[jn], j == 3 ? ok_nxt : ok_cur, jn);  // (past the last panel: zeros that nobody reads)
       TSTAMP(q1);
       x_load(xv[j], ptr_nxt, j);
-      const Limbs wb = read_w(2 * j + 1), xb0 = read_x(2 * j + 1, 0), xb1 = read_x(2 * j + 1, 1);
+      const Frag wb = read_w(2 * j + 1), xb0 = read_x(2 * j + 1, 0), xb1 = read_x(2 * j + 1, 1);
       two(wa, xa0, xa1);
       two(wb, xb0, xb1);
       TSTAMP(q2);
@@ -1064,49 +998,20 @@ __global__ __launch_bounds__(512) void limb_gemm_tn_kernel(const LimbTnArgs a) {
   };
 
   // ---- fragments / products (as in limb_gemm_kernel) ------------------------------------------------------------------
-  struct Limbs { bf16x8 hi, mid, lo; };
-  auto read_planes = [&](const unsigned char* p) {
-    Limbs f;
-    f.hi = *reinterpret_cast<const bf16x8*>(p);
-    if constexpr (NL == 3) {
-      f.mid = *reinterpret_cast<const bf16x8*>(p + 1024);
-      f.lo = *reinterpret_cast<const bf16x8*>(p + 2048);
-    } else {
-      f.lo = *reinterpret_cast<const bf16x8*>(p + 1024);
-      f.mid = f.lo;
-    }
-    return f;
-  };
+  auto planes = [&](const unsigned char* p) { return read_planes<NL>(p, 1024); };      // (NL = 2: hi, lo)
   const int cw = wave % CW, tm0 = (wave / CW) * TPW;               // my column block, my first row tile
   auto read_x = [&](int stage, int tm) {
-    return read_planes(lds + stage * STAGE_BYTES + (NL * (tm0 + tm)) * 1024 + 16 * (lane ^ ((lane >> 3) & 3)));
+    return planes(lds + stage * STAGE_BYTES + (NL * (tm0 + tm)) * 1024 + 16 * (lane ^ ((lane >> 3) & 3)));
   };
   auto read_w = [&](int stage) {
-    return read_planes(lds + stage * STAGE_BYTES + (PA + NL * cw) * 1024 + 16 * (lane ^ ((lane >> 3) & 3)));
+    return planes(lds + stage * STAGE_BYTES + (PA + NL * cw) * 1024 + 16 * (lane ^ ((lane >> 3) & 3)));
   };
   f32x16 acc[TPW];
 #pragma unroll
   for (int tm = 0; tm < TPW; ++tm)
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[tm][r] = 0.f;
-  auto products = [&](f32x16 c, const Limbs& w, const Limbs& x) {
-    if constexpr (NL == 2) {
-      const f16x8 wh = __builtin_bit_cast(f16x8, w.hi), wl = __builtin_bit_cast(f16x8, w.lo);
-      const f16x8 xh_ = __builtin_bit_cast(f16x8, x.hi), xl = __builtin_bit_cast(f16x8, x.lo);
-      c = __builtin_amdgcn_mfma_f32_32x32x16_f16(wh, xl, c, 0, 0, 0);
-      c = __builtin_amdgcn_mfma_f32_32x32x16_f16(wl, xh_, c, 0, 0, 0);
-      c = __builtin_amdgcn_mfma_f32_32x32x16_f16(wh, xh_, c, 0, 0, 0);
-      return c;
-    } else {
-      c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w.hi, x.lo, c, 0, 0, 0);
-      c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w.lo, x.hi, c, 0, 0, 0);
-      c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w.mid, x.mid, c, 0, 0, 0);
-      c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w.hi, x.mid, c, 0, 0, 0);
-      c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w.mid, x.hi, c, 0, 0, 0);
-      c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w.hi, x.hi, c, 0, 0, 0);
-      return c;
-    }
-  };
+  auto products = [&](f32x16 c, const Frag& w, const Frag& x) { return limb_products<NL>(c, w, x); };
 
   // ---- pipeline: super-tile S is loaded during k-tile 2S-4, split and stored during k-tiles 2S-2 (columns 0, 1) and 2S-1
   // (columns 2, 3) — after the barrier inside k-tile 2S-3 released its two stages, before the barrier inside k-tile 2S-1
@@ -1118,7 +1023,7 @@ __global__ __launch_bounds__(512) void limb_gemm_tn_kernel(const LimbTnArgs a) {
   // they occupy the pipe.  (Split first, MFMAs after — what hipcc makes of it when left alone — puts both waves of a SIMD in
   // their VALU phase at the same time, the barrier keeps them in step, and the pipe idles: 124 us instead of 100 at
   // [36 k, 768]^T x [36 k, 256].)
-  Limbs w_cur, w_nxt, xs[2];
+  Frag w_cur, w_nxt, xs[2];
   using I0 = std::integral_constant<int, 0>; using I1 = std::integral_constant<int, 1>;
   using I2 = std::integral_constant<int, 2>; using I3 = std::integral_constant<int, 3>;
   ix_load(0);
@@ -1141,8 +1046,8 @@ __global__ __launch_bounds__(512) void limb_gemm_tn_kernel(const LimbTnArgs a) {
     }
 #pragma unroll
     for (int tm = 0; tm < TPW; ++tm) {
-      Limbs& xc = xs[(tm + PAR) & 1];
-      Limbs& xn = xs[(tm + PAR + 1) & 1];
+      Frag& xc = xs[(tm + PAR) & 1];
+      Frag& xn = xs[(tm + PAR + 1) & 1];
       if (tm == TPW - 1) {
         if (more) {
           wait_lgkm0();                                        // my reads of stage t % 4 and my limb stores are done

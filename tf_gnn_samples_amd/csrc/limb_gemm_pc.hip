@@ -21,6 +21,7 @@
 #include "common.h"
 #include "handover.h"
 #include "lds_dma.h"
+#include "limb_frag.h"
 #include "limb_split.h"
 
 #include <stdlib.h>
@@ -30,13 +31,7 @@ using namespace relgnn;
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
-constexpr int PIECE = 528;              // 32 rows x 16 B (8 k of one limb) + 16 B: consecutive pieces start in consecutive bank quads
-constexpr int PLANE = 16 * PIECE;       // the 16 (k-tile, k half) pieces of one limb of a sub-slab (32 rows x 128 k)
-constexpr int SLAB = 3 * PLANE;         // 3 limbs: 25 344 B
+constexpr int PIECE = SubSlab<16>::PIECE, PLANE = SubSlab<16>::PLANE, SLAB = SubSlab<16>::SLAB;   // 32 rows x 128 k (limb_frag.h)
 constexpr int NBUF = 6;
 constexpr int CTL = 16;                 // control words: [1..6] rows filled per buffer, [8..13] matrix waves done with it
 
@@ -50,20 +45,6 @@ struct PcArgs {
   int32_t units_base, units_rem, groups;
   int32_t* status;
 };
-
-struct Frag { bf16x8 hi, mid, lo; };
-
-// act'(x) as a function of y = act(x) — the expressions of act_bwd_from_output_kernel (seg_reduce.hip) and limb_gemm.hip
-__device__ __forceinline__ float dact_from_output(int act, float yy) {
-  switch (act) {
-    case RELGNN_ACT_TANH: return 1.f - yy * yy;
-    case RELGNN_ACT_RELU: return yy > 0.f ? 1.f : 0.f;
-    case RELGNN_ACT_LEAKY_RELU: return yy > 0.f ? 1.f : 0.2f;
-    case RELGNN_ACT_ELU: return yy > 0.f ? 1.f : yy + 1.f;
-    case RELGNN_ACT_SELU: return yy > 0.f ? 1.0507009873554804934193349852946f : yy + 1.7580993408473768599402175208123f;
-    default: return 1.f;
-  }
-}
 
 // S2 = K / 128 is a template parameter: the k-tiles of a pass are straight-line code.  (With a run-time loop over the half slabs
 // hipcc's wait insertion loses track of the W fragments that are in flight across the loop's back edge and drains them at every
@@ -91,13 +72,7 @@ __global__ __launch_bounds__(1024) void limb_gemm_pc_kernel(const PcArgs a) {
   bool dead = false;
   const int spin_limit = handover_limit(a.status);
   auto poll = [&](int* p, int target) {
-    if (dead) return;
-    int spins = 0;
-    while (__builtin_amdgcn_readfirstlane(handover_counter(p)) < target) {
-      __builtin_amdgcn_s_sleep(1);
-      if (++spins > spin_limit) { dead = true; if (lane == 0 && a.status) atomicOr(a.status, 4 + (wave < 8 ? 0 : 4)); break; }
-    }
-    handover_fence();
+    handover_poll(p, target, spin_limit, dead, a.status, wave < 8 ? RELGNN_HANDOVER_PC_MATRIX : RELGNN_HANDOVER_PC_PRODUCER, lane);
   };
 
   if (wave < 8) {
@@ -112,22 +87,8 @@ __global__ __launch_bounds__(1024) void limb_gemm_pc_kernel(const PcArgs a) {
       f.lo = *reinterpret_cast<const bf16x8*>(p + 1024);
       if (++wt == ntiles) { wt = 0; if (++wc == chunks) wc = 0; }
     };
-    auto products = [&](f32x16 c, const Frag& w, const Frag& x) {        // limb_gemm.hip's order: small terms first
-      c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w.hi, x.lo, c, 0, 0, 0);
-      c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w.lo, x.hi, c, 0, 0, 0);
-      c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w.mid, x.mid, c, 0, 0, 0);
-      c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w.hi, x.mid, c, 0, 0, 0);
-      c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w.mid, x.hi, c, 0, 0, 0);
-      c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w.hi, x.hi, c, 0, 0, 0);
-      return c;
-    };
-    auto xread = [&](const unsigned char* p) {
-      Frag f;
-      f.hi = *reinterpret_cast<const bf16x8*>(p);
-      f.mid = *reinterpret_cast<const bf16x8*>(p + PLANE);
-      f.lo = *reinterpret_cast<const bf16x8*>(p + 2 * PLANE);
-      return f;
-    };
+    auto products = [&](f32x16 c, const Frag& w, const Frag& x) { return limb_products(c, w, x); };
+    auto xread = [&](const unsigned char* p) { return read_planes(p, PLANE); };
     wload(wr[0]); wload(wr[1]); wload(wr[2]);
     int b0 = 0, gen0 = 0;                                     // buffer / generation of the next sub-slab in sequence
     const int xlane = h32 * PIECE + i32 * 16;
@@ -254,21 +215,9 @@ __global__ __launch_bounds__(1024) void limb_gemm_pc_kernel(const PcArgs a) {
     for (int j = 0; j < 2; ++j) {
       f32x4 x = v[j];
       if (r0 + 2 * j >= rend) x = f32x4{0.f, 0.f, 0.f, 0.f};
-      uint32_t h0, m0_, l0, h1, m1, l1;
-      split_pair(x[0], x[1], h0, m0_, l0);
-      split_pair(x[2], x[3], h1, m1, l1);
-      if (__builtin_expect(max3_abs(max3_abs(x[0], x[1], x[2]), x[3], x[3]) >= __uint_as_float(0x7F7F8000u), 0)) {
-        split_pair_sat(x[0], x[1], h0, m0_, l0);
-        split_pair_sat(x[2], x[3], h1, m1, l1);
-      }
-      unsigned char* o = lds + fill * SLAB + (4 * pw + 2 * j + rsub) * 16 + wr_lane;
-      *reinterpret_cast<uint2*>(o) = make_uint2(h0, h1);
-      *reinterpret_cast<uint2*>(o + PLANE) = make_uint2(m0_, m1);
-      *reinterpret_cast<uint2*>(o + 2 * PLANE) = make_uint2(l0, l1);
+      split4(x, lds + fill * SLAB + (4 * pw + 2 * j + rsub) * 16 + wr_lane, PLANE);
     }
-    wait_lgkm0();
-    handover_fence();
-    if (lane == 0) __hip_atomic_fetch_add(ctl + 1 + fill, 4, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    handover_signal(ctl + 1 + fill, 4);
   };
   Pos p0{0, 0, 0, 0}, p1, p2, p3;
   f32x4 v0[2], v1[2], v2[2], v3[2];

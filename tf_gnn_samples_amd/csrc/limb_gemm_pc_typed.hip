@@ -15,9 +15,13 @@
 // (with one unit per wave, six: the fragments' L2 traffic became the larger stream and the N = 128 forms lost to the panel kernels).
 // Same k-tile and limb-product order per accumulator as limb_gemm_tile_kernel / limb_gemm_sel_kernel: bit-identical results
 // (tests/test_gpu_limb_gemm.py).
+#ifdef RELGNN_PCT_TIMING
+#define RELGNN_STAMPS
+#endif
 #include "common.h"
 #include "handover.h"
 #include "lds_dma.h"
+#include "limb_frag.h"
 #include "limb_split.h"
 
 #include <type_traits>
@@ -26,13 +30,7 @@ using namespace relgnn;
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
-constexpr int PIECE = 528;              // 32 rows x 16 B (8 k of one limb) + 16 B: consecutive pieces start in consecutive bank quads
-constexpr int PLANE = 16 * PIECE;       // the 16 (k-tile, k half) pieces of one limb of a sub-slab (32 rows x 128 k)
-constexpr int SLAB = 3 * PLANE;         // 3 limbs: 25 344 B
+constexpr int PIECE = SubSlab<16>::PIECE, PLANE = SubSlab<16>::PLANE, SLAB = SubSlab<16>::SLAB;   // 32 rows x 128 k (limb_frag.h)
 constexpr int NBUF = 6;
 constexpr int CTL = 16;                 // control words: [1..6] rows filled per buffer, [8..13] matrix waves done with it
 constexpr int MAXPAIRS = 512;           // panels per workgroup whose edge types fit the LDS table (M <= 8.4 M rows on 256 workgroups)
@@ -51,15 +49,8 @@ struct PctArgs {
 #endif
 };
 
-struct Frag { bf16x8 hi, mid, lo; };
-
 #ifdef RELGNN_PCT_TIMING
 unsigned long long* g_pct_timing = nullptr;
-#define TSTAMP(v) __builtin_amdgcn_sched_barrier(0); const unsigned long long v = __builtin_amdgcn_s_memtime(); __builtin_amdgcn_sched_barrier(0)
-#define TACC(slot, t1, t0) tacc[slot] += (t1) - (t0)
-#else
-#define TSTAMP(v)
-#define TACC(slot, t1, t0)
 #endif
 
 template <int S2, bool N128, bool GATHER>
@@ -100,16 +91,13 @@ __global__ __launch_bounds__(1024) void limb_gemm_pct_kernel(const PctArgs a) {
   auto poll = [&](int* p, int target) {
     if (dead) return;
     TSTAMP(tp0);
-    int spins = 0;
-    while (__builtin_amdgcn_readfirstlane(handover_counter(p)) < target) {
-      __builtin_amdgcn_s_sleep(1);
-      if (++spins > spin_limit) { dead = true; if (lane == 0 && a.status) atomicOr(a.status, 4 + (wave < 8 ? 0 : 4)); break; }
-    }
-    handover_fence();
+    const int spins = handover_poll(p, target, spin_limit, dead, a.status, wave < 8 ? RELGNN_HANDOVER_PC_MATRIX : RELGNN_HANDOVER_PC_PRODUCER, lane);
 #ifdef RELGNN_PCT_TIMING
     TSTAMP(tp1);
     tacc[1] += tp1 - tp0;
     if (spins) tacc[2] += 1;
+#else
+    (void)spins;
 #endif
   };
 
@@ -129,22 +117,8 @@ __global__ __launch_bounds__(1024) void limb_gemm_pct_kernel(const PctArgs a) {
       f.mid = *reinterpret_cast<const bf16x8*>(p + 512);
       f.lo = *reinterpret_cast<const bf16x8*>(p + 1024);
     };
-    auto products = [&](f32x16 c, const Frag& w, const Frag& x) {        // limb_gemm.hip's order: small terms first
-      c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w.hi, x.lo, c, 0, 0, 0);
-      c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w.lo, x.hi, c, 0, 0, 0);
-      c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w.mid, x.mid, c, 0, 0, 0);
-      c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w.hi, x.mid, c, 0, 0, 0);
-      c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w.mid, x.hi, c, 0, 0, 0);
-      c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w.hi, x.hi, c, 0, 0, 0);
-      return c;
-    };
-    auto xread = [&](const unsigned char* p) {
-      Frag f;
-      f.hi = *reinterpret_cast<const bf16x8*>(p);
-      f.mid = *reinterpret_cast<const bf16x8*>(p + PLANE);
-      f.lo = *reinterpret_cast<const bf16x8*>(p + 2 * PLANE);
-      return f;
-    };
+    auto products = [&](f32x16 c, const Frag& w, const Frag& x) { return limb_products(c, w, x); };
+    auto xread = [&](const unsigned char* p) { return read_planes(p, PLANE); };
     const uint16_t* wcur = base_of(0);
     wload(wr[0], wcur, 0); wload(wr[1], wcur, 1); wload(wr[2], wcur, 2);
     int b0 = 0, gen0 = 0;                                     // buffer / generation of the next sub-slab in sequence
@@ -275,21 +249,9 @@ __global__ __launch_bounds__(1024) void limb_gemm_pct_kernel(const PctArgs a) {
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
       const f32x4 x = v[j];
-      uint32_t h0, m0_, l0, h1, m1, l1;
-      split_pair(x[0], x[1], h0, m0_, l0);
-      split_pair(x[2], x[3], h1, m1, l1);
-      if (__builtin_expect(max3_abs(max3_abs(x[0], x[1], x[2]), x[3], x[3]) >= __uint_as_float(0x7F7F8000u), 0)) {
-        split_pair_sat(x[0], x[1], h0, m0_, l0);
-        split_pair_sat(x[2], x[3], h1, m1, l1);
-      }
-      unsigned char* o = lds + fill * SLAB + (4 * pw + 2 * j + rsub) * 16 + wr_lane;
-      *reinterpret_cast<uint2*>(o) = make_uint2(h0, h1);
-      *reinterpret_cast<uint2*>(o + PLANE) = make_uint2(m0_, m1);
-      *reinterpret_cast<uint2*>(o + 2 * PLANE) = make_uint2(l0, l1);
+      split4(x, lds + fill * SLAB + (4 * pw + 2 * j + rsub) * 16 + wr_lane, PLANE);
     }
-    wait_lgkm0();
-    handover_fence();
-    if (lane == 0) __hip_atomic_fetch_add(ctl + 1 + fill, 4, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    handover_signal(ctl + 1 + fill, 4);
 #ifdef RELGNN_PCT_TIMING
     { TSTAMP(tw2); tacc[4] += tw2 - tw1; }                       // (includes the poll for the buffer: slot 1 says how much)
 #endif

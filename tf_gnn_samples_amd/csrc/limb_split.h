@@ -1,6 +1,7 @@
-// fp32 -> three bf16 limbs, hi + mid + lo == x bit for bit (shared by limb_gemm.hip and rgcn_fused.hip): gfx950 only.
+// fp32 -> three bf16 limbs, hi + mid + lo == x bit for bit (shared by every exact-split kernel): gfx950 only.
 #pragma once
 #include "common.h"
+#include "limb_frag.h"
 
 namespace relgnn {
 
@@ -63,6 +64,19 @@ __device__ __forceinline__ void split8(const float* v, uint4& h, uint4& m, uint4
     split_pair_sat(v[4], v[5], h.z, m.z, l.z);
     split_pair_sat(v[6], v[7], h.w, m.w, l.w);
   }
+}
+// four values of one row (a producer lane of the wave-role kernels) -> 8 bytes in each of the three planes at `o`
+__device__ __forceinline__ void split4(f32x4 x, unsigned char* o, int plane_stride) {
+  uint32_t h0, m0, l0, h1, m1, l1;
+  split_pair(x[0], x[1], h0, m0, l0);
+  split_pair(x[2], x[3], h1, m1, l1);
+  if (__builtin_expect(max3_abs(max3_abs(x[0], x[1], x[2]), x[3], x[3]) >= __uint_as_float(0x7F7F8000u), 0)) {
+    split_pair_sat(x[0], x[1], h0, m0, l0);
+    split_pair_sat(x[2], x[3], h1, m1, l1);
+  }
+  *reinterpret_cast<uint2*>(o) = make_uint2(h0, h1);
+  *reinterpret_cast<uint2*>(o + plane_stride) = make_uint2(m0, m1);
+  *reinterpret_cast<uint2*>(o + 2 * plane_stride) = make_uint2(l0, l1);
 }
 
 }  // namespace relgnn

@@ -33,9 +33,13 @@
 // First form (commit 6b8c427: half rows, 64-row x half-type sub-slabs, a switch re-entered behind every bucket end): bit-identical,
 // 513 us against 164 us for the two kernels on the C2 batch; s_memtime stamps showed the gather waves 97 % busy issuing
 // instructions (row-load wait 0.3 % of their time) and the matrix waves 91 % of the time in polls.
+#ifdef RELGNN_FUSED_TIMING
+#define RELGNN_STAMPS
+#endif
 #include "common.h"
 #include "handover.h"
 #include "lds_dma.h"
+#include "limb_frag.h"
 #include "limb_split.h"
 
 #include <stdlib.h>
@@ -45,14 +49,9 @@ using namespace relgnn;
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x8 __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
-constexpr int PIECE = 528;              // 32 rows x 16 B (8 k of one limb) + 16 B: consecutive pieces start in consecutive bank quads
-constexpr int PLANE = 32 * PIECE;       // the 32 (k-tile, k half) pieces of one limb of a sub-slab (32 rows x 256 columns)
-constexpr int SLAB = 3 * PLANE;         // 3 limbs: 50 688 B
+constexpr int PIECE = SubSlab<32>::PIECE, PLANE = SubSlab<32>::PLANE, SLAB = SubSlab<32>::SLAB;   // 32 rows x 256 columns (limb_frag.h)
 constexpr int NBUF = 3;
 constexpr int GROUP = 16;               // stream positions per group
 constexpr int HALF = 8;                 // row loads per half group
@@ -77,19 +76,9 @@ struct FusedArgs {
 #endif
 };
 
-struct Frag { bf16x8 hi, mid, lo; };
-
 #ifdef RELGNN_FUSED_TIMING
 unsigned long long* g_fused_timing = nullptr;   // diagnostic build: [workgroup][wave][8] cycle totals
-#define TSTAMP(v) __builtin_amdgcn_sched_barrier(0); const unsigned long long v = __builtin_amdgcn_s_memtime(); __builtin_amdgcn_sched_barrier(0)
-#define TACC(slot, t1, t0) tacc[slot] += (t1) - (t0)
-#else
-#define TSTAMP(v)
-#define TACC(slot, t1, t0)
 #endif
-
-__device__ __forceinline__ int lds_counter(int* p) { return handover_counter(p); }
-__device__ __forceinline__ void compiler_fence() { handover_fence(); }
 
 template <bool HAS_W>
 __global__ __launch_bounds__(1024) void rgcn_fused_kernel(const FusedArgs a) {
@@ -129,16 +118,13 @@ __global__ __launch_bounds__(1024) void rgcn_fused_kernel(const FusedArgs a) {
   auto poll = [&](int* p, int target) {
     if (dead) return;
     TSTAMP(tp0);
-    int spins = 0;
-    while (__builtin_amdgcn_readfirstlane(lds_counter(p)) < target) {
-      __builtin_amdgcn_s_sleep(1);
-      if (++spins > spin_limit) { dead = true; if (lane == 0 && a.status) atomicOr(a.status, 1 + (wave < 8 ? 0 : 1)); break; }
-    }
-    compiler_fence();
+    const int spins = handover_poll(p, target, spin_limit, dead, a.status, wave < 8 ? RELGNN_HANDOVER_FUSED_MATRIX : RELGNN_HANDOVER_FUSED_GATHER, lane);
 #ifdef RELGNN_FUSED_TIMING
     TSTAMP(tp1);
     tacc[1] += tp1 - tp0;
     if (spins) tacc[2] += 1;
+#else
+    (void)spins;
 #endif
   };
 
@@ -155,22 +141,8 @@ __global__ __launch_bounds__(1024) void rgcn_fused_kernel(const FusedArgs a) {
       f.lo = *reinterpret_cast<const bf16x8*>(p + 1024);
       tl = tl + 1 == ntiles ? 0 : tl + 1;
     };
-    auto products = [&](f32x16 c, const Frag& w, const Frag& x) {        // limb_gemm.hip's order: small terms first
-      c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w.hi, x.lo, c, 0, 0, 0);
-      c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w.lo, x.hi, c, 0, 0, 0);
-      c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w.mid, x.mid, c, 0, 0, 0);
-      c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w.hi, x.mid, c, 0, 0, 0);
-      c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w.mid, x.hi, c, 0, 0, 0);
-      c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w.hi, x.hi, c, 0, 0, 0);
-      return c;
-    };
-    auto xread = [&](const unsigned char* p) {
-      Frag f;
-      f.hi = *reinterpret_cast<const bf16x8*>(p);
-      f.mid = *reinterpret_cast<const bf16x8*>(p + PLANE);
-      f.lo = *reinterpret_cast<const bf16x8*>(p + 2 * PLANE);
-      return f;
-    };
+    auto products = [&](f32x16 c, const Frag& w, const Frag& x) { return limb_products(c, w, x); };
+    auto xread = [&](const unsigned char* p) { return read_planes(p, PLANE); };
     wload(wr[0]); wload(wr[1]); wload(wr[2]);
     int b0 = 0, gen0 = 0;                                     // buffer / generation of the next sub-slab in sequence
     const int xlane = h32 * PIECE + i32 * 16;
@@ -209,7 +181,7 @@ __global__ __launch_bounds__(1024) void rgcn_fused_kernel(const FusedArgs a) {
           }
         }
         wait_lgkm0();                                          // my reads of both buffers have returned
-        compiler_fence();
+        handover_fence();
         TSTAMP(tk1);
         TACC(6, tk1, tk0);
         if (lane == 0) {
@@ -362,21 +334,9 @@ __global__ __launch_bounds__(1024) void rgcn_fused_kernel(const FusedArgs a) {
     const int grow = c.m0 + (c.sub & 1) * 32 + r;
     if (a.S && grow < rend)
       *reinterpret_cast<f32x4*>(a.S + (int64_t)grow * a.lds_ + (c.sub >> 1) * 256 + 4 * lane) = acc;
-    uint32_t h0, m0_, l0, h1, m1, l1;
-    split_pair(acc[0], acc[1], h0, m0_, l0);
-    split_pair(acc[2], acc[3], h1, m1, l1);
-    if (__builtin_expect(max3_abs(max3_abs(acc[0], acc[1], acc[2]), acc[3], acc[3]) >= __uint_as_float(0x7F7F8000u), 0)) {
-      split_pair_sat(acc[0], acc[1], h0, m0_, l0);
-      split_pair_sat(acc[2], acc[3], h1, m1, l1);
-    }
     const int fill = c.g % NBUF;
-    unsigned char* p = lds + fill * SLAB + r * 16 + wr_lane;
-    *reinterpret_cast<uint2*>(p) = make_uint2(h0, h1);
-    *reinterpret_cast<uint2*>(p + PLANE) = make_uint2(m0_, m1);
-    *reinterpret_cast<uint2*>(p + 2 * PLANE) = make_uint2(l0, l1);
-    wait_lgkm0();
-    compiler_fence();
-    if (lane == 0) __hip_atomic_fetch_add(ctl + 1 + fill, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    split4(acc, lds + fill * SLAB + r * 16 + wr_lane, PLANE);
+    handover_signal(ctl + 1 + fill, 1);
     acc = f32x4{0.f, 0.f, 0.f, 0.f};
   };
   // ONE copy of the bucket-end code per fold: the half group is walked segment by segment — a loop whose body offers every position
