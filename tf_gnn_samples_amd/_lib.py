@@ -1,4 +1,4 @@
-"""ctypes binding of librelgnn.so (C ABI: include/relgnn.h, include/relgnn_dropout.h).
+"""ctypes binding of librelgnn.so (C ABI: include/relgnn.h, include/relgnn_dropout.h, include/relgnn_predict.h).
 
 This is the ONLY compute backend of the package.  There is no CPU / eager-PyTorch fallback:
 if the HIP library is missing, or a tensor is not a float32/int32 CUDA(HIP) tensor, the
@@ -190,6 +190,13 @@ _DROPOUT_SIGNATURES = {
     "relgnn_dropout_residual_bwd": (ctypes.c_int, [_ptr, _ptr, _c_i64, _c_i64, _ptr, _c_i32, _c_u32, _c_f32, _ptr, _ptr, _ptr]),
 }
 
+# include/relgnn_predict.h (probabilities and labels out of the heads' logits): a table of its own for the same reason
+_PREDICT_SIGNATURES = {
+    "relgnn_predict_sigmoid_f32": (ctypes.c_int, [_ptr, _c_i64, _c_i64, _c_i64, _ptr, _c_i64, _ptr, _c_i64, _ptr]),
+    "relgnn_predict_softmax_f32": (ctypes.c_int, [_ptr, _c_i64, _c_i64, _c_i32, _ptr, _c_i64, _ptr, _ptr]),
+    "relgnn_predict_candidates_f32": (ctypes.c_int, [_ptr, _c_i64, _c_i32, _ptr, _ptr, _ptr]),
+}
+
 _lib = None
 
 
@@ -207,7 +214,7 @@ def load_library():
             "%s not found: the HIP extension is not built. Run `python -c 'import __graft_entry__ as g; "
             "g.build()'` (needs hipcc). There is no CPU fallback for this path." % LIB_PATH)
     lib = ctypes.CDLL(str(LIB_PATH))
-    for name, (restype, argtypes) in list(_SIGNATURES.items()) + list(_DROPOUT_SIGNATURES.items()):
+    for name, (restype, argtypes) in list(_SIGNATURES.items()) + list(_DROPOUT_SIGNATURES.items()) + list(_PREDICT_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the symbol is not exported
         fn.restype = restype
         fn.argtypes = argtypes
@@ -224,6 +231,11 @@ def exported_signatures():
 def dropout_signatures():
     """The entry points of include/relgnn_dropout.h (not part of exported_signatures(): that is relgnn.h's list)."""
     return dict(_DROPOUT_SIGNATURES)
+
+
+def predict_signatures():
+    """The entry points of include/relgnn_predict.h (not part of exported_signatures() either)."""
+    return dict(_PREDICT_SIGNATURES)
 
 
 def status_string(code: int) -> str:

@@ -104,6 +104,97 @@ __device__ __forceinline__ float dact_from_output(int act, float yy) {
 // Keras' hard_sigmoid, the recurrent activation of the GRU cell (gru.hip, gru_cell.hip)
 __device__ __forceinline__ float hard_sigmoid(float x) { return fminf(fmaxf(0.2f * x + 0.5f, 0.f), 1.f); }
 
+// ---- label rules shared by the metric kernels and the prediction kernels (predict.hip) ---------------------------------------
+// A predicted label is decided by the code that counts it in the metric: each rule has its one definition here.
+
+// PPI (utils/utils.py:61-74): round(sigmoid(x)) with round-half-even == (1 / (1 + exp(-x)) > 0.5).  For x <= 0, exp(-x) >= 1 makes
+// the quotient <= 0.5 in every rounding; for x > 0, exp(-x) is e = expf(-|x|), which the caller has for the loss / the probability
+// anyway.  NaN is a 0.
+__device__ __forceinline__ bool sigmoid_label(float x, float e) { return x > 0.f && (1.f / (1.f + e)) > 0.5f; }
+
+// VarMisuse (tasks/varmisuse_task.py:422-438): max-subtracted softmax of up to 8 candidate logits and the first maximum of the
+// PROBABILITIES (tf.argmax(tf.nn.softmax(logits))), which is not always the first maximum of the logits: two logits one ulp
+// apart can round to the same quotient.  `rest` is the sum of exp(x - m) over the columns other than the (first) maximum, in
+// index order; the denominator is 1 + rest.  p: the cols probabilities, or nullptr.
+constexpr int kMaxCandidates = 8;
+struct CandidateChoice {
+  float m, rest;      // maximum logit; sum of the other columns' exponentials (log-sum-exp = m + log1p(rest))
+  int arg;            // lowest index of the largest probability
+};
+__device__ __forceinline__ CandidateChoice candidate_choice(const float (&x)[kMaxCandidates], int cols, float* __restrict__ p) {
+  float m = x[0];
+  int am = 0;
+  for (int c = 1; c < cols; ++c)
+    if (x[c] > m) { m = x[c]; am = c; }
+  float e[kMaxCandidates], rest = 0.f;
+  for (int c = 0; c < cols; ++c) {
+    e[c] = expf(x[c] - m);
+    if (c != am) rest += e[c];
+  }
+  const float sum = 1.f + rest;
+  float best = e[0] / sum;
+  int arg = 0;
+  if (p) p[0] = best;
+  for (int c = 1; c < cols; ++c) {
+    const float q = e[c] / sum;
+    if (p) p[c] = q;
+    if (q > best) { best = q; arg = c; }
+  }
+  return {m, rest, arg};
+}
+
+// Citation (tasks/citation_network_task.py:134-148): the class of a row is the lowest index of the maximum of the LOGITS, pure
+// comparisons.  One row of logits belongs to a GROUP of W lanes (W = 1, 16 or 64, softmax_group_width); lane j of the group walks
+// columns j, j + W, ... with a running (maximum, sum of exp(x - maximum) over the other columns, index of the first maximum), and
+// the W partial triples are merged by a butterfly.
+struct RowLse {
+  float m, t;      // running maximum; sum of exp(x - m) over the columns seen so far WITHOUT the 1 of the maximum itself: a confident
+                   // row has a loss of log(1 + t) with t << 1, which log1pf keeps to 1e-7 relative and logf(1 + t) does not
+  int idx;         // lowest column holding m
+};
+
+__device__ __forceinline__ void lse_push(RowLse& a, float x, int c) {
+  // (columns arrive in ascending order per lane: a tie keeps the earlier index; a lane's first column is always taken, -inf too)
+  if (x > a.m || a.idx == 0x7fffffff) {
+    a.t = a.m == -INFINITY ? 0.f : (a.t + 1.f) * expf(a.m - x);
+    a.m = x;
+    a.idx = c;
+  } else {
+    // an equal maximum adds its own 1 (said without the subtraction: -inf next to -inf is a tie, not exp(NaN) — a row whose first
+    // columns are -inf keeps a finite loss as soon as one column is finite, as the max-subtracted form of TF does)
+    a.t += x == a.m ? 1.f : expf(x - a.m);
+  }
+}
+
+__device__ __forceinline__ void lse_merge(RowLse& a, float m2, float t2, int i2) {
+  if (i2 == 0x7fffffff) return;                    // the other lane had no column (cols < W)
+  if (a.idx == 0x7fffffff) { a.m = m2; a.t = t2; a.idx = i2; return; }
+  float t;
+  if (a.m == m2) t = (a.t + t2) + 1.f;
+  else if (a.m > m2) t = a.t + (t2 + 1.f) * expf(m2 - a.m);
+  else t = t2 + (a.t + 1.f) * expf(a.m - m2);
+  a.idx = a.m > m2 ? a.idx : (m2 > a.m ? i2 : min(a.idx, i2));
+  a.m = fmaxf(a.m, m2);
+  a.t = t;
+}
+
+template <int W>
+__device__ __forceinline__ RowLse row_lse(const float* __restrict__ row, int cols, int j) {
+  RowLse a = {-INFINITY, 0.f, 0x7fffffff};
+  for (int c = j; c < cols; c += W) lse_push(a, row[c], c);
+#pragma unroll
+  for (int off = W >> 1; off >= 1; off >>= 1) {
+    const float m2 = __shfl_xor(a.m, off), t2 = __shfl_xor(a.t, off);
+    const int i2 = __shfl_xor(a.idx, off);
+    lse_merge(a, m2, t2, i2);
+  }
+  return a;        // the same triple in every lane of the group
+}
+
+// lanes per row: a lane walks a short row alone, 16 lanes share a row of up to 128 columns, a wave anything longer
+static inline int softmax_group_width(int cols) { return cols <= 8 ? 1 : (cols <= 128 ? 16 : 64); }
+
+
 // ---- per-MESSAGE activations ---------------------------------------------------------------------------------------
 // The edge kernels evaluate the activation once per message and feature (C2 shape: 4.7e8 evaluations per launch).  With
 // the library erff / expf / tanhf (~35-50 VALU slots per GELU) those kernels are ALU-bound: the Edge-MLP0 forward ran

@@ -221,7 +221,7 @@ __device__ __forceinline__ void ce_element(float x, float z, CeAcc& a) {
   a.loss += (double)(fmaxf(x, 0.f) - x * z + log1pf(e));
   // round(sigmoid(x)) with round-half-even == (1 / (1 + exp(-x)) > 0.5).  For x <= 0, exp(-x) >= 1 makes the quotient
   // <= 0.5 in every rounding; for x > 0, exp(-x) is the e above — one exponential serves the loss and the prediction.
-  const bool pred = x > 0.f && (1.f / (1.f + e)) > 0.5f;
+  const bool pred = sigmoid_label(x, e);      // (common.h: the rule relgnn_predict_sigmoid_f32 writes its labels by)
   const int zi = (int)z;
   a.tp += (pred && zi != 0) ? 1 : 0;
   a.fp += (pred && zi != 1) ? 1 : 0;
@@ -327,49 +327,7 @@ __global__ __launch_bounds__(256) void sigmoid_ce_bwd_padded_kernel(const float*
 // One row of logits belongs to a GROUP of W lanes (W = 1, 16 or 64, chosen from cols by the host: the datasets have 3-7 classes,
 // a wave then takes 64 rows at once instead of one); lane j of the group walks columns j, j + W, ... with a running
 // (maximum, sum of exp(x - maximum) over the other columns, index of the first maximum), and the W partial triples are merged by a butterfly.
-struct RowLse {
-  float m, t;      // running maximum; sum of exp(x - m) over the columns seen so far WITHOUT the 1 of the maximum itself: a confident
-                   // row has a loss of log(1 + t) with t << 1, which log1pf keeps to 1e-7 relative and logf(1 + t) does not
-  int idx;         // lowest column holding m
-};
-
-__device__ __forceinline__ void lse_push(RowLse& a, float x, int c) {
-  // (columns arrive in ascending order per lane: a tie keeps the earlier index; a lane's first column is always taken, -inf too)
-  if (x > a.m || a.idx == 0x7fffffff) {
-    a.t = a.m == -INFINITY ? 0.f : (a.t + 1.f) * expf(a.m - x);
-    a.m = x;
-    a.idx = c;
-  } else {
-    // an equal maximum adds its own 1 (said without the subtraction: -inf next to -inf is a tie, not exp(NaN) — a row whose first
-    // columns are -inf keeps a finite loss as soon as one column is finite, as the max-subtracted form of TF does)
-    a.t += x == a.m ? 1.f : expf(x - a.m);
-  }
-}
-
-__device__ __forceinline__ void lse_merge(RowLse& a, float m2, float t2, int i2) {
-  if (i2 == 0x7fffffff) return;                    // the other lane had no column (cols < W)
-  if (a.idx == 0x7fffffff) { a.m = m2; a.t = t2; a.idx = i2; return; }
-  float t;
-  if (a.m == m2) t = (a.t + t2) + 1.f;
-  else if (a.m > m2) t = a.t + (t2 + 1.f) * expf(m2 - a.m);
-  else t = t2 + (a.t + 1.f) * expf(a.m - m2);
-  a.idx = a.m > m2 ? a.idx : (m2 > a.m ? i2 : min(a.idx, i2));
-  a.m = fmaxf(a.m, m2);
-  a.t = t;
-}
-
-template <int W>
-__device__ __forceinline__ RowLse row_lse(const float* __restrict__ row, int cols, int j) {
-  RowLse a = {-INFINITY, 0.f, 0x7fffffff};
-  for (int c = j; c < cols; c += W) lse_push(a, row[c], c);
-#pragma unroll
-  for (int off = W >> 1; off >= 1; off >>= 1) {
-    const float m2 = __shfl_xor(a.m, off), t2 = __shfl_xor(a.t, off);
-    const int i2 = __shfl_xor(a.idx, off);
-    lse_merge(a, m2, t2, i2);
-  }
-  return a;        // the same triple in every lane of the group
-}
+// (RowLse, lse_push, lse_merge, row_lse<W> and softmax_group_width live in common.h: predict.hip takes its class from the same code)
 
 // grid-strided over groups of rows; every lane of a wave runs the same number of iterations (the butterfly needs all lanes), a
 // lane past the last row walks zero columns.  partial[block * 3 + {0, 1, 2}] = the block's sums in double.
@@ -464,9 +422,6 @@ __global__ __launch_bounds__(256) void softmax_ce_bwd_kernel(const float* __rest
 }
 
 constexpr int kSoftmaxBlocks = 256;
-
-// lanes per row: a lane walks a short row alone, 16 lanes share a row of up to 128 columns, a wave anything longer
-static inline int softmax_group_width(int cols) { return cols <= 8 ? 1 : (cols <= 128 ? 16 : 64); }
 
 static inline int softmax_grid(long long rows, int w) {
   const long long per_block = 256 / w;

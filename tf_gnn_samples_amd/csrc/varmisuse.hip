@@ -223,7 +223,7 @@ __global__ __launch_bounds__(256) void charcnn_bwd_combine_kernel(const double* 
 // ---------------------------------------------------------------------------------------------------------------------------------
 // head: one wave per graph
 // ---------------------------------------------------------------------------------------------------------------------------------
-constexpr int kMaxCn = 8, kHeadMaxD = 256, kHeadBlocks = 64;
+constexpr int kMaxCn = kMaxCandidates, kHeadMaxD = 256, kHeadBlocks = 64;      // (8: common.h, candidate_choice)
 
 __device__ __forceinline__ float wave_sum(float x) {
 #pragma unroll
@@ -311,27 +311,13 @@ __global__ __launch_bounds__(256) void head_fwd_kernel(const float* __restrict__
   float s[NV], cv[kMaxCn][NV], ip[kMaxCn], x[kMaxCn];
   head_logits<NV>(H, ld, r, Cn, D, w, mask, g, lane, s, cv, ip, x);
   if (lane == 0) {
-    float m = x[0];
-    int am = 0;
-    for (int c = 1; c < Cn; ++c)
-      if (x[c] > m) { m = x[c]; am = c; }
-    // log-sum-exp as log1p of the sum WITHOUT the maximum's own 1 (a confident graph's loss keeps its relative precision)
-    float e[kMaxCn], rest = 0.f;
-    for (int c = 0; c < Cn; ++c) {
-      e[c] = expf(x[c] - m);
-      if (c != am) rest += e[c];
-    }
-    const float sum = 1.f + rest;
-    // tf.argmax(tf.nn.softmax(logits)): the first of equal PROBABILITIES (:438)
-    float best = e[0] / sum;
-    int arg = 0;
-    for (int c = 1; c < Cn; ++c) {
-      const float p = e[c] / sum;
-      if (p > best) { best = p; arg = c; }
-    }
+    // maximum, exponentials and tf.argmax(tf.nn.softmax(logits)), the first of equal PROBABILITIES (:438): common.h, the one
+    // definition relgnn_predict_candidates_f32 predicts by.  log-sum-exp as log1p of the sum WITHOUT the maximum's own 1 (a
+    // confident graph's loss keeps its relative precision)
+    const CandidateChoice ch = candidate_choice(x, Cn, nullptr);
     for (int c = 0; c < Cn; ++c) logits[g * Cn + c] = x[c];
-    per_graph[2 * g] = (double)log1pf(rest) + ((double)m - (double)x[0]);    // sparse softmax cross-entropy against class 0 (:425-428)
-    per_graph[2 * g + 1] = arg == 0 ? 1.0 : 0.0;
+    per_graph[2 * g] = (double)log1pf(ch.rest) + ((double)ch.m - (double)x[0]);    // sparse softmax cross-entropy against class 0 (:425-428)
+    per_graph[2 * g + 1] = ch.arg == 0 ? 1.0 : 0.0;
   }
 }
 

@@ -302,6 +302,72 @@ class MetricsReadback:
             slot[1] = False
 
 
+class _PredictionArena:
+    """The outputs of ONE batch's predictions as one packed byte arena: `views` are typed tensors over slices of it (16-byte
+    aligned), which the prediction kernels write in place; send() enqueues the single copy to the host right behind them, with
+    the device's hand-over status word (ops.handover_word) in the arena's last four bytes; fetch() waits for THAT copy only and
+    returns NumPy arrays of the host's own (the pinned arena goes back into its turn)."""
+
+    def __init__(self, layout: Dict[str, Any], device, pinned: list, turn: int):
+        self._layout, self._offsets, used = layout, {}, 0
+        for key, (shape, dtype) in layout.items():
+            used = (used + 15) // 16 * 16
+            self._offsets[key] = used
+            used += int(np.prod(shape, dtype=np.int64)) * torch.empty((), dtype=dtype).element_size()
+        self._status_at = (used + 3) // 4 * 4
+        self._nbytes = self._status_at + 4
+        self._device, self._pinned, self._turn, self._event = device, pinned, turn, None
+        self.buf = torch.empty(self._nbytes, dtype=torch.uint8, device=device)
+        self.views = {key: self._view(self.buf, key) for key in layout}
+
+    def _view(self, buf, key):
+        shape, dtype = self._layout[key]
+        nbytes = int(np.prod(shape, dtype=np.int64)) * torch.empty((), dtype=dtype).element_size()
+        off = self._offsets[key]
+        return buf[off:off + nbytes].view(dtype).view(shape)
+
+    def send(self, outputs: Dict[str, torch.Tensor]):
+        for key, view in self.views.items():
+            t = outputs[key]
+            if t.data_ptr() != view.data_ptr() or tuple(t.shape) != tuple(view.shape):      # (a hook that made a tensor of its own)
+                view.copy_(t)
+        if self._device.type != "cuda":
+            self._host = self.buf
+            return
+        from .. import ops as _ops
+        word = _ops._HANDOVER_WORDS.get(self._device.index)
+        status = self.buf[self._status_at:].view(torch.int32)
+        if word is not None:
+            status.copy_(word[0:1])
+        else:
+            status.zero_()
+        host = self._pinned[self._turn]
+        if host is None or host.numel() < self._nbytes:
+            host = self._pinned[self._turn] = torch.empty(self._nbytes, dtype=torch.uint8).pin_memory()
+        self._host = host[:self._nbytes]
+        self._host.copy_(self.buf, non_blocking=True)
+        self._event = torch.cuda.Event()
+        self._event.record(torch.cuda.current_stream(self._device))
+
+    def fetch(self) -> Dict[str, np.ndarray]:
+        if self._event is not None:
+            self._event.synchronize()
+            self._event = None
+            status = int(self._host[self._status_at:].view(torch.int32)[0])
+            if status:
+                from .. import ops as _ops
+                _ops._HANDOVER_WORDS[self._device.index][0].zero_()      # reported once, as a metric fetch does
+                _ops.raise_on_handover(status)
+        own = self._host.numpy().copy()                                  # one host copy out of the pinned arena; the pieces are its views
+        out = {}
+        for key, (shape, dtype) in self._layout.items():
+            nbytes = int(np.prod(shape, dtype=np.int64)) * torch.empty((), dtype=dtype).element_size()
+            off = self._offsets[key]
+            out[key] = own[off:off + nbytes].view(torch.empty((), dtype=dtype).numpy().dtype).reshape(shape)
+        self.buf = self.views = None
+        return out
+
+
 class CapturedTrainStep:
     """A training step recorded as a hipGraph on one fixed batch (Sparse_Graph_Model.capture_train_step), with any of the
     three optimizers.  Adam's step count is device state that every replay advances; the learning rate of an RMSProp or SGD
@@ -573,15 +639,18 @@ class Sparse_Graph_Model(ABC):
                                           momentum=p['momentum'])
 
     # -------------------- Training Loop --------------------
-    def forward_batch(self, batch: DeviceBatch, training: bool):
+    def _final_node_states(self, batch: DeviceBatch, training: bool) -> torch.Tensor:
         keep = self.params['graph_layer_input_dropout_keep_prob'] if training else 1.0
         batch.wait_ready()               # assembled on a side stream (tasks/resident.py)? wait on the GPU, not the host
         # a batch from the input pipeline may carry its bucketing, built on a side stream (tasks/batcher.py)
         graph = getattr(batch, "graph", None)
-        final = self.compute_final_node_representations(
+        return self.compute_final_node_representations(
             self.task.compute_initial_node_features(batch, self.variables.scope("")),
             graph if graph is not None else batch.adjacency_lists,
             batch.type_to_num_incoming_edges, keep)
+
+    def forward_batch(self, batch: DeviceBatch, training: bool):
+        final = self._final_node_states(batch, training)
         return self.task.compute_task_metrics(final, batch, self.variables.scope(self._task_scope))
 
     def capture_train_step(self, batch: DeviceBatch, warmup_steps: int = 3):
@@ -784,6 +853,69 @@ class Sparse_Graph_Model(ABC):
                 self.log_line("Stopping training after %i epochs without improvement." % self.params['patience'])
                 break
         self.log_line("Training took %is." % (time.time() - total_time_start))
+
+    # -------------------- Predictions --------------------
+    def predict_iter(self, data, return_states: bool = False):
+        """Generator over (samples of the batch, their predictions): one dict of NumPy arrays per graph, in the order of `data`
+        (the task's split_predictions says which keys; return_states adds 'node_states' float32 [n, hidden], the rows of
+        compute_final_node_representations).
+
+        The forward runs under torch.no_grad() with training=False over self._batches(data, DataFold.TEST): whichever input pipeline
+        the model's parameters select.  A batch's outputs are written into ONE packed device arena (the task's kernels write their
+        slices in place) that leaves the device as one asynchronous copy into pinned memory, and are read one batch late, as
+        _run_epoch reads metrics: batch i is yielded once batch i + 1 is enqueued; two pinned arenas exist at most.  The fetch
+        reports what a metric fetch reports: check_pending_graph_errors() and the hand-over status word (ops.HandoverError): the
+        predictions of a product kernel that gave up are never handed out.
+
+        Nothing a later training step can see is touched: no .grad, no optimizer state, no torch / NumPy random state, and
+        dropout_state does not advance (nothing is dropped).  No collective: under data parallelism each rank predicts its own data."""
+        data = data if isinstance(data, list) else list(data)
+        # two pinned host arenas, taken in turn (batch i + 1's copy runs while batch i is read); kept with the model between calls
+        # (pinning memory costs more than a small batch's forward) and taken out of it while this generator runs, so that a second
+        # generator on the same model pins its own
+        pinned, self._prediction_pinned = getattr(self, "_prediction_pinned", None) or [None, None], None
+        try:
+            yield from self._predict_batches(data, return_states, pinned)
+        finally:
+            self._prediction_pinned = pinned
+
+    def _predict_batches(self, data, return_states, pinned):
+        cursor, pending, turn = 0, None, 0
+        for mb in self._batches(data, DataFold.TEST):
+            with torch.no_grad():      # (around the device work only: a generator suspended inside it would leave the grad mode of
+                #                         the CONSUMER's code switched off between two batches)
+                batch = mb if isinstance(mb, DeviceBatch) else DeviceBatch(mb, self.device)
+                samples = data[cursor:cursor + batch.num_graphs]
+                cursor += batch.num_graphs
+                final = self._final_node_states(batch, training=False)
+                layout = dict(self.task.prediction_layout(batch, final.shape[1]))
+                if return_states:
+                    layout["node_states"] = (tuple(final.shape), torch.float32)
+                arena = _PredictionArena(layout, final.device, pinned, turn)
+                turn ^= 1
+                outputs = self.task.compute_task_predictions(final, batch, self.variables.scope(self._task_scope), out=arena.views)
+                if return_states:
+                    outputs = dict(outputs, node_states=final)
+                arena.send(outputs)
+            if pending is not None:
+                yield self._fetch_predictions(*pending)
+            pending = (arena, batch, samples)
+        if pending is not None:
+            yield self._fetch_predictions(*pending)
+
+    def _fetch_predictions(self, arena, batch, samples):
+        host = arena.fetch()
+        check_pending_graph_errors()
+        return samples, self.task.split_predictions(host, batch, samples)
+
+    def predict(self, data, return_states: bool = False, quiet: bool = True) -> List[Dict[str, np.ndarray]]:
+        """One entry per graph of `data`, in its order (predict_iter, collected)."""
+        results = []
+        for step, (samples, predictions) in enumerate(self.predict_iter(data, return_states)):
+            results.extend(predictions)
+            if not quiet:
+                print("Predicting, batch %i (has %i graphs). %i graphs so far." % (step, len(samples), len(results)), end='\r')
+        return results
 
     def test(self, data, quiet: bool = False):
         loss, res, n, gs, ns, es = self._run_epoch("Test", list(data), DataFold.TEST, quiet)

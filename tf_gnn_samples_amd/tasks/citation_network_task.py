@@ -288,6 +288,26 @@ class Citation_Network_Task(Sparse_Graph_Task):
         accuracy = ((first_max == labels.long()).to(torch.float32) * mask).sum() / num_masked
         return {'loss': total_loss / num_masked, 'total_loss': total_loss, 'accuracy': accuracy}
 
+    # -------------------- Predictions: the class of every node --------------------
+    PER_NODE_PREDICTIONS = ("probabilities", "classes")
+
+    @staticmethod
+    def num_nodes_of(sample) -> int:
+        return int(sample.node_features.shape[0])
+
+    def prediction_layout(self, batch, hidden_size: int):
+        num_nodes = int(batch.num_nodes)
+        return {"probabilities": ((num_nodes, self.__num_output_classes), torch.float32), "classes": ((num_nodes,), torch.int32)}
+
+    def compute_task_predictions(self, final_node_representations: torch.Tensor, batch, weights, out=None) -> Dict[str, torch.Tensor]:
+        """probabilities float32 [V, classes] = softmax(logits); classes int32 [V] = the first maximum of the logits, as the accuracy
+        of _SoftmaxCEStats counts it (:134-138).  For EVERY node: the fold's mask is not read; no dropout."""
+        from ..predict import predict_softmax
+        out = out or {}
+        logits = dense(final_node_representations, weights["kernel"])
+        probabilities, classes = predict_softmax(logits, out.get("probabilities"), out.get("classes"))
+        return {"probabilities": probabilities, "classes": classes}
+
     NODE_PAYLOADS = {"initial_node_features": ("node_features", np.float32), "labels": ("labels", np.int32),
                      "mask": ("mask", np.float32)}
 

@@ -209,6 +209,22 @@ class PPI_Task(Sparse_Graph_Task):
             f1 = micro_f1(per_node_logits.detach(), labels)
         return {'loss': total_loss / float(num_nodes_in_batch), 'total_loss': total_loss, 'f1_score': f1}
 
+    # -------------------- Predictions: which of the labels each node has --------------------
+    PER_NODE_PREDICTIONS = ("probabilities", "labels")
+
+    def prediction_layout(self, batch, hidden_size: int):
+        shape = (int(batch.num_nodes), self.__num_labels)
+        return {"probabilities": (shape, torch.float32), "labels": (shape, torch.uint8)}
+
+    def compute_task_predictions(self, final_node_representations: torch.Tensor, batch, weights, out=None) -> Dict[str, torch.Tensor]:
+        """probabilities float32 [V, labels] = sigmoid(logits); labels uint8 [V, labels] = the prediction whose true / false
+        positives _SigmoidCEStats counts (utils/utils.py:61-74).  No dropout (the head's keep-prob is 1 outside training)."""
+        from ..predict import predict_sigmoid
+        out = out or {}
+        per_node_logits = dense(final_node_representations, weights["kernel"], weights["bias"])
+        probabilities, labels = predict_sigmoid(per_node_logits, out.get("probabilities"), out.get("labels"))
+        return {"probabilities": probabilities, "labels": labels}
+
     NODE_PAYLOADS = {"initial_node_features": ("node_features", np.float32), "target_labels": ("node_labels", np.float32)}
 
     # -------------------- Minibatching (tasks/ppi_task.py:197-256) --------------------

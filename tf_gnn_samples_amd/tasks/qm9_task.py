@@ -258,6 +258,59 @@ class QM9_Task(Sparse_Graph_Task):
             specs[s + "/regression/dense/bias"] = ((1,), "zeros")
         return specs
 
+    def _fused_head_applies(self, final_node_representations: torch.Tensor, batch, targets) -> bool:
+        features = batch.initial_node_features
+        return (config.settings.qm9_head == "fused" and final_node_representations.is_cuda and features.is_cuda
+                and final_node_representations.dtype == torch.float32 and features.dtype == torch.float32
+                and torch.is_tensor(targets) and targets.dtype == torch.float32
+                and batch.graph_nodes_list.dtype == torch.int32 and batch.num_graphs >= 1 and final_node_representations.dim() == 2
+                and head_supported(len(self.params['task_ids']), final_node_representations.shape[1], features.shape[1]))
+
+    def _fused_head_variables(self, weights):
+        variables = []
+        for task_id in self.params['task_ids']:
+            w = weights.scope("out_layer_task%i" % task_id) if hasattr(weights, "scope") else weights
+            variables.append((w["regression/dense/kernel"], w["regression/dense/bias"],
+                              w["regression_gate/dense/kernel"], w["regression_gate/dense/bias"]))
+        return variables
+
+    def _per_graph_outputs(self, final_node_representations: torch.Tensor, batch, w) -> torch.Tensor:
+        """The composition's readout of ONE task (:163-187): gated per-node regression, summed per graph -> [G]."""
+        # (dense(): the [hidden, 1] weight gradients go through the streaming kernel — as plain `@` autograd handed
+        # them to the library as [V, hidden]^T @ [V, 1] products, 191 us each on a 50 k-node batch)
+        per_node_outputs = dense(final_node_representations, w["regression/dense/kernel"], w["regression/dense/bias"])
+        gate_input = torch.cat([final_node_representations, batch.initial_node_features], dim=-1)
+        gate = torch.sigmoid(dense(gate_input, w["regression_gate/dense/kernel"], w["regression_gate/dense/bias"]))
+        per_node_gated_outputs = gate * per_node_outputs
+        # Sum up all nodes per graph: the HIP segment-sum kernel (2nd call-site family, :185-187)
+        return ops.unsorted_segment_sum(per_node_gated_outputs, batch.graph_nodes_list, batch.num_graphs).squeeze(-1)
+
+    # -------------------- Predictions: the molecule's value per task id --------------------
+    def prediction_layout(self, batch, hidden_size: int):
+        return {"values": ((int(batch.num_graphs), len(self.params['task_ids'])), torch.float32)}
+
+    def compute_task_predictions(self, final_node_representations: torch.Tensor, batch, weights, out=None) -> Dict[str, torch.Tensor]:
+        """values float32 [G, len(task_ids)] in task_ids order: the per-graph outputs the head's errors are taken of, on the route
+        compute_task_metrics takes (config.settings.qm9_head).  The batch's targets are not read: the fused kernel pair computes its
+        outputs next to a loss against zeros, which is dropped."""
+        num_graphs, task_ids = batch.num_graphs, self.params['task_ids']
+        device = final_node_representations.device
+        zeros = torch.zeros((len(task_ids), num_graphs), dtype=torch.float32, device=device)
+        use_hip = self._fused_head_applies(final_node_representations, batch, zeros)
+        ROUTES["head"] = "hip" if use_hip else "composition"
+        if use_hip:
+            y = qm9_head(final_node_representations.detach(), batch.initial_node_features, batch.graph_nodes_list, zeros, num_graphs,
+                         [tuple(v.detach() for v in task) for task in self._fused_head_variables(weights)])[3]
+        else:
+            y = torch.stack([self._per_graph_outputs(final_node_representations,
+                                                     batch, weights.scope("out_layer_task%i" % t) if hasattr(weights, "scope") else weights)
+                             for t in task_ids]).detach()
+        values = y.t()                                                           # [G, tasks]
+        if out is not None and out.get("values") is not None:
+            out["values"].copy_(values)
+            values = out["values"]
+        return {"values": values}
+
     def compute_task_metrics(self, final_node_representations: torch.Tensor, batch, weights) -> Dict[str, torch.Tensor]:
         metrics = {}
         losses = []
@@ -265,18 +318,10 @@ class QM9_Task(Sparse_Graph_Task):
         targets = batch.extra['target_values']                                   # [tasks, G]
         task_ids = self.params['task_ids']
         features = batch.initial_node_features
-        use_hip = (config.settings.qm9_head == "fused" and final_node_representations.is_cuda and features.is_cuda
-                   and final_node_representations.dtype == torch.float32 and features.dtype == torch.float32
-                   and torch.is_tensor(targets) and targets.dtype == torch.float32
-                   and batch.graph_nodes_list.dtype == torch.int32 and num_graphs >= 1 and final_node_representations.dim() == 2
-                   and head_supported(len(task_ids), final_node_representations.shape[1], features.shape[1]))
+        use_hip = self._fused_head_applies(final_node_representations, batch, targets)
         ROUTES["head"] = "hip" if use_hip else "composition"
         if use_hip:
-            variables = []
-            for task_id in task_ids:
-                w = weights.scope("out_layer_task%i" % task_id) if hasattr(weights, "scope") else weights
-                variables.append((w["regression/dense/kernel"], w["regression/dense/bias"],
-                                  w["regression_gate/dense/kernel"], w["regression_gate/dense/bias"]))
+            variables = self._fused_head_variables(weights)
             loss, total_loss, abs_err, _ = qm9_head(final_node_representations, features, batch.graph_nodes_list, targets, num_graphs,
                                                     variables)
             for internal_id, task_id in enumerate(task_ids):
@@ -286,14 +331,7 @@ class QM9_Task(Sparse_Graph_Task):
             return metrics
         for internal_id, task_id in enumerate(self.params['task_ids']):
             w = weights.scope("out_layer_task%i" % task_id) if hasattr(weights, "scope") else weights
-            # (dense(): the [hidden, 1] weight gradients go through the streaming kernel — as plain `@` autograd handed
-            # them to the library as [V, hidden]^T @ [V, 1] products, 191 us each on a 50 k-node batch)
-            per_node_outputs = dense(final_node_representations, w["regression/dense/kernel"], w["regression/dense/bias"])
-            gate_input = torch.cat([final_node_representations, batch.initial_node_features], dim=-1)
-            gate = torch.sigmoid(dense(gate_input, w["regression_gate/dense/kernel"], w["regression_gate/dense/bias"]))
-            per_node_gated_outputs = gate * per_node_outputs
-            # Sum up all nodes per graph: the HIP segment-sum kernel (2nd call-site family, :185-187)
-            per_graph_outputs = ops.unsorted_segment_sum(per_node_gated_outputs, batch.graph_nodes_list, num_graphs).squeeze(-1)
+            per_graph_outputs = self._per_graph_outputs(final_node_representations, batch, w)
             per_graph_errors = per_graph_outputs - targets[internal_id, :]
             metrics['abs_err_task%i' % task_id] = per_graph_errors.abs().sum()
             losses.append((0.5 * per_graph_errors ** 2).mean())

@@ -134,6 +134,44 @@ class Sparse_Graph_Task:
         """model_ops['initial_node_features'] of one batch; `weights` maps the names of input_variables() to the parameters."""
         return batch.initial_node_features
 
+    # ---- predictions (Sparse_Graph_Model.predict): what the task's metric counts, per node or per graph ----
+    PER_NODE_PREDICTIONS: tuple = ()                    # keys of compute_task_predictions whose rows are the batch's nodes
+
+    def prediction_layout(self, batch: "DeviceBatch", hidden_size: int) -> Dict[str, tuple]:
+        """key -> (shape, torch dtype) of what compute_task_predictions returns for this batch: the model lays one packed arena out
+        by it and hands its views to the hook as `out`."""
+        raise NotImplementedError("the %s task defines no predictions" % type(self).__name__)
+
+    def compute_task_predictions(self, final_node_representations: torch.Tensor, batch: "DeviceBatch", weights,
+                                 out: Optional[Dict[str, torch.Tensor]] = None) -> Dict[str, torch.Tensor]:
+        """Batch-level predictions on the tensors' device, decided by the rules the task's metric counts by (predict.py).  Reads no
+        label, target or mask of the batch and applies no dropout.  `out`: tensors of prediction_layout() to write into (optional)."""
+        raise NotImplementedError("the %s task defines no predictions" % type(self).__name__)
+
+    @staticmethod
+    def num_nodes_of(sample) -> int:
+        """Nodes of one data sample (what the batch builders count it as)."""
+        return len(sample.node_features)
+
+    def split_predictions(self, host_arrays: Dict[str, np.ndarray], batch, samples) -> list:
+        """One dict per graph of the batch, in the batch's order: per-node arrays (PER_NODE_PREDICTIONS and 'node_states') are cut
+        by each sample's node count, every other array is indexed by the graph.  The pieces are views of host_arrays."""
+        counts = [int(self.num_nodes_of(s)) for s in samples]
+        if len(samples) != int(batch.num_graphs):
+            raise ValueError("split_predictions: %d samples for a batch of %d graphs" % (len(samples), int(batch.num_graphs)))
+        if sum(counts) != int(batch.num_nodes):
+            raise ValueError("split_predictions: the samples hold %d nodes, the batch %d" % (sum(counts), int(batch.num_nodes)))
+        per_node = set(self.PER_NODE_PREDICTIONS) | {"node_states"}
+        for key, a in host_arrays.items():
+            want = int(batch.num_nodes) if key in per_node else len(samples)
+            if a.shape[0] != want:
+                raise ValueError("split_predictions: %r has %d rows, expected %d" % (key, a.shape[0], want))
+        out, offset = [], 0
+        for g, n in enumerate(counts):
+            out.append({key: (a[offset:offset + n] if key in per_node else a[g]) for key, a in host_arrays.items()})
+            offset += n
+        return out
+
     # ---- native batching (tasks/batcher.py); tasks override the payload tables / post-processing ----
     NODE_PAYLOADS = {"initial_node_features": ("node_features", np.float32)}
     GRAPH_PAYLOADS: Dict[str, tuple] = {}

@@ -537,9 +537,31 @@ class VarMisuse_Task(Sparse_Graph_Task):
             return {"slot_score_linear_layer/kernel": ((2 * hidden_size + 1, 1), "glorot_uniform")}
         return {}
 
+    # -------------------- Predictions: which candidate belongs into the slot --------------------
+    @staticmethod
+    def num_nodes_of(sample) -> int:
+        return len(sample.node_labels_to_unique_labels)          # (the reference's seven fields: the numpy feed sizes a graph by this)
+
+    def prediction_layout(self, batch, hidden_size: int):
+        num_graphs, num_cands = int(batch.num_graphs), int(self.params['max_variable_candidates'])
+        return {"probabilities": ((num_graphs, num_cands), torch.float32), "predicted": ((num_graphs,), torch.int32)}
+
+    def compute_task_predictions(self, final_node_representations: torch.Tensor, batch, weights, out=None) -> Dict[str, torch.Tensor]:
+        """probabilities float32 [G, max_variable_candidates] and predicted int32 [G], the candidate index tf.argmax(tf.nn.softmax(
+        logits)) names (:438; 0 is the correct one): the arithmetic by which the head counts num_correct_predictions
+        (csrc/common.h: candidate_choice).  Runs the head's forward on whichever route compute_task_metrics takes, for either loss
+        function, and drops its metrics; the logits do not depend on the loss.  A padded candidate has probability exactly 0."""
+        from ..predict import predict_candidates
+        out = out or {}
+        with torch.no_grad():
+            self.compute_task_metrics(final_node_representations, batch, weights)
+        probabilities, predicted = predict_candidates(self.last_logits, out.get("probabilities"), out.get("predicted"))
+        return {"probabilities": probabilities, "predicted": predicted}
+
     def compute_task_metrics(self, final_node_representations: torch.Tensor, batch, weights) -> Dict[str, torch.Tensor]:
         """No dropout on the final states in any fold (module docstring).  Metrics: loss (mean over the graphs), total_loss,
-        accuracy, num_correct_predictions (float32 here; an int32 count in the reference)."""
+        accuracy, num_correct_predictions (float32 here; an int32 count in the reference).  `last_logits` keeps the batch's
+        logits [G, candidates] (detached), which compute_task_predictions reads."""
         device = final_node_representations.device
         w = weights["slot_score_linear_layer/kernel"] if self.params['slot_score_via_linear_layer'] else None
         slot = _device_tensor(batch.extra['slot_node_ids'], torch.int32, device).reshape(-1)

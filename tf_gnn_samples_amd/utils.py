@@ -210,7 +210,9 @@ class _GRUCellFn(torch.autograd.Function):
     [u, 3u] tensor (dense.tn_stream_into).  The weight gradients go to the side stream like a Dense layer's (weight_grad_stream.fork)."""
 
     @staticmethod
-    def forward(ctx, x, h, K, U, b, act: int):
+    def forward(ctx, x, h, K, U, b, act: int, grad_mode: bool = True):
+        """grad_mode: torch.is_grad_enabled() as the CALLER saw it (inside forward() it is always off, and needs_input_grad stays
+        true for parameters under no_grad): an evaluation or prediction cell writes and saves nothing for a backward."""
         from . import _lib
         from .dense import GEMM_NN, lib_gemm
         x, h = x.contiguous(), h.contiguous()
@@ -220,7 +222,7 @@ class _GRUCellFn(torch.autograd.Function):
             # are written only when a backward will read them
             from . import ops
             from .dense import WEIGHT_NN, weight_image
-            train = any(ctx.needs_input_grad[:5])
+            train = grad_mode and any(ctx.needs_input_grad[:5])
             im_zr = weight_image([K[:, :2 * u], U[:, :2 * u]], WEIGHT_NN)  # B [2u, D + u]: k = [x | h]
             im_h = weight_image([K[:, 2 * u:], U[:, 2 * u:]], WEIGHT_NN)   # B [u, D + u]:  k = [x | r * h]
             z, r, rh, hh = (torch.empty_like(h) for _ in range(4)) if train else (None,) * 4
@@ -298,7 +300,7 @@ class _GRUCellFn(torch.autograd.Function):
             else:
                 gh = None
         gK, gU, gb = aside.join() if aside is not None else weight_side()
-        return gx, gh, gK, gU, gb, None
+        return gx, gh, gK, gU, gb, None, None
 
 
 def _gru_cell_kernel_ok(x, h, K, U, b, act: int) -> bool:
@@ -345,7 +347,7 @@ class _GatedUnit:
             return out, [out]
         # GRU, reset_after=False, gate order z, r, h (Keras GRUCell, TF 1.13)
         if self.activation_name in _GRU_FUSABLE and _gru_cell_fused_ok(inputs, h, K, U, b, u):
-            out = _GRUCellFn.apply(inputs, h, K, U, b, _GRU_FUSABLE[self.activation_name])
+            out = _GRUCellFn.apply(inputs, h, K, U, b, _GRU_FUSABLE[self.activation_name], torch.is_grad_enabled())
             return out, [out]
         xk = dense(inputs, K, b)                             # [V, 3u]
         rec = dense(h, U[:, :2 * u])                         # [V, 2u]
