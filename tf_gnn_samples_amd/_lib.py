@@ -1,4 +1,5 @@
-"""ctypes binding of librelgnn.so (C ABI: include/relgnn.h, include/relgnn_dropout.h, include/relgnn_predict.h).
+"""ctypes binding of librelgnn.so (C ABI: include/relgnn.h, include/relgnn_dropout.h, include/relgnn_predict.h,
+include/relgnn_parallel.h).
 
 This is the ONLY compute backend of the package.  There is no CPU / eager-PyTorch fallback:
 if the HIP library is missing, or a tensor is not a float32/int32 CUDA(HIP) tensor, the
@@ -197,6 +198,11 @@ _PREDICT_SIGNATURES = {
     "relgnn_predict_candidates_f32": (ctypes.c_int, [_ptr, _c_i64, _c_i32, _ptr, _ptr, _ptr]),
 }
 
+# include/relgnn_parallel.h (data-parallel training: the scaled pack in front of the gradient all-reduce): its own table too
+_PARALLEL_SIGNATURES = {
+    "relgnn_mt_pack_scaled_f32": (ctypes.c_int, [_ptr, _ptr, _c_i32, _c_f32, _ptr, _ptr]),
+}
+
 _lib = None
 
 
@@ -214,7 +220,8 @@ def load_library():
             "%s not found: the HIP extension is not built. Run `python -c 'import __graft_entry__ as g; "
             "g.build()'` (needs hipcc). There is no CPU fallback for this path." % LIB_PATH)
     lib = ctypes.CDLL(str(LIB_PATH))
-    for name, (restype, argtypes) in list(_SIGNATURES.items()) + list(_DROPOUT_SIGNATURES.items()) + list(_PREDICT_SIGNATURES.items()):
+    for name, (restype, argtypes) in list(_SIGNATURES.items()) + list(_DROPOUT_SIGNATURES.items()) + list(_PREDICT_SIGNATURES.items()) \
+            + list(_PARALLEL_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the symbol is not exported
         fn.restype = restype
         fn.argtypes = argtypes
@@ -236,6 +243,11 @@ def dropout_signatures():
 def predict_signatures():
     """The entry points of include/relgnn_predict.h (not part of exported_signatures() either)."""
     return dict(_PREDICT_SIGNATURES)
+
+
+def parallel_signatures():
+    """The entry points of include/relgnn_parallel.h (not part of exported_signatures() either)."""
+    return dict(_PARALLEL_SIGNATURES)
 
 
 def status_string(code: int) -> str:

@@ -441,6 +441,10 @@ class Sparse_Graph_Model(ABC):
         self.device = torch.device(device if device is not None else "cuda")
         self._native_batchers = {}
         self.training = False
+        # under a process group only rank 0 logs (the drivers form the group before they build the model; train(group=...) /
+        # test(group=...) go by the rank within THEIR group)
+        import torch.distributed as _dist
+        self._log_rank = _dist.get_rank() if _dist.is_available() and _dist.is_initialized() else 0
         torch.manual_seed(params['random_seed'])
         np.random.seed(params['random_seed'])
         if self.device.type == "cuda":
@@ -468,6 +472,8 @@ class Sparse_Graph_Model(ABC):
         return os.path.join(self.result_dir, "%s_best_model.pickle" % self.run_id)
 
     def log_line(self, msg):
+        if self._log_rank != 0:
+            return
         try:
             with open(self.log_file, 'a') as log_fh:
                 log_fh.write(msg + '\n')
@@ -687,10 +693,11 @@ class Sparse_Graph_Model(ABC):
     _backward_seed: Dict[Any, torch.Tensor] = {}
 
     def train_step(self, batch: DeviceBatch, grad_hook=None, device_step_count: bool = False,
-                   pre_backward=None) -> Dict[str, torch.Tensor]:
+                   pre_backward=None, lr_num_graphs: Optional[int] = None) -> Dict[str, torch.Tensor]:
         """forward + backward + per-variable clip + optimizer update == one sess.run with train_step (:287-293).
         pre_backward(): called between the forward and the backward (a bucketed gradient all-reduce arms its hooks there);
-        grad_hook(params): between the backward and the clipping (the data-parallel reduction)."""
+        grad_hook(params): between the backward and the clipping (the data-parallel reduction);
+        lr_num_graphs: the graph count lr_for_num_graphs_per_batch scales by (data-parallel: the step's global count)."""
         self.optimizer.zero_grad()
         metrics = self.forward_batch(batch, training=True)
         if pre_backward is not None:
@@ -712,12 +719,13 @@ class Sparse_Graph_Model(ABC):
         ops.join_deferred()
         if grad_hook is not None:  # data-parallel gradient all-reduce goes here (before clipping)
             grad_hook(self.optimizer.params)
-        lr_scale = 1.0
-        lr_n = self.params.get('lr_for_num_graphs_per_batch')
-        if lr_n is not None:
-            lr_scale = float(batch.num_graphs) / float(lr_n)
+        lr_scale = self._lr_scale(batch.num_graphs if lr_num_graphs is None else lr_num_graphs)
         self.optimizer.clip_and_step(lr_scale, device_step_count=device_step_count)
         return metrics
+
+    def _lr_scale(self, num_graphs: int) -> float:
+        lr_n = self.params.get('lr_for_num_graphs_per_batch')
+        return 1.0 if lr_n is None else float(num_graphs) / float(lr_n)
 
     def _batches(self, data, data_fold: DataFold):
         """Batches of one epoch.  On the GPU the data fold is flattened once and batches come from the C++ builder
@@ -727,6 +735,10 @@ class Sparse_Graph_Model(ABC):
             and hasattr(self.task, "make_graph_store")
         if not native:
             return self.task.make_minibatch_iterator(data, data_fold, self.params['max_nodes_in_batch'])
+        return self.task.make_native_minibatch_iterator(self._native_pipeline(data), data_fold, self.params['max_nodes_in_batch'])
+
+    def _native_pipeline(self, data):
+        """The input pipeline of one data fold (ResidentDataset or NativeBatcher over its GraphStore), built once and kept."""
         from ..tasks.batcher import NativeBatcher
         key = (id(data), len(data))
         cached = self._native_batchers.get(key)
@@ -753,7 +765,7 @@ class Sparse_Graph_Model(ABC):
             # passes — is dropped so that its resident copy of the fold and its pinned arenas are released
             while len(self._native_batchers) > 3:
                 self._native_batchers.pop(next(iter(self._native_batchers)))
-        return self.task.make_native_minibatch_iterator(cached[1], data_fold, self.params['max_nodes_in_batch'])
+        return cached[1]
 
     @staticmethod
     def _fold_fits_hbm(store, budget_bytes: int = 32 << 30) -> bool:
@@ -819,9 +831,12 @@ class Sparse_Graph_Model(ABC):
         return (per_graph_loss, task_metric_results, processed_graphs, processed_graphs / epoch_time,
                 processed_nodes / epoch_time, processed_edges / epoch_time)
 
-    def train(self, quiet: bool = False, max_epochs: Optional[int] = None):
-        """:318-371 without TensorBoard: early stopping on the task's validation metric."""
+    def train(self, quiet: bool = False, max_epochs: Optional[int] = None, group=None):
+        """:318-371 without TensorBoard: early stopping on the task's validation metric.
+        group: a torch.distributed process group of W > 1 ranks (one process per GPU, the model built after init_distributed())
+        trains data-parallel by graph (_DataParallel below); None or a group of one rank is the single-GPU loop."""
         total_time_start = time.time()
+        dp = self._data_parallel(group)
         train_data = self.task._loaded_data[DataFold.TRAIN]
         valid_data = self.task._loaded_data[DataFold.VALIDATION]
         # The loaded folds are millions of long-lived Python objects: frozen for the duration of the loop they cost the cyclic
@@ -831,27 +846,40 @@ class Sparse_Graph_Model(ABC):
         gc.collect()
         gc.freeze()
         try:
-            return self._train_loop(train_data, valid_data, total_time_start, quiet, max_epochs)
+            if dp is not None:
+                dp.begin_training()
+            return self._train_loop(train_data, valid_data, total_time_start, quiet, max_epochs, dp)
         finally:
             gc.unfreeze()
+            if dp is not None:
+                dp.end()
 
-    def _train_loop(self, train_data, valid_data, total_time_start, quiet, max_epochs):
+    def _train_loop(self, train_data, valid_data, total_time_start, quiet, max_epochs, dp=None):
         best_valid_metric, best_epoch = float("+inf"), 0
+        self.validation_history = []       # (epoch, early-stopping metric); under a group the same list on every rank
+        run_epoch = self._run_epoch if dp is None else dp.run_epoch
         for epoch in range(1, (max_epochs or self.params['max_epochs']) + 1):
+            if dp is not None:
+                dp.epoch = epoch
             self.log_line("== Epoch %i" % epoch)
-            loss, res, n, gs, ns, es = self._run_epoch("epoch %i (training)" % epoch, train_data, DataFold.TRAIN, quiet)
+            loss, res, n, gs, ns, es = run_epoch("epoch %i (training)" % epoch, train_data, DataFold.TRAIN, quiet)
             self.log_line(" Train: loss: %.5f || %s || graphs/sec: %.2f | nodes/sec: %.0f | edges/sec: %.0f"
                           % (loss, self.task.pretty_print_epoch_task_metrics(res, n), gs, ns, es))
-            loss, res, n, gs, ns, es = self._run_epoch("epoch %i (validation)" % epoch, valid_data, DataFold.VALIDATION, quiet)
+            loss, res, n, gs, ns, es = run_epoch("epoch %i (validation)" % epoch, valid_data, DataFold.VALIDATION, quiet)
             metric = self.task.early_stopping_metric(res, n)
+            self.validation_history.append((epoch, metric))
             self.log_line(" Valid: loss: %.5f || %s || graphs/sec: %.2f | nodes/sec: %.0f | edges/sec: %.0f"
                           % (loss, self.task.pretty_print_epoch_task_metrics(res, n), gs, ns, es))
             if metric < best_valid_metric:
-                self.save_model(self.best_model_file)
+                if dp is None or dp.rank == 0:     # (the parameters are identical on every rank: rank 0's pickle is the model)
+                    self.save_model(self.best_model_file)
                 best_valid_metric, best_epoch = metric, epoch
             elif epoch - best_epoch >= self.params['patience']:
                 self.log_line("Stopping training after %i epochs without improvement." % self.params['patience'])
                 break
+        self.best_epoch = best_epoch
+        if dp is not None:
+            dp.barrier()                   # nobody leaves (and reads rank 0's files) before everyone is done
         self.log_line("Training took %is." % (time.time() - total_time_start))
 
     # -------------------- Predictions --------------------
@@ -917,7 +945,182 @@ class Sparse_Graph_Model(ABC):
                 print("Predicting, batch %i (has %i graphs). %i graphs so far." % (step, len(samples), len(results)), end='\r')
         return results
 
-    def test(self, data, quiet: bool = False):
-        loss, res, n, gs, ns, es = self._run_epoch("Test", list(data), DataFold.TEST, quiet)
+    def test(self, data, quiet: bool = False, group=None):
+        """Loss and task metrics of `data`.  group: as in train(); every rank passes the SAME data, evaluates its shard of it, and
+        rank 0 logs the metrics of the whole."""
+        dp = self._data_parallel(group)
+        if dp is None:
+            loss, res, n, gs, ns, es = self._run_epoch("Test", list(data), DataFold.TEST, quiet)
+        else:
+            try:
+                loss, res, n, gs, ns, es = dp.run_epoch("Test", list(data), DataFold.TEST, quiet)
+            finally:
+                dp.end()
         self.log_line("Loss %.5f on %i graphs" % (loss, n))
         self.log_line("Metrics: %s" % self.task.pretty_print_epoch_task_metrics(res, n))
+
+    # -------------------- Data parallelism by graph (train(group=...), test(group=...)) --------------------
+    def _data_parallel(self, group):
+        """None for the single-GPU loop (no group, or a group of one rank: nothing below runs, no collective is issued); otherwise
+        the driver of data-parallel epochs, after the refusals."""
+        if group is None:
+            return None
+        import torch.distributed as dist
+        if dist.get_world_size(group) == 1:
+            return None
+        from .. import config
+        world = dist.get_world_size(group)
+        self.task.loss_weight(1, 1)        # a task that cannot be split by graph (citation), or does not say how its loss is normalised, raises
+        if self.device.type != "cuda":
+            raise RuntimeError("train(group=...) / test(group=...) need the model on the GPU (one process per GPU; the gradient pack is a "
+                               "HIP kernel): this model is on %s" % self.device)
+        if not self.params.get('native_batching', True) or not hasattr(self.task, "make_graph_store"):
+            raise RuntimeError("data-parallel training uses the native input pipelines only: %s"
+                               % ("native_batching is false" if not self.params.get('native_batching', True)
+                                  else "the %s task has no make_graph_store" % type(self.task).__name__))
+        if config.settings.allreduce == "overlap":
+            raise RuntimeError("allreduce=overlap: the bucketed all-reduce (OverlappedGradientAllReducer) is not wired into train(); "
+                               "train(group=...) runs the flat packed form only and does not fall back to it silently: set allreduce=flat")
+        return _DataParallel(self, group, world)
+
+
+class _DataParallel:
+    """Epochs of Sparse_Graph_Model.train(group=...) / test(group=...) on one rank of W (parallel.py has the host-side pieces;
+    DESIGN.md section 8 the protocol).
+
+    The shard of a fold is fixed for the run (parallel.dp_shard); the rank's pipeline is built over its shard only.  Per epoch and
+    fold: shuffle (training; parallel.dp_epoch_rng), plan the local batches, exchange the plans (one all-gather, one host read).
+    A training epoch then runs max_r(batches_r) steps on EVERY rank.  With a batch: train_step whose grad_hook is the packed
+    reducer with this rank's scale and whose learning rate goes by the step's global graph count.  Without one: zeros into the
+    same collective, the same clip and update.  Evaluation epochs run the local batches without a gradient collective.  At the
+    end of every epoch the per-batch metrics and the counters are gathered in rank order."""
+
+    def __init__(self, model: Sparse_Graph_Model, group, world: int):
+        import torch.distributed as dist
+        self.model, self.group, self.world = model, group, world
+        self.rank = dist.get_rank(group)
+        self.epoch = 0
+        # collectives of small tables: device tensors under nccl, host tensors under gloo
+        self.comm_device = model.device if dist.get_backend(group) == "nccl" else torch.device("cpu")
+        self.reducer = None
+        self._saved_log_rank, model._log_rank = model._log_rank, self.rank
+
+    def end(self):
+        self.model._log_rank = self._saved_log_rank
+
+    def barrier(self):
+        import torch.distributed as dist
+        dist.barrier(group=self.group)
+
+    def begin_training(self):
+        """Rank 0's parameters, optimizer slots and step count everywhere (a restore()d model on rank 0 included); then torch's
+        generator of this device reseeded from (random_seed, rank): the torch dropout route must not share masks across ranks (the
+        fused route's state block already carries the rank as its replica)."""
+        import torch.distributed as dist
+        from ..dense import weights_changed
+        from ..parallel import PackedGradientAllReducer, dp_device_seed
+        model, opt = self.model, self.model.optimizer
+        src = dist.get_global_rank(self.group, 0)
+        with torch.no_grad():
+            for name in model.variables.names():             # (created in the same order on every rank)
+                dist.broadcast(model.variables[name].data, src=src, group=self.group)
+            for _, slots in opt._slots():
+                for t in slots:
+                    dist.broadcast(t, src=src, group=self.group)
+            t_step = torch.tensor([opt.t], dtype=torch.int64, device=self.comm_device)
+            dist.broadcast(t_step, src=src, group=self.group)
+            opt.t = int(t_step.item())
+        opt.sync_device_step_count()
+        weights_changed()
+        torch.cuda.default_generators[model.device.index if model.device.index is not None
+                                      else torch.cuda.current_device()].manual_seed(dp_device_seed(model.params['random_seed'], self.rank))
+        self.reducer = PackedGradientAllReducer(opt.params, group=self.group)
+
+    def _pipeline(self, data):
+        """(the rank's input pipeline over its shard of `data`, or None for an empty shard; the largest shard's graph count)."""
+        model = self.model
+        folds = model.__dict__.setdefault("_dp_folds", {})
+        key = (id(data), len(data), self.world, self.rank)
+        kept = folds.get(key)
+        if kept is None or kept[0] is not data:
+            from ..parallel import dp_shard
+            shards = dp_shard(data, self.world)
+            kept = folds[key] = (data, [data[i] for i in shards[self.rank]], max(len(s) for s in shards))
+            while len(folds) > 3:      # train + validation folds and one more, like the pipelines themselves
+                folds.pop(next(iter(folds)))
+        _, mine, largest = kept
+        return (model._native_pipeline(mine) if mine else None), largest
+
+    def run_epoch(self, epoch_name: str, data, data_fold: DataFold, quiet: bool = False):
+        """_run_epoch across the group: the same six results on every rank, over the whole fold."""
+        from ..parallel import dp_epoch_rng, dp_exchange_plans, dp_merge_epoch, dp_plan_epoch, dp_schedule
+        model, task = self.model, self.model.task
+        train = data_fold == DataFold.TRAIN
+        max_nodes = model.params['max_nodes_in_batch']
+        seed = model.params['random_seed']
+        pipeline, largest_shard = self._pipeline(data)
+        plan = dp_plan_epoch(pipeline.store if pipeline is not None else None, train, max_nodes,
+                             dp_epoch_rng(seed, self.epoch, self.rank))
+        plans = dp_exchange_plans(plan, largest_shard, self.group, self.comm_device)
+        local_steps = len(plan.batches)
+        if train:
+            if self.reducer is None:
+                raise RuntimeError("a data-parallel training epoch outside train(group=...)")
+            schedule = dp_schedule([[(task.loss_weight(g, n), g) for g, n in p] for p in plans])
+            steps = schedule.steps
+        else:
+            schedule, steps = None, local_steps
+        batch_iterator = iter(()) if pipeline is None else iter(task.make_native_minibatch_iterator(
+            pipeline, data_fold, max_nodes, rng=dp_epoch_rng(seed, self.epoch, self.rank)))
+        start_time = time.time()
+        task_metric_results = []
+        state = {"graphs": 0, "nodes": 0, "edges": 0, "loss": 0.0, "step": 0}
+
+        def fetch(pending):
+            m, mb = pending
+            m = m.get()
+            check_pending_graph_errors()
+            state["graphs"] += mb.num_graphs
+            state["nodes"] += mb.num_nodes
+            state["edges"] += mb.num_edges
+            state["loss"] += m['loss'] * mb.num_graphs
+            task_metric_results.append(m)
+            if not quiet and self.rank == 0:
+                print("Running %s, batch %i (has %i graphs on rank 0). Loss so far: %.4f"
+                      % (epoch_name, state["step"], mb.num_graphs, state["loss"] / state["graphs"]), end='\r')
+            state["step"] += 1
+
+        pending = None
+        upcoming = next(batch_iterator, None)
+        for k in range(steps):
+            if k < local_steps:
+                batch = upcoming
+                if batch is None or (batch.num_graphs, batch.num_nodes) != (int(plan.graphs[k]), int(plan.nodes[k])):
+                    raise RuntimeError("%s, step %d: the input pipeline did not assemble the planned batch" % (epoch_name, k))
+                if train:
+                    scale = float(schedule.scales[self.rank, k])
+                    m = model.train_step(batch, grad_hook=lambda params, s=scale: self.reducer(s),
+                                         lr_num_graphs=int(schedule.graph_sums[k]))
+                else:
+                    with torch.no_grad():
+                        m = model.forward_batch(batch, training=False)
+                readback = MetricsReadback(m)
+                upcoming = next(batch_iterator, None)      # (the same pipelining as _run_epoch: metrics are read one step late)
+                if pending is not None:
+                    fetch(pending)
+                pending = (readback, batch)
+            else:
+                # no batch left on this rank: zeros into the step's collective, the same clip and update as everyone else
+                # (parameters, optimizer slots and the step count stay identical across the ranks)
+                model.optimizer.zero_grad()
+                self.reducer(0.0)
+                model.optimizer.clip_and_step(model._lr_scale(int(schedule.graph_sums[k])))
+        if upcoming is not None:
+            raise RuntimeError("%s: the input pipeline holds more batches than planned" % epoch_name)
+        if pending is not None:
+            fetch(pending)
+        merged, (loss_sum, graphs, nodes, edges) = dp_merge_epoch(
+            task_metric_results, (state["loss"], state["graphs"], state["nodes"], state["edges"]), self.group)
+        epoch_time = time.time() - start_time
+        graphs, nodes, edges = int(graphs), int(nodes), int(edges)
+        return (loss_sum / max(graphs, 1), merged, graphs, graphs / epoch_time, nodes / epoch_time, edges / epoch_time)

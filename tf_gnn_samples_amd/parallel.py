@@ -11,10 +11,17 @@ loss = total_loss / num_nodes_in_batch): rank r holds g_r = d(total_r / n_r); th
 is sum_r n_r * g_r / sum_r n_r.  The weight n_r rides in the last slot of the same flat buffer, so
 there is exactly one collective.  Per-variable clip_by_norm (models/sparse_graph_model.py:253-260)
 is applied AFTER the all-reduce.
+
+Sparse_Graph_Model.train(group=...) / test(group=...) drive whole epochs this way.  What they need beyond
+one step is below the reducers: the shard of a fold, the per-epoch shuffle, the local batch plan, its exchange (one all-gather
+per epoch and fold) and the schedule every rank derives from it on the host: the number of steps, the per-step weight sum W_k
+and graph count G_k, and each rank's scale float32(w_rk / W_k).  PackedGradientAllReducer applies that scale while it packs
+(csrc/parallel.hip, one launch), so the one all-reduce(SUM) leaves the weighted mean with nothing behind it.
 """
 import os
-from typing import List, Sequence
+from typing import Any, Dict, List, NamedTuple, Optional, Sequence, Tuple
 
+import numpy as np
 import torch
 import torch.distributed as dist
 
@@ -226,3 +233,169 @@ class OverlappedGradientAllReducer(GradientAllReducer):
         if not self._armed:
             self.arm(local_weight)
         self.finish()
+
+
+# ---- whole epochs: shard, shuffle, plan, exchange, schedule (host only; Sparse_Graph_Model.train(group=...)) -----------------
+
+def dp_shard(data: Sequence, world_size: int) -> List[List[int]]:
+    """The shard of every rank for one data fold, fixed for the run: shard_graphs_by_edges over each sample's edge count
+    (all edge types).  Every rank computes the whole table, so every rank knows every shard's size."""
+    return shard_graphs_by_edges([sum(len(a) for a in g.adjacency_lists) for g in data], world_size)
+
+
+def dp_epoch_rng(random_seed: int, epoch: int, rank: int) -> np.random.RandomState:
+    """The generator that shuffles `rank`'s shard in training epoch `epoch`: seeded from (random_seed, epoch, rank), so a plan
+    and the iterator that assembles its batches draw the same order from two instances."""
+    return np.random.RandomState(np.array([int(random_seed) % 2 ** 32, int(epoch) % 2 ** 32, int(rank)], dtype=np.uint32))
+
+
+def dp_device_seed(random_seed: int, rank: int) -> int:
+    """Seed of torch's device generator on `rank` (the torch dropout route: ranks must not share masks)."""
+    return int(np.random.SeedSequence([int(random_seed) % 2 ** 32, int(rank)]).generate_state(1, dtype=np.uint64)[0] >> np.uint64(1))
+
+
+class DpEpochPlan(NamedTuple):
+    """A rank's batches of one epoch and fold, known before any of them is assembled."""
+    ids: np.ndarray                 # the store's graph ids in the epoch's order
+    batches: List[np.ndarray]       # store.split_batches(ids, max_nodes_per_batch): what iterate() will assemble, in order
+    graphs: np.ndarray              # int64 [local steps]
+    nodes: np.ndarray               # int64 [local steps]
+
+
+def dp_plan_epoch(store, shuffle: bool, max_nodes_per_batch: int, rng: Optional[np.random.RandomState] = None) -> DpEpochPlan:
+    """The batches make_native_minibatch_iterator(pipeline over `store`, fold, max_nodes_per_batch, rng) will yield: the same
+    arange, the same one shuffle (training folds), the same split rule.  store=None is an empty shard."""
+    if store is None or store.num_graphs == 0:
+        empty = np.zeros(0, np.int64)
+        return DpEpochPlan(empty, [], empty, empty)
+    ids = np.arange(store.num_graphs)
+    if shuffle:
+        (rng or np.random).shuffle(ids)
+    batches = store.split_batches(ids, max_nodes_per_batch)
+    graphs = np.array([len(b) for b in batches], dtype=np.int64)
+    nodes = np.array([int((store.node_off[b + 1] - store.node_off[b]).sum()) for b in batches], dtype=np.int64)
+    return DpEpochPlan(ids, batches, graphs, nodes)
+
+
+def dp_exchange_plans(plan: DpEpochPlan, max_local_steps: int, group=None, device=None) -> List[List[Tuple[int, int]]]:
+    """Every rank's (graphs, nodes) per local step, in rank order, on every rank: ONE all-gather of an int64 table of
+    max_local_steps + 1 rows (row 0 holds the rank's step count; max_local_steps is a bound every rank knows, e.g. the largest
+    shard's graph count) and one read of the gathered tables.  `device`: where the table lives (the GPU under nccl, the host under gloo)."""
+    n = len(plan.batches)
+    if n > max_local_steps:
+        raise ValueError("dp_exchange_plans: %d local steps, the agreed bound is %d" % (n, max_local_steps))
+    table = np.zeros((max_local_steps + 1, 2), dtype=np.int64)
+    table[0, 0] = n
+    table[1:n + 1, 0] = plan.graphs
+    table[1:n + 1, 1] = plan.nodes
+    mine = torch.from_numpy(table)
+    if device is not None and torch.device(device).type != "cpu":
+        mine = mine.to(device)
+    world = dist.get_world_size(group)
+    gathered = [torch.empty_like(mine) for _ in range(world)]
+    dist.all_gather(gathered, mine, group=group)
+    host = torch.stack(gathered).cpu().numpy()                      # the epoch's one host read
+    return [[(int(g), int(v)) for g, v in host[r, 1:int(host[r, 0, 0]) + 1]] for r in range(world)]
+
+
+class DpSchedule(NamedTuple):
+    steps: int                      # max_r(local steps): every rank issues this many reductions
+    weight_sums: np.ndarray         # float64 [steps]: W_k = sum_r w_rk
+    graph_sums: np.ndarray          # int64 [steps]:   G_k = sum_r graphs_rk (what lr_for_num_graphs_per_batch scales by)
+    scales: np.ndarray              # float32 [world, steps]: float32(w_rk / W_k), the quotient formed in double; 0 without a batch
+
+
+def dp_schedule(per_rank_steps: Sequence[Sequence[Tuple[float, int]]]) -> DpSchedule:
+    """per_rank_steps[r][k] = (loss weight, graphs) of rank r's k-th batch.  A rank with fewer batches than the longest (none at
+    all included) takes part in the remaining steps with weight 0."""
+    world = len(per_rank_steps)
+    steps = max((len(p) for p in per_rank_steps), default=0)
+    w = np.zeros((world, steps), dtype=np.float64)
+    g = np.zeros((world, steps), dtype=np.int64)
+    for r, p in enumerate(per_rank_steps):
+        for k, (weight, graphs) in enumerate(p):
+            if not weight > 0:
+                raise ValueError("dp_schedule: rank %d step %d has loss weight %r; a batch weighs more than nothing" % (r, k, weight))
+            w[r, k], g[r, k] = float(weight), int(graphs)
+    weight_sums = np.zeros(steps, dtype=np.float64)
+    for r in range(world):                                           # in rank order, the same on every rank
+        weight_sums += w[r]
+    scales = (w / weight_sums).astype(np.float32) if steps else np.zeros((world, 0), np.float32)
+    return DpSchedule(steps, weight_sums, g.sum(axis=0), scales)
+
+
+def dp_merge_epoch(metric_results: List[Dict[str, Any]], sums: Sequence[float], group=None) -> Tuple[List[Dict[str, Any]], List[float]]:
+    """End of an epoch: every rank's per-batch metric dicts concatenated in rank order and the ranks' sums (loss * graphs, graphs,
+    nodes, edges) added in rank order: the same list and the same totals on every rank."""
+    world = dist.get_world_size(group)
+    gathered = [None] * world
+    dist.all_gather_object(gathered, (list(metric_results), [float(x) for x in sums]), group=group)
+    merged = [m for part, _ in gathered for m in part]
+    totals = [0.0] * len(sums)
+    for _, part in gathered:
+        for i, x in enumerate(part):
+            totals[i] += x
+    return merged, totals
+
+
+class PackedGradientAllReducer:
+    """The reduction of train(group=...): ONE launch writes scale * grad of every trainable variable into the flat buffer
+    (relgnn_mt_pack_scaled_f32, one per 48 variables), ONE all-reduce(SUM) follows, every .grad becomes a view of its slice.
+    The scale is this rank's share float32(w_r / sum_r w_r) of the step (dp_schedule), so the sum is the weighted mean:
+    no weight slot, no divide.  A variable without a gradient, and every variable of a rank that holds no batch in this
+    step (scale 0), contributes +0.0."""
+
+    def __init__(self, params: Sequence[torch.nn.Parameter], group=None):
+        import ctypes
+        from . import _lib
+        self.params = [p for p in params if p.requires_grad]
+        self.group = group
+        if not self.params or not all(p.is_cuda and p.dtype == torch.float32 for p in self.params):
+            raise _lib.RelGnnLibraryError("PackedGradientAllReducer packs float32 variables on the GPU with a HIP kernel; "
+                                          "there is no CPU fallback for this path")
+        n = sum(p.numel() for p in self.params)
+        self.flat = torch.zeros(n, dtype=torch.float32, device=self.params[0].device)
+        self.views, offs, off = [], [], 0
+        for p in self.params:
+            self.views.append(self.flat[off:off + p.numel()].view_as(p))
+            offs.append(off)
+            off += p.numel()
+        self._chunks = []                        # (first variable, count, sizes table, destination pointer)
+        for c0 in range(0, len(self.params), _lib.MT_MAX):
+            chunk = self.params[c0:c0 + _lib.MT_MAX]
+            sizes = (ctypes.c_int64 * len(chunk))(*[p.numel() for p in chunk])
+            self._chunks.append((c0, len(chunk), sizes, self.flat.data_ptr() + 4 * offs[c0]))
+        self._ptr_table = ctypes.c_void_p * _lib.MT_MAX
+
+    @property
+    def nbytes(self) -> int:
+        return self.flat.numel() * 4
+
+    @torch.no_grad()
+    def pack(self, scale: float) -> torch.Tensor:
+        """flat <- scale * grads, on the current stream.  Returns the flat buffer."""
+        from . import _lib
+        scale = float(scale)
+        keep = []                                # contiguous copies stay alive until their launch is enqueued
+        for c0, n, sizes, dst in self._chunks:
+            table = self._ptr_table()
+            for j in range(n):
+                g = self.params[c0 + j].grad
+                if g is None:
+                    continue                     # (NULL: +0.0 for the variable's length)
+                if g.dtype != torch.float32 or not g.is_cuda:
+                    raise ValueError("PackedGradientAllReducer: a %s gradient on %s" % (g.dtype, g.device))
+                if not g.is_contiguous():
+                    g = g.contiguous()
+                    keep.append(g)
+                table[j] = g.data_ptr()
+            _lib.launch("relgnn_mt_pack_scaled_f32", table, sizes, n, scale, dst)
+        return self.flat
+
+    @torch.no_grad()
+    def __call__(self, scale: float):
+        """grad <- sum_r scale_r * grad_r, in place of every .grad (views of the flat buffer; nothing is unpacked)."""
+        self.pack(scale)
+        dist.all_reduce(self.flat, op=dist.ReduceOp.SUM, group=self.group)
+        for p, v in zip(self.params, self.views):
+            p.grad = v

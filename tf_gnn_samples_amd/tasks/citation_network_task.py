@@ -355,6 +355,10 @@ class Citation_Network_Task(Sparse_Graph_Task):
             batch = batcher.pack(ids)
         yield batch
 
+    def loss_weight(self, num_graphs: int, num_nodes: int) -> float:
+        raise RuntimeError("the %s task trains on ONE graph that is the whole batch: it cannot be split by graph across ranks; "
+                           "run it on a single GPU" % self.name())
+
     def early_stopping_metric(self, task_metric_results: List[Dict[str, Any]], num_graphs: int) -> float:
         # :179-181: average loss
         return float(np.sum([float(m['total_loss']) for m in task_metric_results]) / num_graphs)

@@ -273,6 +273,9 @@ class PPI_Task(Sparse_Graph_Task):
             }
             yield MinibatchData(feed_dict=feed, num_graphs=len(chunk), num_nodes=node_offset, num_edges=num_edges)
 
+    def loss_weight(self, num_graphs: int, num_nodes: int) -> float:
+        return float(num_nodes)              # loss = total_loss / num_nodes (compute_task_metrics)
+
     def early_stopping_metric(self, task_metric_results: List[Dict[str, Any]], num_graphs: int) -> float:
         return float(np.sum([float(m['total_loss']) for m in task_metric_results]) / num_graphs)
 

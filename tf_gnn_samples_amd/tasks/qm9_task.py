@@ -381,6 +381,9 @@ class QM9_Task(Sparse_Graph_Task):
             }
             yield MinibatchData(feed_dict=feed, num_graphs=len(chunk), num_nodes=node_offset, num_edges=num_edges)
 
+    def loss_weight(self, num_graphs: int, num_nodes: int) -> float:
+        return float(num_graphs)             # the loss is a mean over the batch's graphs (compute_task_metrics)
+
     def early_stopping_metric(self, task_metric_results, num_graphs: int) -> float:
         return float(np.sum([float(m['total_loss']) for m in task_metric_results]) / num_graphs)
 

@@ -197,5 +197,11 @@ class Sparse_Graph_Task:
         for batch in batcher.iterate(ids, max_nodes_per_batch):
             yield self._finish_native_batch(batch)
 
+    def loss_weight(self, num_graphs: int, num_nodes: int) -> float:
+        """The normaliser of the task's loss for a batch of that many graphs and nodes: what the batch weighs in the mean over a
+        data-parallel step (parallel.dp_schedule).  A task that trains under train(group=...) says which one it divides by."""
+        raise NotImplementedError("the %s task does not say what its loss is normalised by (loss_weight): it cannot be trained "
+                                  "data-parallel" % type(self).__name__)
+
     def restore_from_metadata(self, metadata: Dict[str, Any]) -> None:
         pass

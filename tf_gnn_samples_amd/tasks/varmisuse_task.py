@@ -647,6 +647,9 @@ class VarMisuse_Task(Sparse_Graph_Task):
         if current:
             yield finalise(current)
 
+    def loss_weight(self, num_graphs: int, num_nodes: int) -> float:
+        return float(num_graphs)             # the loss is a mean over the batch's graphs (compute_task_metrics)
+
     def early_stopping_metric(self, task_metric_results: List[Dict[str, Any]], num_graphs: int) -> float:
         # :540-543: accuracy, negated (the loop minimises)
         return -(sum(float(m['num_correct_predictions']) for m in task_metric_results) / float(num_graphs))
