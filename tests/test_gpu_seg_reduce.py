@@ -53,7 +53,8 @@ def test_seg_reduce_matches_oracle_bit_exact(gpu_device, D, agg):
 
 
 def test_seg_reduce_unaligned_and_strided_input(gpu_device):
-    """D % 4 != 0 and a row stride larger than D take the scalar-lane kernel."""
+    """D % 4 != 0 takes the scalar-lane kernel, and so does a base that is not 16-byte aligned; a row stride larger than D
+    alone (stride 24, D = 16: still 16-byte aligned rows) stays on the vector kernel."""
     from tf_gnn_samples_amd import ops
     from tf_gnn_samples_amd.graph import RelGraph
     rng = np.random.default_rng(5)
@@ -67,6 +68,10 @@ def test_seg_reduce_unaligned_and_strided_input(gpu_device):
     view = wide[:, :16]  # stride 24, D = 16
     out = ops.seg_gather_reduce(view, g.plan_transformed(None), "sum").cpu().numpy()
     np.testing.assert_array_equal(out, _oracle_gather_reduce(wide.cpu().numpy()[:, :16].copy(), adj, V, L, "sum"))
+    view = wide[:, 1:17]  # stride 24, D = 16, base 4 bytes past a 16-byte boundary
+    assert view.data_ptr() % 16 != 0
+    out = ops.seg_gather_reduce(view, g.plan_transformed(None), "sum").cpu().numpy()
+    np.testing.assert_array_equal(out, _oracle_gather_reduce(wide.cpu().numpy()[:, 1:17].copy(), adj, V, L, "sum"))
 
 
 def test_empty_segments_and_no_messages(gpu_device):
