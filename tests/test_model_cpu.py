@@ -231,3 +231,46 @@ def test_split_plan_virtual_rows_cpu():
     v = sp.virtual_rowptr
     assert (v[1:] >= v[:-1]).all() and v[0] == 0 and v[-1] == rowptr[-1]
     assert int((v[1:] - v[:-1]).max()) <= 4096
+
+
+def test_late_fetch_hands_back_the_previous_item():
+    """readback.LateFetch alone: put() fetches the item before, flush() the last one; a fetch that raises leaves nothing pending."""
+    from tf_gnn_samples_amd.models.readback import LateFetch
+    fetched = []
+    late = LateFetch(lambda item: (fetched.append(item), "got %s" % item)[1])
+    assert late.put("item 0") is None and fetched == []
+    assert late.put("item 1") == "got item 0"
+    assert late.put("item 2") == "got item 1"
+    assert late.flush() == "got item 2" and late.flush() is None
+    assert fetched == ["item 0", "item 1", "item 2"]
+
+    def failing(item):
+        fetched.append(item)
+        raise RuntimeError(item)
+    late = LateFetch(failing)
+    late.put("item 3")
+    with pytest.raises(RuntimeError, match="item 3"):
+        late.put("item 4")
+    assert late.flush() is None and fetched[3:] == ["item 3"]          # item 4 was dropped unread, as by a loop that the exception ends
+
+
+def test_the_status_word_hand_off_without_a_gpu():
+    from tf_gnn_samples_amd import ops
+    nobody = torch.device("cuda", 63)               # (naming a device initialises nothing)
+    assert ops.handover_word_if_any(nobody) is None
+    assert ops.report_handover(0, nobody) is None
+    with pytest.raises(ops.HandoverError, match=r"gave up on an LDS hand-over \(status 0xc: product matrix wave product producer wave\): "
+                                                r"the results of that launch are wrong"):
+        ops.report_handover(12, nobody)
+    assert ops.handover_word_if_any(nobody) is None                    # still nothing allocated
+
+
+def test_the_driver_module_exports_the_moved_classes_themselves():
+    from tf_gnn_samples_amd.models import data_parallel, optimizer, readback, sparse_graph_model as sgm
+    assert sgm.TFStyleOptimizer is optimizer.TFStyleOptimizer and optimizer.TFStyleOptimizer.__module__ == optimizer.__name__
+    assert sgm.MetricsReadback is readback.MetricsReadback and readback.MetricsReadback.__module__ == readback.__name__
+    assert sgm._PredictionArena is readback._PredictionArena and readback._PredictionArena.__module__ == readback.__name__
+    assert sgm.CapturedTrainStep.__module__ == sgm.__name__ and sgm.Sparse_Graph_Model.__module__ == sgm.__name__
+    assert data_parallel._DataParallel.__module__ == data_parallel.__name__
+    import tf_gnn_samples_amd.graph as graph
+    assert sgm.as_rel_graph is graph.as_rel_graph

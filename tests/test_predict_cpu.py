@@ -314,3 +314,77 @@ def test_predict_iter_on_the_cpu_with_a_stand_in_forward(monkeypatch):
     first = stand_in(type("B", (), {"num_nodes": sum(len(g.node_features) for g in data[:2])})(), False)
     want = (first @ kernel + bias)[:len(data[0].node_features)]
     assert np.array_equal(everything[0]["labels"], ((want > 0) & (1 / (1 + torch.exp(-want.abs())) > 0.5)).numpy().astype(np.uint8))
+
+
+class _LoggedBatches:
+    """An iterator over `batches` that writes ("next", k) into `log` for its k-th next(), the exhausted one included."""
+
+    def __init__(self, batches, log):
+        self._it, self._log, self._k = iter(batches), log, 0
+
+    def __iter__(self):
+        return self
+
+    def __next__(self):
+        self._log.append(("next", self._k))
+        self._k += 1
+        return next(self._it)
+
+
+# what one pipelined pass over three batches does after it has asked for batch 0: the readback of step k - 1 is fetched only after
+# the request for batch k + 1, which follows the launch of step k
+PIPELINED_ORDER = [("step", 0), ("next", 1), ("step", 1), ("next", 2), ("fetch", 0), ("step", 2), ("next", 3), ("fetch", 1), ("fetch", 2)]
+
+
+def _cpu_model_with_logged_batches(monkeypatch, log):
+    from tf_gnn_samples_amd.models import RGCN_Model
+    from tf_gnn_samples_amd.tasks import DataFold, PPI_Task
+    task = PPI_Task(PPI_Task.default_params())
+    task.load_synthetic(5, 1, seed=2, mean_nodes=50, std_nodes=5, min_nodes=40, max_nodes=60)
+    p = RGCN_Model.default_params()
+    p.update(hidden_size=16, graph_num_layers=1, max_nodes_in_batch=125, native_batching=False)
+    model = RGCN_Model(p, task, device="cpu")
+    batches = model._batches
+    monkeypatch.setattr(model, "_batches", lambda data, fold: _LoggedBatches(batches(data, fold), log))
+    return model, task._loaded_data[DataFold.TRAIN]
+
+
+def _log_fetches(monkeypatch, cls, method, log):
+    inner, count = getattr(cls, method), [0]
+
+    def logged(self):
+        log.append(("fetch", count[0]))
+        count[0] += 1
+        return inner(self)
+    monkeypatch.setattr(cls, method, logged)
+
+
+def test_an_evaluation_epoch_fetches_a_step_only_after_the_next_batch_is_requested(monkeypatch):
+    from tf_gnn_samples_amd.models.sparse_graph_model import MetricsReadback
+    from tf_gnn_samples_amd.tasks import DataFold
+    log = []
+    model, data = _cpu_model_with_logged_batches(monkeypatch, log)
+
+    def stand_in(batch, training):
+        assert training is False
+        log.append(("step", sum(1 for e in log if e[0] == "step")))
+        return {"loss": torch.tensor(0.5), "num_nodes": batch.num_nodes}
+    monkeypatch.setattr(model, "forward_batch", stand_in)
+    _log_fetches(monkeypatch, MetricsReadback, "get", log)
+    loss, results, graphs = model._run_epoch("epoch 1 (validation)", data, DataFold.VALIDATION, quiet=True)[:3]
+    assert log == [("next", 0)] + PIPELINED_ORDER
+    assert loss == 0.5 and graphs == 5 and len(results) == 3
+
+
+def test_predict_iter_fetches_a_batch_only_after_the_next_one_is_requested(monkeypatch):
+    from tf_gnn_samples_amd.models.sparse_graph_model import _PredictionArena
+    log = []
+    model, data = _cpu_model_with_logged_batches(monkeypatch, log)
+
+    def stand_in(batch, training):
+        log.append(("step", sum(1 for e in log if e[0] == "step")))
+        return torch.randn((batch.num_nodes, 16), generator=torch.Generator().manual_seed(batch.num_nodes))
+    monkeypatch.setattr(model, "_final_node_states", stand_in)
+    _log_fetches(monkeypatch, _PredictionArena, "fetch", log)
+    assert sum(len(predictions) for _, predictions in model.predict_iter(data)) == 5
+    assert log == [("next", 0)] + PIPELINED_ORDER

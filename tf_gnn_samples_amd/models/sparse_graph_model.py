@@ -14,358 +14,22 @@ import os
 import pickle
 import time
 from abc import ABC, abstractmethod
+from contextlib import nullcontext
 from typing import Any, Dict, Iterable, List, Optional
 
 import numpy as np
 import torch
+import torch.distributed as dist
 
-from ..dense import dense
+from .. import ops
+from ..dense import capture_image_cache, dense_act, vouch_sole_consumer, weights_changed
 from ..graph import as_rel_graph, check_pending_graph_errors
 from ..tasks import DataFold, DeviceBatch, Sparse_Graph_Task
-from ..utils import apply_activation, get_activation, layer_norm, layer_norm_scope
+from ..utils import get_activation, layer_norm, layer_norm_scope
 from ..variables import VariableStore
-
-
-class TFStyleOptimizer:
-    """compute_gradients -> per-variable tf.clip_by_norm -> apply_gradients
-    (models/sparse_graph_model.py:227-260) with TF1 update rules [TF-internal]:
-      Adam    : lr_t = lr*sqrt(1-b2^t)/(1-b1^t); m,v EMA; var -= lr_t*m/(sqrt(v)+eps), eps=1e-8
-      RMSProp : ms = d*ms+(1-d)*g^2; mom = momentum*mom + lr*g/sqrt(ms+eps); var -= mom, eps=1e-10, ms0=1
-      SGD     : var -= lr*g
-    """
-
-    def __init__(self, params: List[torch.nn.Parameter], name: str, learning_rate: float, clamp_gradient_norm: float,
-                 decay: float = 0.98, momentum: float = 0.85):
-        self.params = [p for p in params if p.requires_grad]
-        self.name = name.lower()
-        if self.name not in ('sgd', 'rmsprop', 'adam'):
-            raise Exception('Unknown optimizer "%s".' % name)
-        self.lr, self.clip, self.decay, self.momentum = learning_rate, clamp_gradient_norm, decay, momentum
-        self.t = 0
-        if self.name == 'adam':
-            self.m = [torch.zeros_like(p) for p in self.params]
-            self.v = [torch.zeros_like(p) for p in self.params]
-        elif self.name == 'rmsprop':
-            self.ms = [torch.ones_like(p) for p in self.params]
-            self.mom = [torch.zeros_like(p) for p in self.params]
-
-    def _fused_update_available(self):
-        return len(self.params) > 0 and all(p.is_cuda for p in self.params)
-
-    @torch.no_grad()
-    def clip_and_step(self, lr_scale: float = 1.0, device_step_count: bool = False):
-        """clip_by_norm per variable + update.  On the GPU, for all three optimizers: two fused multi-tensor HIP launches per
-        48 variables (relgnn_mt_l2norm, then relgnn_mt_adam_clip / relgnn_mt_rmsprop_clip / relgnn_mt_sgd_clip) instead of the
-        ~15-30 elementwise kernels of clip_gradients() + step(), which stay as the un-fused restatement (and the CPU path).
-        device_step_count=True (hipGraph capture): the caller keeps self.t in step.  Adam's step count and lr_t then live in
-        device memory (relgnn_adam_step_size / relgnn_mt_adam_clip_devlr); RMSProp and SGD have no step-dependent factor:
-        their lr = self.lr * lr_scale is a launch scalar, frozen into a captured graph."""
-        if not self._fused_update_available():
-            if device_step_count:
-                raise RuntimeError("a captured training step needs the fused update: every parameter on the GPU")
-            self.clip_gradients()
-            self.step(lr_scale)
-            return
-        import ctypes
-        from .. import _lib
-        lib = _lib.load_library()
-        idx = [i for i, p in enumerate(self.params) if p.grad is not None]
-        if not idx:
-            return
-        b1, b2, eps = 0.9, 0.999, 1e-8
-        lr = self.lr * lr_scale
-        dev_state = None
-        if device_step_count and self.name == 'adam':
-            dev_state = self._device_state()
-            _lib.launch("relgnn_adam_step_size", _lib.ptr(dev_state), lr, b1, b2)
-        elif not device_step_count:
-            self.t += 1
-            lr_t = lr * (1 - b2 ** self.t) ** 0.5 / (1 - b1 ** self.t)
-        for c0 in range(0, len(idx), _lib.MT_MAX):
-            chunk = idx[c0:c0 + _lib.MT_MAX]
-            n = len(chunk)
-            grads = [self.params[i].grad if self.params[i].grad.is_contiguous() else self.params[i].grad.contiguous()
-                     for i in chunk]
-            arr = ctypes.c_void_p * n
-            h_g = arr(*[g.data_ptr() for g in grads])
-            h_p = arr(*[self.params[i].data_ptr() for i in chunk])
-            h_n = (ctypes.c_int64 * n)(*[self.params[i].numel() for i in chunk])
-            norms = torch.empty(n, dtype=torch.float32, device=self.params[chunk[0]].device)
-            ws_bytes = lib.relgnn_mt_l2norm_workspace_bytes()
-            ws = _lib.scratch(ws_bytes, norms.device)
-            _lib.launch("relgnn_mt_l2norm", h_g, h_n, n, _lib.ptr(norms), _lib.ptr(ws), ws_bytes)
-            h_s = [arr(*[t[i].data_ptr() for i in chunk]) for _, t in self._slots()]      # Adam: m, v; RMSProp: ms, mom; SGD: none
-            d_norms, clip = _lib.ptr(norms), float(self.clip)
-            if self.name == 'sgd':
-                _lib.launch("relgnn_mt_sgd_clip", h_p, h_g, h_n, n, d_norms, clip, lr)
-            elif self.name == 'rmsprop':
-                _lib.launch("relgnn_mt_rmsprop_clip", h_p, h_g, *h_s, h_n, n, d_norms, clip, lr, float(self.decay), float(self.momentum),
-                            1e-10)
-            elif dev_state is not None:
-                _lib.launch("relgnn_mt_adam_clip_devlr", h_p, h_g, *h_s, h_n, n, d_norms, clip, dev_state[1:].data_ptr(), b1, b2, eps)
-            else:
-                _lib.launch("relgnn_mt_adam_clip", h_p, h_g, *h_s, h_n, n, d_norms, clip, lr_t, b1, b2, eps)
-        from ..dense import weights_changed
-        weights_changed()                  # (written through raw pointers: the tensors' version counters did not move)
-
-    def _device_state(self):
-        """[steps taken, lr_t] in device memory, seeded from the host step count."""
-        if getattr(self, "_dev_state", None) is None:
-            self._dev_state = torch.tensor([float(self.t), 0.0], dtype=torch.float32, device=self.params[0].device)
-        return self._dev_state
-
-    def sync_device_step_count(self):
-        """Call before switching to device-side counting (the host count may have advanced since the last time)."""
-        if getattr(self, "_dev_state", None) is not None:
-            self._dev_state[0] = float(self.t)
-
-    @torch.no_grad()
-    def clip_gradients(self):
-        """tf.clip_by_norm per variable: g * clip / max(||g||, clip)."""
-        grads = [p.grad for p in self.params if p.grad is not None]
-        if not grads:
-            return
-        norms = torch.stack(torch._foreach_norm(grads))
-        scales = self.clip / torch.clamp(norms, min=self.clip)       # == 1 where ||g|| <= clip
-        torch._foreach_mul_(grads, list(scales.unbind(0)))
-
-    @torch.no_grad()
-    def step(self, lr_scale: float = 1.0):
-        ps = [p for p in self.params if p.grad is not None]
-        gs = [p.grad for p in ps]
-        if not ps:
-            return
-        lr = self.lr * lr_scale
-        self.t += 1
-        if self.name == 'sgd':
-            torch._foreach_add_(ps, gs, alpha=-lr)
-        elif self.name == 'adam':
-            b1, b2, eps = 0.9, 0.999, 1e-8
-            idx = [i for i, p in enumerate(self.params) if p.grad is not None]
-            m = [self.m[i] for i in idx]
-            v = [self.v[i] for i in idx]
-            torch._foreach_mul_(m, b1)
-            torch._foreach_add_(m, gs, alpha=1 - b1)
-            torch._foreach_mul_(v, b2)
-            torch._foreach_addcmul_(v, gs, gs, value=1 - b2)
-            lr_t = lr * (1 - b2 ** self.t) ** 0.5 / (1 - b1 ** self.t)
-            denom = torch._foreach_sqrt(v)
-            torch._foreach_add_(denom, eps)
-            torch._foreach_addcdiv_(ps, m, denom, value=-lr_t)
-        else:
-            eps = 1e-10
-            idx = [i for i, p in enumerate(self.params) if p.grad is not None]
-            ms = [self.ms[i] for i in idx]
-            mom = [self.mom[i] for i in idx]
-            torch._foreach_mul_(ms, self.decay)
-            torch._foreach_addcmul_(ms, gs, gs, value=1 - self.decay)
-            denom = torch._foreach_add(ms, eps)
-            torch._foreach_sqrt_(denom)
-            torch._foreach_mul_(mom, self.momentum)
-            torch._foreach_addcdiv_(mom, gs, denom, value=lr)
-            torch._foreach_sub_(ps, mom)
-
-    def zero_grad(self):
-        for p in self.params:
-            p.grad = None
-
-    # ---- optimizer state under TF's GLOBAL_VARIABLES names (the reference pickles those too, :91-107) ----
-    def _slots(self):
-        """(TF slot suffix, tensors) per optimizer [TF-internal slot names: Adam -> '<var>/Adam', '<var>/Adam_1';
-        RMSProp -> '<var>/RMSProp' (mean square), '<var>/RMSProp_1' (momentum)]."""
-        if self.name == 'adam':
-            return [("Adam", self.m), ("Adam_1", self.v)]
-        if self.name == 'rmsprop':
-            return [("RMSProp", self.ms), ("RMSProp_1", self.mom)]
-        return []
-
-    def tf_slot_weights(self, names: List[str]) -> Dict[str, np.ndarray]:
-        assert len(names) == len(self.params)
-        out = {}
-        for suffix, tensors in self._slots():
-            for n, t in zip(names, tensors):
-                out["%s/%s:0" % (n, suffix)] = t.detach().cpu().numpy().copy()
-        if self.name == 'adam':      # TF 1.13 keeps beta^(t+1) in two non-trainable scalars
-            out["beta1_power:0"] = np.float32(0.9 ** (self.t + 1))
-            out["beta2_power:0"] = np.float32(0.999 ** (self.t + 1))
-        return out
-
-    @torch.no_grad()
-    def load_tf_slots(self, weights, names: List[str]) -> set:
-        """Restore the slots a reference pickle carries; returns the consumed keys.  The step count is recovered from
-        beta1_power (= 0.9^(t+1))."""
-        used = set()
-        for suffix, tensors in self._slots():
-            for n, t in zip(names, tensors):
-                key = "%s/%s:0" % (n, suffix)
-                if key in weights:
-                    t.copy_(torch.as_tensor(np.asarray(weights[key]), dtype=torch.float32))
-                    used.add(key)
-        if self.name == 'adam' and "beta1_power:0" in weights:
-            self.t = self._steps_from_beta_powers(weights.get("beta1_power:0"), weights.get("beta2_power:0"))
-            used.update(k for k in ("beta1_power:0", "beta2_power:0") if k in weights)
-        return used
-
-    @staticmethod
-    def _steps_from_beta_powers(beta1_power, beta2_power) -> int:
-        """Step count t from TF's float32 scalars beta1_power = 0.9^(t+1), beta2_power = 0.999^(t+1).  0.9^(t+1) leaves the
-        normal float32 range after ~830 steps and is exactly 0.0 after ~985, so it identifies t only for short runs; past
-        that 0.999^(t+1) does (normal up to ~8.7e4 steps); when both have underflowed every bias correction is 1 to fp32
-        precision and any large t reproduces the update rule."""
-        import math
-        tiny = float(np.finfo(np.float32).tiny)
-        for power, beta in ((beta1_power, 0.9), (beta2_power, 0.999)):
-            if power is None:
-                continue
-            p = float(np.asarray(power).reshape(-1)[0])
-            if math.isfinite(p) and tiny <= p < 1.0:
-                return max(0, int(round(math.log(p) / math.log(beta))) - 1)
-            if p >= 1.0:
-                return 0
-        return 10 ** 6
-
-
-class MetricsReadback:
-    """The metric scalars of ONE step on their way to the host: packed into one device vector and copied into pinned
-    memory by an asynchronous D2H enqueued right behind the step's own kernels.  get() waits for THAT copy only.
-
-    float(tensor) / .item() is a stream-ordered copy on the current stream: called one step late it still waits for
-    everything enqueued since — the whole NEXT step — and the GPU then idles until the host has come back and enqueued
-    new work (measured: a ~0.2 ms bubble per 2.9 ms C2 step).  The reference has the same round trip once per
-    sess.run (models/sparse_graph_model.py:293)."""
-    _ring: Dict[Any, list] = {}
-
-    def __init__(self, metrics: Dict[str, Any]):
-        self._host_values = {k: v for k, v in metrics.items() if not (torch.is_tensor(v) and v.is_cuda)}
-        dev = [(k, v.detach()) for k, v in metrics.items() if torch.is_tensor(v) and v.is_cuda]
-        self._names = [k for k, _ in dev]
-        self._event = self._slot = None
-        self._status_at = None
-        if dev:
-            device = dev[0][1].device
-            # one small kernel when the metrics share a dtype (the usual case: fp32 scalars), converted only if they differ
-            dtype = dev[0][1].dtype if all(v.dtype == dev[0][1].dtype for _, v in dev) else torch.float64
-            parts = [v.reshape(()) if v.dtype == dtype else v.reshape(()).to(dtype) for _, v in dev]
-            # The hand-over status word of the device (ops.handover_word: a wave-role product kernel that gave up on an LDS
-            # hand-over has written wrong numbers and says so there) rides in the same copy: its int32 bits as one more fp32
-            # entry of the packed vector (a view, no launch of its own); get() raises when it is not zero.
-            from .. import ops as _ops
-            word = _ops._HANDOVER_WORDS.get(device.index)
-            if word is not None:
-                if dtype == torch.float32:
-                    parts.append(word[0].view(torch.float32))
-                else:
-                    parts.append(word[0].to(dtype))
-                self._status_at = len(dev)
-            packed = torch.stack(parts)
-            ring = MetricsReadback._ring.setdefault((device, len(parts), dtype), [])
-            # a pinned slot is taken until its reader has consumed it (get()) or dropped it
-            slot = next((b for b in ring if not b[1]), None)
-            if slot is None:
-                slot = [torch.empty(len(parts), dtype=dtype).pin_memory(), False]
-                ring.append(slot)
-            slot[1] = True
-            slot[0].copy_(packed, non_blocking=True)
-            self._event = torch.cuda.Event()
-            self._event.record(torch.cuda.current_stream(device))
-            self._slot = slot
-            self._device = device
-
-    def get(self) -> Dict[str, float]:
-        out = {k: (float(v) if torch.is_tensor(v) else v) for k, v in self._host_values.items()}
-        if self._event is not None:
-            self._event.synchronize()
-            host = self._slot[0]
-            status = 0
-            if self._status_at is not None:
-                status = (int(host[self._status_at:self._status_at + 1].view(torch.int32)[0]) if host.dtype == torch.float32
-                          else int(host[self._status_at]))
-            out.update(zip(self._names, host.tolist()))
-            self._event = None
-            self._slot[1] = False
-            self._values = {k: out[k] for k in self._names}
-            if status:
-                from .. import ops as _ops
-                _ops._HANDOVER_WORDS[self._device.index][0].zero_()      # reported once; later steps start clean
-                _ops.raise_on_handover(status)
-        elif self._names:
-            out.update(self._values)
-        return out
-
-    def __del__(self):
-        slot = getattr(self, "_slot", None)
-        if slot is not None and getattr(self, "_event", None) is not None:
-            try:
-                self._event.synchronize()          # the copy must not land in a slot somebody else has taken
-            except Exception:
-                pass
-            slot[1] = False
-
-
-class _PredictionArena:
-    """The outputs of ONE batch's predictions as one packed byte arena: `views` are typed tensors over slices of it (16-byte
-    aligned), which the prediction kernels write in place; send() enqueues the single copy to the host right behind them, with
-    the device's hand-over status word (ops.handover_word) in the arena's last four bytes; fetch() waits for THAT copy only and
-    returns NumPy arrays of the host's own (the pinned arena goes back into its turn)."""
-
-    def __init__(self, layout: Dict[str, Any], device, pinned: list, turn: int):
-        self._layout, self._offsets, used = layout, {}, 0
-        for key, (shape, dtype) in layout.items():
-            used = (used + 15) // 16 * 16
-            self._offsets[key] = used
-            used += int(np.prod(shape, dtype=np.int64)) * torch.empty((), dtype=dtype).element_size()
-        self._status_at = (used + 3) // 4 * 4
-        self._nbytes = self._status_at + 4
-        self._device, self._pinned, self._turn, self._event = device, pinned, turn, None
-        self.buf = torch.empty(self._nbytes, dtype=torch.uint8, device=device)
-        self.views = {key: self._view(self.buf, key) for key in layout}
-
-    def _view(self, buf, key):
-        shape, dtype = self._layout[key]
-        nbytes = int(np.prod(shape, dtype=np.int64)) * torch.empty((), dtype=dtype).element_size()
-        off = self._offsets[key]
-        return buf[off:off + nbytes].view(dtype).view(shape)
-
-    def send(self, outputs: Dict[str, torch.Tensor]):
-        for key, view in self.views.items():
-            t = outputs[key]
-            if t.data_ptr() != view.data_ptr() or tuple(t.shape) != tuple(view.shape):      # (a hook that made a tensor of its own)
-                view.copy_(t)
-        if self._device.type != "cuda":
-            self._host = self.buf
-            return
-        from .. import ops as _ops
-        word = _ops._HANDOVER_WORDS.get(self._device.index)
-        status = self.buf[self._status_at:].view(torch.int32)
-        if word is not None:
-            status.copy_(word[0:1])
-        else:
-            status.zero_()
-        host = self._pinned[self._turn]
-        if host is None or host.numel() < self._nbytes:
-            host = self._pinned[self._turn] = torch.empty(self._nbytes, dtype=torch.uint8).pin_memory()
-        self._host = host[:self._nbytes]
-        self._host.copy_(self.buf, non_blocking=True)
-        self._event = torch.cuda.Event()
-        self._event.record(torch.cuda.current_stream(self._device))
-
-    def fetch(self) -> Dict[str, np.ndarray]:
-        if self._event is not None:
-            self._event.synchronize()
-            self._event = None
-            status = int(self._host[self._status_at:].view(torch.int32)[0])
-            if status:
-                from .. import ops as _ops
-                _ops._HANDOVER_WORDS[self._device.index][0].zero_()      # reported once, as a metric fetch does
-                _ops.raise_on_handover(status)
-        own = self._host.numpy().copy()                                  # one host copy out of the pinned arena; the pieces are its views
-        out = {}
-        for key, (shape, dtype) in self._layout.items():
-            nbytes = int(np.prod(shape, dtype=np.int64)) * torch.empty((), dtype=dtype).element_size()
-            off = self._offsets[key]
-            out[key] = own[off:off + nbytes].view(torch.empty((), dtype=dtype).numpy().dtype).reshape(shape)
-        self.buf = self.views = None
-        return out
+from .data_parallel import data_parallel
+from .optimizer import TFStyleOptimizer
+from .readback import EpochTally, LateFetch, MetricsReadback, _PredictionArena
 
 
 class CapturedTrainStep:
@@ -388,7 +52,6 @@ class CapturedTrainStep:
         if opt.t != self._expected_t:
             opt.sync_device_step_count()
         self.graph.replay()
-        from ..dense import weights_changed
         weights_changed()                  # the replayed update rewrote the parameters: limb images kept by eager code are stale
         opt.t += 1
         self._expected_t = opt.t
@@ -397,8 +60,7 @@ class CapturedTrainStep:
     def handover_status(self) -> int:
         """The device's hand-over status word (ops.handover_status: synchronises).  A replay loop that reads the metric tensors
         itself instead of going through MetricsReadback checks this where it syncs anyway."""
-        from .. import ops as _ops
-        return _ops.handover_status(device=self.model.device)
+        return ops.handover_status(device=self.model.device)
 
 
 class Sparse_Graph_Model(ABC):
@@ -443,21 +105,17 @@ class Sparse_Graph_Model(ABC):
         self.training = False
         # under a process group only rank 0 logs (the drivers form the group before they build the model; train(group=...) /
         # test(group=...) go by the rank within THEIR group)
-        import torch.distributed as _dist
-        self._log_rank = _dist.get_rank() if _dist.is_available() and _dist.is_initialized() else 0
+        self._log_rank = dist.get_rank() if dist.is_available() and dist.is_initialized() else 0
         torch.manual_seed(params['random_seed'])
         np.random.seed(params['random_seed'])
         if self.device.type == "cuda":
             # the hand-over status block of this device (ops.handover_word): exists before any step can be captured into a hipGraph;
             # read back with every step's metrics (MetricsReadback) and by handover_status()
-            from .. import ops as _ops
-            self.handover_word = _ops.handover_word(self.device)
+            self.handover_word = ops.handover_word(self.device)
             # the state block of the fused layer-input dropout (ops.dropout): {seed, replica, step} in HBM, next to the hand-over
             # word for the same reason (a captured step needs a live pointer).  replica = the data-parallel rank (the drivers form
             # their process group before they build the model), so that ranks do not share masks
-            import torch.distributed as dist
-            rank = dist.get_rank() if dist.is_available() and dist.is_initialized() else 0
-            self.dropout_state = _ops.dropout_state(self.device, params['random_seed'], rank, 0)
+            self.dropout_state = ops.dropout_state(self.device, params['random_seed'], self._log_rank, 0)
         self.variables = VariableStore(seed=params['random_seed'])
         self.__make_model()
         self.variables.to(self.device)
@@ -503,7 +161,6 @@ class Sparse_Graph_Model(ABC):
         (= keep the initial value of) the ones it does not, report saved entries nothing consumed."""
         used = self.variables.load_tf_weights(weights, report_unused=False)
         used |= self.optimizer.load_tf_slots(weights, self._trainable_names())
-        from ..dense import weights_changed
         weights_changed()                  # (copy_ moves the version counters too; said once more for limb images kept per step)
         for var_name in weights:
             if var_name not in used:
@@ -564,9 +221,7 @@ class Sparse_Graph_Model(ABC):
         num_nodes = initial_node_features.shape[0]
         # bucketed once, shared by every layer; the index range check is read back at the next fetch
         graph = as_rel_graph(adjacency_lists, num_nodes, validate="deferred")
-        from ..dense import dense_act, vouch_sole_consumer
-        from ..ops import activation_id, dropout as fused_dropout, dropout_residual, dropout_tensor_ok, fused_dropout_on
-        act_id = activation_id(p['graph_model_activation_function'])
+        act_id = ops.activation_id(p['graph_model_activation_function'])
         num_layers, res_every = p['graph_num_layers'], p['graph_residual_connection_every_num_layers']
 
         def only_the_next_layer_reads(next_layer_idx: int) -> bool:
@@ -588,20 +243,20 @@ class Sparse_Graph_Model(ABC):
             cur_node_representations = initial_node_features
         last_residual_representations = None          # (the reference's zeros_like is overwritten at layer 0 before any use)
         pass_state = None
-        if fused_dropout_on(dropout_keep_prob) and getattr(self, "dropout_state", None) is not None:
+        if ops.fused_dropout_on(dropout_keep_prob) and getattr(self, "dropout_state", None) is not None:
             with torch.no_grad():
                 self.dropout_state[2].add_(1)                  # on the device, stream-ordered: every replay of a captured step advances it
                 pass_state = self.dropout_state.clone()        # this pass's 24 bytes: read by its forward kernels and by its backward
         for layer_idx in range(p['graph_num_layers']):
             self._layer_weights = w.scope('gnn_layer_%i' % layer_idx)
             residual_step = layer_idx % res_every == 0
-            if pass_state is not None and dropout_tensor_ok(cur_node_representations):
+            if pass_state is not None and ops.dropout_tensor_ok(cur_node_representations):
                 # csrc/dropout.hip: one kernel for the whole layer-input stage; the layer index is the Philox stream
                 if residual_step and layer_idx > 0:
-                    last_residual_representations, cur_node_representations = dropout_residual(
+                    last_residual_representations, cur_node_representations = ops.dropout_residual(
                         cur_node_representations, last_residual_representations, dropout_keep_prob, pass_state, layer_idx)
                 else:
-                    cur_node_representations = fused_dropout(cur_node_representations, dropout_keep_prob, pass_state, layer_idx)
+                    cur_node_representations = ops.dropout(cur_node_representations, dropout_keep_prob, pass_state, layer_idx)
                     if residual_step:
                         last_residual_representations = cur_node_representations
             else:
@@ -667,12 +322,11 @@ class Sparse_Graph_Model(ABC):
         The learning rate of a captured RMSProp or SGD step is a launch scalar.  With lr_for_num_graphs_per_batch set it is
         learning_rate * num_graphs / lr_for_num_graphs_per_batch of THIS batch: constant for the fixed batch, so freezing it
         into the graph is correct (Adam's lr_t changes per step and is computed on the device instead)."""
-        from ..graph import as_rel_graph as _as_graph
         if self.device.type != "cuda":
             raise RuntimeError("capture_train_step needs a model on the GPU (a hipGraph records GPU work)")
         batch.wait_ready()
         if getattr(batch, "graph", None) is None:           # the bucketing is part of the fixed batch, not of the step
-            batch.graph = _as_graph(batch.adjacency_lists, batch.num_nodes, validate=True)
+            batch.graph = as_rel_graph(batch.adjacency_lists, batch.num_nodes, validate=True)
         opt = self.optimizer
         opt.sync_device_step_count()
         cur = torch.cuda.current_stream(self.device)
@@ -685,7 +339,6 @@ class Sparse_Graph_Model(ABC):
         cur.wait_stream(side)
         graph = torch.cuda.CUDAGraph()
         opt.zero_grad()
-        from ..dense import capture_image_cache
         with capture_image_cache(), torch.cuda.graph(graph):      # (limb images of the weights: split once per captured step)
             metrics = self.train_step(batch, device_step_count=True)
         return CapturedTrainStep(self, graph, {k: v for k, v in metrics.items() if torch.is_tensor(v)}, batch)
@@ -704,8 +357,6 @@ class Sparse_Graph_Model(ABC):
             pre_backward()
         # one process drives one GPU: running the backward on the calling thread instead of the autograd engine's
         # device thread saves the hand-off per node (host enqueue 1.56 -> 1.29 ms per C2 step) and a busy CPU thread
-        from .. import ops
-        from contextlib import nullcontext
         # (the weight gradients of the aggregate-first layers run on a side stream; nothing reads them before the reduction / the
         #  optimizer, so their joins move behind the whole backward — not with a reducer that packs gradients from hooks DURING it)
         # (measured on the C2 step, alternated three times: 1.812 / 1.812 / 1.814 ms with the joins per layer, 1.804 / 1.806 / 1.806 deferred)
@@ -779,31 +430,10 @@ class Sparse_Graph_Model(ABC):
 
     def _run_epoch(self, epoch_name: str, data: Iterable[Any], data_fold: DataFold, quiet: bool = False):
         """__run_epoch, :263-311: returns (avg loss, task metric results, graphs, graphs/s, nodes/s, edges/s)."""
-        batch_iterator = self._batches(data, data_fold)
-        start_time = time.time()
-        processed_graphs = processed_nodes = processed_edges = 0
-        epoch_loss = 0.0
-        task_metric_results = []
-        batch_iterator = iter(batch_iterator)
+        batch_iterator = iter(self._batches(data, data_fold))
+        tally = EpochTally(epoch_name, quiet)
+        late = LateFetch(tally.fetch)
         upcoming = next(batch_iterator, None)
-        state = {"graphs": 0, "nodes": 0, "edges": 0, "loss": 0.0, "step": 0}
-
-        def fetch(pending):
-            """Read one step's metrics back (the host sync of sess.run's fetch, :293)."""
-            m, mb = pending
-            m = m.get()
-            check_pending_graph_errors()
-            state["graphs"] += mb.num_graphs
-            state["nodes"] += mb.num_nodes
-            state["edges"] += mb.num_edges
-            state["loss"] += m['loss'] * mb.num_graphs
-            task_metric_results.append(m)
-            if not quiet:
-                print("Running %s, batch %i (has %i graphs). Loss so far: %.4f"
-                      % (epoch_name, state["step"], mb.num_graphs, state["loss"] / state["graphs"]), end='\r')
-            state["step"] += 1
-
-        pending = None
         while upcoming is not None:
             mb = upcoming
             batch = mb if isinstance(mb, DeviceBatch) else DeviceBatch(mb, self.device)
@@ -812,31 +442,19 @@ class Sparse_Graph_Model(ABC):
             else:
                 with torch.no_grad():
                     m = self.forward_batch(batch, training=False)
-            # Pipeline: the step's metrics start their way to pinned host memory right behind the step (MetricsReadback);
-            # ask for the next batch (its upload / assembly run on a side stream under this step's kernels), THEN read
-            # the metrics of the PREVIOUS step: that wait is for the previous step's copy only, which the GPU has passed
-            # long ago, so the device never idles behind a host round trip.  Every step's metrics are still fetched, one
-            # step late.
+            # (the order of readback.LateFetch: every step's metrics are fetched, one step late, after the next batch is requested)
             readback = MetricsReadback(m)          # (also drops the autograd graph: values are detached)
             upcoming = next(batch_iterator, None)
-            if pending is not None:
-                fetch(pending)
-            pending = (readback, mb)
-        if pending is not None:
-            fetch(pending)
-        processed_graphs, processed_nodes, processed_edges = state["graphs"], state["nodes"], state["edges"]
-        epoch_loss = state["loss"]
-        epoch_time = time.time() - start_time
-        per_graph_loss = epoch_loss / max(processed_graphs, 1)
-        return (per_graph_loss, task_metric_results, processed_graphs, processed_graphs / epoch_time,
-                processed_nodes / epoch_time, processed_edges / epoch_time)
+            late.put((readback, mb))
+        late.flush()
+        return tally.result()
 
     def train(self, quiet: bool = False, max_epochs: Optional[int] = None, group=None):
         """:318-371 without TensorBoard: early stopping on the task's validation metric.
         group: a torch.distributed process group of W > 1 ranks (one process per GPU, the model built after init_distributed())
-        trains data-parallel by graph (_DataParallel below); None or a group of one rank is the single-GPU loop."""
+        trains data-parallel by graph (data_parallel.py); None or a group of one rank is the single-GPU loop."""
         total_time_start = time.time()
-        dp = self._data_parallel(group)
+        dp = data_parallel(self, group)
         train_data = self.task._loaded_data[DataFold.TRAIN]
         valid_data = self.task._loaded_data[DataFold.VALIDATION]
         # The loaded folds are millions of long-lived Python objects: frozen for the duration of the loop they cost the cyclic
@@ -891,7 +509,8 @@ class Sparse_Graph_Model(ABC):
         The forward runs under torch.no_grad() with training=False over self._batches(data, DataFold.TEST): whichever input pipeline
         the model's parameters select.  A batch's outputs are written into ONE packed device arena (the task's kernels write their
         slices in place) that leaves the device as one asynchronous copy into pinned memory, and are read one batch late, as
-        _run_epoch reads metrics: batch i is yielded once batch i + 1 is enqueued; two pinned arenas exist at most.  The fetch
+        _run_epoch reads metrics (readback.LateFetch): batch i is yielded once batch i + 1 is enqueued and batch i + 2 requested; two
+        pinned arenas exist at most.  The fetch
         reports what a metric fetch reports: check_pending_graph_errors() and the hand-over status word (ops.HandoverError): the
         predictions of a product kernel that gave up are never handed out.
 
@@ -908,11 +527,14 @@ class Sparse_Graph_Model(ABC):
             self._prediction_pinned = pinned
 
     def _predict_batches(self, data, return_states, pinned):
-        cursor, pending, turn = 0, None, 0
-        for mb in self._batches(data, DataFold.TEST):
+        cursor, turn = 0, 0
+        late = LateFetch(self._fetch_predictions)
+        batch_iterator = iter(self._batches(data, DataFold.TEST))
+        upcoming = next(batch_iterator, None)
+        while upcoming is not None:
             with torch.no_grad():      # (around the device work only: a generator suspended inside it would leave the grad mode of
                 #                         the CONSUMER's code switched off between two batches)
-                batch = mb if isinstance(mb, DeviceBatch) else DeviceBatch(mb, self.device)
+                batch = upcoming if isinstance(upcoming, DeviceBatch) else DeviceBatch(upcoming, self.device)
                 samples = data[cursor:cursor + batch.num_graphs]
                 cursor += batch.num_graphs
                 final = self._final_node_states(batch, training=False)
@@ -925,13 +547,16 @@ class Sparse_Graph_Model(ABC):
                 if return_states:
                     outputs = dict(outputs, node_states=final)
                 arena.send(outputs)
-            if pending is not None:
-                yield self._fetch_predictions(*pending)
-            pending = (arena, batch, samples)
-        if pending is not None:
-            yield self._fetch_predictions(*pending)
+            upcoming = next(batch_iterator, None)          # (the order of readback.LateFetch: requested before the previous batch is read)
+            fetched = late.put((arena, batch, samples))
+            if fetched is not None:
+                yield fetched
+        fetched = late.flush()
+        if fetched is not None:
+            yield fetched
 
-    def _fetch_predictions(self, arena, batch, samples):
+    def _fetch_predictions(self, pending):
+        arena, batch, samples = pending
         host = arena.fetch()
         check_pending_graph_errors()
         return samples, self.task.split_predictions(host, batch, samples)
@@ -948,7 +573,7 @@ class Sparse_Graph_Model(ABC):
     def test(self, data, quiet: bool = False, group=None):
         """Loss and task metrics of `data`.  group: as in train(); every rank passes the SAME data, evaluates its shard of it, and
         rank 0 logs the metrics of the whole."""
-        dp = self._data_parallel(group)
+        dp = data_parallel(self, group)
         if dp is None:
             loss, res, n, gs, ns, es = self._run_epoch("Test", list(data), DataFold.TEST, quiet)
         else:
@@ -958,169 +583,3 @@ class Sparse_Graph_Model(ABC):
                 dp.end()
         self.log_line("Loss %.5f on %i graphs" % (loss, n))
         self.log_line("Metrics: %s" % self.task.pretty_print_epoch_task_metrics(res, n))
-
-    # -------------------- Data parallelism by graph (train(group=...), test(group=...)) --------------------
-    def _data_parallel(self, group):
-        """None for the single-GPU loop (no group, or a group of one rank: nothing below runs, no collective is issued); otherwise
-        the driver of data-parallel epochs, after the refusals."""
-        if group is None:
-            return None
-        import torch.distributed as dist
-        if dist.get_world_size(group) == 1:
-            return None
-        from .. import config
-        world = dist.get_world_size(group)
-        self.task.loss_weight(1, 1)        # a task that cannot be split by graph (citation), or does not say how its loss is normalised, raises
-        if self.device.type != "cuda":
-            raise RuntimeError("train(group=...) / test(group=...) need the model on the GPU (one process per GPU; the gradient pack is a "
-                               "HIP kernel): this model is on %s" % self.device)
-        if not self.params.get('native_batching', True) or not hasattr(self.task, "make_graph_store"):
-            raise RuntimeError("data-parallel training uses the native input pipelines only: %s"
-                               % ("native_batching is false" if not self.params.get('native_batching', True)
-                                  else "the %s task has no make_graph_store" % type(self.task).__name__))
-        if config.settings.allreduce == "overlap":
-            raise RuntimeError("allreduce=overlap: the bucketed all-reduce (OverlappedGradientAllReducer) is not wired into train(); "
-                               "train(group=...) runs the flat packed form only and does not fall back to it silently: set allreduce=flat")
-        return _DataParallel(self, group, world)
-
-
-class _DataParallel:
-    """Epochs of Sparse_Graph_Model.train(group=...) / test(group=...) on one rank of W (parallel.py has the host-side pieces;
-    DESIGN.md section 8 the protocol).
-
-    The shard of a fold is fixed for the run (parallel.dp_shard); the rank's pipeline is built over its shard only.  Per epoch and
-    fold: shuffle (training; parallel.dp_epoch_rng), plan the local batches, exchange the plans (one all-gather, one host read).
-    A training epoch then runs max_r(batches_r) steps on EVERY rank.  With a batch: train_step whose grad_hook is the packed
-    reducer with this rank's scale and whose learning rate goes by the step's global graph count.  Without one: zeros into the
-    same collective, the same clip and update.  Evaluation epochs run the local batches without a gradient collective.  At the
-    end of every epoch the per-batch metrics and the counters are gathered in rank order."""
-
-    def __init__(self, model: Sparse_Graph_Model, group, world: int):
-        import torch.distributed as dist
-        self.model, self.group, self.world = model, group, world
-        self.rank = dist.get_rank(group)
-        self.epoch = 0
-        # collectives of small tables: device tensors under nccl, host tensors under gloo
-        self.comm_device = model.device if dist.get_backend(group) == "nccl" else torch.device("cpu")
-        self.reducer = None
-        self._saved_log_rank, model._log_rank = model._log_rank, self.rank
-
-    def end(self):
-        self.model._log_rank = self._saved_log_rank
-
-    def barrier(self):
-        import torch.distributed as dist
-        dist.barrier(group=self.group)
-
-    def begin_training(self):
-        """Rank 0's parameters, optimizer slots and step count everywhere (a restore()d model on rank 0 included); then torch's
-        generator of this device reseeded from (random_seed, rank): the torch dropout route must not share masks across ranks (the
-        fused route's state block already carries the rank as its replica)."""
-        import torch.distributed as dist
-        from ..dense import weights_changed
-        from ..parallel import PackedGradientAllReducer, dp_device_seed
-        model, opt = self.model, self.model.optimizer
-        src = dist.get_global_rank(self.group, 0)
-        with torch.no_grad():
-            for name in model.variables.names():             # (created in the same order on every rank)
-                dist.broadcast(model.variables[name].data, src=src, group=self.group)
-            for _, slots in opt._slots():
-                for t in slots:
-                    dist.broadcast(t, src=src, group=self.group)
-            t_step = torch.tensor([opt.t], dtype=torch.int64, device=self.comm_device)
-            dist.broadcast(t_step, src=src, group=self.group)
-            opt.t = int(t_step.item())
-        opt.sync_device_step_count()
-        weights_changed()
-        torch.cuda.default_generators[model.device.index if model.device.index is not None
-                                      else torch.cuda.current_device()].manual_seed(dp_device_seed(model.params['random_seed'], self.rank))
-        self.reducer = PackedGradientAllReducer(opt.params, group=self.group)
-
-    def _pipeline(self, data):
-        """(the rank's input pipeline over its shard of `data`, or None for an empty shard; the largest shard's graph count)."""
-        model = self.model
-        folds = model.__dict__.setdefault("_dp_folds", {})
-        key = (id(data), len(data), self.world, self.rank)
-        kept = folds.get(key)
-        if kept is None or kept[0] is not data:
-            from ..parallel import dp_shard
-            shards = dp_shard(data, self.world)
-            kept = folds[key] = (data, [data[i] for i in shards[self.rank]], max(len(s) for s in shards))
-            while len(folds) > 3:      # train + validation folds and one more, like the pipelines themselves
-                folds.pop(next(iter(folds)))
-        _, mine, largest = kept
-        return (model._native_pipeline(mine) if mine else None), largest
-
-    def run_epoch(self, epoch_name: str, data, data_fold: DataFold, quiet: bool = False):
-        """_run_epoch across the group: the same six results on every rank, over the whole fold."""
-        from ..parallel import dp_epoch_rng, dp_exchange_plans, dp_merge_epoch, dp_plan_epoch, dp_schedule
-        model, task = self.model, self.model.task
-        train = data_fold == DataFold.TRAIN
-        max_nodes = model.params['max_nodes_in_batch']
-        seed = model.params['random_seed']
-        pipeline, largest_shard = self._pipeline(data)
-        plan = dp_plan_epoch(pipeline.store if pipeline is not None else None, train, max_nodes,
-                             dp_epoch_rng(seed, self.epoch, self.rank))
-        plans = dp_exchange_plans(plan, largest_shard, self.group, self.comm_device)
-        local_steps = len(plan.batches)
-        if train:
-            if self.reducer is None:
-                raise RuntimeError("a data-parallel training epoch outside train(group=...)")
-            schedule = dp_schedule([[(task.loss_weight(g, n), g) for g, n in p] for p in plans])
-            steps = schedule.steps
-        else:
-            schedule, steps = None, local_steps
-        batch_iterator = iter(()) if pipeline is None else iter(task.make_native_minibatch_iterator(
-            pipeline, data_fold, max_nodes, rng=dp_epoch_rng(seed, self.epoch, self.rank)))
-        start_time = time.time()
-        task_metric_results = []
-        state = {"graphs": 0, "nodes": 0, "edges": 0, "loss": 0.0, "step": 0}
-
-        def fetch(pending):
-            m, mb = pending
-            m = m.get()
-            check_pending_graph_errors()
-            state["graphs"] += mb.num_graphs
-            state["nodes"] += mb.num_nodes
-            state["edges"] += mb.num_edges
-            state["loss"] += m['loss'] * mb.num_graphs
-            task_metric_results.append(m)
-            if not quiet and self.rank == 0:
-                print("Running %s, batch %i (has %i graphs on rank 0). Loss so far: %.4f"
-                      % (epoch_name, state["step"], mb.num_graphs, state["loss"] / state["graphs"]), end='\r')
-            state["step"] += 1
-
-        pending = None
-        upcoming = next(batch_iterator, None)
-        for k in range(steps):
-            if k < local_steps:
-                batch = upcoming
-                if batch is None or (batch.num_graphs, batch.num_nodes) != (int(plan.graphs[k]), int(plan.nodes[k])):
-                    raise RuntimeError("%s, step %d: the input pipeline did not assemble the planned batch" % (epoch_name, k))
-                if train:
-                    scale = float(schedule.scales[self.rank, k])
-                    m = model.train_step(batch, grad_hook=lambda params, s=scale: self.reducer(s),
-                                         lr_num_graphs=int(schedule.graph_sums[k]))
-                else:
-                    with torch.no_grad():
-                        m = model.forward_batch(batch, training=False)
-                readback = MetricsReadback(m)
-                upcoming = next(batch_iterator, None)      # (the same pipelining as _run_epoch: metrics are read one step late)
-                if pending is not None:
-                    fetch(pending)
-                pending = (readback, batch)
-            else:
-                # no batch left on this rank: zeros into the step's collective, the same clip and update as everyone else
-                # (parameters, optimizer slots and the step count stay identical across the ranks)
-                model.optimizer.zero_grad()
-                self.reducer(0.0)
-                model.optimizer.clip_and_step(model._lr_scale(int(schedule.graph_sums[k])))
-        if upcoming is not None:
-            raise RuntimeError("%s: the input pipeline holds more batches than planned" % epoch_name)
-        if pending is not None:
-            fetch(pending)
-        merged, (loss_sum, graphs, nodes, edges) = dp_merge_epoch(
-            task_metric_results, (state["loss"], state["graphs"], state["nodes"], state["edges"]), self.group)
-        epoch_time = time.time() - start_time
-        graphs, nodes, edges = int(graphs), int(nodes), int(edges)
-        return (loss_sum / max(graphs, 1), merged, graphs, graphs / epoch_time, nodes / epoch_time, edges / epoch_time)

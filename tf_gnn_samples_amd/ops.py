@@ -982,9 +982,10 @@ def handover_word(device=None) -> torch.Tensor:
 
 
 def handover_status(reset: bool = True, device=None) -> int:
-    """Word 0 of handover_word(device): 0 = every poll of every launch so far completed.  Synchronises: a training / evaluation
-    loop does not call this — it reads the word with every step's metrics copy (models.sparse_graph_model.MetricsReadback) and
-    raises there; this is for code that launches the kernels directly (tests, scripts, smoke())."""
+    """Word 0 of handover_word(device): 0 = every poll of every launch so far completed.  Waits for the current stream (.item() is a
+    stream-ordered copy), not for the device: a training / evaluation loop does not call this — it reads the word with every step's
+    metrics copy (models.readback.MetricsReadback) and raises there; this is for code that launches the kernels directly (tests,
+    scripts, smoke())."""
     w = handover_word(device)
     v = int(w[0].item())
     if reset and v:
@@ -1003,6 +1004,22 @@ def raise_on_handover(value: int):
             "step since the last clean check is suspect" % (
                 value, " fused-layer matrix wave" if value & 1 else "", " fused-layer gather wave" if value & 2 else "",
                 " product matrix wave" if value & 4 else "", " product producer wave" if value & 8 else ""))
+
+
+def handover_word_if_any(device) -> Optional[torch.Tensor]:
+    """The hand-over status block of `device` if somebody has allocated one (handover_word), else None; allocates nothing.  For a
+    readback that carries the word to the host with a copy of its own (models/readback.py)."""
+    return _HANDOVER_WORDS.get(torch.device(device).index)
+
+
+def report_handover(value: int, device):
+    """`value`: word 0 of `device`'s status block as read on the host, by whatever copy brought it there.  Not zero: raises
+    HandoverError after zeroing the device's word — reported once; later steps start clean."""
+    if value:
+        word = handover_word_if_any(device)
+        if word is not None:
+            word[0].zero_()
+        raise_on_handover(value)
 
 
 def _fused_layer_ok(H, graph, w, kernels) -> bool:
