@@ -67,22 +67,22 @@ def test_which_products_take_the_wave_role_kernel(mode, kind, n, k, act, expect)
 def test_a_backward_that_raises_leaves_no_deferred_join_state_behind():
     """ops.deferred_weight_gradient_join: when the backward inside it raises, nobody calls join_deferred() for that pass — the
     context forgets the pass itself, so that the next step's join does not verify (or keep alive) this step's parameters."""
-    from tf_gnn_samples_amd import ops
+    from tf_gnn_samples_amd import ops, weight_grad_stream
     p = torch.nn.Parameter(torch.zeros(3))
     with pytest.raises(RuntimeError, match="boom"):
         with ops.deferred_weight_gradient_join():
-            assert ops._DEFER["on"]
-            ops._DEFER["handed"].append((p, 1234, 0))
-            ops._DEFER["targets"].add(id(p))
+            assert weight_grad_stream._DEFER["on"]
+            weight_grad_stream._DEFER["handed"].append((p, 1234, 0))
+            weight_grad_stream._DEFER["targets"].add(id(p))
             raise RuntimeError("boom")
-    assert not ops._DEFER["on"] and ops._DEFER["handed"] == [] and not ops._DEFER["targets"] and ops._DEFER["pending"] == []
+    assert not weight_grad_stream._DEFER["on"] and weight_grad_stream._DEFER["handed"] == [] and not weight_grad_stream._DEFER["targets"] and weight_grad_stream._DEFER["pending"] == []
     ops.join_deferred()                                   # nothing to verify: does not raise
     # a clean exit keeps the pass for join_deferred()
     with ops.deferred_weight_gradient_join():
-        ops._DEFER["targets"].add(id(p))
-    assert ops._DEFER["targets"]
+        weight_grad_stream._DEFER["targets"].add(id(p))
+    assert weight_grad_stream._DEFER["targets"]
     ops.join_deferred()
-    assert not ops._DEFER["targets"]
+    assert not weight_grad_stream._DEFER["targets"]
 
 
 def test_combined_node_csr_of_both_pair_tables_sums_what_the_two_reductions_sum():

@@ -112,6 +112,30 @@ def test_typed_linear_matches_per_row_matmul(gpu_device, monkeypatch, typed):
         assert np.abs(Wd[t].grad.cpu().numpy() - gW[t]).max() < 2e-5 * max(1.0, np.abs(gW[t]).max())
 
 
+def test_typed_linear_odd_shape_sums_its_tile_partials_per_type(gpu_device, monkeypatch):
+    """Din * Dout = 1200 is neither a multiple of 1024 nor at most 1024: the per-tile weight-gradient partials of the bmm route are
+    summed per edge type by torch (ops.typed._sum_tiles_per_type's fallback), not by the gather-reduce kernel."""
+    from tf_gnn_samples_amd import ops
+    from tf_gnn_samples_amd.graph import RelGraph
+    set_switch(monkeypatch, "RELGNN_TYPED", "bmm")
+    V, L, Din, Dout = 50, 3, 12, 100
+    rng, adj, _ = _sparse_many_type_graph(5, V=V, L=L)
+    side = RelGraph([torch.as_tensor(a, device=gpu_device) for a in adj], V).pair_tables().src
+    H = rng.standard_normal((V, Din)).astype(np.float32)
+    Ws = [glorot(rng, (Din, Dout)) for _ in range(L)]
+    Wd = [torch.as_tensor(w, device=gpu_device).requires_grad_(True) for w in Ws]
+    Y = ops.typed_linear(torch.as_tensor(H, device=gpu_device), side, Wd)
+    gY = rng.standard_normal(Y.shape).astype(np.float32)
+    Y.backward(torch.as_tensor(gY, device=gpu_device))
+    node = side.node.cpu().numpy()
+    types = np.repeat(np.arange(L), np.diff(side.offsets))
+    real = node != V                                                   # padding rows carry no gradient
+    for t in range(L):
+        rows = real & (types == t)
+        gW = H[node[rows]].astype(np.float64).T @ gY[rows].astype(np.float64)
+        assert np.abs(Wd[t].grad.cpu().numpy() - gW).max() < 2e-5 * max(1.0, np.abs(gW).max())
+
+
 def test_typed_weight_gradient_on_the_side_stream_is_the_same_bits(gpu_device):
     """bwd_overlap: the typed products' weight gradient (panel TN + per-type sum of the tile partials) runs on the side stream next to
     the input gradient — joined inside backward(), or behind it under deferred_weight_gradient_join (train_step).  Same kernels,

@@ -216,7 +216,7 @@ def test_deferred_weight_gradients_only_go_aside_where_nothing_reads_them_early(
     join_deferred() only when it goes straight into a leaf parameter that is seen once in the backward pass.  The gradient of a VIEW
     of a parameter (the GRU's recurrent_kernel[:, :2u]) is consumed by the view's backward on the main stream at once, and a
     parameter used twice has its contributions summed there: both must stay on one stream — and give the bits of the plain order."""
-    from tf_gnn_samples_amd import config, dense as DN, ops
+    from tf_gnn_samples_amd import config, dense as DN, ops, weight_grad_stream
     torch.manual_seed(0)
     x = torch.randn(6000, 128, device=gpu_device)
     U0 = torch.randn(128, 384, device=gpu_device) * 0.05
@@ -232,9 +232,9 @@ def test_deferred_weight_gradients_only_go_aside_where_nothing_reads_them_early(
             if deferred:
                 with ops.deferred_weight_gradient_join():
                     y.square().sum().backward()
-                pend = len(ops._DEFER["pending"])
+                pend = len(weight_grad_stream._DEFER["pending"])
                 ops.join_deferred()
-                assert not ops._DEFER["pending"] and not ops._DEFER["targets"] and not ops._DEFER["handed"]
+                assert not weight_grad_stream._DEFER["pending"] and not weight_grad_stream._DEFER["targets"] and not weight_grad_stream._DEFER["handed"]
             else:
                 y.square().sum().backward()
         torch.cuda.synchronize()
@@ -262,7 +262,7 @@ def test_deferred_weight_gradients_stay_on_the_main_stream_whenever_autograd_wou
     needs no gradient (its contribution is summed on the main stream: it must wait for the side stream first).  None of them may go
     aside; all give the bits of the plain order.  And a use the package cannot see (a plain torch op on the same leaf whose
     gradient arrives AFTER the deferred one) is reported by join_deferred() instead of racing silently."""
-    from tf_gnn_samples_amd import config, dense as DN, ops
+    from tf_gnn_samples_amd import config, dense as DN, ops, weight_grad_stream
     torch.manual_seed(1)
     x = torch.randn(6000, 128, device=gpu_device)
     U0 = torch.randn(128, 256, device=gpu_device) * 0.05
@@ -277,7 +277,7 @@ def test_deferred_weight_gradients_stay_on_the_main_stream_whenever_autograd_wou
             if deferred:
                 with ops.deferred_weight_gradient_join():
                     y.square().sum().backward(**backward_kw)
-                pend = len(ops._DEFER["pending"])
+                pend = len(weight_grad_stream._DEFER["pending"])
                 ops.join_deferred()
             else:
                 pend = None
@@ -324,7 +324,7 @@ def test_deferred_weight_gradients_stay_on_the_main_stream_whenever_autograd_wou
         assert "deferred weight-gradient join" in str(e)
     else:
         assert pend == 0                    # (the plain op's gradient arrived first: nothing went aside)
-    assert not ops._DEFER["pending"] and not ops._DEFER["targets"] and not ops._DEFER["handed"]
+    assert not weight_grad_stream._DEFER["pending"] and not weight_grad_stream._DEFER["targets"] and not weight_grad_stream._DEFER["handed"]
     torch.cuda.synchronize()
 
 

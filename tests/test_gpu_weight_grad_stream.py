@@ -16,15 +16,15 @@ MODES = (("0", False), ("1", False), ("1", True))
 def _backward(out, gout, overlap, deferred):
     """The backward of `out` (a tensor or several) in one mode -> the number of pending joins the deferred pass left (None when not
     deferred)."""
-    from tf_gnn_samples_amd import config, ops
+    from tf_gnn_samples_amd import config, ops, weight_grad_stream
     pending = None
     with config.override(bwd_overlap=overlap):
         if deferred:
             with ops.deferred_weight_gradient_join():
                 torch.autograd.backward(out, gout)
-            pending = len(ops._DEFER["pending"])
+            pending = len(weight_grad_stream._DEFER["pending"])
             ops.join_deferred()
-            assert not ops._DEFER["pending"] and not ops._DEFER["targets"] and not ops._DEFER["handed"]
+            assert not weight_grad_stream._DEFER["pending"] and not weight_grad_stream._DEFER["targets"] and not weight_grad_stream._DEFER["handed"]
         else:
             torch.autograd.backward(out, gout)
     torch.cuda.synchronize()
@@ -100,7 +100,7 @@ def test_aggregate_then_transform_with_a_side_stream_intermediate_is_the_same_bi
 def test_kernels_shared_by_two_aggregate_then_transform_calls_go_aside_once(gpu_device):
     """The shared weights of a second timestep: the backward sees the kernels twice, the second sight stays on the main stream (and
     makes it wait for the first), the two contributions are summed there in the one-stream order."""
-    from tf_gnn_samples_amd import ops
+    from tf_gnn_samples_amd import ops, weight_grad_stream
     g, H0, W0, gout = _aggregate_case(gpu_device, 12)
 
     def grads(overlap, deferred):
@@ -114,7 +114,7 @@ def test_kernels_shared_by_two_aggregate_then_transform_calls_go_aside_once(gpu_
     pending, got = grads("1", True)
     assert pending == 1
     _same_bits(want, got, "deferred")
-    assert not ops._DEFER["on"] and not ops._DEFER["pending"] and not ops._DEFER["targets"] and not ops._DEFER["handed"]
+    assert not weight_grad_stream._DEFER["on"] and not weight_grad_stream._DEFER["pending"] and not weight_grad_stream._DEFER["targets"] and not weight_grad_stream._DEFER["handed"]
 
 
 def test_gru_cell_under_a_deferred_join_is_the_same_bits(gpu_device):

@@ -16,9 +16,10 @@ def _never():
 
 
 def test_ops_re_exports_the_protocol_objects():
-    for name in ("_SIDE_STREAMS", "_DEFER", "deferred_weight_gradient_join", "_accumulator_keeps_the_tensor", "deferred_targets_ok",
-                 "wait_if_in_flight", "hand_over_deferred", "join_deferred", "_side_stream"):
+    for name in ("deferred_weight_gradient_join", "deferred_targets_ok", "wait_if_in_flight", "hand_over_deferred", "join_deferred", "fork"):
         assert getattr(ops, name) is getattr(wgs, name), name
+    for name in ("_SIDE_STREAMS", "_DEFER", "_accumulator_keeps_the_tensor", "_side_stream"):       # the module's own: read them there
+        assert hasattr(wgs, name) and not hasattr(ops, name), name
 
 
 @pytest.mark.parametrize("join_in_backward", [True, False])

@@ -21,7 +21,6 @@ ERRFLAG_NOT_SORTED = 2
 AGG_SUM, AGG_MEAN, AGG_SQRT_N, AGG_MAX = 0, 1, 2, 3
 MT_MAX = 48
 ACT_LINEAR, ACT_TANH, ACT_RELU, ACT_LEAKY_RELU, ACT_ELU, ACT_SELU, ACT_GELU = range(7)
-ACT_NAMES = ("linear", "tanh", "relu", "leaky_relu", "elu", "selu", "gelu")      # utils.get_activation's strings, by id
 
 _c_i32, _c_i64, _c_f32 = ctypes.c_int32, ctypes.c_int64, ctypes.c_float
 _c_u32 = ctypes.c_uint32

@@ -3,6 +3,7 @@ factor a consumer may fold into its input-gradient product, a gradient that alre
 zero-padded to a multiple of 16 columns.  Nothing here launches a kernel; dense.py reads the tags when it routes a product."""
 import torch
 
+from .activations import FROM_OUTPUT_ACTS as _FROM_OUTPUT_ACTS, IDEMPOTENT_ACTS as _IDEMPOTENT_ACTS
 from .config import settings as _cfg
 
 # ---- activation gradients folded into the product that feeds them ------------------------------------------------------------------
@@ -22,8 +23,7 @@ from .config import settings as _cfg
 # only the function it is handed to will read it (the tag's flag: the driver loop of models/sparse_graph_model.py knows its own
 # dataflow), and that function says that it reads it exactly once (sole_reader=True: the aggregate-first RGCN layer's first
 # timestep, the driver's Dense between layers; a GGNN layer, which feeds its input to the messages AND to the cell, does not).
-_FROM_OUTPUT_ACTS = (1, 2, 3, 4, 5)          # _lib.ACT_TANH .. ACT_SELU (GELU needs the pre-activation)
-_IDEMPOTENT_ACTS = (2,)                      # _lib.ACT_RELU
+# (_FROM_OUTPUT_ACTS: tanh .. selu — gelu needs the pre-activation; _IDEMPOTENT_ACTS: relu — both columns of activations.ACTIVATIONS)
 
 
 def mark_activation_output(y: torch.Tensor, act: int, sole_consumer: bool = False) -> torch.Tensor:

@@ -40,6 +40,7 @@ import torch
 # float64 on the C2 shapes neither arithmetic is systematically closer end to end (profiles/r04_*).
 from . import _lib
 from ._lib import ACT_LINEAR, ACT_RELU
+from .activations import activation_of_id, apply_activation
 from .activation_tags import (_FROM_OUTPUT_ACTS, _IDEMPOTENT_ACTS, fusable_activation_of, is_premasked, mark_activation_output,
                               mark_premasked, mark_zero_padded, vouch_sole_consumer, zero_padded_operand)
 from .config import settings as _cfg
@@ -277,7 +278,7 @@ def grouped_nt_gemm(g: torch.Tensor, kernels, xmax: torch.Tensor = None, xgroups
 
 def mm_into(layout: int, a: torch.Tensor, b: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
     """out[:] = a @ b (GEMM_NN) | a @ b^T (GEMM_NT) into a preallocated row block: the limb route when the shapes allow
-    (RELGNN_GEMM=limb), else the library through torch.mm.  For the per-edge-type row blocks of an edge MLP (ops._BlockedLinear)."""
+    (RELGNN_GEMM=limb), else the library through torch.mm.  For the per-edge-type row blocks of an edge MLP (ops.edge._BlockedLinear)."""
     if _cfg.limb_gemm and _limb_columns(layout, a, b, None) == 256 and rows_aligned(out):
         return limb_dense(layout, a, b, out=out)
     return torch.mm(a, b if layout == GEMM_NN else b.t(), out=out)
@@ -462,8 +463,7 @@ def dense_act(x: torch.Tensor, kernel: torch.Tensor, bias: torch.Tensor = None, 
         return dense(x, kernel, bias, sole_reader=sole_reader)
     if not (act in _FROM_OUTPUT_ACTS and x.is_cuda and x.dtype == torch.float32 and x.dim() == 2 and _cfg.gemm != "torch"
             and (_cfg.act_fusion == "1" or act == ACT_RELU)):
-        from .utils import apply_activation, get_activation
-        return apply_activation(get_activation(_lib.ACT_NAMES[act]), dense(x, kernel, bias, sole_reader=sole_reader))
+        return apply_activation(activation_of_id(act), dense(x, kernel, bias, sole_reader=sole_reader))
     y = _DenseFn.apply(x, kernel, bias, act, fusable_activation_of(x, sole_reader) if x.requires_grad else 0)
     return mark_activation_output(y, act, sole_consumer)
 

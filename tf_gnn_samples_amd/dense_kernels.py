@@ -8,6 +8,7 @@ import torch
 
 from . import _lib
 from .config import settings as _cfg
+from .handover import handover_word
 from .weight_images import (GEMM_NN, GEMM_NT, GEMM_TN, WEIGHT_NN, WEIGHT_NT, _PerStream, _weight_image_shape, _weight_matrices,
                             weight_image, weight_limbs)
 
@@ -234,8 +235,7 @@ def limb_gemm_xf32(a: torch.Tensor, b: "Limbs", bias: torch.Tensor = None, act: 
 
 # ---- limb products: a fp32 left operand against the limb image of weights -----------------------------------------------------------
 def _handover(device) -> int:
-    from . import ops            # (ops imports dense lazily too)
-    return ops.handover_word(device).data_ptr()
+    return handover_word(device).data_ptr()
 
 
 def limb_gemm_weight(a: torch.Tensor, w, kind: str, bias: torch.Tensor = None, act: int = 0,
@@ -243,7 +243,7 @@ def limb_gemm_weight(a: torch.Tensor, w, kind: str, bias: torch.Tensor = None, a
                      dy: torch.Tensor = None) -> torch.Tensor:
     """act(bias + a @ B^T) (times dact'(dy) with dy [M, n], an activation's output) with B = the cached limb image of the weight
     operand w, a fp32 [M, K] split inside the kernel.  Five entry points, one product:
-      xmax [M * xgroups] (per-row magnitudes of `a` from its producer, ops._seg_reduce_raw(rowmax=)): the two-fp16-limb form,
+      xmax [M * xgroups] (per-row magnitudes of `a` from its producer, ops.segment._seg_reduce_raw(rowmax=)): the two-fp16-limb form,
                          relgnn_limb16_gemm_xf32 / _dact
       _limb_pc_ok        wave roles instead of k-loop phases (csrc/limb_gemm_pc.hip): the same bits, the matrix waves at their
                          MFMA-only time — relgnn_limb_gemm_xf32_pc, which carries dact itself

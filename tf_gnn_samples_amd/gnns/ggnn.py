@@ -10,7 +10,7 @@ import torch
 from .. import ops
 from ..dense import dense_multi
 from ..graph import as_rel_graph
-from ..utils import gated_unit_variable_shapes, get_gated_unit
+from ..utils import GATED_UNIT_SCOPES, gated_unit_variable_shapes, get_gated_unit
 from ._common import require_weights
 
 
@@ -32,7 +32,6 @@ def sparse_ggnn_layer(node_embeddings: torch.Tensor,
                       ) -> torch.Tensor:
     """See gnns/ggnn.py:16-49.  `weights`: "Edge_%i_Weight/kernel" plus the cell's
     "<cell>/kernel", "<cell>/recurrent_kernel", "<cell>/bias" (cell scope: gru_cell / simple_rnn_cell)."""
-    from ..utils import GATED_UNIT_SCOPES
     weights = require_weights(weights, "sparse_ggnn_layer")
     num_nodes, in_dim = node_embeddings.shape
     if state_dim is None:

@@ -15,9 +15,8 @@ from typing import List, Mapping, Optional
 
 import torch
 
-import os
-
 from .. import _lib, ops
+from ..config import settings
 from ..dense import dense
 from ..graph import as_rel_graph
 from ._common import concat_edge_kernels, reduce_and_activate, require_weights
@@ -28,7 +27,6 @@ def aggregate_first_enabled() -> bool:
     """Default order for sum / mean / sqrt_n: gather + reduce the raw states into the (target, type) buckets, then ONE
     GEMM with the stacked kernels (ops.aggregate_then_transform).  RELGNN_RGCN_ORDER=transform_first restores
     transform-then-aggregate."""
-    from ..config import settings
     return settings.rgcn_order != "transform_first"
 
 

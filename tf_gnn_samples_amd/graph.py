@@ -16,13 +16,13 @@ relgnn_segment_plan, relgnn_gather_*): it is integer work and is tested bit-exac
 the NumPy oracle.
 """
 import ctypes
-import os
 from collections import OrderedDict
 from typing import List, Optional, Sequence
 
 import torch
 
 from . import _lib
+from .config import settings
 
 
 _ZERO_FLAGS = {}
@@ -30,6 +30,39 @@ _ZERO_FLAGS = {}
 
 def _i32(n, device):
     return torch.empty(int(n), dtype=torch.int32, device=device)
+
+
+# ---- long buckets -----------------------------------------------------------------------------------------------------
+# The gather kernel gives ONE wave to a bucket and folds its messages in order: a hub with 1e5 incoming edges keeps one
+# wave busy for milliseconds while the rest of the chip has long finished.  A graph that knows it has such buckets
+# (RelGraph.split_long_segments: the lengths are read back once, where the graph is validated anyway) attaches a
+# SplitPlan to the row-pointer tensor; ops.segment._seg_reduce_raw then runs two launches of the SAME kernel: chunks of at
+# most LONG_SEGMENT messages as virtual rows, then the virtual rows of a bucket combined in chunk order (deterministic; the
+# fp32 summation order of a hub differs from the sequential fold by the chunking only).
+LONG_SEGMENT = 4096
+
+
+class SplitPlan:
+    def __init__(self, rowptr: torch.Tensor, stride: int, num_out: int, chunk: int = LONG_SEGMENT):
+        dev = rowptr.device
+        bounds = rowptr[0:num_out * stride + 1:stride].long()                     # [num_out + 1]
+        starts, ends = bounds[:-1], bounds[1:]
+        self.lengths = ends - starts
+        chunks = torch.clamp((self.lengths + chunk - 1) // chunk, min=1)
+        off = torch.zeros(num_out + 1, dtype=torch.int64, device=dev)
+        off[1:] = torch.cumsum(chunks, 0)
+        self.num_virtual = int(off[-1])                                            # host sync, once per plan
+        seg_of = torch.repeat_interleave(torch.arange(num_out, device=dev), chunks)
+        first = starts[seg_of] + (torch.arange(self.num_virtual, device=dev) - off[seg_of]) * chunk
+        self.virtual_rowptr = torch.cat([first, bounds[-1:]]).to(torch.int32).contiguous()
+        self.combine_rowptr = off.to(torch.int32).contiguous()
+        self.iota = torch.arange(self.num_virtual, dtype=torch.int32, device=dev)
+
+
+def split_plan_of(rowptr, stride: int) -> Optional[SplitPlan]:
+    """The SplitPlan attached to this bucketing (row pointers read with `stride`), None where it has no long buckets."""
+    plans = getattr(rowptr, "_relgnn_split", None)
+    return None if plans is None else plans.get(stride)
 
 
 class GatherReducePlan:
@@ -312,16 +345,14 @@ class RelGraph:
         return torch.cat(out)
 
     def _attach_split_plans(self, longest, threshold: int = None) -> bool:
-        from . import ops
-        threshold = ops.LONG_SEGMENT if threshold is None else threshold
+        threshold = LONG_SEGMENT if threshold is None else threshold
         any_long = False
         for (rp, stride), n in zip(self._bucketings(), longest):
             if n > threshold:
-                plans = getattr(rp, "_relgnn_split", None)
-                if plans is None:
-                    plans = rp._relgnn_split = {}
-                if stride not in plans:
-                    plans[stride] = ops.SplitPlan(rp, stride, self.V * self.L // stride, threshold)
+                if split_plan_of(rp, stride) is None:
+                    if not hasattr(rp, "_relgnn_split"):
+                        rp._relgnn_split = {}
+                    rp._relgnn_split[stride] = SplitPlan(rp, stride, self.V * self.L // stride, threshold)
                 any_long = True
         self.has_long_buckets = any_long
         return any_long
@@ -329,8 +360,8 @@ class RelGraph:
     has_long_buckets = False
 
     def split_long_segments(self, threshold: int = None) -> bool:
-        """One host round trip: find buckets longer than `threshold` messages (default ops.LONG_SEGMENT) and route the
-        gather / reduce launches that walk them through chunked virtual rows (ops.SplitPlan).  Called by check() for
+        """One host round trip: find buckets longer than `threshold` messages (default LONG_SEGMENT) and route the
+        gather / reduce launches that walk them through chunked virtual rows (SplitPlan).  Called by check() for
         validated graphs and by tasks/resident.py for batches of a fold that is known to hold such hubs; graphs built
         with validate="deferred" keep one wave per bucket (PPI-, QM9- and VarMisuse-shaped data: longest bucket < 2 k)."""
         return self._attach_split_plans(self._longest_buckets().tolist(), threshold)
@@ -488,7 +519,6 @@ class RelGraph:
         """Node-side per-type transforms over all V*L (node,type) rows waste work when most buckets are empty
         (VarMisuse-shaped graphs: 23 edge types, ~2/3 of the buckets empty).  Few-type graphs (PPI: every bucket
         non-empty) keep the dense [V*L, D] tables and one big GEMM.  RELGNN_PAIR_TABLES=0/1 overrides."""
-        from .config import settings
         if settings.pair_tables != "auto":
             return settings.pair_tables == "1"
         if self.L < 8 or self.M == 0:
@@ -611,7 +641,7 @@ class SidePairs:
 
     Rows are TYPE-MAJOR and every type's block is padded to a multiple of PAIR_CHUNK rows, so the whole table is a
     batch of [PAIR_CHUNK, D] tiles that each belong to ONE edge type: the per-type transforms become a single batched
-    GEMM with the weight picked per tile (ops.typed_linear).  Padding rows gather an all-zero input row, are never
+    GEMM with the weight picked per tile (ops.typed.typed_linear).  Padding rows gather an all-zero input row, are never
     referenced by a message, and cost <= L * PAIR_CHUNK rows.
 
     P            number of table rows (including padding); num_pairs = non-empty (node, type) buckets
@@ -732,7 +762,7 @@ class PairTables:
     def node_csr_both(self):
         """(rowptr [V+1], col [num_pairs_src + num_pairs_tgt]) int32: node -> its rows in the by-source table FOLLOWED by its rows in
         the by-target table, the latter numbered behind the former (row + P_s) — the CSR of ONE reduction that sums the per-row
-        input gradients of both typed transforms of a layer into the nodes (ops._TypedLinearPanel over both tables)."""
+        input gradients of both typed transforms of a layer into the nodes (ops.typed._TypedLinearPanel over both tables)."""
         both = getattr(self, "_both", None)
         if both is None:
             a, b = self.src, self.tgt

@@ -1,4 +1,5 @@
 """Model driver + the seven adapters (table-driven, adapters.py) under the reference's class names."""
+from ..tasks import CHECKPOINT_TASK_CLASSES, name_to_task_class
 from .adapters import ADAPTER_CLASSES
 from .sparse_graph_model import Sparse_Graph_Model
 
@@ -38,7 +39,6 @@ def restore(saved_model_path: str, result_dir: str, run_id: str = None, device=N
     import os
     import pickle
     import time
-    from ..tasks import CHECKPOINT_TASK_CLASSES, name_to_task_class
     print("Loading model from file %s." % saved_model_path)
     with open(saved_model_path, 'rb') as in_file:
         data_to_load = pickle.load(in_file)

@@ -25,6 +25,8 @@ from .. import ops
 from ..dense import capture_image_cache, dense_act, vouch_sole_consumer, weights_changed
 from ..graph import as_rel_graph, check_pending_graph_errors
 from ..tasks import DataFold, DeviceBatch, Sparse_Graph_Task
+from ..tasks.batcher import NativeBatcher
+from ..tasks.resident import ResidentDataset
 from ..utils import get_activation, layer_norm, layer_norm_scope
 from ..variables import VariableStore
 from .data_parallel import data_parallel
@@ -390,7 +392,6 @@ class Sparse_Graph_Model(ABC):
 
     def _native_pipeline(self, data):
         """The input pipeline of one data fold (ResidentDataset or NativeBatcher over its GraphStore), built once and kept."""
-        from ..tasks.batcher import NativeBatcher
         key = (id(data), len(data))
         cached = self._native_batchers.get(key)
         if cached is not None and cached[0] is data:
@@ -402,7 +403,6 @@ class Sparse_Graph_Model(ABC):
             # keeps the host packer, `true` insists
             want = self.params.get('resident_dataset', 'auto')
             if want is True or (want == 'auto' and self._fold_fits_hbm(store)):
-                from ..tasks.resident import ResidentDataset
                 try:
                     pipeline = ResidentDataset(store, self.device)
                 except ValueError:

@@ -25,6 +25,8 @@ import numpy as np
 import torch
 import torch.distributed as dist
 
+from . import _lib
+
 
 def shard_graphs_by_edges(edge_counts: Sequence[int], world_size: int) -> List[List[int]]:
     """Greedy longest-processing-time assignment of whole graphs to ranks, balancing sum_l E_l.
@@ -347,7 +349,6 @@ class PackedGradientAllReducer:
 
     def __init__(self, params: Sequence[torch.nn.Parameter], group=None):
         import ctypes
-        from . import _lib
         self.params = [p for p in params if p.requires_grad]
         self.group = group
         if not self.params or not all(p.is_cuda and p.dtype == torch.float32 for p in self.params):
@@ -374,7 +375,6 @@ class PackedGradientAllReducer:
     @torch.no_grad()
     def pack(self, scale: float) -> torch.Tensor:
         """flat <- scale * grads, on the current stream.  Returns the flat buffer."""
-        from . import _lib
         scale = float(scale)
         keep = []                                # contiguous copies stay alive until their launch is enqueued
         for c0, n, sizes, dst in self._chunks:

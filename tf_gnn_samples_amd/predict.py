@@ -13,6 +13,8 @@ from typing import Optional, Tuple
 
 import torch
 
+from . import _lib
+
 
 def _rows_ok(t: torch.Tensor) -> bool:
     return t.dim() == 2 and (t.shape[0] <= 1 or t.shape[1] == 0 or (t.stride(1) == 1 and t.stride(0) >= t.shape[1]))
@@ -59,7 +61,6 @@ def predict_sigmoid(logits: torch.Tensor, out_probs: Optional[torch.Tensor] = No
     if rows == 0 or cols == 0:
         return probs, labels
     if _kernel_route(logits) and _rows_ok(probs) and _rows_ok(labels):
-        from . import _lib
         _lib.launch("relgnn_predict_sigmoid_f32", _lib.ptr(logits, rows_strided=True), _ld(logits), rows, cols,
                     _lib.ptr(probs, rows_strided=True), _ld(probs), _lib.ptr(labels, rows_strided=True), _ld(labels))
         return probs, labels
@@ -82,7 +83,6 @@ def predict_softmax(logits: torch.Tensor, out_probs: Optional[torch.Tensor] = No
     if rows == 0:
         return probs, classes
     if _kernel_route(logits) and _rows_ok(probs) and classes.is_contiguous():
-        from . import _lib
         _lib.launch("relgnn_predict_softmax_f32", _lib.ptr(logits, rows_strided=True), _ld(logits), rows, cols,
                     _lib.ptr(probs, rows_strided=True), _ld(probs), _lib.ptr(classes))
         return probs, classes
@@ -108,7 +108,6 @@ def predict_candidates(logits: torch.Tensor, out_probs: Optional[torch.Tensor] =
     if rows == 0:
         return probs, predicted
     if _kernel_route(logits) and cols <= MAX_CANDIDATES and probs.is_contiguous() and predicted.is_contiguous():
-        from . import _lib
         _lib.launch("relgnn_predict_candidates_f32", _lib.ptr(logits), rows, cols, _lib.ptr(probs), _lib.ptr(predicted))
         return probs, predicted
     top, first = logits.max(dim=1, keepdim=True).values, _first_max(logits).long().unsqueeze(1)

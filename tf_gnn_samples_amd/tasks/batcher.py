@@ -19,6 +19,8 @@ import numpy as np
 import torch
 
 from .. import _lib
+from ..graph import RelGraph
+from ..parallel import effective_cpu_count
 from .sparse_graph_task import DeviceBatch
 
 _LAY_V, _LAY_M, _LAY_BYTES, _LAY_DEG, _LAY_N2G, _LAY_FIXED = 0, 1, 2, 3, 4, 5
@@ -132,7 +134,6 @@ class NativeBatcher:
     def __init__(self, store: GraphStore, device, num_threads: Optional[int] = None, depth: int = 2,
                  features: str = "initial_node_features", constants: Optional[dict] = None, bucket: bool = True):
         self.store, self.device = store, torch.device(device)
-        from ..parallel import effective_cpu_count
         self.num_threads = int(num_threads or max(1, min(8, effective_cpu_count() // 2)))   # leave the quota's other half to torch
         self.depth = max(2, int(depth))
         self.features = features
@@ -214,7 +215,6 @@ class NativeBatcher:
             payload[name] = dev[off:off + rows * cols * dtype.itemsize].view(tdt).view(rows, cols)
         graph = None
         if self.bucket and int(lay[_LAY_M]) > 0:
-            from ..graph import RelGraph
             graph = RelGraph.build_on_stream(adj, int(lay[_LAY_V]), self._copy_stream)
         batch = DeviceBatch.from_tensors(
             num_graphs=len(graph_ids), num_nodes=int(lay[_LAY_V]), num_edges=int(lay[_LAY_M]),

@@ -14,8 +14,11 @@ from typing import Any, Dict, Iterator, List, NamedTuple, Optional
 import numpy as np
 import torch
 
-from .. import config as _cfg
-from ..dense import dense
+from .. import _lib, config as _cfg
+from ..dense import dense, mark_zero_padded
+from ..parallel import refuse_single_graph_task
+from ..predict import predict_softmax
+from .resident import ResidentDataset
 from .sparse_graph_task import DataFold, MinibatchData, Sparse_Graph_Task
 
 
@@ -35,7 +38,6 @@ class _SoftmaxCEStats(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, logits, labels, mask):
-        from .. import _lib
         lib = _lib.load_library()
         if logits.dim() != 2 or logits.stride(1) != 1:
             logits = logits.contiguous()
@@ -55,7 +57,6 @@ class _SoftmaxCEStats(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g_loss, g_total, g_accuracy, g_counts):
-        from .. import _lib
         logits, labels, mask, stats = ctx.saved_tensors
         if g_loss is None and g_total is None:
             return None, None, None
@@ -68,7 +69,6 @@ class _SoftmaxCEStats(torch.autograd.Function):
         if cols % 16 and _cfg.settings.limb_gemm and _cfg.settings.head_pad == "1":
             # rows of the next multiple of 16 floats, zeros behind the classes: the head's input-gradient product then runs on the limb
             # route with the activation gradient of the last GNN layer's Dense in its epilogue (dense.mark_zero_padded), as PPI's
-            from ..dense import mark_zero_padded
             ldg = (cols + 15) // 16 * 16
             buf = torch.empty((rows, ldg), dtype=torch.float32, device=logits.device)
             _lib.launch("relgnn_softmax_ce_bwd", _lib.ptr(logits, rows_strided=True), ld, _lib.ptr(labels), _lib.ptr(mask), rows, cols,
@@ -302,7 +302,6 @@ class Citation_Network_Task(Sparse_Graph_Task):
     def compute_task_predictions(self, final_node_representations: torch.Tensor, batch, weights, out=None) -> Dict[str, torch.Tensor]:
         """probabilities float32 [V, classes] = softmax(logits); classes int32 [V] = the first maximum of the logits, as the accuracy
         of _SoftmaxCEStats counts it (:134-138).  For EVERY node: the fold's mask is not read; no dropout."""
-        from ..predict import predict_softmax
         out = out or {}
         logits = dense(final_node_representations, weights["kernel"])
         probabilities, classes = predict_softmax(logits, out.get("probabilities"), out.get("classes"))
@@ -318,7 +317,6 @@ class Citation_Network_Task(Sparse_Graph_Task):
     def make_minibatch_iterator(self, data, data_fold: DataFold, max_nodes_per_batch: int,
                                 rng: Optional[np.random.RandomState] = None) -> Iterator[MinibatchData]:
         """Exactly one minibatch per epoch, the whole graph; max_nodes_per_batch is not consulted (:157-177)."""
-        from ..parallel import refuse_single_graph_task
         refuse_single_graph_task(self.name())
         fold = next(iter(data))
         feed = {
@@ -338,14 +336,12 @@ class Citation_Network_Task(Sparse_Graph_Task):
         """The same single batch from the flattened fold.  The packer's rule (graphs are taken while the node count stays BELOW
         max_nodes_per_batch) is not asked: the graph is the batch whatever its size.  A resident fold (tasks/resident.py) was
         bucketed once when it was made; its one assembled batch is kept and handed out again every epoch."""
-        from ..parallel import refuse_single_graph_task
         refuse_single_graph_task(self.name())
         if batcher.store.num_graphs != 1:
             raise ValueError("a citation-network fold is ONE graph; got %d" % batcher.store.num_graphs)
         keep = self._out_keep(data_fold)
         batcher.constants['out_layer_dropout_keep_prob'] = keep
         ids = np.zeros(1, dtype=np.int64)
-        from .resident import ResidentDataset
         if isinstance(batcher, ResidentDataset):
             batch = self._resident_batches.get(batcher)
             if batch is None:

@@ -12,8 +12,9 @@ from typing import Any, Dict, Iterator, List, Optional
 import numpy as np
 import torch
 
-from .. import config as _cfg
-from ..dense import dense
+from .. import _lib, config as _cfg
+from ..dense import dense, mark_zero_padded
+from ..predict import predict_sigmoid
 from ..utils import micro_f1
 from .sparse_graph_task import DataFold, MinibatchData, Sparse_Graph_Task
 from .synthetic import GraphSample, make_ppi_shaped_graphs
@@ -26,7 +27,6 @@ class _SigmoidCEStats(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, logits, labels, inv_n: float):
-        from .. import _lib
         lib = _lib.load_library()
         logits, labels = logits.contiguous(), labels.contiguous()
         stats = torch.empty(6, dtype=torch.float32, device=logits.device)
@@ -44,7 +44,6 @@ class _SigmoidCEStats(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g_mean, g_total, g_f1, g_counts):
-        from .. import _lib
         logits, labels = ctx.saved_tensors
         if g_mean is None and g_total is None:
             return None, None, None
@@ -57,7 +56,6 @@ class _SigmoidCEStats(torch.autograd.Function):
             # rows of the next multiple of 16 floats, zeros behind the labels: the head's input-gradient product then runs on the limb
             # route with the ReLU' of the last GNN layer in its epilogue (dense.mark_zero_padded) instead of a K = 121 library
             # product + a pass over [V, 256]
-            from ..dense import mark_zero_padded
             ld = (cols + 15) // 16 * 16
             buf = torch.empty((rows, ld), dtype=torch.float32, device=logits.device)
             _lib.launch("relgnn_sigmoid_ce_bwd_padded", _lib.ptr(logits), _lib.ptr(labels), rows, cols, _lib.ptr(g_mean), ctx.inv_n,
@@ -219,7 +217,6 @@ class PPI_Task(Sparse_Graph_Task):
     def compute_task_predictions(self, final_node_representations: torch.Tensor, batch, weights, out=None) -> Dict[str, torch.Tensor]:
         """probabilities float32 [V, labels] = sigmoid(logits); labels uint8 [V, labels] = the prediction whose true / false
         positives _SigmoidCEStats counts (utils/utils.py:61-74).  No dropout (the head's keep-prob is 1 outside training)."""
-        from ..predict import predict_sigmoid
         out = out or {}
         per_node_logits = dense(final_node_representations, weights["kernel"], weights["bias"])
         probabilities, labels = predict_sigmoid(per_node_logits, out.get("probabilities"), out.get("labels"))

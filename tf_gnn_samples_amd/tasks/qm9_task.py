@@ -15,8 +15,9 @@ from typing import Any, Dict, Iterator, List, NamedTuple, Optional
 import numpy as np
 import torch
 
-from .. import config, ops
+from .. import _lib, config, ops
 from ..dense import dense
+from ..graph import _PENDING_CHECKS
 from .sparse_graph_task import DataFold, MinibatchData, Sparse_Graph_Task
 
 
@@ -34,8 +35,6 @@ _NOT_SORTED = "graph_nodes_list is not non-decreasing (a node's graph id is smal
 
 def _err_flag(device, num_graphs: int) -> torch.Tensor:
     """A fresh device word for the kernel's check of graph_nodes_list, read back with the graphs' own at the next metric fetch."""
-    from .. import _lib
-    from ..graph import _PENDING_CHECKS
     flag = torch.zeros(1, dtype=torch.int32, device=device)
     _PENDING_CHECKS.append((flag, {_lib.ERRFLAG_INDEX_OUT_OF_RANGE: "graph_nodes_list holds a graph id outside [0, %d)" % num_graphs,
                                    _lib.ERRFLAG_NOT_SORTED: _NOT_SORTED}))
@@ -45,7 +44,6 @@ def _err_flag(device, num_graphs: int) -> torch.Tensor:
 def _pointer_table(tensors):
     """Host array of device pointers (the C ABI hands them to the kernel by value)."""
     import ctypes
-    from .. import _lib
     return (ctypes.c_void_p * len(tensors))(*[_lib.ptr(t) for t in tensors])
 
 
@@ -62,7 +60,6 @@ class _Head(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, states, features, graph_nodes_list, targets, num_graphs, *variables):
-        from .. import _lib
         num_tasks = len(variables) // 4
         if states.stride(1) != 1 or states.stride(0) % 4 != 0 or states.data_ptr() % 16 != 0:
             states = states.contiguous()
@@ -92,7 +89,6 @@ class _Head(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g_loss, g_total, g_abs_err, g_y):
-        from .. import _lib
         lib = _lib.load_library()
         states, features, graph_nodes_list, targets, y, node_range, *flat = ctx.saved_tensors
         num_tasks = len(flat) // 4
@@ -121,7 +117,6 @@ class _Head(torch.autograd.Function):
 
 
 def head_supported(num_tasks: int, hidden: int, annotation_size: int) -> bool:
-    from .. import _lib
     return bool(_lib.load_library().relgnn_qm9_head_supported(int(num_tasks), int(hidden), int(annotation_size)))
 
 

@@ -178,7 +178,7 @@ class Sparse_Graph_Task:
 
     def make_graph_store(self, data):
         """Flatten one data fold once for the C++ batch builder (include/relgnn.h section 9)."""
-        from .batcher import GraphStore
+        from .batcher import GraphStore           # (cycle: batcher imports DeviceBatch from this module at its top)
         return GraphStore(data, self.num_edge_types, self.NODE_PAYLOADS, self.GRAPH_PAYLOADS)
 
     def _finish_native_batch(self, batch: "DeviceBatch") -> "DeviceBatch":

@@ -40,7 +40,11 @@ from typing import Any, Dict, Iterable, Iterator, List, NamedTuple, Optional, Se
 import numpy as np
 import torch
 
+from .. import _lib, ops
+from ..graph import _PENDING_CHECKS
+from ..predict import predict_candidates
 from .sparse_graph_task import DataFold, MinibatchData, Sparse_Graph_Task
+from .synthetic import make_varmisuse_shaped_graph
 
 BIG_NUMBER = 1e7                                        # utils/utils.py of the reference
 ALPHABET = "abcdefghijklmnopqrstuvwxyz0123456789,;.!?:'\"/\\|_@#$%^&*~`+-=<>()[]{}"      # :15, 68 characters
@@ -261,7 +265,6 @@ def head_metrics_composition(logits: torch.Tensor, loss_function: str, margin: f
 # ---------------------------------------------------------------------------------------------------------------------------------
 def _err_flag(device, what: str) -> torch.Tensor:
     """A fresh device word for the kernels' index check, read back with the graphs' own at the next metric fetch."""
-    from ..graph import _PENDING_CHECKS
     flag = torch.zeros(1, dtype=torch.int32, device=device)
     _PENDING_CHECKS.append((flag, what))
     return flag
@@ -270,7 +273,6 @@ def _err_flag(device, what: str) -> torch.Tensor:
 class _CharCNN(torch.autograd.Function):
     @staticmethod
     def forward(ctx, chars, label_of_node, w1, b1, w2, b2):
-        from .. import _lib
         lib = _lib.load_library()
         chars = chars.contiguous()
         w1c, b1c, w2c, b2c = (t.detach().contiguous() for t in (w1, b1, w2, b2))
@@ -288,7 +290,6 @@ class _CharCNN(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g):
-        from .. import _lib, ops
         lib = _lib.load_library()
         chars, label_of_node, w1, b1, w2, b2 = ctx.saved_tensors
         num_labels, num_chars = chars.shape
@@ -305,7 +306,6 @@ class _CharCNN(torch.autograd.Function):
 
 
 def charcnn_supported(num_chars: int, out_dim: int, w1: torch.Tensor) -> bool:
-    from .. import _lib
     return tuple(w1.shape) == (5, ONE_HOT_DEPTH, 16) and bool(_lib.load_library().relgnn_charcnn_supported(int(num_chars), int(out_dim)))
 
 
@@ -329,7 +329,6 @@ class _Head(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, states, slot_ids, cand_ids, mask, first_node, w):
-        from .. import _lib
         lib = _lib.load_library()
         if states.dim() != 2 or states.stride(1) != 1:
             states = states.contiguous()
@@ -354,7 +353,6 @@ class _Head(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g_loss, g_total, g_accuracy, g_correct, g_logits):
-        from .. import _lib
         lib = _lib.load_library()
         states, slot_ids, cand_ids, mask, first_node, wv = ctx.saved_tensors
         if g_loss is None and g_total is None:
@@ -377,7 +375,6 @@ class _Head(torch.autograd.Function):
 
 
 def head_supported(num_candidates: int, hidden: int) -> bool:
-    from .. import _lib
     return bool(_lib.load_library().relgnn_varmisuse_head_supported(int(num_candidates), int(hidden)))
 
 
@@ -471,7 +468,6 @@ class VarMisuse_Task(Sparse_Graph_Task):
         candidate nodes per graph (the correct one first, as the loader leaves them).  num_graphs train graphs; the validation and
         test folds hold num_valid / num_test graphs (default: a quarter each, at least one); the test fold is kept as
         `synthetic_test_data`."""
-        from .synthetic import make_varmisuse_shaped_graph
         rng = np.random.default_rng([seed, 0x5a])
         stems = ["get", "set", "is", "num", "index", "count", "value", "name", "list", "item", "node", "result", "buffer", "length",
                  "key", "current", "next", "total", "max", "min", "file", "path", "data", "id", "size", "temp", "source", "target"]
@@ -551,7 +547,6 @@ class VarMisuse_Task(Sparse_Graph_Task):
         logits)) names (:438; 0 is the correct one): the arithmetic by which the head counts num_correct_predictions
         (csrc/common.h: candidate_choice).  Runs the head's forward on whichever route compute_task_metrics takes, for either loss
         function, and drops its metrics; the logits do not depend on the loss.  A padded candidate has probability exactly 0."""
-        from ..predict import predict_candidates
         out = out or {}
         with torch.no_grad():
             self.compute_task_metrics(final_node_representations, batch, weights)

@@ -1,8 +1,8 @@
 """Host-side mirror of the reference's utils/utils.py (same names, argument meaning and
 error behaviour) on PyTorch-ROCm tensors.
 
-  get_aggregation_function  utils/utils.py:23-33   -> HIP segment kernels (ops.py)
-  get_activation            utils/utils.py:36-58
+  get_aggregation_function  utils/utils.py:23-33   -> HIP segment kernels (ops/segment.py)
+  get_activation            utils/utils.py:36-58   (activations.py: the one table)
   get_gated_unit            utils/utils.py:10-20   (Keras SimpleRNNCell / GRUCell semantics, TF 1.13)
   MLP                       utils/utils.py:77-126
   micro_f1                  utils/utils.py:61-74
@@ -11,13 +11,15 @@ error behaviour) on PyTorch-ROCm tensors.
 Node-wise GEMMs (Dense, GRU) are library GEMMs (hipBLASLt, dense.lib_gemm); the elementwise halves of the GRU cell and the layer
 normalisation are HIP kernels of librelgnn (csrc/gru.hip, csrc/layer_norm.hip).
 """
-import math
 from typing import Callable, List, Mapping, Optional, Union
 
 import torch
 
-from . import ops
-from .dense import dense, dense_relu
+from . import _lib, ops
+from .activations import ACTIVATIONS, FUSABLE_ACTS, _gelu, _leaky_relu, apply_activation, get_activation  # noqa: F401
+from .config import settings as cfg
+from .dense import (GEMM_NN, GEMM_NT, WEIGHT_NN, WEIGHT_NT, column_sum, dense, dense_relu, lib_gemm, matmul_tn_splitk, tn_stream_group,
+                    tn_stream_group_ok, tn_stream_into, weight_image, weight_image_ok)
 from .weight_grad_stream import fork
 
 BIG_NUMBER = 1e7
@@ -37,42 +39,6 @@ def get_aggregation_function(aggregation_fun: Optional[str]):
         raise ValueError("Unknown aggregation function '%s'!" % aggregation_fun)
 
 
-def _gelu(x):
-    # erf form of the reference (utils/utils.py:53-55)
-    cdf = 0.5 * (1.0 + torch.erf(x / math.sqrt(2.0)))
-    return x * cdf
-
-
-def _leaky_relu(x):
-    return torch.nn.functional.leaky_relu(x, 0.2)  # tf.nn.leaky_relu default alpha
-
-
-def get_activation(activation_fun: Optional[str]):
-    if activation_fun is None:
-        return None
-    activation_fun = activation_fun.lower()
-    if activation_fun == 'linear':
-        return None
-    if activation_fun == 'tanh':
-        return torch.tanh
-    if activation_fun == 'relu':
-        return torch.relu
-    if activation_fun == 'leaky_relu':
-        return _leaky_relu
-    if activation_fun == 'elu':
-        return torch.nn.functional.elu
-    if activation_fun == 'selu':
-        return torch.selu
-    if activation_fun == 'gelu':
-        return _gelu
-    else:
-        raise ValueError("Unknown activation function '%s'!" % activation_fun)
-
-
-def apply_activation(fn, x):
-    return x if fn is None else fn(x)
-
-
 def hard_sigmoid(x):
     """Keras hard_sigmoid (GRUCell's default recurrent_activation in TF 1.13): clip(0.2x+0.5, 0, 1)."""
     return torch.clamp(0.2 * x + 0.5, 0.0, 1.0)
@@ -83,7 +49,6 @@ class _LayerNormFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, gamma, beta, eps: float):
-        from . import _lib
         x, gamma, beta = x.contiguous(), gamma.contiguous(), beta.contiguous()
         V, D = x.shape
         y = torch.empty_like(x)
@@ -96,8 +61,6 @@ class _LayerNormFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, gy):
-        from . import _lib
-        from .dense import column_sum
         lib = _lib.load_library()
         x, gamma, mean, rstd = ctx.saved_tensors
         V, D = x.shape
@@ -140,7 +103,6 @@ def layer_norm(x, gamma, beta, eps: float = 1e-12):
 
 def _gru_gates_fwd(xk, rec, h):
     """(z, r, r * h) from xk = x @ K + b [V, 3u], rec = h @ U[:, :2u] and h [V, u] (csrc/gru.hip)."""
-    from . import _lib
     V, u = h.shape
     z, r, rh = torch.empty_like(h), torch.empty_like(h), torch.empty_like(h)
     _lib.launch("relgnn_gru_gates_fwd", _lib.ptr(xk), _lib.ptr(rec), _lib.ptr(h), V, u, _lib.ptr(z), _lib.ptr(r), _lib.ptr(rh))
@@ -149,7 +111,6 @@ def _gru_gates_fwd(xk, rec, h):
 
 def _gru_out_fwd(xk, q, z, h, act: int):
     """(hh, out): the candidate hh = act(xk_h + q), q = (r * h) @ U[:, 2u:], and out = z h + (1 - z) hh."""
-    from . import _lib
     V, u = h.shape
     hh, out = torch.empty_like(h), torch.empty_like(h)
     _lib.launch("relgnn_gru_out_fwd", _lib.ptr(xk), _lib.ptr(q), _lib.ptr(z), _lib.ptr(h), V, u, act, _lib.ptr(hh), _lib.ptr(out))
@@ -159,8 +120,6 @@ def _gru_out_fwd(xk, q, z, h, act: int):
 def _gru_composition_bwd(gout, z, r, h, hh, u_h, act: int):
     """(gxk [V, 3u], gq [V, u], gh [V, u]) of the two kernels above around q = (r * h) @ u_h: output backward, gq @ u_h^T, gates
     backward.  gxk[:, :2u] is also the gradient of rec; gh does not hold the products' share (rec = h @ U[:, :2u]) yet."""
-    from . import _lib
-    from .dense import GEMM_NT, lib_gemm
     V, u = h.shape
     gxk = torch.empty((V, 3 * u), dtype=torch.float32, device=h.device)
     gq, gz, gh = torch.empty_like(h), torch.empty_like(h), torch.empty_like(h)
@@ -178,7 +137,6 @@ class _FusedGRU(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, xk, rec, h, u_h, act: int):
-        from .dense import GEMM_NN, lib_gemm
         xk, rec, h = xk.contiguous(), rec.contiguous(), h.contiguous()
         # (u_h = recurrent_kernel[:, 2u:] stays the strided view of the parameter it is: the product reads it with its leading
         #  dimension and keeps its limb image with the step's other weights — round 6: no copy, no split launch per cell)
@@ -192,7 +150,6 @@ class _FusedGRU(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, gout):
-        from .dense import matmul_tn_splitk
         z, r, rh, h, hh, u_h = ctx.saved_tensors
         u = h.shape[1]
         gxk, gq, gh = _gru_composition_bwd(gout.contiguous(), z, r, h, hh, u_h, ctx.act)
@@ -213,15 +170,11 @@ class _GRUCellFn(torch.autograd.Function):
     def forward(ctx, x, h, K, U, b, act: int, grad_mode: bool = True):
         """grad_mode: torch.is_grad_enabled() as the CALLER saw it (inside forward() it is always off, and needs_input_grad stays
         true for parameters under no_grad): an evaluation or prediction cell writes and saves nothing for a backward."""
-        from . import _lib
-        from .dense import GEMM_NN, lib_gemm
         x, h = x.contiguous(), h.contiguous()
         V, u = h.shape
         if _gru_cell_kernel_ok(x, h, K, U, b, act):
             # one launch (csrc/gru_cell.hip): both products, the gates, the candidate and the blend; z, r, r * h and the candidate
             # are written only when a backward will read them
-            from . import ops
-            from .dense import WEIGHT_NN, weight_image
             train = grad_mode and any(ctx.needs_input_grad[:5])
             im_zr = weight_image([K[:, :2 * u], U[:, :2 * u]], WEIGHT_NN)  # B [2u, D + u]: k = [x | h]
             im_h = weight_image([K[:, 2 * u:], U[:, 2 * u:]], WEIGHT_NN)   # B [u, D + u]:  k = [x | r * h]
@@ -247,8 +200,6 @@ class _GRUCellFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, gout):
-        from . import _lib
-        from .dense import GEMM_NT, column_sum, lib_gemm, matmul_tn_splitk, tn_stream_into
         x, h, K, U, z, r, rh, hh = ctx.saved_tensors
         V, u = h.shape
         gout = gout.contiguous()
@@ -256,8 +207,6 @@ class _GRUCellFn(torch.autograd.Function):
         if fused:
             # one launch (csrc/gru_cell.hip): the gate / candidate gradients and the three input-gradient products; gxk for the
             # weight gradients below
-            from . import ops
-            from .dense import WEIGHT_NT, weight_image
             im_h = weight_image([K[:, 2 * u:], U[:, 2 * u:]], WEIGHT_NT, separate=True)
             im_zr = weight_image([K[:, :2 * u], U[:, :2 * u]], WEIGHT_NT, separate=True)
             gxk = torch.empty((V, 3 * u), dtype=torch.float32, device=h.device)
@@ -274,7 +223,6 @@ class _GRUCellFn(torch.autograd.Function):
             if all(ctx.needs_input_grad[2:5]):
                 # the three products over the same rows and the bias gradient (the column sums of gxk, which the first product
                 # reads anyway): one launch pair instead of four products, four reductions and two column-sum launches
-                from .dense import tn_stream_group, tn_stream_group_ok
                 gK = torch.empty((x.shape[1], 3 * u), dtype=torch.float32, device=h.device)
                 gU = torch.empty((u, 3 * u), dtype=torch.float32, device=h.device)
                 products = [(x, gxk, gK), (h, grec, gU[:, :2 * u]), (rh, gq, gU[:, 2 * u:])]
@@ -305,9 +253,6 @@ class _GRUCellFn(torch.autograd.Function):
 
 def _gru_cell_kernel_ok(x, h, K, U, b, act: int) -> bool:
     """The one-kernel forward (relgnn_gru_cell_fwd_xf32): the limb route, 128 units over 128-wide inputs, rows it can read in place."""
-    from . import _lib
-    from .config import settings as cfg
-    from .dense import WEIGHT_NN, weight_image_ok
     u = h.shape[1]
     if not (cfg.limb_gemm and cfg.gru_cell == "1" and h.is_cuda and 0 < h.shape[0] <= (1 << 21) and h.shape[0] * h.stride(0) < (1 << 30) and K.shape[0] == x.shape[1]
             and (b is None or (b.is_contiguous() and b.data_ptr() % 16 == 0))
@@ -326,7 +271,7 @@ def _gru_cell_fused_ok(x, h, K, U, b, u: int) -> bool:
             and 2 * u * u <= 256 * 256 and 0 < h.shape[0] <= (1 << 18))
 
 
-_GRU_FUSABLE = {None: 0, "linear": 0, "tanh": 1, "relu": 2, "leaky_relu": 3, "elu": 4, "selu": 5}
+_GRU_FUSABLE = {None: _lib.ACT_LINEAR, **{a.name: a.id for a in ACTIVATIONS if a.id in FUSABLE_ACTS}}
 
 
 class _GatedUnit:

@@ -2,8 +2,8 @@
 input gradient, and the one helper (fork) every autograd function that does so goes through.  The main stream joins the side stream
 at the end of the layer's backward() or, inside train_step (deferred_weight_gradient_join), once behind the whole backward
 (join_deferred); deferred_targets_ok states when the second is safe, join_deferred verifies afterwards that autograd kept to it.
-Users: ops._TypedLinearPanel (one pair table or both of a layer), _AggregateThenTransform (either join), dense._DenseFn, _DenseMultiFn and
-utils._GRUCellFn (deferred only).  ops re-exports the names below."""
+Users: ops.typed._TypedLinearPanel (one pair table or both of a layer), ops.rgcn._AggregateThenTransform (either join),
+dense._DenseFn, _DenseMultiFn and utils._GRUCellFn (deferred only).  ops re-exports the public names below."""
 import torch
 
 from .config import settings as _cfg
