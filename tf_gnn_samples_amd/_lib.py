@@ -1,5 +1,5 @@
 """ctypes binding of librelgnn.so (C ABI: include/relgnn.h, include/relgnn_dropout.h, include/relgnn_predict.h,
-include/relgnn_parallel.h).
+include/relgnn_parallel.h, include/relgnn_sparse_features.h).
 
 This is the ONLY compute backend of the package.  There is no CPU / eager-PyTorch fallback:
 if the HIP library is missing, or a tensor is not a float32/int32 CUDA(HIP) tensor, the
@@ -202,6 +202,15 @@ _PARALLEL_SIGNATURES = {
     "relgnn_mt_pack_scaled_f32": (ctypes.c_int, [_ptr, _ptr, _c_i32, _c_f32, _ptr, _ptr]),
 }
 
+# include/relgnn_sparse_features.h (CSR rows times a row table: the citation task's sparse node features): its own table too
+_SPARSE_FEATURES_SIGNATURES = {
+    "relgnn_csr_project_supported": (ctypes.c_int, [_c_i32]),
+    "relgnn_csr_project_split_above": (_c_i64, []),
+    "relgnn_csr_project_slab": (_c_i64, []),
+    "relgnn_csr_project_f32": (ctypes.c_int, [_c_i32, _ptr, _c_i64, _ptr, _ptr, _c_i64, _ptr, _c_i64, _c_i64, _ptr, _c_i64, _c_i32, _ptr,
+                                              _c_i64, _ptr, _c_i64, _ptr, _c_i64, _ptr, _c_i64, _ptr]),
+}
+
 _lib = None
 
 
@@ -220,7 +229,7 @@ def load_library():
             "g.build()'` (needs hipcc). There is no CPU fallback for this path." % LIB_PATH)
     lib = ctypes.CDLL(str(LIB_PATH))
     for name, (restype, argtypes) in list(_SIGNATURES.items()) + list(_DROPOUT_SIGNATURES.items()) + list(_PREDICT_SIGNATURES.items()) \
-            + list(_PARALLEL_SIGNATURES.items()):
+            + list(_PARALLEL_SIGNATURES.items()) + list(_SPARSE_FEATURES_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the symbol is not exported
         fn.restype = restype
         fn.argtypes = argtypes
@@ -247,6 +256,11 @@ def predict_signatures():
 def parallel_signatures():
     """The entry points of include/relgnn_parallel.h (not part of exported_signatures() either)."""
     return dict(_PARALLEL_SIGNATURES)
+
+
+def sparse_features_signatures():
+    """The entry points of include/relgnn_sparse_features.h (not part of exported_signatures() either)."""
+    return dict(_SPARSE_FEATURES_SIGNATURES)
 
 
 def status_string(code: int) -> str:

@@ -27,6 +27,7 @@ from ..graph import as_rel_graph, check_pending_graph_errors
 from ..tasks import DataFold, DeviceBatch, Sparse_Graph_Task
 from ..tasks.batcher import NativeBatcher
 from ..tasks.resident import ResidentDataset
+from ..tasks.sparse_features import SparseRows
 from ..utils import get_activation, layer_norm, layer_norm_scope
 from ..variables import VariableStore
 from .data_parallel import data_parallel
@@ -205,6 +206,19 @@ class Sparse_Graph_Model(ABC):
         vs.create_all(self._task_scope, self.task.output_variables(h_dim))
         self.log_line("Model has %i parameters." % vs.num_parameters())
 
+    def _project_input(self, initial_node_features, w, act_id: int, sole_consumer: bool) -> torch.Tensor:
+        """:165-170: the unnamed Dense in front of the first layer, when the feature size differs from hidden_size.  Features that
+        a task keeps sparse (tasks/sparse_features.py, the citation task's sparse_node_features mode) gather rows of the same
+        `dense/kernel` instead (ops.csr_rows_project); without a projection they are densified on the device."""
+        has_projection = self.task.initial_node_feature_size != self.params['hidden_size']
+        if isinstance(initial_node_features, SparseRows):
+            if has_projection:
+                return ops.csr_rows_project(initial_node_features, w["dense/kernel"], act_id)
+            return initial_node_features.to_dense()
+        if has_projection:
+            return dense_act(initial_node_features, w["dense/kernel"], None, act_id, sole_consumer=sole_consumer)
+        return initial_node_features
+
     def compute_final_node_representations(self, initial_node_features: torch.Tensor,
                                            adjacency_lists, type_to_num_incoming_edges: torch.Tensor,
                                            dropout_keep_prob: float = 1.0) -> torch.Tensor:
@@ -238,11 +252,7 @@ class Sparse_Graph_Model(ABC):
                 return next_layer_idx == 0 and res_every >= num_layers
             return True
 
-        if self.task.initial_node_feature_size != p['hidden_size']:
-            cur_node_representations = dense_act(initial_node_features, w["dense/kernel"], None, act_id,
-                                                 sole_consumer=only_the_next_layer_reads(0))
-        else:
-            cur_node_representations = initial_node_features
+        cur_node_representations = self._project_input(initial_node_features, w, act_id, only_the_next_layer_reads(0))
         last_residual_representations = None          # (the reference's zeros_like is overwritten at layer 0 before any use)
         pass_state = None
         if ops.fused_dropout_on(dropout_keep_prob) and getattr(self, "dropout_state", None) is not None:

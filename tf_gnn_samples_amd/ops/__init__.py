@@ -11,6 +11,7 @@ from .edge import (_BlockedLinear, _fill_rows, _FusedEdgeMessages, _PairMaterial
 from .rgat import rgat_attention, rgat_layer_attention, rgat_scores_supported  # noqa: F401
 from .rgcn import _AggregateThenTransform, _rgcn_fused, _weight_gradient, aggregate_acc64, aggregate_then_transform  # noqa: F401
 from .rgdcn import rgdcn_apply, rgdcn_apply_supported  # noqa: F401
-from .segment import (SegmentPlanCache, _seg_reduce_raw, acc64_supported, aggregation_mode_id, message_act_reduce, rowmax_supported,  # noqa: F401
-                      seg_gather_reduce, unsorted_segment_max, unsorted_segment_mean, unsorted_segment_sqrt_n, unsorted_segment_sum)
+from .segment import (ROUTES, SegmentPlanCache, _csr_project_raw, _seg_reduce_raw, acc64_supported, aggregation_mode_id,  # noqa: F401
+                      csr_project_supported, csr_rows_project, message_act_reduce, rowmax_supported, seg_gather_reduce,
+                      unsorted_segment_max, unsorted_segment_mean, unsorted_segment_sqrt_n, unsorted_segment_sum)
 from .typed import _typed_panel_ok, _TypedLinearPanel, typed_linear, typed_linear_pair  # noqa: F401

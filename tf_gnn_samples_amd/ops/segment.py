@@ -5,13 +5,14 @@ get_aggregation_function (utils/utils.py:23-33), same argument names and meaning
 `seg_gather_reduce` is the fused form the layer functions use: the gather
 (tf.nn.embedding_lookup), the per-message scale and the segment reduction in ONE kernel.
 """
+import warnings
 from typing import Optional
 
 import torch
 
 from .. import _lib
 from ..activations import FUSABLE_ACTS as _FUSABLE_ACTS, activation_id, activation_of_id, apply_activation, get_activation
-from ..dense import act_bwd_from_output
+from ..dense import act_bwd_from_output, dense_act
 from ..graph import GatherReducePlan, SplitPlan, build_segment_plan, split_plan_of
 
 _MODE_IDS = {
@@ -206,6 +207,92 @@ def unsorted_segment_sqrt_n(data, segment_ids, num_segments):
 def unsorted_segment_max(data, segment_ids, num_segments):
     """Empty segments yield float32 lowest (-3.4028235e38), as TF does."""
     return _unsorted_segment("max", data, segment_ids, num_segments)
+
+
+# ---- CSR rows times a row table: sparse node features through the input projection (csrc/csr_project.hip) --------------------
+ROUTES = {"csr_project": None}       # which implementation the last csr_rows_project took: "hip", "composition" or "dense"
+_WARNED = set()
+
+
+def csr_project_supported(n: int) -> bool:
+    """Row widths relgnn_csr_project_f32 takes (relgnn_csr_project_supported, restated: asked before the library is loaded)."""
+    return n % 4 == 0 and 4 <= n <= 1024
+
+
+def _csr_project_raw(structure, table, act: int, y=None):
+    """One launch of relgnn_csr_project_f32 over `structure` (rowptr / col / val / slabs / combos of one device): the forward with
+    the epilogue `act` (y None), or the gradient form that scales every gathered row of `table` by act'(y row)."""
+    n = table.shape[1]
+    def float4_rows(t):                   # dense rows on 16-byte boundaries, any leading dimension; anything else is copied
+        ok = t.stride(1) == 1 and t.stride(0) % 4 == 0 and t.stride(0) >= t.shape[1] and t.data_ptr() % 16 == 0
+        return t if ok else t.contiguous()
+    table = float4_rows(table)
+    y = float4_rows(y) if y is not None else None
+    out = torch.empty((structure.num_rows, n), dtype=torch.float32, device=table.device)
+    ws = torch.empty((structure.ws_rows, n), dtype=torch.float32, device=table.device) if structure.ws_rows else None
+    _lib.launch("relgnn_csr_project_f32", act, _lib.ptr(structure.rowptr), structure.num_rows, _lib.ptr(structure.col),
+                _lib.ptr(structure.val), structure.nnz, _lib.ptr(table, rows_strided=True), table.shape[0], max(table.stride(0), n),
+                _lib.ptr(y, rows_strided=True), max(y.stride(0), n) if y is not None else 0, n,
+                _lib.ptr(structure.slabs) if structure.slabs.shape[0] else None, structure.slabs.shape[0],
+                _lib.ptr(structure.combos) if structure.combos.shape[0] else None, structure.combos.shape[0], _lib.ptr(ws),
+                structure.ws_rows, _lib.ptr(out), n)
+    return out
+
+
+class _CsrRowsProject(torch.autograd.Function):
+    """out = act(rows @ weight) for a CSR container: one launch forward, one launch over the transposed structure backward
+    (dW[f] = sum_v X[v, f] * dOut[v] * act'(out[v])).  No gradient towards the container: the features are data."""
+
+    @staticmethod
+    def forward(ctx, weight, rows, act: int):
+        out = _csr_project_raw(rows.rows, weight, act)
+        ctx.rows, ctx.act = rows, act
+        ctx.save_for_backward(out if act != _lib.ACT_LINEAR else None)
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        (out,) = ctx.saved_tensors
+        return _csr_project_raw(ctx.rows.transposed, gout, ctx.act, out), None, None
+
+
+def _csr_rows_composition(rows, weight, act: int):
+    """The same sum in torch: index_select, scale, index_add_ in ascending entry order (any device and dtype)."""
+    s = rows.rows
+    terms = weight.index_select(0, s.col.long()) * s.val.to(weight.dtype).unsqueeze(1)
+    out = torch.zeros((s.num_rows, weight.shape[1]), dtype=weight.dtype, device=weight.device).index_add_(0, s.row_ids(), terms)
+    return apply_activation(activation_of_id(act), out)
+
+
+def csr_rows_project(rows, weight: torch.Tensor, act_id: int = _lib.ACT_LINEAR) -> torch.Tensor:
+    """act(X @ weight) [V, n] for sparse features `rows` (tasks.sparse_features.SparseRows, [V, F]) and weight [F, n].
+
+    float32 GPU operands of a width the kernel takes run csrc/csr_project.hip (gelu: the linear kernel, then the torch activation,
+    as the Dense route); any other GPU shape densifies the container on the device and takes the Dense route, with one warning;
+    CPU tensors and other dtypes take the torch composition.  ROUTES["csr_project"] says which.  A column that is not stored
+    contributes nothing, even against a non-finite weight (the dense product gives 0 * inf = NaN)."""
+    if getattr(rows, "requires_grad", False) or rows.rows.val.requires_grad:
+        raise ValueError("csr_rows_project: the feature container requires grad, but the features are data: no gradient towards "
+                         "them exists")
+    if weight.dim() != 2 or weight.shape[0] != rows.shape[1]:
+        raise ValueError("weight must be [%d, n], got %s" % (rows.shape[1], tuple(weight.shape)))
+    if rows.device != weight.device:
+        raise ValueError("csr_rows_project: the features live on %s, the weight on %s" % (rows.device, weight.device))
+    n = weight.shape[1]
+    if not (weight.is_cuda and weight.dtype == torch.float32):
+        ROUTES["csr_project"] = "composition"
+        return _csr_rows_composition(rows, weight, act_id)
+    if not csr_project_supported(n):
+        if n not in _WARNED:
+            _WARNED.add(n)
+            warnings.warn("csr_rows_project: rows of %d floats are not taken by the CSR kernel (a multiple of 4 up to 1024 is); "
+                          "the features are densified on the device for the Dense route" % n)
+        ROUTES["csr_project"] = "dense"
+        return dense_act(rows.to_dense(), weight, None, act_id)
+    ROUTES["csr_project"] = "hip"
+    if act_id in _FUSABLE_ACTS:
+        return _CsrRowsProject.apply(weight, rows, act_id)
+    return apply_activation(activation_of_id(act_id), _CsrRowsProject.apply(weight, rows, _lib.ACT_LINEAR))
 
 
 def _mode_factor(graph, mode: int):

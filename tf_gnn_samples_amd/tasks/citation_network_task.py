@@ -5,6 +5,12 @@ ONE graph is always the whole batch: the three folds share the graph and the row
 class labels and the 0/1 node mask.  The output head is a bias-free Dense followed by a masked sparse softmax cross-entropy and an
 accuracy count; on the GPU that is one kernel pair (csrc/train_utils.hip: relgnn_softmax_ce_stats / relgnn_softmax_ce_bwd).
 Without the datasets `load_synthetic` fills the folds with a Cora-shaped graph.
+
+Task parameter `sparse_node_features` (False by default; read with params.get, not part of default_params(), which is pinned against
+the reference's): the features stay sparse from the file to the input projection.  The folds then share ONE tasks.sparse_features
+.SparseRows under `node_features` (no dense [V, F] array is ever built), every device holds one copy of it, the input pipelines
+carry a float32 [V, 1] stand-in under `initial_node_features`, and compute_initial_node_features hands the model the device's
+SparseRows, which its input projection takes through ops.csr_rows_project (csrc/csr_project.hip).
 """
 import os
 import pickle
@@ -19,6 +25,7 @@ from ..dense import dense, mark_zero_padded
 from ..parallel import refuse_single_graph_task
 from ..predict import predict_softmax
 from .resident import ResidentDataset
+from .sparse_features import SparseRows, node_stand_in, random_rows, resident_copy
 from .sparse_graph_task import DataFold, MinibatchData, Sparse_Graph_Task
 
 
@@ -26,7 +33,7 @@ class CitationData(NamedTuple):
     """One fold = the whole graph (the reference's CitationData, :12, under the attribute names tasks/batcher.py flattens)."""
     adjacency_lists: List[np.ndarray]                      # [self loops, both directions of every (node, neighbour)], int32 [E_l, 2]
     type_to_node_to_num_incoming_edges: np.ndarray         # int32 [2, V]
-    node_features: np.ndarray                              # float32 [V, F], row-normalised
+    node_features: Any                                     # float32 [V, F], row-normalised (sparse_node_features: a SparseRows)
     labels: np.ndarray                                     # int32 [V]
     mask: np.ndarray                                       # float32 [V], 1 = the node counts in this fold
 
@@ -180,6 +187,7 @@ class Citation_Network_Task(Sparse_Graph_Task):
     def __init__(self, params: Dict[str, Any]):
         super().__init__(params)
         self._resident_batches = weakref.WeakKeyDictionary()      # resident fold -> its one assembled batch (released with the fold)
+        self._device_rows = weakref.WeakKeyDictionary()           # host SparseRows -> {device: its one copy there}
         self.__num_edge_types = 2
         self.__initial_node_feature_size = 0
         self.__num_output_classes = 0
@@ -194,6 +202,10 @@ class Citation_Network_Task(Sparse_Graph_Task):
         self.params = metadata.get('params', self.params)
         self.__initial_node_feature_size = metadata['initial_node_feature_size']
         self.__num_output_classes = metadata['num_output_classes']
+
+    @property
+    def sparse_node_features(self) -> bool:
+        return bool(self.params.get('sparse_node_features', False))
 
     @property
     def num_edge_types(self) -> int:
@@ -222,8 +234,11 @@ class Citation_Network_Task(Sparse_Graph_Task):
         graph, features, label_tables, masks = load_planetoid(data_path, self.params['data_kind'])
         self.__initial_node_feature_size = features.shape[1]
         self.__num_output_classes = label_tables[0].shape[1]
-        # the reference feeds its array into a float32 placeholder: the cast happens once, here
-        features = np.ascontiguousarray(row_normalise(features), dtype=np.float32)
+        if self.sparse_node_features:
+            features = SparseRows.row_normalised(features)            # one container for the three folds; never dense
+        else:
+            # the reference feeds its array into a float32 placeholder: the cast happens once, here
+            features = np.ascontiguousarray(row_normalise(features), dtype=np.float32)
         adjacency, degrees = graph_to_edge_lists(graph)
         return tuple([self._fold(adjacency, degrees, features, np.argmax(table, axis=1), mask)]
                      for table, mask in zip(label_tables, masks))
@@ -239,15 +254,23 @@ class Citation_Network_Task(Sparse_Graph_Task):
                        seed: int = 0) -> None:
         """Cora-shaped stand-in for load_data (no dataset on the machines): 2708 nodes, 1433 binary bag-of-words features at Cora's
         density, row-normalised, 7 classes, ~5.4 k neighbour-list entries = 10.8 k directed edges + self loops; folds of
-        140 / 500 / 1000 nodes laid out as Planetoid's (first, next, last).  The test fold is kept as `synthetic_test_data`."""
+        140 / 500 / 1000 nodes laid out as Planetoid's (first, next, last).  The test fold is kept as `synthetic_test_data`.
+        sparse_node_features: the words of every row are drawn directly (a Binomial(num_features, feature_density) count of uniform
+        draws per row, a word drawn twice counted once), no [V, F] array is built, and the folds share one SparseRows."""
         rng = np.random.default_rng(seed)
         graph = {}
         lengths = rng.poisson(neighbours_per_node, size=num_nodes)
         for node in range(num_nodes):
             graph[node] = rng.integers(0, num_nodes, size=int(lengths[node])).tolist()
-        bag = (rng.random((num_nodes, num_features)) < feature_density).astype(np.float32)
-        row_sum = bag.sum(1, keepdims=True)
-        features = np.divide(bag, row_sum, out=np.zeros_like(bag), where=row_sum > 0)
+        if self.sparse_node_features:
+            rowptr, col = random_rows(rng, num_nodes, num_features, rng.binomial(num_features, feature_density, size=num_nodes))
+            words = np.diff(rowptr)
+            features = SparseRows(rowptr, col, np.repeat(np.float32(1.0) / np.maximum(words, 1).astype(np.float32), words),
+                                  (num_nodes, num_features))
+        else:
+            bag = (rng.random((num_nodes, num_features)) < feature_density).astype(np.float32)
+            row_sum = bag.sum(1, keepdims=True)
+            features = np.divide(bag, row_sum, out=np.zeros_like(bag), where=row_sum > 0)
         labels = rng.integers(0, num_classes, size=num_nodes)
         adjacency, degrees = graph_to_edge_lists(graph)
         self.__initial_node_feature_size, self.__num_output_classes = num_features, num_classes
@@ -319,8 +342,9 @@ class Citation_Network_Task(Sparse_Graph_Task):
         """Exactly one minibatch per epoch, the whole graph; max_nodes_per_batch is not consulted (:157-177)."""
         refuse_single_graph_task(self.name())
         fold = next(iter(data))
+        sparse = isinstance(fold.node_features, SparseRows)
         feed = {
-            'initial_node_features': fold.node_features,
+            'initial_node_features': node_stand_in(len(fold.node_features)) if sparse else fold.node_features,
             'adjacency_lists': list(fold.adjacency_lists),
             'type_to_num_incoming_edges': fold.type_to_node_to_num_incoming_edges,
             'num_graphs': 1,
@@ -328,8 +352,29 @@ class Citation_Network_Task(Sparse_Graph_Task):
             'mask': fold.mask,
             'out_layer_dropout_keep_prob': self._out_keep(data_fold),
         }
+        if sparse:
+            feed['sparse_node_features'] = fold.node_features       # (not an array: DeviceBatch keeps it as it is, in `extra`)
         yield MinibatchData(feed_dict=feed, num_graphs=1, num_nodes=fold.node_features.shape[0],
                             num_edges=sum(len(a) for a in fold.adjacency_lists))
+
+    def make_graph_store(self, data):
+        """A fold with sparse features is flattened with the per-node stand-in in the table's place; the store remembers the
+        container (`sparse_rows`) for make_native_minibatch_iterator."""
+        folds = list(data)
+        rows = folds[0].node_features if folds and isinstance(folds[0].node_features, SparseRows) else None
+        if rows is None:
+            return super().make_graph_store(folds)
+        store = super().make_graph_store([f._replace(node_features=node_stand_in(len(f.node_features))) for f in folds])
+        store.sparse_rows = rows
+        return store
+
+    def compute_initial_node_features(self, batch, weights):
+        """The batch's feature table, or in the sparse mode the SparseRows on the batch's device: one copy per device, kept weakly
+        with the host container."""
+        rows = batch.extra.get('sparse_node_features')
+        if rows is None:
+            return batch.initial_node_features
+        return resident_copy(self._device_rows, rows, batch.initial_node_features.device)
 
     def make_native_minibatch_iterator(self, batcher, data_fold: DataFold, max_nodes_per_batch: int,
                                        rng: Optional[np.random.RandomState] = None):
@@ -341,6 +386,9 @@ class Citation_Network_Task(Sparse_Graph_Task):
             raise ValueError("a citation-network fold is ONE graph; got %d" % batcher.store.num_graphs)
         keep = self._out_keep(data_fold)
         batcher.constants['out_layer_dropout_keep_prob'] = keep
+        rows = getattr(batcher.store, "sparse_rows", None)
+        if rows is not None:
+            batcher.constants['sparse_node_features'] = rows
         ids = np.zeros(1, dtype=np.int64)
         if isinstance(batcher, ResidentDataset):
             batch = self._resident_batches.get(batcher)

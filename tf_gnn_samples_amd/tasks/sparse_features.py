@@ -1,0 +1,226 @@
+"""Sparse node features: a [V, F] float32 matrix as CSR plus its transpose, the operand of ops.csr_rows_project
+(csrc/csr_project.hip, include/relgnn_sparse_features.h).
+
+The citation-network task's `sparse_node_features` mode keeps the bag-of-words features in this container instead of a dense
+[V, F] table: the three folds share ONE SparseRows, every device holds one copy of it, and the input projection gathers rows of the
+weight matrix.  The transpose (the structure the weight gradient runs over) and the long-row plans of both structures are built once,
+on the host, when the container is made; so is the validation the kernels rely on.
+"""
+from typing import Optional, Tuple
+
+import numpy as np
+import torch
+
+# The summation order of include/relgnn_sparse_features.h (relgnn_csr_project_split_above / relgnn_csr_project_slab; the library
+# is not loaded to build a container, tests/test_gpu_sparse_features.py holds the two against each other)
+SPLIT_ABOVE = 128
+SLAB = 512
+_INT32_MAX = 2 ** 31 - 1
+
+
+def split_plan(rowptr: np.ndarray) -> Tuple[np.ndarray, np.ndarray, int]:
+    """(slabs int32 [S, 4], combos int32 [C, 3], workspace rows) of include/relgnn_sparse_features.h for one row-pointer array:
+    rows of more than SPLIT_ABOVE entries in slabs of SLAB; a row of one slab is written directly (dest -1), the slabs of a longer
+    row go to consecutive workspace rows."""
+    rowptr = np.asarray(rowptr, np.int64)
+    length = np.diff(rowptr)
+    long_rows = np.flatnonzero(length > SPLIT_ABOVE)
+    if not len(long_rows):
+        return np.zeros((0, 4), np.int32), np.zeros((0, 3), np.int32), 0
+    per_row = (length[long_rows] + SLAB - 1) // SLAB
+    row_of_slab = np.repeat(long_rows, per_row)
+    first_slab = np.concatenate([[0], np.cumsum(per_row)])[:-1]
+    index_in_row = np.arange(int(per_row.sum())) - np.repeat(first_slab, per_row)
+    begin = rowptr[row_of_slab] + index_in_row * SLAB
+    end = np.minimum(begin + SLAB, rowptr[row_of_slab + 1])
+    several = per_row > 1
+    ws_first = np.concatenate([[0], np.cumsum(np.where(several, per_row, 0))])[:-1]
+    dest = np.where(np.repeat(several, per_row), np.repeat(ws_first, per_row) + index_in_row, -1)
+    slabs = np.stack([row_of_slab, begin, end, dest], axis=1).astype(np.int32)
+    combos = np.stack([long_rows[several], ws_first[several], per_row[several]], axis=1).astype(np.int32).reshape(-1, 3)
+    return np.ascontiguousarray(slabs), np.ascontiguousarray(combos), int(per_row[several].sum())
+
+
+class CsrStructure:
+    """rowptr int32 [R + 1], col int32 [nnz], val float32 [nnz] and the long-row plan, as tensors of one device."""
+
+    def __init__(self, rowptr, col, val, slabs, combos, ws_rows: int, num_cols: int):
+        self.rowptr, self.col, self.val, self.slabs, self.combos = rowptr, col, val, slabs, combos
+        self.ws_rows, self.num_cols = int(ws_rows), int(num_cols)
+
+    @property
+    def num_rows(self) -> int:
+        return int(self.rowptr.shape[0]) - 1
+
+    @property
+    def nnz(self) -> int:
+        return int(self.col.shape[0])
+
+    def row_ids(self) -> torch.Tensor:
+        """The row of every entry, int64 [nnz] (the torch composition's index_add_ target)."""
+        counts = (self.rowptr[1:] - self.rowptr[:-1]).long()
+        return torch.repeat_interleave(torch.arange(self.num_rows, device=self.rowptr.device), counts)
+
+    def to(self, device) -> "CsrStructure":
+        move = lambda t: t.to(device)
+        return CsrStructure(move(self.rowptr), move(self.col), move(self.val), move(self.slabs), move(self.combos), self.ws_rows,
+                            self.num_cols)
+
+
+def _validated(rowptr, col, val, shape):
+    V, F = int(shape[0]), int(shape[1])
+    rowptr, col, val = np.asarray(rowptr), np.asarray(col), np.asarray(val)
+    if V < 0 or F < 0:
+        raise ValueError("SparseRows: negative shape %r" % (shape,))
+    if rowptr.ndim != 1 or col.ndim != 1 or val.ndim != 1 or rowptr.dtype.kind not in "iu" or col.dtype.kind not in "iu":
+        raise ValueError("SparseRows: rowptr, col and val are one-dimensional, rowptr and col integers")
+    if len(rowptr) != V + 1:
+        raise ValueError("SparseRows: rowptr has %d entries, expected %d" % (len(rowptr), V + 1))
+    nnz = len(col)
+    if len(val) != nnz:
+        raise ValueError("SparseRows: %d column ids but %d values" % (nnz, len(val)))
+    if nnz >= _INT32_MAX or V >= _INT32_MAX or F >= _INT32_MAX:
+        raise ValueError("SparseRows: the structure is indexed with 32 bits (nnz, rows and columns below 2^31 - 1)")
+    rowptr = rowptr.astype(np.int64)
+    if rowptr[0] != 0 or rowptr[-1] != nnz or (np.diff(rowptr) < 0).any():
+        raise ValueError("SparseRows: rowptr must rise from 0 to nnz = %d without a step down" % nnz)
+    col = col.astype(np.int64)
+    if nnz and (col.min() < 0 or col.max() >= F):
+        raise ValueError("SparseRows: column id outside [0, %d)" % F)
+    if nnz > 1:
+        rising = col[1:] > col[:-1]
+        rising[rowptr[1:-1][(rowptr[1:-1] > 0) & (rowptr[1:-1] < nnz)] - 1] = True      # the first entry of a row follows another row
+        if not rising.all():
+            raise ValueError("SparseRows: the column ids of a row must be sorted and unique")
+    val = np.ascontiguousarray(val, dtype=np.float32)
+    if (val == 0).any():
+        raise ValueError("SparseRows: explicit zeros are not stored (eliminate_zeros)")
+    return rowptr, col, val
+
+
+def _structure(rowptr, col, val, num_cols) -> CsrStructure:
+    slabs, combos, ws_rows = split_plan(rowptr)
+    t = torch.from_numpy                                   # (np.array copies: the container owns its arrays)
+    return CsrStructure(t(np.array(rowptr, dtype=np.int32)), t(np.array(col, dtype=np.int32)), t(np.array(val, dtype=np.float32)),
+                        t(slabs), t(combos), ws_rows, num_cols)
+
+
+class SparseRows:
+    """A [V, F] float32 matrix in CSR (`rows`) and in CSR of its transpose (`transposed`: F rows over V columns), both with
+    ascending ids inside a row and built once on the host with a stable sort.  The structure is validated here — monotone rowptr,
+    0 <= col < F, sorted and unique columns per row, no explicit zeros — and raises ValueError: the kernels trust what they read."""
+
+    requires_grad = False            # the features are data
+
+    def __init__(self, rowptr, col, val, shape, _structures=None):
+        self.shape = (int(shape[0]), int(shape[1]))
+        if _structures is not None:                       # (to(): already validated)
+            self.rows, self.transposed = _structures
+            return
+        rowptr, col, val = _validated(rowptr, col, val, shape)
+        V, F = self.shape
+        self.rows = _structure(rowptr, col, val, F)
+        # the transpose: entries by (column, row); a stable sort on the column keeps the rows of a column ascending
+        order = np.argsort(col, kind="stable")
+        row_of = np.repeat(np.arange(V, dtype=np.int64), np.diff(rowptr))
+        rowptr_t = np.zeros(F + 1, np.int64)
+        np.cumsum(np.bincount(col, minlength=F), out=rowptr_t[1:])
+        self.transposed = _structure(rowptr_t, row_of[order], val[order], V)
+
+    # ---- makers ----
+    @classmethod
+    def from_scipy(cls, matrix) -> "SparseRows":
+        """Any scipy sparse matrix: duplicates summed, explicit zeros dropped, columns sorted, values cast to float32."""
+        import scipy.sparse as sp
+        m = sp.csr_matrix(matrix, copy=True)
+        m.sum_duplicates()
+        m = m.astype(np.float32)
+        m.eliminate_zeros()
+        m.sort_indices()
+        return cls(m.indptr, m.indices, m.data, m.shape)
+
+    @classmethod
+    def row_normalised(cls, matrix) -> "SparseRows":
+        """tasks.citation_network_task.row_normalise without the dense table: the same diags(reciprocal).dot(features), kept
+        sparse, then eliminate_zeros, sort_indices and the cast to float32 — every stored value is the dense table's entry bit
+        for bit."""
+        import scipy.sparse as sp
+        row_sum = np.array(matrix.sum(1))
+        with np.errstate(divide="ignore"):
+            reciprocal = np.power(row_sum, -1).flatten()
+        reciprocal[np.isinf(reciprocal)] = 0.
+        m = sp.csr_matrix(sp.diags(reciprocal).dot(matrix))
+        m.sum_duplicates()
+        m.eliminate_zeros()
+        m.sort_indices()
+        m = m.astype(np.float32)
+        m.eliminate_zeros()                                # (a value that the cast flushed to zero is not stored either)
+        return cls(m.indptr, m.indices, m.data, m.shape)
+
+    # ---- what a feature table answers ----
+    def __len__(self) -> int:
+        return self.shape[0]
+
+    @property
+    def nnz(self) -> int:
+        return self.rows.nnz
+
+    @property
+    def device(self) -> torch.device:
+        return self.rows.val.device
+
+    @property
+    def dtype(self) -> torch.dtype:
+        return self.rows.val.dtype
+
+    @property
+    def is_cuda(self) -> bool:
+        return self.rows.val.is_cuda
+
+    def to(self, device) -> "SparseRows":
+        if torch.device(device) == self.device:
+            return self
+        return SparseRows(None, None, None, self.shape, _structures=(self.rows.to(device), self.transposed.to(device)))
+
+    def to_dense(self) -> torch.Tensor:
+        """The [V, F] float32 table on the container's device."""
+        out = torch.zeros(self.shape, dtype=torch.float32, device=self.device)
+        if self.nnz:
+            out[self.rows.row_ids(), self.rows.col.long()] = self.rows.val
+        return out
+
+    def record_stream(self, stream) -> None:
+        pass                                               # (a fold-lifetime table: never returned to the allocator under a batch)
+
+
+def node_stand_in(num_nodes: int) -> np.ndarray:
+    """The per-node payload the input pipelines carry under `initial_node_features` in place of the table: float32 [V, 1] zeros
+    (the pipelines read its length for the node count, DeviceBatch.wait_ready its device)."""
+    return np.zeros((int(num_nodes), 1), np.float32)
+
+
+def random_rows(rng, num_rows: int, num_cols: int, per_row, draw=None) -> Tuple[np.ndarray, np.ndarray]:
+    """(rowptr, col) of a structure whose row r holds per_row[r] draws of a column id (uniform, or draw(size) -> ids), ascending,
+    a column drawn twice for a row counted once: drawn per entry, never through a [rows, cols] array."""
+    per_row = np.asarray(per_row, np.int64)
+    row_of = np.repeat(np.arange(num_rows, dtype=np.int64), per_row)
+    ids = rng.integers(0, num_cols, size=len(row_of)) if draw is None else np.asarray(draw(len(row_of)), np.int64)
+    key = np.unique(row_of * np.int64(num_cols) + ids)
+    rowptr = np.zeros(num_rows + 1, np.int64)
+    np.cumsum(np.bincount(key // num_cols, minlength=num_rows), out=rowptr[1:])
+    return rowptr, key % num_cols
+
+
+def resident_copy(cache, rows: Optional[SparseRows], device) -> Optional[SparseRows]:
+    """The one copy of `rows` on `device`, kept in `cache` (a WeakKeyDictionary: released with the host container)."""
+    if rows is None:
+        return None
+    device = torch.device(device)
+    if device.type == "cuda" and device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    if rows.device == device:
+        return rows
+    per_device = cache.setdefault(rows, {})
+    if device not in per_device:
+        per_device[device] = rows.to(device)
+    return per_device[device]
