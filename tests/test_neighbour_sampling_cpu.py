@@ -1,0 +1,249 @@
+"""Neighbour sampling without a GPU: the properties of the rule as tests/neighbour_sampling_reference.py states it, its uniformity,
+the epoch's seed batches, the task parameter's validation and refusals, checkpoint metadata, the epoch's accuracy line, the header."""
+import ctypes
+import re
+import sys
+from pathlib import Path
+
+import numpy as np
+import pytest
+import torch
+
+HERE = Path(__file__).resolve().parent
+if str(HERE) not in sys.path:
+    sys.path.insert(0, str(HERE))
+
+import neighbour_sampling_reference as R  # noqa: E402
+
+
+def small_graph(V=60, L=2, seed=0, hub=200):
+    """Random typed graph with duplicate edges, empty buckets and one hub bucket (node 0, type L - 1) of `hub` entries."""
+    rng = np.random.default_rng(seed)
+    adjacency = []
+    for l in range(L):
+        e = rng.integers(0, V, size=(4 * V, 2))
+        e[:10] = e[10:20]                                               # duplicates
+        e = e[e[:, 1] % 7 != l]                                          # some empty buckets
+        if l == L - 1:
+            e = np.concatenate([e, np.stack([rng.integers(0, V, size=hub), np.zeros(hub, np.int64)], axis=1)])
+        adjacency.append(e.astype(np.int32))
+    return adjacency
+
+
+def sampled(adjacency, V, seeds, fanouts, draw=0, seed=3, replica=0):
+    rowptr, col, _ = R.bucketing(adjacency, V)
+    return R.sample(rowptr, col, V, len(adjacency), seeds, fanouts, draw, seed, replica), rowptr.astype(np.int64), col.astype(np.int64)
+
+
+@pytest.mark.parametrize("fanouts", [[3], [3, 2], [0, 4], [5, 0], [64]])
+def test_reference_properties(fanouts):
+    V, L = 60, 2
+    adjacency = small_graph(V, L)
+    seeds = np.array([0, 5, 17, 18, 59])
+    s, rowptr, col = sampled(adjacency, V, seeds, fanouts)
+    assert np.array_equal(s.nodes, np.sort(s.nodes)) and len(np.unique(s.nodes)) == len(s.nodes)
+    assert np.array_equal(s.nodes[s.seed_mask == 1], np.sort(seeds)) and set(np.unique(s.seed_mask)) <= {0.0, 1.0}
+    expanded = np.concatenate(s.frontiers)
+    assert len(np.unique(expanded)) == len(expanded)                                    # each node is expanded at most once
+    hop_of = {int(t): h for h, f in enumerate(s.frontiers) for t in f}
+    for l in range(L):
+        edges, pos = s.adjacency_lists[l], s.positions[l]
+        src, tgt = s.nodes[edges[:, 0]].astype(np.int64), s.nodes[edges[:, 1]].astype(np.int64)
+        # every sampled edge is an edge of the graph at its stated position
+        assert np.array_equal(col[pos], src * L + l)
+        assert ((rowptr[tgt * L + l] <= pos) & (pos < rowptr[tgt * L + l + 1])).all()
+        # order: hops ascending, targets ascending inside a hop, positions ascending inside a target (hence distinct)
+        keys = [(hop_of[int(t)], int(t), int(p)) for t, p in zip(tgt, pos)]
+        assert keys == sorted(keys) and len(set(keys)) == len(keys)
+        for t, h in hop_of.items():
+            deg = int(rowptr[t * L + l + 1] - rowptr[t * L + l])
+            k = fanouts[h]
+            want = deg if (k == 0 or deg <= k) else k
+            assert int((tgt == t).sum()) == want == int(s.degrees[l, np.searchsorted(s.nodes, t)])
+            if k == 0 or deg <= k:                                                      # everything is taken, in order
+                assert np.array_equal(pos[tgt == t], np.arange(rowptr[t * L + l], rowptr[t * L + l + 1]))
+    leaves = np.setdiff1d(s.nodes, expanded)
+    assert not s.degrees[:, np.searchsorted(s.nodes, leaves)].any()                     # first reached in the last hop: no incoming edge
+    assert all(len(np.intersect1d(s.adjacency_lists[l][:, 1], np.searchsorted(s.nodes, leaves))) == 0 for l in range(L))
+    # the same arguments give the same arrays, another draw gives others
+    again, _, _ = sampled(adjacency, V, seeds[::-1], fanouts)
+    other, _, _ = sampled(adjacency, V, seeds, fanouts, draw=1)
+    for a, b in zip(s.adjacency_lists + [s.nodes, s.degrees, s.seed_mask], again.adjacency_lists + [again.nodes, again.degrees, again.seed_mask]):
+        assert np.array_equal(a, b)
+    if any(0 < k < 64 for k in fanouts):
+        assert any(not np.array_equal(a, b) for a, b in zip(s.positions, other.positions))
+
+
+def test_take_is_the_k_smallest_words_and_differs_by_key_and_counter():
+    w = R.words(300, 11, 1, 5, 7, 0)
+    js = R.take(300, 9, 11, 1, 5, 7, 0)
+    assert len(js) == 9 and (np.diff(js) > 0).all()
+    assert w[js].max() <= np.delete(w, js).min()
+    for other in (R.take(300, 9, 12, 1, 5, 7, 0), R.take(300, 9, 11, 2, 5, 7, 0), R.take(300, 9, 11, 1, 6, 7, 0),
+                  R.take(300, 9, 11, 1, 5, 8, 0), R.take(300, 9, 11, 1, 5, 7, 1)):
+        assert not np.array_equal(js, other)
+    # the key's second word is 0x80000000 | replica: not the dropout kernels' (seed, replica)
+    import philox_reference as P
+    plain = P.philox4x32_10((np.arange(2, dtype=np.uint64), 11, 1, 5), (7, 0))
+    assert not np.array_equal(np.stack(plain)[:, 0], w[:4])
+
+
+def test_rule_is_uniform_over_a_bucket():
+    """A bucket of 8 entries, k = 2, 4096 draws (seed 0, the default): every entry is taken with frequency 0.25 within five standard
+    deviations of a Binomial(4096, 0.25) proportion."""
+    draws = 4096
+    hits = np.zeros(8)
+    for draw in range(draws):
+        hits[R.take(8, 2, 5, 0, draw, 0, 0)] += 1
+    assert hits.sum() == 2 * draws
+    bound = 5 * np.sqrt(0.25 * 0.75 / draws)
+    print("frequencies", hits / draws, "bound", bound)
+    assert (np.abs(hits / draws - 0.25) <= bound).all()
+
+
+def test_epoch_seed_batches():
+    from tf_gnn_samples_amd.tasks.neighbour_sampling import epoch_seed_batches
+    mask = np.zeros(500, np.float32)
+    fold = np.arange(30, 170)
+    mask[fold] = 1.0
+    batches = epoch_seed_batches(mask, 32, seed=4, epoch=0)
+    assert [len(b) for b in batches] == [32, 32, 32, 32, 12]                            # ceil(140 / 32), the last one short
+    assert all(b.dtype == np.int32 and (np.diff(b) > 0).all() for b in batches)
+    assert np.array_equal(np.sort(np.concatenate(batches)), fold)                       # every fold node exactly once
+    same = epoch_seed_batches(mask, 32, seed=4, epoch=0)
+    assert all(np.array_equal(a, b) for a, b in zip(batches, same))
+    for other in (epoch_seed_batches(mask, 32, seed=4, epoch=1), epoch_seed_batches(mask, 32, seed=5, epoch=0)):
+        assert np.array_equal(np.sort(np.concatenate(other)), fold)
+        assert any(not np.array_equal(a, b) for a, b in zip(batches, other))
+    assert [len(b) for b in epoch_seed_batches(mask, 140, 0, 0)] == [140] and [len(b) for b in epoch_seed_batches(mask, 1000, 0, 0)] == [140]
+    with pytest.raises(ValueError):
+        epoch_seed_batches(mask, 0, 0, 0)
+
+
+def _task(**params):
+    from tf_gnn_samples_amd.tasks import Citation_Network_Task
+    return Citation_Network_Task(dict(Citation_Network_Task.default_params(), **params))
+
+
+GOOD = {"fanouts": [5, 5], "seeds_per_batch": 32, "seed": 1}
+
+
+@pytest.mark.parametrize("bad", [
+    {"fanouts": [], "seeds_per_batch": 4}, {"fanouts": [65], "seeds_per_batch": 4}, {"fanouts": [3, -1], "seeds_per_batch": 4},
+    {"fanouts": [1] * 9, "seeds_per_batch": 4}, {"fanouts": [2.5], "seeds_per_batch": 4}, {"fanouts": "3", "seeds_per_batch": 4},
+    {"fanouts": 3, "seeds_per_batch": 4}, {"fanouts": [3], "seeds_per_batch": 0}, {"fanouts": [3]}, {"seeds_per_batch": 4},
+    {"fanouts": [3], "seeds_per_batch": 4, "fanout": 2}, [3, 3], {"fanouts": [True], "seeds_per_batch": 4}])
+def test_bad_parameters_are_value_errors(bad):
+    with pytest.raises(ValueError):
+        _task(sampled_batches=bad)
+
+
+def test_parameter_is_optional_and_refuses_sparse_features():
+    from tf_gnn_samples_amd.tasks import Citation_Network_Task
+    from tf_gnn_samples_amd.tasks.neighbour_sampling import MAX_FANOUT, MAX_HOPS, check_fanouts
+    assert "sampled_batches" not in Citation_Network_Task.default_params()
+    assert _task().sampled_batches is None and _task(sampled_batches=None).sampled_batches is None
+    assert _task(sampled_batches={"fanouts": [0, 64], "seeds_per_batch": 7}).sampled_batches == {"fanouts": [0, 64], "seeds_per_batch": 7, "seed": 0}
+    assert (MAX_FANOUT, MAX_HOPS) == (R.MAX_FANOUT, R.MAX_HOPS) == (64, 8)
+    assert check_fanouts([64] * 8) == [64] * 8
+    with pytest.raises(ValueError, match="sparse_node_features"):
+        _task(sampled_batches=GOOD, sparse_node_features=True)
+
+
+def _cpu_model(task):
+    from tf_gnn_samples_amd.models import RGCN_Model
+    p = RGCN_Model.default_params()
+    p.update(hidden_size=16, graph_num_layers=1, random_seed=1)
+    return RGCN_Model(p, task, device="cpu")
+
+
+def test_a_cpu_model_is_refused_and_so_is_a_captured_step(tmp_path):
+    from tf_gnn_samples_amd.tasks import DataFold, DeviceBatch
+    task = _task(sampled_batches=GOOD)
+    task.load_synthetic(num_nodes=200, num_features=12, num_classes=3, num_train=40, num_valid=50, num_test=50)
+    model = _cpu_model(task)
+    train = task._loaded_data[DataFold.TRAIN]
+    with pytest.raises(RuntimeError, match="GPU"):
+        model._batches(train, DataFold.TRAIN)
+    with pytest.raises(RuntimeError, match="no device bound"):              # the iterators alone, without a model
+        next(iter(task.make_minibatch_iterator(train, DataFold.TRAIN, 100)))
+    # the other folds are the full graph, as ever
+    (mb,) = model._batches(task._loaded_data[DataFold.VALIDATION], DataFold.VALIDATION)
+    assert mb.num_nodes == 200 and "sampled_nodes" not in mb.feed_dict
+    batch = DeviceBatch(mb, "cpu")
+    batch.extra["sampled_nodes"] = torch.arange(200, dtype=torch.int32)
+    with pytest.raises(RuntimeError, match="sampled batch"):
+        model.capture_train_step(batch)
+
+
+def test_process_groups_stay_refused(monkeypatch):
+    import torch.distributed as dist
+    from tf_gnn_samples_amd.tasks import DataFold
+    task = _task(sampled_batches=GOOD)
+    task.load_synthetic(num_nodes=100, num_features=8, num_classes=3, num_train=20, num_valid=20, num_test=20)
+    monkeypatch.setattr(dist, "is_initialized", lambda: True)
+    monkeypatch.setattr(dist, "get_world_size", lambda *a, **k: 2)
+    with pytest.raises(RuntimeError, match="cannot be split by graph"):
+        list(task.make_minibatch_iterator(task._loaded_data[DataFold.TRAIN], DataFold.TRAIN, 100))
+
+
+def test_checkpoint_metadata_keeps_the_parameter(tmp_path):
+    from tf_gnn_samples_amd import models
+    task = _task(sampled_batches=GOOD)
+    task.load_synthetic(num_nodes=120, num_features=10, num_classes=4, num_train=30, num_valid=30, num_test=30)
+    assert task.get_metadata()["params"]["sampled_batches"] == GOOD
+    model = _cpu_model(task)
+    path = str(tmp_path / "model.pickle")
+    model.save_model(path)
+    restored = models.restore(path, str(tmp_path), device="cpu")
+    assert restored.task.sampled_batches == GOOD and restored.task.get_metadata() == task.get_metadata()
+    plain = _task()
+    plain.restore_from_metadata(task.get_metadata())
+    assert plain.sampled_batches == GOOD
+
+
+def test_epoch_accuracy_line():
+    task = _task(sampled_batches=GOOD)
+    one = [{"accuracy": 0.4321, "loss": 1.0, "total_loss": 3.0}]
+    assert task.pretty_print_epoch_task_metrics(one, 1) == _task().pretty_print_epoch_task_metrics(one, 1) == "Acc: 43.21%"
+    assert task.pretty_print_epoch_task_metrics([dict(one[0], num_masked=32.0, num_correct=8.0)], 1) == "Acc: 43.21%"
+    several = [{"accuracy": 0.25, "num_masked": 32.0, "num_correct": 8.0}, {"accuracy": 0.5, "num_masked": 32.0, "num_correct": 16.0},
+               {"accuracy": 1.0, "num_masked": 12.0, "num_correct": 12.0}]
+    assert task.pretty_print_epoch_task_metrics(several, 3) == "Acc: %.2f%%" % (36.0 / 76.0 * 100)      # not the mean of the three
+
+
+def test_header_binding_and_library_agree():
+    """include/relgnn_sampling.h <-> exported symbols <-> _lib.sampling_signatures(), as the other side headers are held."""
+    from tf_gnn_samples_amd import _build, _lib
+    header = HERE.parent / "include" / "relgnn_sampling.h"
+    assert header in _build.HEADERS
+    c_types = {"int32_t": ctypes.c_int32, "uint32_t": ctypes.c_uint32, "int64_t": ctypes.c_int64, "float": ctypes.c_float,
+               "size_t": ctypes.c_size_t, "int": ctypes.c_int}
+    c_type = lambda text: ctypes.c_void_p if "*" in text else c_types[[w for w in text.split() if w != "const"][0]]
+    text = re.sub(r"//[^\n]*", "", re.sub(r"/\*.*?\*/", "", header.read_text(), flags=re.S))
+    declared = {}
+    for ret, name, params in re.findall(r"^\s*((?:const\s+)?\w+\s*\**)\s*\b(relgnn_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", text, flags=re.M):
+        params = " ".join(params.split())
+        declared[name] = (c_type(ret), [] if params == "void" else [c_type(a) for a in params.split(",")])
+    bound = _lib.sampling_signatures()
+    assert sorted(declared) == sorted(bound) and len(declared) == 11
+    assert "relgnn_neighbour_sample_supported" in declared and "relgnn_neighbour_sample_take" in declared
+    wrong = {n: (bound[n], declared[n]) for n in declared if (bound[n][0], list(bound[n][1])) != declared[n]}
+    assert not wrong, "bound (restype, argtypes) vs the header's: %s" % wrong
+    others = set(_lib.exported_signatures()) | set(_lib.dropout_signatures()) | set(_lib.predict_signatures()) \
+        | set(_lib.parallel_signatures()) | set(_lib.sparse_features_signatures())
+    assert not others & set(bound)
+    if not _lib.LIB_PATH.exists():
+        _build.build_library()
+    raw = ctypes.CDLL(str(_lib.LIB_PATH))
+    assert not [n for n in declared if not hasattr(raw, n)]
+    lib = _lib.load_library()
+    assert lib.relgnn_neighbour_sample_max_fanout() == 64 and lib.relgnn_neighbour_sample_max_hops() == 8
+    fan = lambda *k: (ctypes.c_int32 * len(k))(*k)
+    assert lib.relgnn_neighbour_sample_supported(fan(10, 10), 2, 1 << 20, 2) == 1
+    assert lib.relgnn_neighbour_sample_supported(fan(0, 64), 2, 300, 3) == 1
+    assert lib.relgnn_neighbour_sample_supported(fan(65), 1, 300, 3) == 0
+    assert lib.relgnn_neighbour_sample_supported(fan(-1), 1, 300, 3) == 0
+    assert lib.relgnn_neighbour_sample_supported(fan(*[1] * 9), 9, 300, 3) == 0
+    assert lib.relgnn_neighbour_sample_supported(fan(1), 1, 1 << 30, 2) == 0              # V * L = 2^31
+    assert lib.relgnn_neighbour_sample_supported(fan(1), 1, (1 << 30) - 1, 2) == 1

@@ -1,5 +1,5 @@
 """ctypes binding of librelgnn.so (C ABI: include/relgnn.h, include/relgnn_dropout.h, include/relgnn_predict.h,
-include/relgnn_parallel.h, include/relgnn_sparse_features.h).
+include/relgnn_parallel.h, include/relgnn_sparse_features.h, include/relgnn_sampling.h).
 
 This is the ONLY compute backend of the package.  There is no CPU / eager-PyTorch fallback:
 if the HIP library is missing, or a tensor is not a float32/int32 CUDA(HIP) tensor, the
@@ -211,6 +211,23 @@ _SPARSE_FEATURES_SIGNATURES = {
                                               _c_i64, _ptr, _c_i64, _ptr, _c_i64, _ptr, _c_i64, _ptr]),
 }
 
+# include/relgnn_sampling.h (neighbour sampling from the by-target bucketing: the citation task's sampled batches): its own table too
+_SAMPLING_SIGNATURES = {
+    "relgnn_neighbour_sample_supported": (ctypes.c_int, [_ptr, _c_i32, _c_i64, _c_i32]),
+    "relgnn_neighbour_sample_max_fanout": (_c_i64, []),
+    "relgnn_neighbour_sample_max_hops": (_c_i64, []),
+    "relgnn_neighbour_sample_workspace_bytes": (ctypes.c_size_t, [_c_i64]),
+    "relgnn_neighbour_sample_begin": (ctypes.c_int, [_ptr, _c_i64, _ptr, _c_i64, _ptr]),
+    "relgnn_neighbour_sample_count": (ctypes.c_int, [_ptr, _c_i64, _c_i32, _ptr, _ptr, _c_i64, _c_i32, _ptr, _ptr, _ptr, _ptr,
+                                                     ctypes.c_size_t, _ptr]),
+    "relgnn_neighbour_sample_take": (ctypes.c_int, [_ptr, _ptr, _c_i64, _c_i32, _ptr, _ptr, _c_i64, _c_i32, _c_i32, _c_u32, _c_u32, _c_u32,
+                                                    _ptr, _c_i64, _ptr, _ptr, _ptr]),
+    "relgnn_neighbour_sample_compact": (ctypes.c_int, [_ptr, _c_i64, _c_i32, _ptr, _c_i64, _ptr, _ptr, ctypes.c_size_t, _ptr]),
+    "relgnn_neighbour_sample_relabel": (ctypes.c_int, [_ptr, _c_i64, _c_i64, _ptr, _c_i64, _ptr, _ptr]),
+    "relgnn_neighbour_sample_degrees": (ctypes.c_int, [_ptr, _c_i64, _c_i64, _c_i32, _ptr, _ptr, _c_i64, _ptr, _ptr]),
+    "relgnn_neighbour_sample_finish": (ctypes.c_int, [_ptr, _c_i64, _ptr, _c_i64, _ptr, _ptr]),
+}
+
 _lib = None
 
 
@@ -229,7 +246,7 @@ def load_library():
             "g.build()'` (needs hipcc). There is no CPU fallback for this path." % LIB_PATH)
     lib = ctypes.CDLL(str(LIB_PATH))
     for name, (restype, argtypes) in list(_SIGNATURES.items()) + list(_DROPOUT_SIGNATURES.items()) + list(_PREDICT_SIGNATURES.items()) \
-            + list(_PARALLEL_SIGNATURES.items()) + list(_SPARSE_FEATURES_SIGNATURES.items()):
+            + list(_PARALLEL_SIGNATURES.items()) + list(_SPARSE_FEATURES_SIGNATURES.items()) + list(_SAMPLING_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the symbol is not exported
         fn.restype = restype
         fn.argtypes = argtypes
@@ -261,6 +278,11 @@ def parallel_signatures():
 def sparse_features_signatures():
     """The entry points of include/relgnn_sparse_features.h (not part of exported_signatures() either)."""
     return dict(_SPARSE_FEATURES_SIGNATURES)
+
+
+def sampling_signatures():
+    """The entry points of include/relgnn_sampling.h (not part of exported_signatures() either)."""
+    return dict(_SAMPLING_SIGNATURES)
 
 
 def status_string(code: int) -> str:

@@ -17,30 +17,12 @@
 // Bound: HBM / Infinity Cache bandwidth, 8 bytes per element (16 for the residual forms): 5.1-5.5 TB/s from 64 MiB to 1 GiB per
 // tensor, the rate torch.clone reaches on the same tensors; the Philox rounds hide behind the loads (profiles/layer_dropout.jsonl).
 #include "common.h"
+#include "philox.h"
 #include "../../include/relgnn_dropout.h"
 
 using namespace relgnn;
 
 namespace {
-
-struct u32x4 { uint32_t x, y, z, w; };
-
-__device__ __forceinline__ u32x4 philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1) {
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const uint64_t p0 = (uint64_t)0xD2511F53u * c0;
-    const uint64_t p1 = (uint64_t)0xCD9E8D57u * c2;
-    const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0;
-    const uint32_t n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
-    c1 = (uint32_t)p1;
-    c3 = (uint32_t)p0;
-    c0 = n0;
-    c2 = n2;
-    k0 += 0x9E3779B9u;
-    k1 += 0xBB67AE85u;
-  }
-  return {c0, c1, c2, c3};
-}
 
 __device__ __forceinline__ float keep_of(uint32_t word, uint32_t T) { return (word >> 8) < T ? 1.0f : 0.0f; }
 

@@ -334,6 +334,9 @@ class Sparse_Graph_Model(ABC):
         The learning rate of a captured RMSProp or SGD step is a launch scalar.  With lr_for_num_graphs_per_batch set it is
         learning_rate * num_graphs / lr_for_num_graphs_per_batch of THIS batch: constant for the fixed batch, so freezing it
         into the graph is correct (Adam's lr_t changes per step and is computed on the device instead)."""
+        if 'sampled_nodes' in batch.extra:
+            raise RuntimeError("capture_train_step records ONE fixed batch; a sampled batch (tasks/neighbour_sampling.py) has another "
+                               "shape every step")
         if self.device.type != "cuda":
             raise RuntimeError("capture_train_step needs a model on the GPU (a hipGraph records GPU work)")
         batch.wait_ready()
@@ -396,6 +399,11 @@ class Sparse_Graph_Model(ABC):
         the reference's ThreadedIterator (:272); `native_batching: false` keeps the numpy iterator."""
         native = self.params.get('native_batching', True) and torch.device(self.device).type == "cuda" \
             and hasattr(self.task, "make_graph_store")
+        if data_fold == DataFold.TRAIN and getattr(self.task, "sampled_batches", None) is not None:
+            # a single-graph task that trains on sampled subgraphs (tasks/neighbour_sampling.py): drawn on this model's device by
+            # either iterator, so no flattened or resident copy of the fold is built for them
+            self.task.bind_sampling_device(self.device)
+            native = False
         if not native:
             return self.task.make_minibatch_iterator(data, data_fold, self.params['max_nodes_in_batch'])
         return self.task.make_native_minibatch_iterator(self._native_pipeline(data), data_fold, self.params['max_nodes_in_batch'])

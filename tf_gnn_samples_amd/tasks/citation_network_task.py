@@ -11,6 +11,15 @@ the reference's): the features stay sparse from the file to the input projection
 .SparseRows under `node_features` (no dense [V, F] array is ever built), every device holds one copy of it, the input pipelines
 carry a float32 [V, 1] stand-in under `initial_node_features`, and compute_initial_node_features hands the model the device's
 SparseRows, which its input projection takes through ops.csr_rows_project (csrc/csr_project.hip).
+
+Task parameter `sampled_batches` ({"fanouts": [k_1, ..., k_H], "seeds_per_batch": B, "seed": s}; absent or None by default, read
+with params.get like the one above and kept in the checkpoint's metadata with the other task parameters): the TRAIN fold is no longer
+one batch.  An epoch is a permutation of the fold's nodes cut into ceil(n_train / B) seed lists (neighbour_sampling
+.epoch_seed_batches); every seed list becomes a fanout-limited subgraph drawn on the device (neighbour_sampling.NeighbourSampler,
+csrc/neighbour_sample.hip) whose loss counts the seeds only.  The sampler, the full graph's RelGraph and the device copies of the
+feature table, the labels and the fold's mask are built once per (fold, device).  The task counts the epochs and the sampled batches
+(the sampler's `draw`) itself.  VALIDATION, TEST, test() and predict() stay on the full graph.  GPU only; not together with
+sparse_node_features, capture_train_step or a process group.
 """
 import os
 import pickle
@@ -22,8 +31,10 @@ import torch
 
 from .. import _lib, config as _cfg
 from ..dense import dense, mark_zero_padded
+from ..graph import RelGraph
 from ..parallel import refuse_single_graph_task
 from ..predict import predict_softmax
+from .neighbour_sampling import NeighbourSampler, parse_sampled_batches, epoch_seed_batches
 from .resident import ResidentDataset
 from .sparse_features import SparseRows, node_stand_in, random_rows, resident_copy
 from .sparse_graph_task import DataFold, MinibatchData, Sparse_Graph_Task
@@ -36,6 +47,14 @@ class CitationData(NamedTuple):
     node_features: Any                                     # float32 [V, F], row-normalised (sparse_node_features: a SparseRows)
     labels: np.ndarray                                     # int32 [V]
     mask: np.ndarray                                       # float32 [V], 1 = the node counts in this fold
+
+
+class _SamplingState(NamedTuple):
+    """What the sampled TRAIN batches of one fold on one device are cut from."""
+    sampler: NeighbourSampler
+    features: torch.Tensor                                 # float32 [V, F]
+    labels: torch.Tensor                                   # int32 [V]
+    mask: torch.Tensor                                     # float32 [V], the fold's
 
 
 class _SoftmaxCEStats(torch.autograd.Function):
@@ -188,6 +207,10 @@ class Citation_Network_Task(Sparse_Graph_Task):
         super().__init__(params)
         self._resident_batches = weakref.WeakKeyDictionary()      # resident fold -> its one assembled batch (released with the fold)
         self._device_rows = weakref.WeakKeyDictionary()           # host SparseRows -> {device: its one copy there}
+        self._sampling_state = {}                                 # (id of a fold's label array, device) -> (weak reference to the array, _SamplingState)
+        self._sampling_device = None                              # where the model runs (bind_sampling_device)
+        self._sampling_epoch = self._sampling_draw = 0            # TRAIN epochs started / batches sampled so far
+        self.sampled_batches                                      # (a malformed parameter fails here, not in the first epoch)
         self.__num_edge_types = 2
         self.__initial_node_feature_size = 0
         self.__num_output_classes = 0
@@ -206,6 +229,15 @@ class Citation_Network_Task(Sparse_Graph_Task):
     @property
     def sparse_node_features(self) -> bool:
         return bool(self.params.get('sparse_node_features', False))
+
+    @property
+    def sampled_batches(self) -> Optional[Dict[str, Any]]:
+        """The validated `sampled_batches` parameter, None when the TRAIN fold is one full-graph batch."""
+        sampled = parse_sampled_batches(self.params.get('sampled_batches'))
+        if sampled is not None and self.sparse_node_features:
+            raise ValueError("sampled_batches cannot be combined with sparse_node_features: the weight gradient of the sparse input "
+                             "projection over a row subset needs the transposed structure of that subset")
+        return sampled
 
     @property
     def num_edge_types(self) -> int:
@@ -251,17 +283,28 @@ class Citation_Network_Task(Sparse_Graph_Task):
 
     def load_synthetic(self, num_nodes: int = 2708, num_features: int = 1433, num_classes: int = 7, num_train: int = 140,
                        num_valid: int = 500, num_test: int = 1000, neighbours_per_node: float = 2.0, feature_density: float = 0.0127,
-                       seed: int = 0) -> None:
+                       seed: int = 0, hub_nodes: int = 0, hub_share: float = 0.02) -> None:
         """Cora-shaped stand-in for load_data (no dataset on the machines): 2708 nodes, 1433 binary bag-of-words features at Cora's
         density, row-normalised, 7 classes, ~5.4 k neighbour-list entries = 10.8 k directed edges + self loops; folds of
         140 / 500 / 1000 nodes laid out as Planetoid's (first, next, last).  The test fold is kept as `synthetic_test_data`.
         sparse_node_features: the words of every row are drawn directly (a Binomial(num_features, feature_density) count of uniform
-        draws per row, a word drawn twice counted once), no [V, F] array is built, and the folds share one SparseRows."""
+        draws per row, a word drawn twice counted once), no [V, F] array is built, and the folds share one SparseRows.
+        hub_nodes > 0 (the benchmark graph of scripts/bench_neighbour_sampling.py): every neighbour-list entry is redirected with
+        probability hub_share to one of the first hub_nodes nodes, node (Zipf(1.5) - 1) % hub_nodes: a heavy tail of in-degrees.  The
+        redirection draws from a generator of its own; with hub_nodes == 0 nothing of what a seed gave before changes."""
         rng = np.random.default_rng(seed)
         graph = {}
         lengths = rng.poisson(neighbours_per_node, size=num_nodes)
         for node in range(num_nodes):
             graph[node] = rng.integers(0, num_nodes, size=int(lengths[node])).tolist()
+        if hub_nodes > 0:
+            hub_rng = np.random.default_rng([seed, 1])
+            total = int(lengths.sum())
+            flat = np.fromiter((n for v in graph.values() for n in v), dtype=np.int64, count=total)
+            to_hub = hub_rng.random(total) < hub_share
+            flat[to_hub] = (hub_rng.zipf(1.5, size=int(to_hub.sum())) - 1) % hub_nodes
+            ends = np.cumsum(lengths).tolist()
+            graph = {node: flat[end - int(n):end].tolist() for node, (end, n) in enumerate(zip(ends, lengths))}
         if self.sparse_node_features:
             rowptr, col = random_rows(rng, num_nodes, num_features, rng.binomial(num_features, feature_density, size=num_nodes))
             words = np.diff(rowptr)
@@ -299,8 +342,11 @@ class Citation_Network_Task(Sparse_Graph_Task):
         if logits.is_cuda:
             if labels.dtype != torch.int32:           # (the numpy iterator's DeviceBatch widens integer arrays; the native one keeps int32)
                 labels = labels.to(torch.int32)
-            loss, total_loss, accuracy, _ = softmax_ce_stats(logits, labels, mask)
-            return {'loss': loss, 'total_loss': total_loss, 'accuracy': accuracy}
+            loss, total_loss, accuracy, counts = softmax_ce_stats(logits, labels, mask)
+            metrics = {'loss': loss, 'total_loss': total_loss, 'accuracy': accuracy}
+            if 'sampled_nodes' in batch.extra:        # one of several batches of an epoch: the counts the epoch's accuracy adds up
+                metrics.update(num_masked=counts[1], num_correct=counts[2])
+            return metrics
         # :133-148 in torch
         num_masked = mask.sum()
         losses = torch.nn.functional.cross_entropy(logits, labels.long(), reduction='none')
@@ -342,6 +388,9 @@ class Citation_Network_Task(Sparse_Graph_Task):
         """Exactly one minibatch per epoch, the whole graph; max_nodes_per_batch is not consulted (:157-177)."""
         refuse_single_graph_task(self.name())
         fold = next(iter(data))
+        if data_fold == DataFold.TRAIN and self.sampled_batches is not None:
+            yield from self._sampled_batches_of(fold)
+            return
         sparse = isinstance(fold.node_features, SparseRows)
         feed = {
             'initial_node_features': node_stand_in(len(fold.node_features)) if sparse else fold.node_features,
@@ -363,10 +412,50 @@ class Citation_Network_Task(Sparse_Graph_Task):
         folds = list(data)
         rows = folds[0].node_features if folds and isinstance(folds[0].node_features, SparseRows) else None
         if rows is None:
-            return super().make_graph_store(folds)
+            store = super().make_graph_store(folds)
+            store.citation_fold = folds[0] if folds else None        # (what the sampled TRAIN batches are cut from)
+            return store
         store = super().make_graph_store([f._replace(node_features=node_stand_in(len(f.node_features))) for f in folds])
         store.sparse_rows = rows
         return store
+
+    # -------------------- Sampled mini-batches of the TRAIN fold --------------------
+    def bind_sampling_device(self, device) -> None:
+        """The model tells the task where it runs (the NumPy iterator is not told otherwise).  The sampler is a HIP kernel and the
+        package has no CPU fallback: a model on the CPU is refused."""
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise RuntimeError("sampled_batches needs a model on the GPU: the neighbour sampler is a HIP kernel and there is no CPU "
+                               "fallback (the model is on %s)" % device)
+        self._sampling_device = device
+
+    def _sampling_state_of(self, fold: CitationData, device):
+        key = (id(fold.labels), str(device))
+        held = self._sampling_state.get(key)
+        if held is not None and held[0]() is fold.labels:
+            return held[1]
+        from_host = lambda a, dtype: torch.as_tensor(np.ascontiguousarray(a), dtype=dtype).to(device)
+        sampled = self.sampled_batches
+        graph = RelGraph([from_host(a.reshape(-1, 2), torch.int32) for a in fold.adjacency_lists], len(fold.labels))
+        state = _SamplingState(NeighbourSampler(graph, sampled["fanouts"], seed=sampled["seed"]),
+                               from_host(fold.node_features, torch.float32), from_host(fold.labels, torch.int32),
+                               from_host(fold.mask, torch.float32))
+        # released with the fold's arrays, as _resident_batches is with the resident fold
+        self._sampling_state[key] = (weakref.ref(fold.labels, lambda _, key=key, table=self._sampling_state: table.pop(key, None)), state)
+        return state
+
+    def _sampled_batches_of(self, fold: CitationData):
+        """ceil(n_train / B) sampled batches: one TRAIN epoch."""
+        if self._sampling_device is None:
+            raise RuntimeError("sampled_batches: no device bound (Citation_Network_Task.bind_sampling_device); the model does that "
+                               "when it asks for the TRAIN fold's batches")
+        sampled = self.sampled_batches
+        state = self._sampling_state_of(fold, self._sampling_device)
+        epoch, self._sampling_epoch = self._sampling_epoch, self._sampling_epoch + 1
+        keep = self._out_keep(DataFold.TRAIN)
+        for seeds in epoch_seed_batches(fold.mask, sampled["seeds_per_batch"], sampled["seed"], epoch):
+            draw, self._sampling_draw = self._sampling_draw, self._sampling_draw + 1
+            yield state.sampler.sample(seeds, draw).device_batch(state.features, state.labels, state.mask, keep)
 
     def compute_initial_node_features(self, batch, weights):
         """The batch's feature table, or in the sparse mode the SparseRows on the batch's device: one copy per device, kept weakly
@@ -384,6 +473,9 @@ class Citation_Network_Task(Sparse_Graph_Task):
         refuse_single_graph_task(self.name())
         if batcher.store.num_graphs != 1:
             raise ValueError("a citation-network fold is ONE graph; got %d" % batcher.store.num_graphs)
+        if data_fold == DataFold.TRAIN and self.sampled_batches is not None:
+            yield from self._sampled_batches_of(batcher.store.citation_fold)
+            return
         keep = self._out_keep(data_fold)
         batcher.constants['out_layer_dropout_keep_prob'] = keep
         rows = getattr(batcher.store, "sparse_rows", None)
@@ -408,4 +500,7 @@ class Citation_Network_Task(Sparse_Graph_Task):
         return float(np.sum([float(m['total_loss']) for m in task_metric_results]) / num_graphs)
 
     def pretty_print_epoch_task_metrics(self, task_metric_results: List[Dict[str, Any]], num_graphs: int) -> str:
+        if len(task_metric_results) > 1 and all('num_masked' in m for m in task_metric_results):     # an epoch of sampled batches
+            masked = sum(float(m['num_masked']) for m in task_metric_results)
+            return "Acc: %.2f%%" % (sum(float(m['num_correct']) for m in task_metric_results) / masked * 100,)
         return "Acc: %.2f%%" % (float(task_metric_results[0]['accuracy']) * 100,)

@@ -1,0 +1,194 @@
+"""Neighbour-sampled mini-batches of ONE graph (csrc/neighbour_sample.hip, include/relgnn_sampling.h): seed nodes, a fanout-limited
+neighbourhood around them drawn on the device from the by-target bucketing the full graph's RelGraph already holds, and the
+relabelled subgraph as a DeviceBatch.
+
+Host round trips of NeighbourSampler.sample(): the seed list is validated on the host (in range, distinct; one small copy of a
+device seed list), and the subgraph's sizes are read back ONCE behind the last hop, because its tensors are sized by them.  With
+every fanout positive the hops themselves run without a read-back: their buffers are sized from frontier bound x types x fanout.  A
+hop whose fanout is 0 (take every neighbour) has no such bound and reads its edge count back before it emits: one more round trip
+per such hop.
+"""
+import ctypes
+from typing import Dict, List, NamedTuple, Optional, Sequence
+
+import numpy as np
+import torch
+
+from .. import _lib
+from ..graph import RelGraph
+from .sparse_graph_task import DeviceBatch
+
+# relgnn_neighbour_sample_max_fanout / _max_hops (the library is not loaded to validate a parameter; tests/test_gpu_neighbour_sampling.py
+# holds the two against each other)
+MAX_FANOUT = 64
+MAX_HOPS = 8
+
+
+def check_fanouts(fanouts) -> List[int]:
+    """The fanout list as python ints, or a ValueError that says what include/relgnn_sampling.h supports."""
+    if not isinstance(fanouts, (list, tuple)) or not all(isinstance(k, (int, np.integer)) and not isinstance(k, bool) for k in fanouts):
+        raise ValueError("fanouts must be a list of integers, got %r" % (fanouts,))
+    out = [int(k) for k in fanouts]
+    if not 1 <= len(out) <= MAX_HOPS or any(k < 0 or k > MAX_FANOUT for k in out):
+        raise ValueError("fanouts must be 1 to %d integers in [0, %d] (0 takes every neighbour), got %r" % (MAX_HOPS, MAX_FANOUT, fanouts))
+    return out
+
+
+def epoch_seed_batches(fold_mask, seeds_per_batch: int, seed: int, epoch: int) -> List[np.ndarray]:
+    """The seed lists of one epoch: a permutation of the fold's nodes (mask != 0) from np.random.RandomState([seed, epoch]), cut into
+    batches of seeds_per_batch; every batch int32 and ascending, the last one possibly short."""
+    seeds_per_batch = int(seeds_per_batch)
+    if seeds_per_batch < 1:
+        raise ValueError("seeds_per_batch must be positive, got %r" % (seeds_per_batch,))
+    nodes = np.flatnonzero(np.asarray(fold_mask) != 0)
+    order = np.random.RandomState([int(seed) & 0xffffffff, int(epoch) & 0xffffffff]).permutation(len(nodes))
+    shuffled = nodes[order]
+    return [np.sort(shuffled[i:i + seeds_per_batch]).astype(np.int32) for i in range(0, len(shuffled), seeds_per_batch)]
+
+
+class SampledSubgraph(NamedTuple):
+    nodes: torch.Tensor                         # int32 [n]: ascending global ids; local id = position
+    adjacency_lists: List[torch.Tensor]         # per edge type int32 [E_l, 2] = (source, target) in local ids
+    type_to_num_incoming_edges: torch.Tensor    # float32 [L, n]: the sampled in-degrees
+    seed_mask: torch.Tensor                     # float32 [n]
+    num_nodes: int
+    num_edges: int
+
+    def device_batch(self, features: torch.Tensor, labels: torch.Tensor, fold_mask: torch.Tensor, out_keep: float = 1.0) -> DeviceBatch:
+        """The subgraph as one training batch: feature and label rows of the device-resident [V, ...] tables, the loss mask
+        seed_mask * fold_mask[nodes]."""
+        index = self.nodes.long()
+        extra = {'labels': labels.index_select(0, index), 'mask': self.seed_mask * fold_mask.index_select(0, index),
+                 'out_layer_dropout_keep_prob': out_keep, 'sampled_nodes': self.nodes}
+        return DeviceBatch.from_tensors(1, self.num_nodes, self.num_edges, features.index_select(0, index), self.adjacency_lists,
+                                        self.type_to_num_incoming_edges, extra=extra)
+
+
+class NeighbourSampler:
+    """Sampler over one RelGraph (its rowptr_t / col_t are read in place).  Holds the [V] int32 stamp array, all zero between calls."""
+
+    def __init__(self, graph: RelGraph, fanouts: Sequence[int], seed: int = 0, replica: int = 0):
+        self.fanouts = check_fanouts(fanouts)
+        if not graph.rowptr_t.is_cuda:
+            raise _lib.RelGnnLibraryError("neighbour sampling runs on the GPU only; the graph is on %s" % graph.rowptr_t.device)
+        lib = _lib.load_library()
+        host = (ctypes.c_int32 * len(self.fanouts))(*self.fanouts)
+        if not lib.relgnn_neighbour_sample_supported(host, len(self.fanouts), graph.V, graph.L):
+            raise ValueError("neighbour sampling does not support fanouts %r on a graph of %d nodes and %d edge types "
+                             "(relgnn_neighbour_sample_supported)" % (self.fanouts, graph.V, graph.L))
+        if not 0 <= int(replica) < 2 ** 31:
+            raise ValueError("replica must be in [0, 2^31), got %r" % (replica,))
+        graph.check()                                             # (node ids in range: the kernels trust col_t)
+        self.graph, self.seed, self.replica = graph, int(seed) & 0xffffffff, int(replica)
+        self.stamp = torch.zeros(graph.V, dtype=torch.int32, device=graph.device)
+        self._ws_bytes = lib.relgnn_neighbour_sample_workspace_bytes(graph.V)     # the compaction's; a hop's count fits unless L * bound > V
+        self.synced_hops = [h for h, k in enumerate(self.fanouts) if k == 0]     # the hops that read their edge count back
+        self.trace = None            # a list collects (phase, timed event recorded behind it) of every call (scripts/bench_neighbour_sampling.py)
+
+    def _mark(self, phase: str) -> None:
+        if self.trace is not None:
+            event = torch.cuda.Event(enable_timing=True)
+            event.record()
+            self.trace.append((phase, event))
+
+    def _validated(self, seeds) -> torch.Tensor:
+        host = seeds.detach().cpu().numpy() if torch.is_tensor(seeds) else np.asarray(seeds)
+        if host.ndim != 1 or host.dtype != np.int32:
+            raise ValueError("seeds must be a one-dimensional int32 array")
+        if len(host) == 0:
+            raise ValueError("the seed list is empty")
+        if host.min() < 0 or host.max() >= self.graph.V:
+            raise ValueError("seed outside [0, %d)" % self.graph.V)
+        ordered = np.sort(host)
+        if (ordered[1:] == ordered[:-1]).any():
+            raise ValueError("the seed list names a node twice")
+        if torch.is_tensor(seeds) and seeds.is_cuda and np.array_equal(ordered, host):
+            return seeds.contiguous()
+        return torch.as_tensor(ordered, device=self.graph.device)
+
+    def sample(self, seeds, draw: int) -> SampledSubgraph:
+        """seeds: int32 device tensor (a host array is uploaded), distinct node ids; draw: the count of sampled batches so far."""
+        seeds = self._validated(seeds)
+        try:
+            with torch.cuda.device(self.graph.device):
+                return self._sample(seeds, int(draw) & 0xffffffff)
+        except BaseException:
+            self.stamp.zero_()                                    # whatever a half-run call stamped
+            raise
+
+    def _sample(self, seeds: torch.Tensor, draw: int) -> SampledSubgraph:
+        lib, g = _lib.load_library(), self.graph
+        V, L, dev = g.V, g.L, g.device
+        i32 = lambda n: torch.empty(int(n), dtype=torch.int32, device=dev)
+        ws_bytes = self._ws_bytes
+        ws = _lib.scratch(ws_bytes, dev)
+        self._mark("start")
+        _lib.launch("relgnn_neighbour_sample_begin", _lib.ptr(seeds), seeds.numel(), _lib.ptr(self.stamp), V)
+        frontier, bound = seeds, int(seeds.numel())
+        count = torch.full((1,), bound, dtype=torch.int32, device=dev)
+        hops = []
+        # per hop [L + 1 totals | next frontier's length], then the subgraph's node count: read back once
+        summary = torch.zeros(len(self.fanouts) * (L + 2) + 1, dtype=torch.int32, device=dev)
+        for h, k in enumerate(self.fanouts):
+            counts, offsets = i32(bound * L + 1), i32(bound * L + 1)
+            totals = summary[h * (L + 2):h * (L + 2) + L + 1]
+            hop_ws, hop_ws_bytes = ws, ws_bytes
+            if bound * L + 1 > V:                                 # (the compaction's workspace covers V items)
+                hop_ws_bytes = lib.relgnn_neighbour_sample_workspace_bytes(bound * L + 1)
+                hop_ws = _lib.scratch(hop_ws_bytes, dev)
+            _lib.launch("relgnn_neighbour_sample_count", _lib.ptr(g.rowptr_t), V, L, _lib.ptr(frontier), _lib.ptr(count), bound, k,
+                        _lib.ptr(counts), _lib.ptr(offsets), _lib.ptr(totals), _lib.ptr(hop_ws), hop_ws_bytes)
+            edge_bound = min(bound * L * k, g.M) if k > 0 else int(totals[L])          # k == 0: this hop's one read-back
+            edges = torch.empty((edge_bound, 2), dtype=torch.int32, device=dev)
+            _lib.launch("relgnn_neighbour_sample_take", _lib.ptr(g.rowptr_t), _lib.ptr(g.col_t), V, L, _lib.ptr(frontier), _lib.ptr(count),
+                        bound, k, h, draw, self.seed, self.replica, _lib.ptr(offsets), edge_bound, _lib.ptr(self.stamp),
+                        _lib.ptr(edges) if edge_bound else None)
+            hops.append((frontier, bound, counts, edges))
+            self._mark("hops")
+            next_bound = max(1, min(V, edge_bound))
+            frontier, count = i32(next_bound), summary[h * (L + 2) + L + 1:h * (L + 2) + L + 2]
+            _lib.launch("relgnn_neighbour_sample_compact", _lib.ptr(self.stamp), V, h + 1, _lib.ptr(frontier), next_bound, _lib.ptr(count),
+                        _lib.ptr(ws), ws_bytes)
+            self._mark("compaction")
+            bound = next_bound
+        node_bound = min(V, seeds.numel() + sum(int(e.shape[0]) for _, _, _, e in hops))
+        nodes_buf = i32(node_bound)
+        _lib.launch("relgnn_neighbour_sample_compact", _lib.ptr(self.stamp), V, 0, _lib.ptr(nodes_buf), node_bound, _lib.ptr(summary[-1:]),
+                    _lib.ptr(ws), ws_bytes)
+        self._mark("compaction")
+        sizes = summary.tolist()                                  # the one read-back of a call whose fanouts are all positive
+        self._mark("readback")
+        n = sizes[-1]
+        nodes = nodes_buf[:n]
+        per_hop = [sizes[h * (L + 2):(h + 1) * (L + 2)] for h in range(len(self.fanouts))]
+        lengths = [int(seeds.numel())] + [p[L + 1] for p in per_hop[:-1]]              # the true length of every hop's frontier
+        type_edges = [sum(p[l] for p in per_hop) for l in range(L)]
+        adjacency = [torch.empty((e, 2), dtype=torch.int32, device=dev) for e in type_edges]
+        degrees = torch.zeros((L, n), dtype=torch.float32, device=dev)
+        written = [0] * L
+        for (hop_frontier, hop_bound, counts, edges), p, nf in zip(hops, per_hop, lengths):
+            first = 0
+            for l in range(L):
+                if p[l]:
+                    _lib.launch("relgnn_neighbour_sample_relabel", _lib.ptr(edges), first, p[l], _lib.ptr(nodes), n,
+                                _lib.ptr(adjacency[l][written[l]:written[l] + p[l]]))
+                first += p[l]
+                written[l] += p[l]
+            _lib.launch("relgnn_neighbour_sample_degrees", _lib.ptr(counts), hop_bound, nf, L, _lib.ptr(hop_frontier), _lib.ptr(nodes), n,
+                        _lib.ptr(degrees))
+        seed_mask = torch.empty(n, dtype=torch.float32, device=dev)
+        _lib.launch("relgnn_neighbour_sample_finish", _lib.ptr(nodes), n, _lib.ptr(self.stamp), V, _lib.ptr(seed_mask))
+        self._mark("relabel")
+        return SampledSubgraph(nodes, adjacency, degrees, seed_mask, n, sum(type_edges))
+
+
+def parse_sampled_batches(value) -> Optional[Dict]:
+    """The task parameter `sampled_batches` as {"fanouts": [ints], "seeds_per_batch": int, "seed": int}, None when it is absent."""
+    if value is None:
+        return None
+    if not isinstance(value, dict) or not {"fanouts", "seeds_per_batch"} <= set(value) or set(value) - {"fanouts", "seeds_per_batch", "seed"}:
+        raise ValueError('sampled_batches must be {"fanouts": [k_1, ..., k_H], "seeds_per_batch": B, "seed": s}, got %r' % (value,))
+    per_batch = value["seeds_per_batch"]
+    if isinstance(per_batch, bool) or not isinstance(per_batch, (int, np.integer)) or per_batch < 1:
+        raise ValueError("sampled_batches: seeds_per_batch must be a positive integer, got %r" % (per_batch,))
+    return {"fanouts": check_fanouts(value["fanouts"]), "seeds_per_batch": int(per_batch), "seed": int(value.get("seed", 0))}
