@@ -1,0 +1,188 @@
+"""SparseRows.take_rows and the `"sparse_features": true` key of `sampled_batches` without a GPU: the NumPy reference
+(tests/sparse_subset_reference.py) against the host constructor, the host route of take_rows, its validation, the task parameter,
+checkpoint metadata, and the header <-> binding <-> library agreement of include/relgnn_sparse_subset.h."""
+import ctypes
+import re
+import sys
+from pathlib import Path
+
+import numpy as np
+import pytest
+import torch
+
+HERE = Path(__file__).resolve().parent
+if str(HERE) not in sys.path:
+    sys.path.insert(0, str(HERE))
+
+import sparse_subset_reference as S  # noqa: E402
+
+
+def _container():
+    from tf_gnn_samples_amd.tasks.sparse_features import SparseRows
+    rowptr, col, val = S.structure()
+    return SparseRows(rowptr, col, val, (S.V, S.F))
+
+
+def test_structure_has_the_stated_rows_and_words():
+    rowptr, col, _ = S.structure()
+    assert set(S.ROW_LENGTHS) <= set(np.diff(rowptr).tolist())
+    per_word = np.bincount(col, minlength=S.F)
+    assert all(per_word[w] == c for w, c in S.WORD_NODES.items()) and not per_word[8:S.FIRST_PLAIN_WORD].any()
+    assert np.bincount(col[np.repeat(np.arange(S.V), np.diff(rowptr)) % 2 == 0], minlength=S.F)[7] == 513
+    assert np.diff(S.reference("empty rows only").rows.rowptr).max() == 0 and S.reference("few words").rows.rowptr[-1] == 4
+    assert {0, 1, 128, 129, 512, 513, 1025} <= set(np.diff(S.reference("all").transposed.rowptr).tolist())
+    assert len(S.reference("all").transposed.combos) >= 2 and len(S.reference("all").rows.combos) >= 4
+
+
+@pytest.mark.parametrize("name", list(S.subsets()))
+def test_reference_agrees_with_the_constructor_on_scipy_s_rows(name):
+    import scipy.sparse as sp
+    from tf_gnn_samples_amd.tasks.sparse_features import SparseRows
+    rowptr, col, val = S.structure()
+    nodes = S.subsets()[name]
+    picked = sp.csr_matrix((val, col, rowptr), shape=(S.V, S.F))[nodes]
+    picked.sort_indices()
+    S.compare(SparseRows(picked.indptr, picked.indices, picked.data, picked.shape), S.reference(name), name)
+
+
+def test_host_route_reproduces_the_container_and_the_reference():
+    from tf_gnn_samples_amd.tasks import sparse_features
+    rows = _container()
+    sparse_features.ROUTES["take_rows"] = None
+    whole = rows.take_rows(np.arange(S.V, dtype=np.int32))
+    assert sparse_features.ROUTES["take_rows"] == "host"
+    S.compare(whole, S.reference("all"), "all")
+    for side in ("rows", "transposed"):
+        for field in S.FIELDS:
+            assert torch.equal(getattr(getattr(whole, side), field), getattr(getattr(rows, side), field)), (side, field)
+        assert getattr(whole, side).ws_rows == getattr(rows, side).ws_rows
+    for name, nodes in S.subsets().items():
+        S.compare(rows.take_rows(torch.as_tensor(nodes)), S.reference(name), name)
+        S.compare(rows.take_rows(nodes, validated=True), S.reference(name), name + " (trusted)")
+    empty = rows.take_rows(np.zeros(0, np.int32))
+    assert empty.shape == (0, S.F) and empty.nnz == 0 and empty.transposed.rowptr.shape == (S.F + 1,)
+    assert sparse_features.take_rows_supported(S.V, S.F, 10) and not sparse_features.take_rows_supported(S.V, S.F, 2 ** 31 - 1)
+
+
+def test_a_per_batch_container_records_its_tensors_and_the_fold_s_does_not():
+    rows = _container()
+    taken = rows.take_rows(np.array([3, 200], np.int32))
+    assert type(rows).record_stream is not type(taken).record_stream
+    assert rows.record_stream(None) is None and taken.record_stream(None) is None        # (CPU tensors: nothing to record)
+    assert taken.to("cpu") is taken and isinstance(taken, type(rows))
+
+
+@pytest.mark.parametrize("bad", [np.array([0, S.V], np.int32), np.array([-1, 4], np.int32), np.array([0, 1], np.int64),
+                                 np.array([0.0, 1.0], np.float32), np.array([[0, 1], [2, 3]], np.int32)])
+def test_bad_node_lists_are_value_errors(bad):
+    rows = _container()
+    with pytest.raises(ValueError):
+        rows.take_rows(bad)
+    with pytest.raises(ValueError):
+        rows.take_rows(torch.as_tensor(bad))
+
+
+def _task(**params):
+    from tf_gnn_samples_amd.tasks import Citation_Network_Task
+    return Citation_Network_Task(dict(Citation_Network_Task.default_params(), **params))
+
+
+PLAIN = {"fanouts": [3, 2], "seeds_per_batch": 16, "seed": 1}
+BOTH = dict(PLAIN, sparse_features=True)
+
+
+def test_the_key_is_accepted_with_sparse_node_features_only():
+    from tf_gnn_samples_amd.tasks.neighbour_sampling import parse_sampled_batches
+    assert _task(sampled_batches=BOTH, sparse_node_features=True).sampled_batches == BOTH
+    with pytest.raises(ValueError, match="sparse_node_features"):
+        _task(sampled_batches=BOTH)                                           # the key alone
+    with pytest.raises(ValueError, match="sparse_node_features"):
+        _task(sampled_batches=BOTH, sparse_node_features=False)
+    with pytest.raises(ValueError, match="sparse_features"):                  # the refusal of the two plain parameters names the key
+        _task(sampled_batches=PLAIN, sparse_node_features=True)
+    with pytest.raises(ValueError, match="sparse_features"):
+        _task(sampled_batches=dict(PLAIN, sparse_features=False), sparse_node_features=True)
+    for value in (1, 0, "true", None, [True]):
+        with pytest.raises(ValueError):
+            parse_sampled_batches(dict(PLAIN, sparse_features=value))
+        with pytest.raises(ValueError):
+            _task(sampled_batches=dict(PLAIN, sparse_features=value), sparse_node_features=True)
+    assert parse_sampled_batches(PLAIN) == PLAIN and "sparse_features" not in parse_sampled_batches(PLAIN)
+    assert parse_sampled_batches({"fanouts": [4], "seeds_per_batch": 2}) == {"fanouts": [4], "seeds_per_batch": 2, "seed": 0}
+    assert parse_sampled_batches(dict(PLAIN, sparse_features=False)) == dict(PLAIN, sparse_features=False)
+    assert _task(sampled_batches=dict(PLAIN, sparse_features=False)).sampled_batches == dict(PLAIN, sparse_features=False)
+
+
+def _cpu_model(task):
+    from tf_gnn_samples_amd.models import RGCN_Model
+    p = RGCN_Model.default_params()
+    p.update(hidden_size=16, graph_num_layers=1, random_seed=1)
+    return RGCN_Model(p, task, device="cpu")
+
+
+def test_checkpoint_metadata_keeps_the_key(tmp_path):
+    from tf_gnn_samples_amd import models
+    task = _task(sampled_batches=BOTH, sparse_node_features=True)
+    task.load_synthetic(num_nodes=120, num_features=10, num_classes=4, num_train=30, num_valid=30, num_test=30)
+    assert task.get_metadata()["params"]["sampled_batches"] == BOTH and task.get_metadata()["params"]["sparse_node_features"] is True
+    model = _cpu_model(task)
+    path = str(tmp_path / "model.pickle")
+    model.save_model(path)
+    restored = models.restore(path, str(tmp_path), device="cpu")
+    assert restored.task.sampled_batches == BOTH and restored.task.sparse_node_features is True
+    assert restored.task.get_metadata() == task.get_metadata()
+    plain = _task()
+    plain.restore_from_metadata(task.get_metadata())
+    assert plain.sampled_batches == BOTH
+
+
+def test_a_cpu_model_is_still_refused_and_the_store_knows_the_fold():
+    from tf_gnn_samples_amd.tasks import DataFold
+    from tf_gnn_samples_amd.tasks.sparse_features import SparseRows
+    task = _task(sampled_batches=BOTH, sparse_node_features=True)
+    task.load_synthetic(num_nodes=200, num_features=12, num_classes=3, num_train=40, num_valid=50, num_test=50)
+    train = task._loaded_data[DataFold.TRAIN]
+    model = _cpu_model(task)
+    with pytest.raises(RuntimeError, match="GPU"):
+        model._batches(train, DataFold.TRAIN)
+    with pytest.raises(RuntimeError, match="no device bound"):
+        next(iter(task.make_minibatch_iterator(train, DataFold.TRAIN, 100)))
+    (mb,) = model._batches(task._loaded_data[DataFold.VALIDATION], DataFold.VALIDATION)      # the other folds: the full graph, sparse
+    assert mb.num_nodes == 200 and isinstance(mb.feed_dict["sparse_node_features"], SparseRows)
+    store = task.make_graph_store(train)
+    assert store.citation_fold is train[0] and store.sparse_rows is train[0].node_features
+
+
+def test_header_binding_and_library_agree():
+    """include/relgnn_sparse_subset.h <-> exported symbols <-> _lib.sparse_subset_signatures(), as the other side headers are held."""
+    from tf_gnn_samples_amd import _build, _lib
+    header = HERE.parent / "include" / "relgnn_sparse_subset.h"
+    assert header in _build.HEADERS
+    c_types = {"int32_t": ctypes.c_int32, "uint32_t": ctypes.c_uint32, "int64_t": ctypes.c_int64, "float": ctypes.c_float,
+               "size_t": ctypes.c_size_t, "int": ctypes.c_int}
+    c_type = lambda text: ctypes.c_void_p if "*" in text else c_types[[w for w in text.split() if w != "const"][0]]
+    text = re.sub(r"//[^\n]*", "", re.sub(r"/\*.*?\*/", "", header.read_text(), flags=re.S))
+    declared = {}
+    for ret, name, params in re.findall(r"^\s*((?:const\s+)?\w+\s*\**)\s*\b(relgnn_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", text, flags=re.M):
+        params = " ".join(params.split())
+        declared[name] = (c_type(ret), [] if params == "void" else [c_type(a) for a in params.split(",")])
+    bound = _lib.sparse_subset_signatures()
+    assert sorted(declared) == sorted(bound) and len(declared) == 9
+    assert "relgnn_split_plan_count" in declared and "relgnn_split_plan_fill" in declared and "relgnn_sparse_subset_count" in declared
+    wrong = {n: (bound[n], declared[n]) for n in declared if (bound[n][0], list(bound[n][1])) != declared[n]}
+    assert not wrong, "bound (restype, argtypes) vs the header's: %s" % wrong
+    others = [_lib.exported_signatures(), _lib.dropout_signatures(), _lib.predict_signatures(), _lib.parallel_signatures(),
+              _lib.sparse_features_signatures(), _lib.sampling_signatures()]
+    assert all(not set(o) & set(bound) for o in others)
+    assert len(_lib.sparse_features_signatures()) == 4
+    if not _lib.LIB_PATH.exists():
+        _build.build_library()
+    raw = ctypes.CDLL(str(_lib.LIB_PATH))
+    assert not [n for n in declared if not hasattr(raw, n)]
+    lib = _lib.load_library()
+    assert lib.relgnn_sparse_subset_supported(1 << 20, 1 << 17, 98765) == 1 and lib.relgnn_sparse_subset_supported(0, 0, 0) == 1
+    assert lib.relgnn_sparse_subset_supported(2 ** 31 - 1, 4, 4) == 0 and lib.relgnn_sparse_subset_supported(4, 4, 2 ** 31 - 1) == 0
+    assert lib.relgnn_sparse_subset_supported(4, -1, 4) == 0
+    assert lib.relgnn_split_plan_workspace_bytes(1000) > 0 and lib.relgnn_sparse_subset_count_workspace_bytes(1000, 800) >= 801 * 4
+    assert lib.relgnn_sparse_subset_transpose_workspace_bytes(0, 800) > 0
+    assert lib.relgnn_sparse_subset_transpose_workspace_bytes(5000, 800) >= 2 * 5000 * 4

@@ -1,5 +1,5 @@
 """ctypes binding of librelgnn.so (C ABI: include/relgnn.h, include/relgnn_dropout.h, include/relgnn_predict.h,
-include/relgnn_parallel.h, include/relgnn_sparse_features.h, include/relgnn_sampling.h).
+include/relgnn_parallel.h, include/relgnn_sparse_features.h, include/relgnn_sampling.h, include/relgnn_sparse_subset.h).
 
 This is the ONLY compute backend of the package.  There is no CPU / eager-PyTorch fallback:
 if the HIP library is missing, or a tensor is not a float32/int32 CUDA(HIP) tensor, the
@@ -228,6 +228,21 @@ _SAMPLING_SIGNATURES = {
     "relgnn_neighbour_sample_finish": (ctypes.c_int, [_ptr, _c_i64, _ptr, _c_i64, _ptr, _ptr]),
 }
 
+# include/relgnn_sparse_subset.h (a row subset of sparse node features and its transpose, built on the device: sampled batches over
+# sparse features): its own table too
+_SPARSE_SUBSET_SIGNATURES = {
+    "relgnn_sparse_subset_supported": (ctypes.c_int, [_c_i64, _c_i64, _c_i64]),
+    "relgnn_split_plan_workspace_bytes": (ctypes.c_size_t, [_c_i64]),
+    "relgnn_split_plan_count": (ctypes.c_int, [_ptr, _c_i64, _ptr, _ptr, _ptr, ctypes.c_size_t, _ptr]),
+    "relgnn_split_plan_fill": (ctypes.c_int, [_ptr, _c_i64, _ptr, _ptr, _c_i64, _ptr, _c_i64, _ptr]),
+    "relgnn_sparse_subset_count_workspace_bytes": (ctypes.c_size_t, [_c_i64, _c_i64]),
+    "relgnn_sparse_subset_count": (ctypes.c_int, [_ptr, _ptr, _c_i64, _c_i64, _ptr, _c_i64, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr,
+                                                  ctypes.c_size_t, _ptr]),
+    "relgnn_sparse_subset_copy": (ctypes.c_int, [_ptr, _ptr, _ptr, _c_i64, _ptr, _c_i64, _ptr, _c_i64, _ptr, _ptr, _ptr]),
+    "relgnn_sparse_subset_transpose_workspace_bytes": (ctypes.c_size_t, [_c_i64, _c_i64]),
+    "relgnn_sparse_subset_transpose": (ctypes.c_int, [_ptr, _c_i64, _ptr, _ptr, _c_i64, _c_i64, _ptr, _ptr, _ptr, ctypes.c_size_t, _ptr]),
+}
+
 _lib = None
 
 
@@ -246,7 +261,8 @@ def load_library():
             "g.build()'` (needs hipcc). There is no CPU fallback for this path." % LIB_PATH)
     lib = ctypes.CDLL(str(LIB_PATH))
     for name, (restype, argtypes) in list(_SIGNATURES.items()) + list(_DROPOUT_SIGNATURES.items()) + list(_PREDICT_SIGNATURES.items()) \
-            + list(_PARALLEL_SIGNATURES.items()) + list(_SPARSE_FEATURES_SIGNATURES.items()) + list(_SAMPLING_SIGNATURES.items()):
+            + list(_PARALLEL_SIGNATURES.items()) + list(_SPARSE_FEATURES_SIGNATURES.items()) + list(_SAMPLING_SIGNATURES.items()) \
+            + list(_SPARSE_SUBSET_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the symbol is not exported
         fn.restype = restype
         fn.argtypes = argtypes
@@ -283,6 +299,11 @@ def sparse_features_signatures():
 def sampling_signatures():
     """The entry points of include/relgnn_sampling.h (not part of exported_signatures() either)."""
     return dict(_SAMPLING_SIGNATURES)
+
+
+def sparse_subset_signatures():
+    """The entry points of include/relgnn_sparse_subset.h (not part of exported_signatures() either)."""
+    return dict(_SPARSE_SUBSET_SIGNATURES)
 
 
 def status_string(code: int) -> str:

@@ -19,7 +19,15 @@ one batch.  An epoch is a permutation of the fold's nodes cut into ceil(n_train 
 csrc/neighbour_sample.hip) whose loss counts the seeds only.  The sampler, the full graph's RelGraph and the device copies of the
 feature table, the labels and the fold's mask are built once per (fold, device).  The task counts the epochs and the sampled batches
 (the sampler's `draw`) itself.  VALIDATION, TEST, test() and predict() stay on the full graph.  GPU only; not together with
-sparse_node_features, capture_train_step or a process group.
+capture_train_step or a process group.
+
+The two together: `sampled_batches` takes one more optional key, "sparse_features": true, which requires sparse_node_features
+(and sparse_node_features with a sampled_batches that lacks the key stays a ValueError).  The sampling state then keeps the device's
+SparseRows instead of a dense table, and every sampled batch carries the [n, 1] stand-in plus SparseRows.take_rows(nodes): the CSR of
+the batch's rows, the CSR of that subset's transpose (what the projection's weight gradient runs over) and both long-row plans,
+built on the device per batch (csrc/sparse_subset.hip, include/relgnn_sparse_subset.h) with one read-back of eight sizes.  No
+[V, F] or [n, F] dense array exists on the host or the device.  The weight gradient itself stays a dense [F, hidden] tensor, and the
+optimizer still walks all of it.
 """
 import os
 import pickle
@@ -52,7 +60,7 @@ class CitationData(NamedTuple):
 class _SamplingState(NamedTuple):
     """What the sampled TRAIN batches of one fold on one device are cut from."""
     sampler: NeighbourSampler
-    features: torch.Tensor                                 # float32 [V, F]
+    features: Any                                          # float32 [V, F], or the device's SparseRows
     labels: torch.Tensor                                   # int32 [V]
     mask: torch.Tensor                                     # float32 [V], the fold's
 
@@ -234,9 +242,14 @@ class Citation_Network_Task(Sparse_Graph_Task):
     def sampled_batches(self) -> Optional[Dict[str, Any]]:
         """The validated `sampled_batches` parameter, None when the TRAIN fold is one full-graph batch."""
         sampled = parse_sampled_batches(self.params.get('sampled_batches'))
-        if sampled is not None and self.sparse_node_features:
-            raise ValueError("sampled_batches cannot be combined with sparse_node_features: the weight gradient of the sparse input "
-                             "projection over a row subset needs the transposed structure of that subset")
+        if sampled is None:
+            return None
+        if self.sparse_node_features and not sampled.get("sparse_features", False):
+            raise ValueError("sampled_batches cannot be combined with sparse_node_features unless it says \"sparse_features\": true: "
+                             "the weight gradient of the sparse input projection over a row subset needs the transposed structure of "
+                             "that subset, which is then built per batch (SparseRows.take_rows)")
+        if sampled.get("sparse_features", False) and not self.sparse_node_features:
+            raise ValueError("sampled_batches: \"sparse_features\": true requires the task parameter sparse_node_features: True")
         return sampled
 
     @property
@@ -417,6 +430,7 @@ class Citation_Network_Task(Sparse_Graph_Task):
             return store
         store = super().make_graph_store([f._replace(node_features=node_stand_in(len(f.node_features))) for f in folds])
         store.sparse_rows = rows
+        store.citation_fold = folds[0]
         return store
 
     # -------------------- Sampled mini-batches of the TRAIN fold --------------------
@@ -437,9 +451,12 @@ class Citation_Network_Task(Sparse_Graph_Task):
         from_host = lambda a, dtype: torch.as_tensor(np.ascontiguousarray(a), dtype=dtype).to(device)
         sampled = self.sampled_batches
         graph = RelGraph([from_host(a.reshape(-1, 2), torch.int32) for a in fold.adjacency_lists], len(fold.labels))
-        state = _SamplingState(NeighbourSampler(graph, sampled["fanouts"], seed=sampled["seed"]),
-                               from_host(fold.node_features, torch.float32), from_host(fold.labels, torch.int32),
-                               from_host(fold.mask, torch.float32))
+        if isinstance(fold.node_features, SparseRows):            # the device's one copy of the container: no dense table anywhere
+            features = resident_copy(self._device_rows, fold.node_features, device)
+        else:
+            features = from_host(fold.node_features, torch.float32)
+        state = _SamplingState(NeighbourSampler(graph, sampled["fanouts"], seed=sampled["seed"]), features,
+                               from_host(fold.labels, torch.int32), from_host(fold.mask, torch.float32))
         # released with the fold's arrays, as _resident_batches is with the resident fold
         self._sampling_state[key] = (weakref.ref(fold.labels, lambda _, key=key, table=self._sampling_state: table.pop(key, None)), state)
         return state

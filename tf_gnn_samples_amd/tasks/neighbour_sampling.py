@@ -16,6 +16,7 @@ import torch
 
 from .. import _lib
 from ..graph import RelGraph
+from .sparse_features import SparseRows
 from .sparse_graph_task import DeviceBatch
 
 # relgnn_neighbour_sample_max_fanout / _max_hops (the library is not loaded to validate a parameter; tests/test_gpu_neighbour_sampling.py
@@ -54,13 +55,19 @@ class SampledSubgraph(NamedTuple):
     num_nodes: int
     num_edges: int
 
-    def device_batch(self, features: torch.Tensor, labels: torch.Tensor, fold_mask: torch.Tensor, out_keep: float = 1.0) -> DeviceBatch:
+    def device_batch(self, features, labels: torch.Tensor, fold_mask: torch.Tensor, out_keep: float = 1.0) -> DeviceBatch:
         """The subgraph as one training batch: feature and label rows of the device-resident [V, ...] tables, the loss mask
-        seed_mask * fold_mask[nodes]."""
+        seed_mask * fold_mask[nodes].  `features` a SparseRows: the [n, 1] stand-in takes the table's place and the rows' subset
+        (SparseRows.take_rows, csrc/sparse_subset.hip) travels under extra['sparse_node_features']; no dense row is built."""
         index = self.nodes.long()
         extra = {'labels': labels.index_select(0, index), 'mask': self.seed_mask * fold_mask.index_select(0, index),
                  'out_layer_dropout_keep_prob': out_keep, 'sampled_nodes': self.nodes}
-        return DeviceBatch.from_tensors(1, self.num_nodes, self.num_edges, features.index_select(0, index), self.adjacency_lists,
+        if isinstance(features, SparseRows):
+            extra['sparse_node_features'] = features.take_rows(self.nodes, validated=True)
+            rows = torch.zeros((self.num_nodes, 1), dtype=torch.float32, device=self.nodes.device)      # sparse_features.node_stand_in
+        else:
+            rows = features.index_select(0, index)
+        return DeviceBatch.from_tensors(1, self.num_nodes, self.num_edges, rows, self.adjacency_lists,
                                         self.type_to_num_incoming_edges, extra=extra)
 
 
@@ -183,12 +190,20 @@ class NeighbourSampler:
 
 
 def parse_sampled_batches(value) -> Optional[Dict]:
-    """The task parameter `sampled_batches` as {"fanouts": [ints], "seeds_per_batch": int, "seed": int}, None when it is absent."""
+    """The task parameter `sampled_batches` as {"fanouts": [ints], "seeds_per_batch": int, "seed": int}, None when it is absent;
+    the optional key "sparse_features" (a bool: the batches take their feature rows from a SparseRows) is carried only when given."""
     if value is None:
         return None
-    if not isinstance(value, dict) or not {"fanouts", "seeds_per_batch"} <= set(value) or set(value) - {"fanouts", "seeds_per_batch", "seed"}:
-        raise ValueError('sampled_batches must be {"fanouts": [k_1, ..., k_H], "seeds_per_batch": B, "seed": s}, got %r' % (value,))
+    if not isinstance(value, dict) or not {"fanouts", "seeds_per_batch"} <= set(value) \
+            or set(value) - {"fanouts", "seeds_per_batch", "seed", "sparse_features"}:
+        raise ValueError('sampled_batches must be {"fanouts": [k_1, ..., k_H], "seeds_per_batch": B, "seed": s, "sparse_features": bool}, '
+                         'the last two optional, got %r' % (value,))
     per_batch = value["seeds_per_batch"]
     if isinstance(per_batch, bool) or not isinstance(per_batch, (int, np.integer)) or per_batch < 1:
         raise ValueError("sampled_batches: seeds_per_batch must be a positive integer, got %r" % (per_batch,))
-    return {"fanouts": check_fanouts(value["fanouts"]), "seeds_per_batch": int(per_batch), "seed": int(value.get("seed", 0))}
+    parsed = {"fanouts": check_fanouts(value["fanouts"]), "seeds_per_batch": int(per_batch), "seed": int(value.get("seed", 0))}
+    if "sparse_features" in value:
+        if not isinstance(value["sparse_features"], bool):
+            raise ValueError("sampled_batches: sparse_features must be true or false, got %r" % (value["sparse_features"],))
+        parsed["sparse_features"] = value["sparse_features"]
+    return parsed

@@ -11,6 +11,8 @@ from typing import Optional, Tuple
 import numpy as np
 import torch
 
+from .. import _lib
+
 # The summation order of include/relgnn_sparse_features.h (relgnn_csr_project_split_above / relgnn_csr_project_slab; the library
 # is not loaded to build a container, tests/test_gpu_sparse_features.py holds the two against each other)
 SPLIT_ABOVE = 128
@@ -191,6 +193,116 @@ class SparseRows:
 
     def record_stream(self, stream) -> None:
         pass                                               # (a fold-lifetime table: never returned to the allocator under a batch)
+
+    # ---- a row subset (include/relgnn_sparse_subset.h) ----
+    def take_rows(self, nodes, validated: bool = False) -> "SparseRows":
+        """The [n, F] container of the rows `nodes` names (one-dimensional int32 tensor or array, any order, a row possibly twice;
+        local id = position), on this container's device, with every array equal to what SparseRows(rowptr, col, val, (n, F))
+        builds from the same rows.  A GPU container runs csrc/sparse_subset.hip (one read-back of eight sizes), a CPU container the
+        host constructor; ROUTES["take_rows"] says which.  validated=True trusts `nodes` (the sampler's own output)."""
+        if not validated:
+            host = nodes.detach().cpu().numpy() if torch.is_tensor(nodes) else np.asarray(nodes)
+            if host.ndim != 1 or host.dtype != np.int32:
+                raise ValueError("take_rows: nodes must be a one-dimensional int32 array")
+            if len(host) and (host.min() < 0 or host.max() >= self.shape[0]):
+                raise ValueError("take_rows: row id outside [0, %d)" % self.shape[0])
+        n, F = int(nodes.shape[0]), self.shape[1]
+        if not take_rows_supported(self.shape[0], F, n):
+            raise ValueError("take_rows: %d rows of a %r matrix are outside what the subset kernels index with 32 bits "
+                             "(take_rows_supported)" % (n, self.shape))
+        if not self.is_cuda or n == 0:
+            ROUTES["take_rows"] = "host"
+            return self._take_rows_host(nodes.detach().cpu().numpy() if torch.is_tensor(nodes) else np.asarray(nodes))
+        ROUTES["take_rows"] = "hip"
+        nodes = nodes.to(self.device).contiguous() if torch.is_tensor(nodes) else torch.as_tensor(np.ascontiguousarray(nodes), device=self.device)
+        with torch.cuda.device(self.device):
+            return self._take_rows_device(nodes, n)
+
+    def _take_rows_host(self, nodes: np.ndarray) -> "SparseRows":
+        s = self.rows
+        rowptr, nodes = s.rowptr.cpu().numpy().astype(np.int64), nodes.astype(np.int64)
+        length = rowptr[nodes + 1] - rowptr[nodes]
+        sub_rowptr = np.zeros(len(nodes) + 1, np.int64)
+        np.cumsum(length, out=sub_rowptr[1:])
+        if sub_rowptr[-1] >= _INT32_MAX:
+            raise ValueError("take_rows: the subset holds %d entries; the structure is indexed with 32 bits" % sub_rowptr[-1])
+        entry = np.repeat(rowptr[nodes] - sub_rowptr[:-1], length) + np.arange(sub_rowptr[-1])      # the source entry of every entry
+        taken = SparseRows(sub_rowptr, s.col.cpu().numpy()[entry], s.val.cpu().numpy()[entry], (len(nodes), self.shape[1]))
+        return _PerBatchRows.of(taken.to(self.device))
+
+    def _take_rows_device(self, nodes: torch.Tensor, n: int) -> "SparseRows":
+        lib, s, dev = _lib.load_library(), self.rows, self.device
+        V, F = self.shape
+        i32 = lambda *shape: torch.empty(shape, dtype=torch.int32, device=dev)
+        sub_rowptr, sub_rowptr_t, offsets, offsets_t, sizes = i32(n + 1), i32(F + 1), i32(n + 1, 4), i32(F + 1, 4), i32(8)
+        nbytes = lib.relgnn_sparse_subset_count_workspace_bytes(n, F)
+        ws = _lib.scratch(nbytes, dev)
+        self._mark("start")
+        _lib.launch("relgnn_sparse_subset_count", _lib.ptr(s.rowptr), _lib.ptr(s.col) if s.nnz else None, V, F, _lib.ptr(nodes), n,
+                    _lib.ptr(sub_rowptr), _lib.ptr(sub_rowptr_t), _lib.ptr(offsets), _lib.ptr(offsets_t), _lib.ptr(sizes), _lib.ptr(ws),
+                    nbytes)
+        self._mark("count")
+        nnz, *plan_sizes = sizes.tolist()[:7]                 # the one read-back: everything below is sized by these
+        self._mark("readback")
+        if nnz >= _INT32_MAX:
+            raise ValueError("take_rows: the subset holds 2^31 - 1 entries or more; the structure is indexed with 32 bits")
+        sub_col, sub_val = i32(nnz), torch.empty(nnz, dtype=torch.float32, device=dev)
+        sub_col_t, sub_val_t = i32(nnz), torch.empty(nnz, dtype=torch.float32, device=dev)
+        if nnz:
+            _lib.launch("relgnn_sparse_subset_copy", _lib.ptr(s.rowptr), _lib.ptr(s.col), _lib.ptr(s.val), V, _lib.ptr(nodes), n,
+                        _lib.ptr(sub_rowptr), nnz, _lib.ptr(sub_col), _lib.ptr(sub_val))
+        self._mark("copy")
+        if nnz:
+            nbytes = lib.relgnn_sparse_subset_transpose_workspace_bytes(nnz, F)
+            ws = _lib.scratch(nbytes, dev)
+            _lib.launch("relgnn_sparse_subset_transpose", _lib.ptr(sub_rowptr), n, _lib.ptr(sub_col), _lib.ptr(sub_val), nnz, F,
+                        _lib.ptr(sub_col_t), _lib.ptr(sub_val_t), _lib.ptr(ws), nbytes)
+        self._mark("transpose")
+        structures = []
+        for rowptr, off, col, val, (num_slabs, num_combos, ws_rows), cols in ((sub_rowptr, offsets, sub_col, sub_val, plan_sizes[:3], F),
+                                                                              (sub_rowptr_t, offsets_t, sub_col_t, sub_val_t, plan_sizes[3:], n)):
+            slabs, combos = i32(num_slabs, 4), i32(num_combos, 3)
+            if num_slabs:
+                _lib.launch("relgnn_split_plan_fill", _lib.ptr(rowptr), int(rowptr.shape[0]) - 1, _lib.ptr(off), _lib.ptr(slabs), num_slabs,
+                            _lib.ptr(combos) if num_combos else None, num_combos)
+            structures.append(CsrStructure(rowptr, col, val, slabs, combos, ws_rows, cols))
+        self._mark("plans")
+        return _PerBatchRows(None, None, None, (n, F), _structures=tuple(structures))
+
+    trace = None                     # a list collects (phase, timed event recorded behind it) of every take_rows (scripts/bench_sparse_sampling.py)
+
+    def _mark(self, phase: str) -> None:
+        if self.trace is not None:
+            event = torch.cuda.Event(enable_timing=True)
+            event.record()
+            self.trace.append((phase, event))
+
+
+class _PerBatchRows(SparseRows):
+    """What take_rows returns: a container that lives as long as its batch, so a consumer on another stream records its tensors."""
+
+    @classmethod
+    def of(cls, rows: SparseRows) -> "_PerBatchRows":
+        return cls(None, None, None, rows.shape, _structures=(rows.rows, rows.transposed))
+
+    def to(self, device) -> "SparseRows":
+        return self if torch.device(device) == self.device else _PerBatchRows.of(super().to(device))
+
+    def record_stream(self, stream) -> None:
+        if not self.is_cuda:
+            return
+        for s in (self.rows, self.transposed):
+            for t in (s.rowptr, s.col, s.val, s.slabs, s.combos):
+                t.record_stream(stream)
+
+
+ROUTES = {"take_rows": None}         # which implementation the last SparseRows.take_rows took: "hip" or "host"
+
+
+def take_rows_supported(num_rows: int, num_cols: int, n: int) -> bool:
+    """What relgnn_sparse_subset_supported takes (restated: asked before the library is loaded); the subset's own nnz must stay
+    below 2^31 - 1 too, which only the count step knows."""
+    return all(0 <= x < _INT32_MAX for x in (int(num_rows), int(num_cols), int(n)))
 
 
 def node_stand_in(num_nodes: int) -> np.ndarray:

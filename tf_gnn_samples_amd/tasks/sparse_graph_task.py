@@ -92,6 +92,9 @@ class DeviceBatch:
         for t in tensors:
             if t is not None and t.is_cuda:
                 t.record_stream(cur)
+        for v in self.extra.values():                    # a feature container (tasks/sparse_features.py): a per-batch one records its tensors
+            if not torch.is_tensor(v) and hasattr(v, "record_stream"):
+                v.record_stream(cur)
         return self
 
 
