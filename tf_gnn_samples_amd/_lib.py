@@ -1,5 +1,6 @@
 """ctypes binding of librelgnn.so (C ABI: include/relgnn.h, include/relgnn_dropout.h, include/relgnn_predict.h,
-include/relgnn_parallel.h, include/relgnn_sparse_features.h, include/relgnn_sampling.h, include/relgnn_sparse_subset.h).
+include/relgnn_parallel.h, include/relgnn_sparse_features.h, include/relgnn_sampling.h, include/relgnn_sparse_subset.h,
+include/relgnn_sparse_update.h).
 
 This is the ONLY compute backend of the package.  There is no CPU / eager-PyTorch fallback:
 if the HIP library is missing, or a tensor is not a float32/int32 CUDA(HIP) tensor, the
@@ -243,6 +244,15 @@ _SPARSE_SUBSET_SIGNATURES = {
     "relgnn_sparse_subset_transpose": (ctypes.c_int, [_ptr, _c_i64, _ptr, _ptr, _c_i64, _c_i64, _ptr, _ptr, _ptr, ctypes.c_size_t, _ptr]),
 }
 
+# include/relgnn_sparse_update.h (row-deferred Adam for a row table whose gradient is +0 outside the rows a batch names): its own table too
+_SPARSE_UPDATE_SIGNATURES = {
+    "relgnn_rows_adam_supported": (ctypes.c_int, [_c_i32]),
+    "relgnn_rows_adam_catch_up": (ctypes.c_int, [_ptr, _c_i64, _ptr, _ptr, _ptr, _c_i64, _c_i32, _ptr, _ptr, _c_i32, _c_i32, _c_f32, _c_f32,
+                                                 _c_f32, _ptr]),
+    "relgnn_rows_adam_step": (ctypes.c_int, [_ptr, _c_i64, _ptr, _ptr, _c_i64, _ptr, _ptr, _c_i64, _c_i32, _ptr, _ptr, _c_i32, _c_i32, _ptr,
+                                             _c_f32, _c_f32, _c_f32, _c_f32, _c_f32, _ptr]),
+}
+
 _lib = None
 
 
@@ -262,7 +272,7 @@ def load_library():
     lib = ctypes.CDLL(str(LIB_PATH))
     for name, (restype, argtypes) in list(_SIGNATURES.items()) + list(_DROPOUT_SIGNATURES.items()) + list(_PREDICT_SIGNATURES.items()) \
             + list(_PARALLEL_SIGNATURES.items()) + list(_SPARSE_FEATURES_SIGNATURES.items()) + list(_SAMPLING_SIGNATURES.items()) \
-            + list(_SPARSE_SUBSET_SIGNATURES.items()):
+            + list(_SPARSE_SUBSET_SIGNATURES.items()) + list(_SPARSE_UPDATE_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the symbol is not exported
         fn.restype = restype
         fn.argtypes = argtypes
@@ -304,6 +314,11 @@ def sampling_signatures():
 def sparse_subset_signatures():
     """The entry points of include/relgnn_sparse_subset.h (not part of exported_signatures() either)."""
     return dict(_SPARSE_SUBSET_SIGNATURES)
+
+
+def sparse_update_signatures():
+    """The entry points of include/relgnn_sparse_update.h (not part of exported_signatures() either)."""
+    return dict(_SPARSE_UPDATE_SIGNATURES)
 
 
 def status_string(code: int) -> str:

@@ -5,6 +5,7 @@
 //   * citation head: masked softmax cross-entropy + accuracy     tasks/citation_network_task.py:133-148
 // Deterministic (no float atomics): fixed-shape tree reductions only.
 #include "common.h"
+#include "adam_element.h"
 
 using namespace relgnn;
 
@@ -99,12 +100,11 @@ __global__ __launch_bounds__(256) void mt_adam_clip_kernel(MtArgs a, const float
   float* m = a.m[t];
   float* v = a.v[t];
   for (long long i = beg + threadIdx.x; i < end; i += blockDim.x) {
-    const float gi = g[i] * scale;
-    const float mi = b1 * m[i] + (1.f - b1) * gi;
-    const float vi = b2 * v[i] + (1.f - b2) * (gi * gi);
+    float pi = p[i], mi = m[i], vi = v[i];
+    adam_element(pi, g[i] * scale, mi, vi, lr_t, b1, b2, eps);      // (adam_element.h: the rule the row-deferred launches replay)
     m[i] = mi;
     v[i] = vi;
-    p[i] = p[i] - lr_t * mi / (sqrtf(vi) + eps);
+    p[i] = pi;
   }
 }
 

@@ -11,6 +11,23 @@ from .. import _lib
 from ..dense import weights_changed
 
 
+class _DeferredRows:
+    """The state of the row-deferred parameter (TFStyleOptimizer.defer_rows; include/relgnn_sparse_update.h): stamps int32 [F], the
+    step each row is current to; step_sizes float32 [capacity], lr_t of steps base + 1 ... ; rowptr, what rows_touched() kept."""
+
+    def __init__(self, index: int, param: torch.Tensor, capacity: int, t: int):
+        self.index, self.capacity = index, capacity
+        self.rows, self.width = int(param.shape[0]), int(param.shape[1])
+        self.stamps = torch.empty(self.rows, dtype=torch.int32, device=param.device)
+        self.step_sizes = torch.zeros(capacity, dtype=torch.float32, device=param.device)
+        self.reset(t)
+
+    def reset(self, t: int) -> None:
+        self.base = int(t)
+        self.stamps.fill_(int(t))
+        self.rowptr = None
+
+
 class TFStyleOptimizer:
     """compute_gradients -> per-variable tf.clip_by_norm -> apply_gradients
     (models/sparse_graph_model.py:227-260) with TF1 update rules [TF-internal]:
@@ -33,6 +50,72 @@ class TFStyleOptimizer:
         elif self.name == 'rmsprop':
             self.ms = [torch.ones_like(p) for p in self.params]
             self.mom = [torch.zeros_like(p) for p in self.params]
+        self._deferred = None              # defer_rows(): the one row-deferred parameter's _DeferredRows
+
+    # ---- a row-deferred parameter (include/relgnn_sparse_update.h) ----
+    def defer_rows(self, param: torch.nn.Parameter, capacity: int = 1024) -> None:
+        """Register ONE 2-D [F, n] parameter whose gradient is +0 outside the rows a step's batch names (the weight of the sparse
+        input projection under sampled batches) as row-deferred.  Adam only.  The parameter keeps dense Adam's values bit for
+        bit, but a step reads and writes only the named rows: rows_touched(rowptr_t) before the step's forward brings the rows
+        the batch names up to date (the steps they missed, replayed with g = +0 and each step's own lr_t), clip_and_step() updates
+        those rows alone.  BETWEEN STEPS THE PARAMETER TENSOR AND ITS TWO SLOTS HOLD STALE ROWS; flush_deferred() brings all of
+        them up to date, and whoever reads the tensor outside a training step calls it first (tf_slot_weights / load_tf_slots do).
+        capacity: the length of the table of step sizes = the number of steps any row may fall behind = the bound of any launch's
+        replay loop; when the table is full the next step flushes first."""
+        if self.name != 'adam':
+            raise ValueError("defer_rows: a row-deferred update exists for Adam only (the optimizer is %r)" % self.name)
+        if self._deferred is not None:
+            raise ValueError("defer_rows: one parameter can be registered, and one already is")
+        index = [i for i, p in enumerate(self.params) if p is param]
+        if not index:
+            raise ValueError("defer_rows: the parameter is not one this optimizer updates")
+        if param.dim() != 2 or not param.is_contiguous() or param.dtype != torch.float32:
+            raise ValueError("defer_rows: a contiguous two-dimensional float32 parameter is needed, got shape %r" % (tuple(param.shape),))
+        n = int(param.shape[1])
+        if n % 4 or not 4 <= n <= 1024:            # relgnn_rows_adam_supported, restated: asked before the library is loaded
+            raise ValueError("defer_rows: rows of %d floats are outside what the row kernels take (a multiple of 4 in 4 .. 1024)" % n)
+        if isinstance(capacity, bool) or not isinstance(capacity, int) or capacity < 1:
+            raise ValueError("defer_rows: capacity must be a positive integer, got %r" % (capacity,))
+        self._deferred = _DeferredRows(index[0], param, capacity, self.t)
+
+    def rows_touched(self, rowptr_t: torch.Tensor) -> None:
+        """Before the forward of a training step: `rowptr_t` (int32 [F + 1], the row pointer of the batch's transposed structure)
+        names the rows the step reads and updates.  Those that are behind catch up to self.t on the current stream; the tensor is
+        kept for this step's clip_and_step()."""
+        d = self._require_deferred()
+        if rowptr_t.dtype != torch.int32 or rowptr_t.dim() != 1 or int(rowptr_t.shape[0]) != d.rows + 1:
+            raise ValueError("rows_touched: an int32 row pointer of %d entries is needed" % (d.rows + 1))
+        self._catch_up(rowptr_t)
+        d.rowptr = rowptr_t
+
+    def flush_deferred(self) -> None:
+        """Every row of the registered parameter up to date with self.t (nothing is launched when none can be behind, nor
+        without a registered parameter)."""
+        d = self._deferred
+        if d is None or d.base == self.t:
+            return
+        self._catch_up(None)
+        d.base = self.t
+
+    def pending_rows(self) -> int:
+        """How many rows of the registered parameter are behind self.t (synchronises: tests and diagnostics)."""
+        d = self._require_deferred()
+        return int((d.stamps < self.t).sum())
+
+    def _require_deferred(self):
+        if self._deferred is None:
+            raise RuntimeError("no parameter is registered as row-deferred (TFStyleOptimizer.defer_rows)")
+        return self._deferred
+
+    def _catch_up(self, rowptr_t) -> None:
+        d = self._deferred
+        if d.base == self.t:               # no step since the last flush: every stamp is self.t
+            return
+        i = d.index
+        p = self.params[i]
+        _lib.launch("relgnn_rows_adam_catch_up", _lib.ptr(rowptr_t), d.rows, _lib.ptr(p), _lib.ptr(self.m[i]), _lib.ptr(self.v[i]),
+                    d.width, d.width, _lib.ptr(d.stamps), _lib.ptr(d.step_sizes), d.base, self.t, 0.9, 0.999, 1e-8)
+        weights_changed()                  # (written through raw pointers, as the update itself)
 
     def _fused_update_available(self):
         return len(self.params) > 0 and all(p.is_cuda for p in self.params)
@@ -44,10 +127,14 @@ class TFStyleOptimizer:
         ~15-30 elementwise kernels of clip_gradients() + step(), which stay as the un-fused restatement (and the CPU path).
         device_step_count=True (hipGraph capture): the caller keeps self.t in step.  Adam's step count and lr_t then live in
         device memory (relgnn_adam_step_size / relgnn_mt_adam_clip_devlr); RMSProp and SGD have no step-dependent factor:
-        their lr = self.lr * lr_scale is a launch scalar, frozen into a captured graph."""
+        their lr = self.lr * lr_scale is a launch scalar, frozen into a captured graph.
+        A row-deferred parameter (defer_rows) stays in the norm launch, ordered last, so its norm has the bits it always had; it
+        leaves the Adam launch and takes relgnn_rows_adam_step over the rows rows_touched() named, with a pointer to its norm."""
         if not self._fused_update_available():
             if device_step_count:
                 raise RuntimeError("a captured training step needs the fused update: every parameter on the GPU")
+            if self._deferred is not None:
+                raise RuntimeError("a row-deferred parameter (defer_rows) needs the fused update: every parameter on the GPU")
             self.clip_gradients()
             self.step(lr_scale)
             return
@@ -55,6 +142,18 @@ class TFStyleOptimizer:
         idx = [i for i, p in enumerate(self.params) if p.grad is not None]
         if not idx:
             return
+        deferred = self._deferred
+        if deferred is not None:
+            if device_step_count:
+                raise RuntimeError("a captured training step cannot update a row-deferred parameter (defer_rows): the rows a step "
+                                   "names and the table of step sizes change with every step")
+            if deferred.index not in idx:
+                raise RuntimeError("the row-deferred parameter has no gradient in a step that updates other variables: dense Adam "
+                                   "would skip it, the replay would not")
+            if self.t - deferred.base == deferred.capacity:       # the table of step sizes is full
+                self.flush_deferred()
+            # last of the last chunk: the dense launch takes the entries in front of it, norms[n - 1] is its own
+            idx = [i for i in idx if i != deferred.index] + [deferred.index]
         b1, b2, eps = 0.9, 0.999, 1e-8
         lr = self.lr * lr_scale
         dev_state = None
@@ -86,6 +185,14 @@ class TFStyleOptimizer:
                             1e-10)
             elif dev_state is not None:
                 _lib.launch("relgnn_mt_adam_clip_devlr", h_p, h_g, *h_s, h_n, n, d_norms, clip, dev_state[1:].data_ptr(), b1, b2, eps)
+            elif deferred is not None and chunk[-1] == deferred.index:
+                if n > 1:
+                    _lib.launch("relgnn_mt_adam_clip", h_p, h_g, *h_s, h_n, n - 1, d_norms, clip, lr_t, b1, b2, eps)
+                i, d = deferred.index, deferred
+                _lib.launch("relgnn_rows_adam_step", _lib.ptr(d.rowptr), d.rows, _lib.ptr(self.params[i]), grads[-1].data_ptr(), d.width,
+                            _lib.ptr(self.m[i]), _lib.ptr(self.v[i]), d.width, d.width, _lib.ptr(d.stamps), _lib.ptr(d.step_sizes), d.base,
+                            self.t, norms[n - 1:].data_ptr(), clip, lr_t, b1, b2, eps)
+                d.rowptr = None            # (this step's; without rows_touched() before the next one every row is named)
             else:
                 _lib.launch("relgnn_mt_adam_clip", h_p, h_g, *h_s, h_n, n, d_norms, clip, lr_t, b1, b2, eps)
         weights_changed()                  # (written through raw pointers: the tensors' version counters did not move)
@@ -163,6 +270,7 @@ class TFStyleOptimizer:
 
     def tf_slot_weights(self, names: List[str]) -> Dict[str, np.ndarray]:
         assert len(names) == len(self.params)
+        self.flush_deferred()
         out = {}
         for suffix, tensors in self._slots():
             for n, t in zip(names, tensors):
@@ -177,6 +285,7 @@ class TFStyleOptimizer:
         """Restore the slots a reference pickle carries; returns the consumed keys.  The step count is recovered from
         beta1_power (= 0.9^(t+1))."""
         used = set()
+        self.flush_deferred()              # (a caller that overwrites the parameters too flushes before IT does: load_weights)
         for suffix, tensors in self._slots():
             for n, t in zip(names, tensors):
                 key = "%s/%s:0" % (n, suffix)
@@ -186,6 +295,8 @@ class TFStyleOptimizer:
         if self.name == 'adam' and "beta1_power:0" in weights:
             self.t = self._steps_from_beta_powers(weights.get("beta1_power:0"), weights.get("beta2_power:0"))
             used.update(k for k in ("beta1_power:0", "beta2_power:0") if k in weights)
+        if self._deferred is not None:     # what was loaded is current to the restored step count, every row of it
+            self._deferred.reset(self.t)
         return used
 
     @staticmethod

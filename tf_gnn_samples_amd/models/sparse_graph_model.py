@@ -144,6 +144,7 @@ class Sparse_Graph_Model(ABC):
 
     # -------------------- Model Saving/Loading (reference pickle layout :91-126) --------------------
     def save_model(self, path: str) -> None:
+        self.optimizer.flush_deferred()    # (a row-deferred parameter, `sparse_update`: its tensor holds stale rows between training steps)
         data_to_save = {
             "model_class": self.name(self.params),
             "task_class": self.task.name(),
@@ -162,6 +163,7 @@ class Sparse_Graph_Model(ABC):
     def load_weights(self, weights: Dict[str, np.ndarray]) -> None:
         """:109-126: assign every variable the pickle names (model variables and optimizer slots), freshly initialise
         (= keep the initial value of) the ones it does not, report saved entries nothing consumed."""
+        self.optimizer.flush_deferred()    # (before anything is overwritten: a replay behind it would run on the loaded values)
         used = self.variables.load_tf_weights(weights, report_unused=False)
         used |= self.optimizer.load_tf_slots(weights, self._trainable_names())
         weights_changed()                  # (copy_ moves the version counters too; said once more for limb images kept per step)
@@ -310,6 +312,18 @@ class Sparse_Graph_Model(ABC):
         self.optimizer = TFStyleOptimizer(list(self.variables.parameters()), p['optimizer'], p['learning_rate'],
                                           p['clamp_gradient_norm'], decay=p['learning_rate_decay'],
                                           momentum=p['momentum'])
+        if getattr(self.task, "sparse_update", False):
+            # the citation task's `sampled_batches` key "sparse_update": the weight of the sparse input projection is updated by rows.
+            # CONTRACT: between training steps that parameter's tensor (and its two Adam slots) hold stale rows; everything here that
+            # reads them outside a training step calls self.optimizer.flush_deferred() first (forward_batch(training=False),
+            # predict_iter, save_model, load_weights), and so must anyone who reads self.variables directly.
+            if self.optimizer.name != 'adam':
+                raise ValueError('sampled_batches: "sparse_update": true requires the optimizer Adam (got %r): the row-deferred update '
+                                 'replays Adam steps' % (p['optimizer'],))
+            if "graph_model/dense/kernel" not in self.variables:
+                raise ValueError('sampled_batches: "sparse_update": true requires a model with the input projection '
+                                 'graph_model/dense/kernel (hidden_size %d equals the feature size: there is none)' % p['hidden_size'])
+            self.optimizer.defer_rows(self.variables["graph_model/dense/kernel"])
 
     # -------------------- Training Loop --------------------
     def _final_node_states(self, batch: DeviceBatch, training: bool) -> torch.Tensor:
@@ -323,6 +337,10 @@ class Sparse_Graph_Model(ABC):
             batch.type_to_num_incoming_edges, keep)
 
     def forward_batch(self, batch: DeviceBatch, training: bool):
+        """training=False with a row-deferred parameter (`sparse_update`): every row is brought up to date first; a training forward
+        relies on train_step's rows_touched()."""
+        if not training:
+            self.optimizer.flush_deferred()
         final = self._final_node_states(batch, training)
         return self.task.compute_task_metrics(final, batch, self.variables.scope(self._task_scope))
 
@@ -367,6 +385,7 @@ class Sparse_Graph_Model(ABC):
         grad_hook(params): between the backward and the clipping (the data-parallel reduction);
         lr_num_graphs: the graph count lr_for_num_graphs_per_batch scales by (data-parallel: the step's global count)."""
         self.optimizer.zero_grad()
+        self._name_touched_rows(batch)
         metrics = self.forward_batch(batch, training=True)
         if pre_backward is not None:
             pre_backward()
@@ -388,6 +407,18 @@ class Sparse_Graph_Model(ABC):
         lr_scale = self._lr_scale(batch.num_graphs if lr_num_graphs is None else lr_num_graphs)
         self.optimizer.clip_and_step(lr_scale, device_step_count=device_step_count)
         return metrics
+
+    def _name_touched_rows(self, batch: DeviceBatch) -> None:
+        """With a row-deferred projection weight (`sparse_update`): the rows this step's forward reads and its update writes are the
+        non-empty rows of the transposed structure of the batch's SparseRows (a sampled batch's own container, or the fold's for a
+        full-graph sparse batch); they catch up before the forward.  Nothing otherwise."""
+        if getattr(self.optimizer, "_deferred", None) is None:
+            return
+        batch.wait_ready()                 # (a batch assembled on a side stream: a per-batch container records its tensors for this one)
+        rows = self.task.compute_initial_node_features(batch, self.variables.scope(""))
+        if not isinstance(rows, SparseRows):
+            raise RuntimeError("sparse_update: a training batch without sparse node features cannot name the rows it touches")
+        self.optimizer.rows_touched(rows.transposed.rowptr)
 
     def _lr_scale(self, num_graphs: int) -> float:
         lr_n = self.params.get('lr_for_num_graphs_per_batch')
@@ -546,6 +577,7 @@ class Sparse_Graph_Model(ABC):
 
     def _predict_batches(self, data, return_states, pinned):
         cursor, turn = 0, 0
+        self.optimizer.flush_deferred()    # (`sparse_update`: the projection's weight holds stale rows between training steps)
         late = LateFetch(self._fetch_predictions)
         batch_iterator = iter(self._batches(data, DataFold.TEST))
         upcoming = next(batch_iterator, None)

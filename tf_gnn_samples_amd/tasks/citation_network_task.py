@@ -27,7 +27,13 @@ SparseRows instead of a dense table, and every sampled batch carries the [n, 1] 
 the batch's rows, the CSR of that subset's transpose (what the projection's weight gradient runs over) and both long-row plans,
 built on the device per batch (csrc/sparse_subset.hip, include/relgnn_sparse_subset.h) with one read-back of eight sizes.  No
 [V, F] or [n, F] dense array exists on the host or the device.  The weight gradient itself stays a dense [F, hidden] tensor, and the
-optimizer still walks all of it.
+optimizer walks all of it unless the next key says otherwise.
+
+One more optional key, "sparse_update": true (requires "sparse_features": true, optimizer Adam and a model with the input projection
+`graph_model/dense/kernel`; each is a ValueError when the task or the model is built): the optimizer registers the projection's weight
+as row-deferred (TFStyleOptimizer.defer_rows, csrc/sparse_update.hip, include/relgnn_sparse_update.h).  A training step then reads and
+writes only the rows of the weight and its two Adam slots whose words the batch holds, and every stored value is still dense Adam's,
+bit for bit.  The dense gradient and the norm over it stay.
 """
 import os
 import pickle
@@ -251,6 +257,12 @@ class Citation_Network_Task(Sparse_Graph_Task):
         if sampled.get("sparse_features", False) and not self.sparse_node_features:
             raise ValueError("sampled_batches: \"sparse_features\": true requires the task parameter sparse_node_features: True")
         return sampled
+
+    @property
+    def sparse_update(self) -> bool:
+        """Does `sampled_batches` ask for the row-deferred update of the input projection's weight?"""
+        sampled = self.sampled_batches
+        return bool(sampled is not None and sampled.get("sparse_update", False))
 
     @property
     def num_edge_types(self) -> int:

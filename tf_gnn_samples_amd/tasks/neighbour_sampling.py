@@ -191,13 +191,14 @@ class NeighbourSampler:
 
 def parse_sampled_batches(value) -> Optional[Dict]:
     """The task parameter `sampled_batches` as {"fanouts": [ints], "seeds_per_batch": int, "seed": int}, None when it is absent;
-    the optional key "sparse_features" (a bool: the batches take their feature rows from a SparseRows) is carried only when given."""
+    the optional keys "sparse_features" (a bool: the batches take their feature rows from a SparseRows) and "sparse_update" (a bool:
+    the optimizer updates only the rows of the input projection's weight that a batch names) are carried only when given."""
     if value is None:
         return None
     if not isinstance(value, dict) or not {"fanouts", "seeds_per_batch"} <= set(value) \
-            or set(value) - {"fanouts", "seeds_per_batch", "seed", "sparse_features"}:
-        raise ValueError('sampled_batches must be {"fanouts": [k_1, ..., k_H], "seeds_per_batch": B, "seed": s, "sparse_features": bool}, '
-                         'the last two optional, got %r' % (value,))
+            or set(value) - {"fanouts", "seeds_per_batch", "seed", "sparse_features", "sparse_update"}:
+        raise ValueError('sampled_batches must be {"fanouts": [k_1, ..., k_H], "seeds_per_batch": B, "seed": s, "sparse_features": bool, '
+                         '"sparse_update": bool}, the last three optional, got %r' % (value,))
     per_batch = value["seeds_per_batch"]
     if isinstance(per_batch, bool) or not isinstance(per_batch, (int, np.integer)) or per_batch < 1:
         raise ValueError("sampled_batches: seeds_per_batch must be a positive integer, got %r" % (per_batch,))
@@ -206,4 +207,11 @@ def parse_sampled_batches(value) -> Optional[Dict]:
         if not isinstance(value["sparse_features"], bool):
             raise ValueError("sampled_batches: sparse_features must be true or false, got %r" % (value["sparse_features"],))
         parsed["sparse_features"] = value["sparse_features"]
+    if "sparse_update" in value:
+        if not isinstance(value["sparse_update"], bool):
+            raise ValueError("sampled_batches: sparse_update must be true or false, got %r" % (value["sparse_update"],))
+        if value["sparse_update"] and not parsed.get("sparse_features", False):
+            raise ValueError("sampled_batches: \"sparse_update\": true requires \"sparse_features\": true (the rows a batch names are "
+                             "read from the transposed structure of its SparseRows)")
+        parsed["sparse_update"] = value["sparse_update"]
     return parsed
