@@ -1,6 +1,6 @@
 """ctypes binding of librelgnn.so (C ABI: include/relgnn.h, include/relgnn_dropout.h, include/relgnn_predict.h,
 include/relgnn_parallel.h, include/relgnn_sparse_features.h, include/relgnn_sampling.h, include/relgnn_sparse_subset.h,
-include/relgnn_sparse_update.h).
+include/relgnn_sparse_update.h, include/relgnn_sparse_gradient.h).
 
 This is the ONLY compute backend of the package.  There is no CPU / eager-PyTorch fallback:
 if the HIP library is missing, or a tensor is not a float32/int32 CUDA(HIP) tensor, the
@@ -253,6 +253,18 @@ _SPARSE_UPDATE_SIGNATURES = {
                                              _c_f32, _c_f32, _c_f32, _c_f32, _c_f32, _ptr]),
 }
 
+# include/relgnn_sparse_gradient.h (the compact gradient of that row table: named rows, the dense norm's bits over them, the row step
+# on compact rows): its own table too
+_SPARSE_GRADIENT_SIGNATURES = {
+    "relgnn_named_rows_workspace_bytes": (ctypes.c_size_t, [_c_i64]),
+    "relgnn_named_rows_count": (ctypes.c_int, [_ptr, _c_i64, _ptr, _ptr, _ptr, ctypes.c_size_t, _ptr]),
+    "relgnn_named_rows_fill": (ctypes.c_int, [_ptr, _c_i64, _ptr, _c_i64, _ptr, _ptr, _ptr, _ptr, _c_i64, _ptr, _ptr, _c_i64, _ptr]),
+    "relgnn_rows_l2norm_workspace_bytes": (ctypes.c_size_t, []),
+    "relgnn_rows_l2norm": (ctypes.c_int, [_ptr, _c_i64, _ptr, _c_i64, _c_i32, _c_i64, _ptr, _ptr, ctypes.c_size_t, _ptr]),
+    "relgnn_rows_adam_step_compact": (ctypes.c_int, [_ptr, _c_i64, _c_i64, _ptr, _ptr, _c_i64, _ptr, _ptr, _c_i64, _c_i32, _ptr, _ptr, _c_i32,
+                                                     _c_i32, _ptr, _c_f32, _c_f32, _c_f32, _c_f32, _c_f32, _ptr]),
+}
+
 _lib = None
 
 
@@ -272,7 +284,8 @@ def load_library():
     lib = ctypes.CDLL(str(LIB_PATH))
     for name, (restype, argtypes) in list(_SIGNATURES.items()) + list(_DROPOUT_SIGNATURES.items()) + list(_PREDICT_SIGNATURES.items()) \
             + list(_PARALLEL_SIGNATURES.items()) + list(_SPARSE_FEATURES_SIGNATURES.items()) + list(_SAMPLING_SIGNATURES.items()) \
-            + list(_SPARSE_SUBSET_SIGNATURES.items()) + list(_SPARSE_UPDATE_SIGNATURES.items()):
+            + list(_SPARSE_SUBSET_SIGNATURES.items()) + list(_SPARSE_UPDATE_SIGNATURES.items()) \
+            + list(_SPARSE_GRADIENT_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the symbol is not exported
         fn.restype = restype
         fn.argtypes = argtypes
@@ -319,6 +332,11 @@ def sparse_subset_signatures():
 def sparse_update_signatures():
     """The entry points of include/relgnn_sparse_update.h (not part of exported_signatures() either)."""
     return dict(_SPARSE_UPDATE_SIGNATURES)
+
+
+def sparse_gradient_signatures():
+    """The entry points of include/relgnn_sparse_gradient.h (not part of exported_signatures() either)."""
+    return dict(_SPARSE_GRADIENT_SIGNATURES)
 
 
 def status_string(code: int) -> str:

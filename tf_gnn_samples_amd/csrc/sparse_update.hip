@@ -5,10 +5,12 @@
 // Streaming kernels: per named row 3 (catch-up) or 4 (step) arrays of n floats are read and 3 written, 16 bytes per lane, a row's
 // n floats contiguous.  A wave takes 64 consecutive rows: lane l reads the rowptr_t pair and the stamp of row 64 c + l (two coalesced
 // 256-byte reads and, for named rows, a third), the ballot of "has work" is the wave's to-do list, and the wave walks it row by row.
+// The compact step (relgnn_rows_adam_step_compact) walks a list of named words instead: 64 list entries per wave, no row pointer.
 // One wave per ROW would make a 2^20-row table 2^20 mostly empty waves; this way an unnamed row costs 8 bytes of one read.
 #include "common.h"
 #include "adam_element.h"
 #include "../../include/relgnn_sparse_update.h"
+#include "../../include/relgnn_sparse_gradient.h"
 
 using namespace relgnn;
 
@@ -28,9 +30,12 @@ __device__ __forceinline__ void adam_element4(float4& p, const float4& gi, float
 // STEP = false: named rows behind t replay steps stamp + 1 .. t.
 // STEP = true : named rows replay steps stamp + 1 .. t - 1, then take step t with g * scale and lr_t; step_sizes[t - base - 1] = lr_t
 //               (the replays read entries below that one only).
+// COMPACT (include/relgnn_sparse_gradient.h): F counts the named rows, which are words[0 .. F), each in [0, table_rows), and the
+//               gradient row of words[i] is g row i.  Otherwise rows 0 .. F of the table are walked and row f's gradient is g row f.
 // n4 = n / 4; ld and ld_g in floats, multiples of 4.  Every loop is bounded by F, n4 and t - base.
-template <bool STEP>
-__global__ __launch_bounds__(kBlock) void rows_adam_kernel(const int32_t* __restrict__ rowptr_t, long long F, float* __restrict__ p,
+template <bool STEP, bool COMPACT>
+__global__ __launch_bounds__(kBlock) void rows_adam_kernel(const int32_t* __restrict__ rowptr_t, const int32_t* __restrict__ words,
+                                                           long long table_rows, long long F, float* __restrict__ p,
                                                            const float* __restrict__ g, long long ld_g, float* __restrict__ m,
                                                            float* __restrict__ v, long long ld, int n4, int32_t* __restrict__ stamps,
                                                            float* step_sizes, int base, int t, const float* __restrict__ norm,
@@ -47,10 +52,18 @@ __global__ __launch_bounds__(kBlock) void rows_adam_kernel(const int32_t* __rest
   const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
   const long long chunks = (F + RELGNN_WAVE - 1) / RELGNN_WAVE;
   for (long long chunk = wave; chunk < chunks; chunk += num_waves) {
-    const long long f = chunk * RELGNN_WAVE + lane;
-    bool work = false;
+    long long f = chunk * RELGNN_WAVE + lane;
+    bool work = false, named = false;
     int stamp = 0;
-    if (f < F && (!rowptr_t || rowptr_t[f + 1] > rowptr_t[f])) {
+    if (COMPACT) {
+      if (f < F) {
+        f = words[f];
+        named = f >= 0 && f < table_rows;
+      }
+    } else {
+      named = f < F && (!rowptr_t || rowptr_t[f + 1] > rowptr_t[f]);
+    }
+    if (named) {
       stamp = max(stamps[f], base);                           // (a stamp below base: the loop is clamped to the table)
       work = STEP || stamp < replay_to;
     }
@@ -59,14 +72,16 @@ __global__ __launch_bounds__(kBlock) void rows_adam_kernel(const int32_t* __rest
       const int l = __ffsll(todo) - 1;
       todo &= todo - 1;
       const int from = __builtin_amdgcn_readfirstlane(__shfl(stamp, l));
-      const long long row = chunk * RELGNN_WAVE + l;
+      const long long g_row = chunk * RELGNN_WAVE + l;
+      long long row = g_row;
+      if (COMPACT) row = __builtin_amdgcn_readfirstlane(__shfl((int)f, l));
       float4* p4 = reinterpret_cast<float4*>(p + row * ld);
       float4* m4 = reinterpret_cast<float4*>(m + row * ld);
       float4* v4 = reinterpret_cast<float4*>(v + row * ld);
       for (int c = lane; c < n4; c += RELGNN_WAVE) {
         float4 pv = p4[c], mv = m4[c], vv = v4[c], gv = zero;
         if (STEP) {
-          gv = reinterpret_cast<const float4*>(g + row * ld_g)[c];
+          gv = reinterpret_cast<const float4*>(g + g_row * ld_g)[c];
           gv.x = gv.x * scale; gv.y = gv.y * scale; gv.z = gv.z * scale; gv.w = gv.w * scale;
         }
         for (int step = from + 1; step <= replay_to; ++step)
@@ -105,7 +120,7 @@ int relgnn_rows_adam_catch_up(const int32_t* rowptr_t, int64_t F, float* p, floa
   if (!relgnn_rows_adam_supported(n)) return RELGNN_EUNSUPPORTED;
   if (F == 0 || t_now == base) return RELGNN_OK;              // no stamp is below base: nothing is behind
   if (!rows_ok(p, ld, n) || !rows_ok(m, ld, n) || !rows_ok(v, ld, n) || !stamps || !step_sizes) return RELGNN_EINVAL;
-  rows_adam_kernel<false><<<rows_grid(F), kBlock, 0, as_stream(stream)>>>(rowptr_t, F, p, nullptr, 0, m, v, ld, n / 4, stamps,
+  rows_adam_kernel<false, false><<<rows_grid(F), kBlock, 0, as_stream(stream)>>>(rowptr_t, nullptr, 0, F, p, nullptr, 0, m, v, ld, n / 4, stamps,
                                                                          const_cast<float*>(step_sizes), base, t_now, nullptr,
                                                                          0.f, 0.f, beta1, beta2, eps);
   return launch_status();
@@ -118,9 +133,24 @@ int relgnn_rows_adam_step(const int32_t* rowptr_t, int64_t F, float* p, const fl
   if (!relgnn_rows_adam_supported(n)) return RELGNN_EUNSUPPORTED;
   if (F > 0 && (!rows_ok(p, ld, n) || !rows_ok(m, ld, n) || !rows_ok(v, ld, n) || !rows_ok(g, ld_g, n) || !stamps))
     return RELGNN_EINVAL;
-  rows_adam_kernel<true><<<rows_grid(F), kBlock, 0, as_stream(stream)>>>(rowptr_t, F, p, g, ld_g, m, v, ld, n / 4, stamps,
+  rows_adam_kernel<true, false><<<rows_grid(F), kBlock, 0, as_stream(stream)>>>(rowptr_t, nullptr, 0, F, p, g, ld_g, m, v, ld, n / 4, stamps,
                                                                         step_sizes, base, t_new, norm, clip, lr_t, beta1, beta2,
                                                                         eps);
+  return launch_status();
+}
+
+int relgnn_rows_adam_step_compact(const int32_t* words, int64_t T, int64_t F, float* p, const float* g, int64_t ld_g, float* m,
+                                  float* v, int64_t ld, int32_t n, int32_t* stamps, float* step_sizes, int32_t base, int32_t t_new,
+                                  const float* norm, float clip, float lr_t, float beta1, float beta2, float eps, void* stream) {
+  if (F < 0 || F >= INT32_MAX || T < 0 || T > F || base < 0 || t_new <= base || !step_sizes || (clip > 0.f && !norm))
+    return RELGNN_EINVAL;
+  if (!relgnn_rows_adam_supported(n)) return RELGNN_EUNSUPPORTED;
+  if (T > 0 && (!words || !rows_ok(p, ld, n) || !rows_ok(m, ld, n) || !rows_ok(v, ld, n) || !rows_ok(g, ld_g, n) || !stamps))
+    return RELGNN_EINVAL;
+  // (T == 0: one block that stores the step size and finds no row)
+  rows_adam_kernel<true, true><<<rows_grid(T), kBlock, 0, as_stream(stream)>>>(nullptr, words, F, T, p, g, ld_g, m, v, ld, n / 4,
+                                                                              stamps, step_sizes, base, t_new, norm, clip, lr_t,
+                                                                              beta1, beta2, eps);
   return launch_status();
 }
 

@@ -6,6 +6,7 @@
 // Deterministic (no float atomics): fixed-shape tree reductions only.
 #include "common.h"
 #include "adam_element.h"
+#include "norm_tree.h"
 
 using namespace relgnn;
 
@@ -40,10 +41,8 @@ __device__ __forceinline__ double block_sum_1024(double x, double* red) {
 
 // norms[t] = sqrt(sum g^2): grid (kNormChunks, tensors) of partial sums in double, then one small block per tensor
 // adds the kNormChunks partials in a fixed order (deterministic; a single block per tensor took 35 us for the
-// 196 k-element kernels of C2, this pair takes ~10 us)
-constexpr int kNormChunks = 32;
-
-__global__ __launch_bounds__(256) void mt_l2norm_partial_kernel(NormArgs a, double* __restrict__ partial) {
+// 196 k-element kernels of C2, this pair takes ~10 us).  The tree is norm_tree.h's, shared with sparse_gradient.hip.
+__global__ __launch_bounds__(kNormBlock) void mt_l2norm_partial_kernel(NormArgs a, double* __restrict__ partial) {
   __shared__ double red[4];
   const int t = blockIdx.y;
   const float* g = a.g[t];
@@ -53,20 +52,14 @@ __global__ __launch_bounds__(256) void mt_l2norm_partial_kernel(NormArgs a, doub
     const double x = g[i];
     acc += x * x;
   }
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) acc += __shfl_xor(acc, off);
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  if (lane == 0) red[wave] = acc;
-  __syncthreads();
-  if (threadIdx.x == 0) partial[(long long)t * kNormChunks + blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+  const double sum = norm_block_partial(acc, red);
+  if (threadIdx.x == 0) partial[(long long)t * kNormChunks + blockIdx.x] = sum;
 }
 
 __global__ __launch_bounds__(64) void mt_l2norm_final_kernel(const double* __restrict__ partial, float* __restrict__ norms) {
   const int t = blockIdx.x;
-  double x = threadIdx.x < kNormChunks ? partial[(long long)t * kNormChunks + threadIdx.x] : 0.0;
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) x += __shfl_xor(x, off);
-  if (threadIdx.x == 0) norms[t] = (float)sqrt(x);
+  const float norm = norm_of_partials(partial + (long long)t * kNormChunks);
+  if (threadIdx.x == 0) norms[t] = norm;
 }
 
 // grid (chunks, tensors): g' = g * clip / max(||g||, clip)  (tf.clip_by_norm), then TF1 Adam:
@@ -450,7 +443,7 @@ int relgnn_mt_l2norm(const float* const* h_grads, const int64_t* h_sizes, int32_
     a.n[i] = h_sizes[i];
   }
   double* partial = static_cast<double*>(workspace);
-  mt_l2norm_partial_kernel<<<dim3(kNormChunks, (unsigned)n), 256, 0, as_stream(stream)>>>(a, partial);
+  mt_l2norm_partial_kernel<<<dim3(kNormChunks, (unsigned)n), kNormBlock, 0, as_stream(stream)>>>(a, partial);
   mt_l2norm_final_kernel<<<n, 64, 0, as_stream(stream)>>>(partial, norms);
   return launch_status();
 }

@@ -18,6 +18,7 @@ class _DeferredRows:
     def __init__(self, index: int, param: torch.Tensor, capacity: int, t: int):
         self.index, self.capacity = index, capacity
         self.rows, self.width = int(param.shape[0]), int(param.shape[1])
+        self.sink = None                   # compact_row_gradient(): the RowGradientSink
         self.stamps = torch.empty(self.rows, dtype=torch.int32, device=param.device)
         self.step_sizes = torch.zeros(capacity, dtype=torch.float32, device=param.device)
         self.reset(t)
@@ -26,6 +27,51 @@ class _DeferredRows:
         self.base = int(t)
         self.stamps.fill_(int(t))
         self.rowptr = None
+
+
+class RowGradient:
+    """One step's compact gradient of the row-deferred [F, n] parameter: values float32 [T, n] are its rows `words` (int32 [T],
+    ascending); slot int32 [F + 1] maps a word to its row of `values`; every other row of the gradient is +0."""
+
+    def __init__(self, words: torch.Tensor, slot: torch.Tensor, values: torch.Tensor, rows: int):
+        self.words, self.slot, self.values, self.rows = words, slot, values, int(rows)
+
+    def to_dense(self) -> torch.Tensor:
+        """The [F, n] gradient (tests and debugging: the step itself never builds it)."""
+        dense = torch.zeros((self.rows, self.values.shape[1]), dtype=self.values.dtype, device=self.values.device)
+        dense[self.words.long()] = self.values
+        return dense
+
+
+class RowGradientSink:
+    """Where ops.csr_rows_project's backward leaves the compact gradient of the row-deferred parameter (TFStyleOptimizer.
+    compact_row_gradient owns it).  One deposit per step; clip_and_step() and zero_grad() empty it."""
+
+    def __init__(self, rows: int, width: int):
+        self.rows, self.width = int(rows), int(width)
+        self.gradient = None
+
+    def check(self, container) -> None:
+        if self.gradient is not None:
+            raise RuntimeError("row gradient sink: a second deposit in one step (the projection ran its backward twice; a compact "
+                               "gradient is not accumulated)")
+        if not getattr(container, "has_named_rows", False):
+            raise RuntimeError("row gradient sink: the feature container carries no named rows (SparseRows.named_rows / "
+                               "take_rows(named_rows=True) before the step)")
+
+    def deposit(self, named, values: torch.Tensor) -> None:
+        self.check_shape(named, values)
+        self.gradient = RowGradient(named.words, named.slot, values, self.rows)
+
+    def check_shape(self, named, values: torch.Tensor) -> None:
+        if self.gradient is not None:
+            raise RuntimeError("row gradient sink: a second deposit in one step")
+        if int(named.slot.shape[0]) != self.rows + 1 or tuple(values.shape) != (named.count, self.width):
+            raise RuntimeError("row gradient sink: a [%d, %d] gradient over %d words does not belong to the registered [%d, %d] "
+                               "parameter" % (values.shape[0], values.shape[1], int(named.slot.shape[0]) - 1, self.rows, self.width))
+
+    def clear(self) -> None:
+        self.gradient = None
 
 
 class TFStyleOptimizer:
@@ -78,6 +124,21 @@ class TFStyleOptimizer:
             raise ValueError("defer_rows: capacity must be a positive integer, got %r" % (capacity,))
         self._deferred = _DeferredRows(index[0], param, capacity, self.t)
 
+    def compact_row_gradient(self) -> RowGradientSink:
+        """On top of defer_rows(): the registered parameter's gradient arrives as the rows a step names only
+        (include/relgnn_sparse_gradient.h).  Returns the sink to hand to ops.csr_rows_project(row_gradient_sink=...); its backward
+        deposits (words, slot, values [T, n]) there and leaves the parameter's .grad None.  clip_and_step() then computes the
+        parameter's norm over those rows with the bits relgnn_mt_l2norm gives the dense gradient, and updates the rows from them."""
+        d = self._require_deferred()
+        if d.sink is None:
+            d.sink = RowGradientSink(d.rows, d.width)
+        return d.sink
+
+    @property
+    def row_gradient_sink(self):
+        """The sink of compact_row_gradient(), None without one."""
+        return self._deferred.sink if self._deferred is not None else None
+
     def rows_touched(self, rowptr_t: torch.Tensor) -> None:
         """Before the forward of a training step: `rowptr_t` (int32 [F + 1], the row pointer of the batch's transposed structure)
         names the rows the step reads and updates.  Those that are behind catch up to self.t on the current stream; the tensor is
@@ -129,7 +190,9 @@ class TFStyleOptimizer:
         device memory (relgnn_adam_step_size / relgnn_mt_adam_clip_devlr); RMSProp and SGD have no step-dependent factor:
         their lr = self.lr * lr_scale is a launch scalar, frozen into a captured graph.
         A row-deferred parameter (defer_rows) stays in the norm launch, ordered last, so its norm has the bits it always had; it
-        leaves the Adam launch and takes relgnn_rows_adam_step over the rows rows_touched() named, with a pointer to its norm."""
+        leaves the Adam launch and takes relgnn_rows_adam_step over the rows rows_touched() named, with a pointer to its norm.
+        With a compact gradient (compact_row_gradient) it leaves the norm launch too: relgnn_rows_l2norm gives the same float
+        from the deposited rows, relgnn_rows_adam_step_compact updates from them, and the sink is emptied."""
         if not self._fused_update_available():
             if device_step_count:
                 raise RuntimeError("a captured training step needs the fused update: every parameter on the GPU")
@@ -140,20 +203,25 @@ class TFStyleOptimizer:
             return
         lib = _lib.load_library()
         idx = [i for i, p in enumerate(self.params) if p.grad is not None]
-        if not idx:
-            return
         deferred = self._deferred
+        compact = deferred.sink.gradient if deferred is not None and deferred.sink is not None else None
+        if not idx and compact is None:
+            return
         if deferred is not None:
+            if deferred.sink is not None and deferred.index in idx:
+                raise RuntimeError("the row-deferred parameter has a dense gradient although its gradient is registered as compact "
+                                   "(compact_row_gradient): the projection ran without the sink")
             if device_step_count:
                 raise RuntimeError("a captured training step cannot update a row-deferred parameter (defer_rows): the rows a step "
                                    "names and the table of step sizes change with every step")
-            if deferred.index not in idx:
+            if compact is None and deferred.index not in idx:
                 raise RuntimeError("the row-deferred parameter has no gradient in a step that updates other variables: dense Adam "
                                    "would skip it, the replay would not")
             if self.t - deferred.base == deferred.capacity:       # the table of step sizes is full
                 self.flush_deferred()
-            # last of the last chunk: the dense launch takes the entries in front of it, norms[n - 1] is its own
-            idx = [i for i in idx if i != deferred.index] + [deferred.index]
+            if compact is None:
+                # last of the last chunk: the dense launch takes the entries in front of it, norms[n - 1] is its own
+                idx = [i for i in idx if i != deferred.index] + [deferred.index]
         b1, b2, eps = 0.9, 0.999, 1e-8
         lr = self.lr * lr_scale
         dev_state = None
@@ -195,7 +263,26 @@ class TFStyleOptimizer:
                 d.rowptr = None            # (this step's; without rows_touched() before the next one every row is named)
             else:
                 _lib.launch("relgnn_mt_adam_clip", h_p, h_g, *h_s, h_n, n, d_norms, clip, lr_t, b1, b2, eps)
+        if compact is not None:
+            self._compact_step(compact, float(self.clip), lr_t, b1, b2, eps)
         weights_changed()                  # (written through raw pointers: the tensors' version counters did not move)
+
+    def _compact_step(self, gradient: RowGradient, clip: float, lr_t: float, b1: float, b2: float, eps: float) -> None:
+        """The registered parameter's norm and update from its compact gradient (include/relgnn_sparse_gradient.h)."""
+        lib, d = _lib.load_library(), self._deferred
+        i, T = d.index, int(gradient.values.shape[0])
+        values = gradient.values if gradient.values.is_contiguous() else gradient.values.contiguous()
+        some = lambda t: _lib.ptr(t) if T else None
+        norm = torch.empty(1, dtype=torch.float32, device=values.device)
+        ws_bytes = lib.relgnn_rows_l2norm_workspace_bytes()
+        ws = _lib.scratch(ws_bytes, values.device)
+        _lib.launch("relgnn_rows_l2norm", some(gradient.words), T, some(values), d.width, d.width, d.rows, _lib.ptr(norm), _lib.ptr(ws),
+                    ws_bytes)
+        _lib.launch("relgnn_rows_adam_step_compact", some(gradient.words), T, d.rows, _lib.ptr(self.params[i]), some(values), d.width,
+                    _lib.ptr(self.m[i]), _lib.ptr(self.v[i]), d.width, d.width, _lib.ptr(d.stamps), _lib.ptr(d.step_sizes), d.base,
+                    self.t, _lib.ptr(norm), clip, lr_t, b1, b2, eps)
+        d.sink.clear()
+        d.rowptr = None
 
     def _device_state(self):
         """[steps taken, lr_t] in device memory, seeded from the host step count."""
@@ -257,6 +344,8 @@ class TFStyleOptimizer:
     def zero_grad(self):
         for p in self.params:
             p.grad = None
+        if self.row_gradient_sink is not None:
+            self.row_gradient_sink.clear()
 
     # ---- optimizer state under TF's GLOBAL_VARIABLES names (the reference pickles those too, :91-107) ----
     def _slots(self):

@@ -211,11 +211,15 @@ class Sparse_Graph_Model(ABC):
     def _project_input(self, initial_node_features, w, act_id: int, sole_consumer: bool) -> torch.Tensor:
         """:165-170: the unnamed Dense in front of the first layer, when the feature size differs from hidden_size.  Features that
         a task keeps sparse (tasks/sparse_features.py, the citation task's sparse_node_features mode) gather rows of the same
-        `dense/kernel` instead (ops.csr_rows_project); without a projection they are densified on the device."""
+        `dense/kernel` instead (ops.csr_rows_project); without a projection they are densified on the device.  With the citation
+        task's `"sparse_gradient": true` the optimizer's sink goes along: the backward leaves the weight's gradient there as the
+        rows the batch names, not in `.grad`."""
         has_projection = self.task.initial_node_feature_size != self.params['hidden_size']
         if isinstance(initial_node_features, SparseRows):
             if has_projection:
-                return ops.csr_rows_project(initial_node_features, w["dense/kernel"], act_id)
+                optimizer = getattr(self, "optimizer", None)
+                sink = optimizer.row_gradient_sink if optimizer is not None and torch.is_grad_enabled() else None
+                return ops.csr_rows_project(initial_node_features, w["dense/kernel"], act_id, row_gradient_sink=sink)
             return initial_node_features.to_dense()
         if has_projection:
             return dense_act(initial_node_features, w["dense/kernel"], None, act_id, sole_consumer=sole_consumer)
@@ -324,6 +328,9 @@ class Sparse_Graph_Model(ABC):
                 raise ValueError('sampled_batches: "sparse_update": true requires a model with the input projection '
                                  'graph_model/dense/kernel (hidden_size %d equals the feature size: there is none)' % p['hidden_size'])
             self.optimizer.defer_rows(self.variables["graph_model/dense/kernel"])
+            if getattr(self.task, "sparse_gradient", False):
+                # "sparse_gradient": that weight's gradient exists only as the rows a batch names (_project_input hands the sink on)
+                self.optimizer.compact_row_gradient()
 
     # -------------------- Training Loop --------------------
     def _final_node_states(self, batch: DeviceBatch, training: bool) -> torch.Tensor:
@@ -418,6 +425,8 @@ class Sparse_Graph_Model(ABC):
         rows = self.task.compute_initial_node_features(batch, self.variables.scope(""))
         if not isinstance(rows, SparseRows):
             raise RuntimeError("sparse_update: a training batch without sparse node features cannot name the rows it touches")
+        if self.optimizer.row_gradient_sink is not None:
+            rows.named_rows()              # (`sparse_gradient`: a sampled batch's container brought them along; any other builds them now)
         self.optimizer.rows_touched(rows.transposed.rowptr)
 
     def _lr_scale(self, num_graphs: int) -> float:

@@ -241,19 +241,30 @@ def _csr_project_raw(structure, table, act: int, y=None):
 
 class _CsrRowsProject(torch.autograd.Function):
     """out = act(rows @ weight) for a CSR container: one launch forward, one launch over the transposed structure backward
-    (dW[f] = sum_v X[v, f] * dOut[v] * act'(out[v])).  No gradient towards the container: the features are data."""
+    (dW[f] = sum_v X[v, f] * dOut[v] * act'(out[v])).  No gradient towards the container: the features are data.
+    With a `sink` the backward's launch runs over the container's named rows (a CSR of T rows, tasks/sparse_features.py NamedRows):
+    the [T, n] result goes to the sink with the words it belongs to, and the weight receives no gradient tensor at all."""
 
     @staticmethod
-    def forward(ctx, weight, rows, act: int):
+    def forward(ctx, weight, rows, act: int, sink=None):
         out = _csr_project_raw(rows.rows, weight, act)
-        ctx.rows, ctx.act = rows, act
+        ctx.rows, ctx.act, ctx.sink = rows, act, sink
         ctx.save_for_backward(out if act != _lib.ACT_LINEAR else None)
         return out
 
     @staticmethod
     def backward(ctx, gout):
         (out,) = ctx.saved_tensors
-        return _csr_project_raw(ctx.rows.transposed, gout, ctx.act, out), None, None
+        if ctx.sink is None:
+            return _csr_project_raw(ctx.rows.transposed, gout, ctx.act, out), None, None, None
+        ctx.sink.check(ctx.rows)              # (RuntimeError: a second deposit in one step, a container without named rows)
+        named = ctx.rows.named_rows()
+        if named.count:
+            values = _csr_project_raw(named.structure, gout, ctx.act, out)
+        else:                                 # no word named: nothing to launch
+            values = torch.empty((0, gout.shape[1]), dtype=torch.float32, device=gout.device)
+        ctx.sink.deposit(named, values)
+        return None, None, None, None
 
 
 def _csr_rows_composition(rows, weight, act: int):
@@ -264,13 +275,18 @@ def _csr_rows_composition(rows, weight, act: int):
     return apply_activation(activation_of_id(act), out)
 
 
-def csr_rows_project(rows, weight: torch.Tensor, act_id: int = _lib.ACT_LINEAR) -> torch.Tensor:
+def csr_rows_project(rows, weight: torch.Tensor, act_id: int = _lib.ACT_LINEAR, row_gradient_sink=None) -> torch.Tensor:
     """act(X @ weight) [V, n] for sparse features `rows` (tasks.sparse_features.SparseRows, [V, F]) and weight [F, n].
 
     float32 GPU operands of a width the kernel takes run csrc/csr_project.hip (gelu: the linear kernel, then the torch activation,
     as the Dense route); any other GPU shape densifies the container on the device and takes the Dense route, with one warning;
     CPU tensors and other dtypes take the torch composition.  ROUTES["csr_project"] says which.  A column that is not stored
-    contributes nothing, even against a non-finite weight (the dense product gives 0 * inf = NaN)."""
+    contributes nothing, even against a non-finite weight (the dense product gives 0 * inf = NaN).
+
+    row_gradient_sink (models.optimizer.RowGradientSink, owned by the optimizer that registered `weight` as row-deferred with a
+    compact gradient): the backward deposits (words, slot, values [T, n]) there — the rows of the weight gradient that the
+    container names, bit for bit — and weight.grad stays None; no [F, n] tensor is allocated.  Only the kernel route takes a sink
+    (anything else is a ValueError), and the container must carry its named rows (SparseRows.named_rows) before the backward."""
     if getattr(rows, "requires_grad", False) or rows.rows.val.requires_grad:
         raise ValueError("csr_rows_project: the feature container requires grad, but the features are data: no gradient towards "
                          "them exists")
@@ -279,6 +295,9 @@ def csr_rows_project(rows, weight: torch.Tensor, act_id: int = _lib.ACT_LINEAR) 
     if rows.device != weight.device:
         raise ValueError("csr_rows_project: the features live on %s, the weight on %s" % (rows.device, weight.device))
     n = weight.shape[1]
+    if row_gradient_sink is not None and not (weight.is_cuda and weight.dtype == torch.float32 and csr_project_supported(n)):
+        raise ValueError("csr_rows_project: a row gradient sink needs the CSR kernel (a float32 GPU weight with rows of a multiple of "
+                         "4 up to 1024 floats); got %s %s rows of %d" % (weight.device, weight.dtype, n))
     if not (weight.is_cuda and weight.dtype == torch.float32):
         ROUTES["csr_project"] = "composition"
         return _csr_rows_composition(rows, weight, act_id)
@@ -291,8 +310,8 @@ def csr_rows_project(rows, weight: torch.Tensor, act_id: int = _lib.ACT_LINEAR) 
         return dense_act(rows.to_dense(), weight, None, act_id)
     ROUTES["csr_project"] = "hip"
     if act_id in _FUSABLE_ACTS:
-        return _CsrRowsProject.apply(weight, rows, act_id)
-    return apply_activation(activation_of_id(act_id), _CsrRowsProject.apply(weight, rows, _lib.ACT_LINEAR))
+        return _CsrRowsProject.apply(weight, rows, act_id, row_gradient_sink)
+    return apply_activation(activation_of_id(act_id), _CsrRowsProject.apply(weight, rows, _lib.ACT_LINEAR, row_gradient_sink))
 
 
 def _mode_factor(graph, mode: int):

@@ -33,7 +33,13 @@ One more optional key, "sparse_update": true (requires "sparse_features": true, 
 `graph_model/dense/kernel`; each is a ValueError when the task or the model is built): the optimizer registers the projection's weight
 as row-deferred (TFStyleOptimizer.defer_rows, csrc/sparse_update.hip, include/relgnn_sparse_update.h).  A training step then reads and
 writes only the rows of the weight and its two Adam slots whose words the batch holds, and every stored value is still dense Adam's,
-bit for bit.  The dense gradient and the norm over it stay.
+bit for bit.  The dense gradient and the norm over it stay unless the next key says otherwise.
+
+One more optional key, "sparse_gradient": true (requires "sparse_update": true, a ValueError otherwise): the projection's weight
+gradient exists only as the [touched, hidden] rows whose words the batch holds (csrc/sparse_gradient.hip,
+include/relgnn_sparse_gradient.h).  The weight's `.grad` stays None, no [F, hidden] tensor is allocated in a step, the clip norm is
+computed over the touched rows with the bits of the dense norm, and the row update reads the compact rows: the optimizer still stores
+dense Adam's values bit for bit.
 """
 import os
 import pickle
@@ -265,6 +271,12 @@ class Citation_Network_Task(Sparse_Graph_Task):
         return bool(sampled is not None and sampled.get("sparse_update", False))
 
     @property
+    def sparse_gradient(self) -> bool:
+        """Does `sampled_batches` ask for the compact gradient of the input projection's weight (on top of sparse_update)?"""
+        sampled = self.sampled_batches
+        return bool(sampled is not None and sampled.get("sparse_gradient", False))
+
+    @property
     def num_edge_types(self) -> int:
         return self.__num_edge_types
 
@@ -484,7 +496,8 @@ class Citation_Network_Task(Sparse_Graph_Task):
         keep = self._out_keep(DataFold.TRAIN)
         for seeds in epoch_seed_batches(fold.mask, sampled["seeds_per_batch"], sampled["seed"], epoch):
             draw, self._sampling_draw = self._sampling_draw, self._sampling_draw + 1
-            yield state.sampler.sample(seeds, draw).device_batch(state.features, state.labels, state.mask, keep)
+            yield state.sampler.sample(seeds, draw).device_batch(state.features, state.labels, state.mask, keep,
+                                                                  named_rows=sampled.get("sparse_gradient", False))
 
     def compute_initial_node_features(self, batch, weights):
         """The batch's feature table, or in the sparse mode the SparseRows on the batch's device: one copy per device, kept weakly

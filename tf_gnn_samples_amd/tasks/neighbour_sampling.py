@@ -55,15 +55,17 @@ class SampledSubgraph(NamedTuple):
     num_nodes: int
     num_edges: int
 
-    def device_batch(self, features, labels: torch.Tensor, fold_mask: torch.Tensor, out_keep: float = 1.0) -> DeviceBatch:
+    def device_batch(self, features, labels: torch.Tensor, fold_mask: torch.Tensor, out_keep: float = 1.0,
+                     named_rows: bool = False) -> DeviceBatch:
         """The subgraph as one training batch: feature and label rows of the device-resident [V, ...] tables, the loss mask
         seed_mask * fold_mask[nodes].  `features` a SparseRows: the [n, 1] stand-in takes the table's place and the rows' subset
-        (SparseRows.take_rows, csrc/sparse_subset.hip) travels under extra['sparse_node_features']; no dense row is built."""
+        (SparseRows.take_rows, csrc/sparse_subset.hip) travels under extra['sparse_node_features']; no dense row is built.
+        named_rows: the subset also carries the words it names (`"sparse_gradient": true`; SparseRows.named_rows)."""
         index = self.nodes.long()
         extra = {'labels': labels.index_select(0, index), 'mask': self.seed_mask * fold_mask.index_select(0, index),
                  'out_layer_dropout_keep_prob': out_keep, 'sampled_nodes': self.nodes}
         if isinstance(features, SparseRows):
-            extra['sparse_node_features'] = features.take_rows(self.nodes, validated=True)
+            extra['sparse_node_features'] = features.take_rows(self.nodes, validated=True, named_rows=named_rows)
             rows = torch.zeros((self.num_nodes, 1), dtype=torch.float32, device=self.nodes.device)      # sparse_features.node_stand_in
         else:
             rows = features.index_select(0, index)
@@ -191,14 +193,15 @@ class NeighbourSampler:
 
 def parse_sampled_batches(value) -> Optional[Dict]:
     """The task parameter `sampled_batches` as {"fanouts": [ints], "seeds_per_batch": int, "seed": int}, None when it is absent;
-    the optional keys "sparse_features" (a bool: the batches take their feature rows from a SparseRows) and "sparse_update" (a bool:
-    the optimizer updates only the rows of the input projection's weight that a batch names) are carried only when given."""
+    the optional keys "sparse_features" (a bool: the batches take their feature rows from a SparseRows), "sparse_update" (a bool:
+    the optimizer updates only the rows of the input projection's weight that a batch names) and "sparse_gradient" (a bool: that
+    weight's gradient exists only as the rows a batch names) are carried only when given."""
     if value is None:
         return None
     if not isinstance(value, dict) or not {"fanouts", "seeds_per_batch"} <= set(value) \
-            or set(value) - {"fanouts", "seeds_per_batch", "seed", "sparse_features", "sparse_update"}:
+            or set(value) - {"fanouts", "seeds_per_batch", "seed", "sparse_features", "sparse_update", "sparse_gradient"}:
         raise ValueError('sampled_batches must be {"fanouts": [k_1, ..., k_H], "seeds_per_batch": B, "seed": s, "sparse_features": bool, '
-                         '"sparse_update": bool}, the last three optional, got %r' % (value,))
+                         '"sparse_update": bool, "sparse_gradient": bool}, the last four optional, got %r' % (value,))
     per_batch = value["seeds_per_batch"]
     if isinstance(per_batch, bool) or not isinstance(per_batch, (int, np.integer)) or per_batch < 1:
         raise ValueError("sampled_batches: seeds_per_batch must be a positive integer, got %r" % (per_batch,))
@@ -214,4 +217,11 @@ def parse_sampled_batches(value) -> Optional[Dict]:
             raise ValueError("sampled_batches: \"sparse_update\": true requires \"sparse_features\": true (the rows a batch names are "
                              "read from the transposed structure of its SparseRows)")
         parsed["sparse_update"] = value["sparse_update"]
+    if "sparse_gradient" in value:
+        if not isinstance(value["sparse_gradient"], bool):
+            raise ValueError("sampled_batches: sparse_gradient must be true or false, got %r" % (value["sparse_gradient"],))
+        if value["sparse_gradient"] and not parsed.get("sparse_update", False):
+            raise ValueError("sampled_batches: \"sparse_gradient\": true requires \"sparse_update\": true (the compact gradient is "
+                             "what the row-deferred update consumes; dense Adam reads a dense one)")
+        parsed["sparse_gradient"] = value["sparse_gradient"]
     return parsed

@@ -69,6 +69,48 @@ class CsrStructure:
                             self.num_cols)
 
 
+class NamedRows:
+    """The words a container's transposed structure names (include/relgnn_sparse_gradient.h): words int32 [T] ascending, slot int32
+    [F + 1] (slot[words[t]] == t, slot[F] == T) and `structure`, the transposed structure as a CSR of T rows — it SHARES col and val
+    with it (rows without entries hold none, so the entries are contiguous already), rowptr without its repeats, the long-row plan
+    with its rows mapped through slot.  ops.csr_rows_project's gradient over `structure` is [T, n]: row t has the bits of row
+    words[t] of the gradient over the transposed structure."""
+
+    def __init__(self, words, slot, structure: CsrStructure):
+        self.words, self.slot, self.structure = words, slot, structure
+
+    @property
+    def count(self) -> int:
+        return int(self.words.shape[0])
+
+    def tensors(self):
+        s = self.structure
+        return (self.words, self.slot, s.rowptr, s.slabs, s.combos)
+
+    def to(self, device) -> "NamedRows":
+        return NamedRows(self.words.to(device), self.slot.to(device), self.structure.to(device))
+
+
+def named_rows_of(transposed: CsrStructure) -> NamedRows:
+    """NamedRows of a transposed structure, in NumPy (what a host-built container uses; the device arrays of
+    csrc/sparse_gradient.hip equal these element for element)."""
+    rowptr = transposed.rowptr.cpu().numpy().astype(np.int64)
+    named = np.diff(rowptr) > 0
+    words = np.flatnonzero(named)
+    slot = np.zeros(len(rowptr), np.int64)
+    np.cumsum(named, out=slot[1:])
+    rowptr_c = np.concatenate([rowptr[words], rowptr[-1:]])
+    slabs, combos = transposed.slabs.cpu().numpy().copy(), transposed.combos.cpu().numpy().copy()
+    if len(slabs):
+        slabs[:, 0] = slot[slabs[:, 0]]
+    if len(combos):
+        combos[:, 0] = slot[combos[:, 0]]
+    dev = transposed.rowptr.device
+    t = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).to(dev)
+    return NamedRows(t(words), t(slot), CsrStructure(t(rowptr_c), transposed.col, transposed.val, t(slabs), t(combos),
+                                                      transposed.ws_rows, transposed.num_cols))
+
+
 def _validated(rowptr, col, val, shape):
     V, F = int(shape[0]), int(shape[1])
     rowptr, col, val = np.asarray(rowptr), np.asarray(col), np.asarray(val)
@@ -113,6 +155,7 @@ class SparseRows:
     0 <= col < F, sorted and unique columns per row, no explicit zeros — and raises ValueError: the kernels trust what they read."""
 
     requires_grad = False            # the features are data
+    _named = None                    # named_rows(): built when asked
 
     def __init__(self, rowptr, col, val, shape, _structures=None):
         self.shape = (int(shape[0]), int(shape[1]))
@@ -182,7 +225,12 @@ class SparseRows:
     def to(self, device) -> "SparseRows":
         if torch.device(device) == self.device:
             return self
-        return SparseRows(None, None, None, self.shape, _structures=(self.rows.to(device), self.transposed.to(device)))
+        moved = SparseRows(None, None, None, self.shape, _structures=(self.rows.to(device), self.transposed.to(device)))
+        if self._named is not None:                       # (col and val stay shared with the moved transposed structure)
+            n, t = self._named.to(device), moved.transposed
+            moved._named = NamedRows(n.words, n.slot, CsrStructure(n.structure.rowptr, t.col, t.val, n.structure.slabs,
+                                                                   n.structure.combos, t.ws_rows, t.num_cols))
+        return moved
 
     def to_dense(self) -> torch.Tensor:
         """The [V, F] float32 table on the container's device."""
@@ -194,12 +242,57 @@ class SparseRows:
     def record_stream(self, stream) -> None:
         pass                                               # (a fold-lifetime table: never returned to the allocator under a batch)
 
+    # ---- the words the container names (include/relgnn_sparse_gradient.h) ----
+    @property
+    def has_named_rows(self) -> bool:
+        return self._named is not None
+
+    def named_rows(self) -> NamedRows:
+        """The NamedRows of this container, built once: a GPU container runs csrc/sparse_gradient.hip (a read-back of T;
+        take_rows(named_rows=True) folds it into its own), a CPU container NumPy."""
+        if self._named is None:
+            if self.is_cuda:
+                with torch.cuda.device(self.device):
+                    slot, count = self._named_rows_count(self.transposed.rowptr, None)
+                    self._named = self._named_rows_fill(self.transposed, slot, int(count.item()))
+            else:
+                self._named = named_rows_of(self.transposed)
+        return self._named
+
+    def _named_rows_count(self, rowptr_t: torch.Tensor, sizes: Optional[torch.Tensor]):
+        """The count step over a transposed row pointer: (slot, the int32 tensor that T is written to — sizes[8:9] when `sizes`,
+        the buffer of take_rows' one read-back, is given)."""
+        lib, dev, F = _lib.load_library(), rowptr_t.device, int(rowptr_t.shape[0]) - 1
+        slot = torch.empty(F + 1, dtype=torch.int32, device=dev)
+        count = sizes[8:9] if sizes is not None else torch.empty(1, dtype=torch.int32, device=dev)
+        nbytes = lib.relgnn_named_rows_workspace_bytes(F)
+        ws = _lib.scratch(nbytes, dev)
+        _lib.launch("relgnn_named_rows_count", _lib.ptr(rowptr_t), F, _lib.ptr(slot), count.data_ptr(), _lib.ptr(ws), nbytes)
+        return slot, count
+
+    @staticmethod
+    def _named_rows_fill(transposed: CsrStructure, slot: torch.Tensor, T: int) -> NamedRows:
+        dev, F = slot.device, int(slot.shape[0]) - 1
+        i32 = lambda *shape: torch.empty(shape, dtype=torch.int32, device=dev)
+        num_slabs, num_combos = int(transposed.slabs.shape[0]), int(transposed.combos.shape[0])
+        if T == 0:                                            # nothing named: no entries, no plan, nothing to launch
+            return NamedRows(i32(0), slot, CsrStructure(torch.zeros(1, dtype=torch.int32, device=dev), transposed.col, transposed.val,
+                                                        i32(0, 4), i32(0, 3), 0, transposed.num_cols))
+        words, rowptr_c, slabs, combos = i32(T), i32(T + 1), i32(num_slabs, 4), i32(num_combos, 3)
+        _lib.launch("relgnn_named_rows_fill", _lib.ptr(transposed.rowptr), F, _lib.ptr(slot), T, _lib.ptr(words), _lib.ptr(rowptr_c),
+                    _lib.ptr(transposed.slabs) if num_slabs else None, _lib.ptr(slabs) if num_slabs else None, num_slabs,
+                    _lib.ptr(transposed.combos) if num_combos else None, _lib.ptr(combos) if num_combos else None, num_combos)
+        return NamedRows(words, slot, CsrStructure(rowptr_c, transposed.col, transposed.val, slabs, combos, transposed.ws_rows,
+                                                   transposed.num_cols))
+
     # ---- a row subset (include/relgnn_sparse_subset.h) ----
-    def take_rows(self, nodes, validated: bool = False) -> "SparseRows":
+    def take_rows(self, nodes, validated: bool = False, named_rows: bool = False) -> "SparseRows":
         """The [n, F] container of the rows `nodes` names (one-dimensional int32 tensor or array, any order, a row possibly twice;
         local id = position), on this container's device, with every array equal to what SparseRows(rowptr, col, val, (n, F))
         builds from the same rows.  A GPU container runs csrc/sparse_subset.hip (one read-back of eight sizes), a CPU container the
-        host constructor; ROUTES["take_rows"] says which.  validated=True trusts `nodes` (the sampler's own output)."""
+        host constructor; ROUTES["take_rows"] says which.  validated=True trusts `nodes` (the sampler's own output).
+        named_rows=True builds the subset's NamedRows too (named_rows() then costs nothing): on the GPU its count rides in the
+        same read-back, one int behind the eight sizes."""
         if not validated:
             host = nodes.detach().cpu().numpy() if torch.is_tensor(nodes) else np.asarray(nodes)
             if host.ndim != 1 or host.dtype != np.int32:
@@ -212,13 +305,13 @@ class SparseRows:
                              "(take_rows_supported)" % (n, self.shape))
         if not self.is_cuda or n == 0:
             ROUTES["take_rows"] = "host"
-            return self._take_rows_host(nodes.detach().cpu().numpy() if torch.is_tensor(nodes) else np.asarray(nodes))
+            return self._take_rows_host(nodes.detach().cpu().numpy() if torch.is_tensor(nodes) else np.asarray(nodes), named_rows)
         ROUTES["take_rows"] = "hip"
         nodes = nodes.to(self.device).contiguous() if torch.is_tensor(nodes) else torch.as_tensor(np.ascontiguousarray(nodes), device=self.device)
         with torch.cuda.device(self.device):
-            return self._take_rows_device(nodes, n)
+            return self._take_rows_device(nodes, n, named_rows)
 
-    def _take_rows_host(self, nodes: np.ndarray) -> "SparseRows":
+    def _take_rows_host(self, nodes: np.ndarray, named_rows: bool = False) -> "SparseRows":
         s = self.rows
         rowptr, nodes = s.rowptr.cpu().numpy().astype(np.int64), nodes.astype(np.int64)
         length = rowptr[nodes + 1] - rowptr[nodes]
@@ -228,21 +321,26 @@ class SparseRows:
             raise ValueError("take_rows: the subset holds %d entries; the structure is indexed with 32 bits" % sub_rowptr[-1])
         entry = np.repeat(rowptr[nodes] - sub_rowptr[:-1], length) + np.arange(sub_rowptr[-1])      # the source entry of every entry
         taken = SparseRows(sub_rowptr, s.col.cpu().numpy()[entry], s.val.cpu().numpy()[entry], (len(nodes), self.shape[1]))
+        if named_rows:
+            taken.named_rows()                                # (in NumPy, before the move)
         return _PerBatchRows.of(taken.to(self.device))
 
-    def _take_rows_device(self, nodes: torch.Tensor, n: int) -> "SparseRows":
+    def _take_rows_device(self, nodes: torch.Tensor, n: int, named_rows: bool = False) -> "SparseRows":
         lib, s, dev = _lib.load_library(), self.rows, self.device
         V, F = self.shape
         i32 = lambda *shape: torch.empty(shape, dtype=torch.int32, device=dev)
-        sub_rowptr, sub_rowptr_t, offsets, offsets_t, sizes = i32(n + 1), i32(F + 1), i32(n + 1, 4), i32(F + 1, 4), i32(8)
+        sub_rowptr, sub_rowptr_t, offsets, offsets_t, sizes = i32(n + 1), i32(F + 1), i32(n + 1, 4), i32(F + 1, 4), i32(9 if named_rows else 8)
         nbytes = lib.relgnn_sparse_subset_count_workspace_bytes(n, F)
         ws = _lib.scratch(nbytes, dev)
         self._mark("start")
         _lib.launch("relgnn_sparse_subset_count", _lib.ptr(s.rowptr), _lib.ptr(s.col) if s.nnz else None, V, F, _lib.ptr(nodes), n,
                     _lib.ptr(sub_rowptr), _lib.ptr(sub_rowptr_t), _lib.ptr(offsets), _lib.ptr(offsets_t), _lib.ptr(sizes), _lib.ptr(ws),
                     nbytes)
+        if named_rows:                                        # T goes to sizes[8]: the same read-back
+            slot, _ = self._named_rows_count(sub_rowptr_t, sizes)
         self._mark("count")
-        nnz, *plan_sizes = sizes.tolist()[:7]                 # the one read-back: everything below is sized by these
+        host_sizes = sizes.tolist()                           # the one read-back: everything below is sized by these
+        nnz, *plan_sizes = host_sizes[:7]
         self._mark("readback")
         if nnz >= _INT32_MAX:
             raise ValueError("take_rows: the subset holds 2^31 - 1 entries or more; the structure is indexed with 32 bits")
@@ -267,7 +365,11 @@ class SparseRows:
                             _lib.ptr(combos) if num_combos else None, num_combos)
             structures.append(CsrStructure(rowptr, col, val, slabs, combos, ws_rows, cols))
         self._mark("plans")
-        return _PerBatchRows(None, None, None, (n, F), _structures=tuple(structures))
+        taken = _PerBatchRows(None, None, None, (n, F), _structures=tuple(structures))
+        if named_rows:
+            taken._named = self._named_rows_fill(taken.transposed, slot, host_sizes[8])
+            self._mark("named")
+        return taken
 
     trace = None                     # a list collects (phase, timed event recorded behind it) of every take_rows (scripts/bench_sparse_sampling.py)
 
@@ -283,7 +385,9 @@ class _PerBatchRows(SparseRows):
 
     @classmethod
     def of(cls, rows: SparseRows) -> "_PerBatchRows":
-        return cls(None, None, None, rows.shape, _structures=(rows.rows, rows.transposed))
+        taken = cls(None, None, None, rows.shape, _structures=(rows.rows, rows.transposed))
+        taken._named = rows._named
+        return taken
 
     def to(self, device) -> "SparseRows":
         return self if torch.device(device) == self.device else _PerBatchRows.of(super().to(device))
@@ -293,6 +397,9 @@ class _PerBatchRows(SparseRows):
             return
         for s in (self.rows, self.transposed):
             for t in (s.rowptr, s.col, s.val, s.slabs, s.combos):
+                t.record_stream(stream)
+        if self._named is not None:
+            for t in self._named.tensors():
                 t.record_stream(stream)
 
 
