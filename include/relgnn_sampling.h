@@ -36,6 +36,16 @@
  *     compact(0)                                all stamped nodes, ascending: the subgraph's `nodes`
  *     per hop and type: relabel;  per hop: degrees;  finish (seed mask, stamps of the n visited nodes back to 0)
  *
+ * The hop-ordered numbering (NeighbourSampler.sample_by_hop; the citation task's `"layered": true`).  The same hops, draws and
+ *   edges; only the local ids differ.  `nodes` is the seed list, then the frontier of hop 1, ..., then the nodes first reached in
+ *   hop H (the list compact(H) gives), each segment in ascending id; local id = position.  With n_d the number of nodes at most d hops
+ *   from a seed, the nodes first reached in hop d are the local range [n_{d-1}, n_d), and because hops come out ascending inside every
+ *   type's list, the edges whose target is below n_d are a prefix of that list.  Order of calls: as above through the last hop's
+ *   compact(H); no compact(0); `nodes` is the concatenation of the frontier buffers cut to their true lengths (the caller's one
+ *   read-back holds them); per hop and type relabel_by_hop, per hop degrees_by_hop, while the stamps still hold every node's hop;
+ *   then finish over the hop-ordered `nodes` (it does not ask for an order), which clears the stamps and gives ones on [0, n_0).
+ *   The two entry points are declared in relgnn_layered_sampling.h.
+ *
  * Layout of a hop's arrays, with B = frontier_bound (>= the frontier's true length, which the kernels read from
  *   `frontier_count` on the device and clamp to B):
  *     counts  int32 [L * B + 1]  TYPE-MAJOR: counts[l * B + i] = min(deg, k) (deg where k == 0) of frontier node i and type l,
@@ -96,7 +106,7 @@ int relgnn_neighbour_sample_relabel(const int32_t* edges, int64_t first, int64_t
 int relgnn_neighbour_sample_degrees(const int32_t* counts, int64_t frontier_bound, int64_t frontier_count, int32_t num_edge_types,
                                     const int32_t* frontier, const int32_t* nodes, int64_t n, float* degrees, void* stream);
 
-/* seed_mask[i] = (stamp[nodes[i]] == -1), then stamp[nodes[i]] = 0 */
+/* seed_mask[i] = (stamp[nodes[i]] == -1), then stamp[nodes[i]] = 0; `nodes` in any order */
 int relgnn_neighbour_sample_finish(const int32_t* nodes, int64_t n, int32_t* stamp, int64_t num_nodes, float* seed_mask,
                                    void* stream);
 

@@ -1,6 +1,6 @@
 """ctypes binding of librelgnn.so (C ABI: include/relgnn.h, include/relgnn_dropout.h, include/relgnn_predict.h,
 include/relgnn_parallel.h, include/relgnn_sparse_features.h, include/relgnn_sampling.h, include/relgnn_sparse_subset.h,
-include/relgnn_sparse_update.h, include/relgnn_sparse_gradient.h).
+include/relgnn_sparse_update.h, include/relgnn_sparse_gradient.h, include/relgnn_layered_sampling.h).
 
 This is the ONLY compute backend of the package.  There is no CPU / eager-PyTorch fallback:
 if the HIP library is missing, or a tensor is not a float32/int32 CUDA(HIP) tensor, the
@@ -229,6 +229,13 @@ _SAMPLING_SIGNATURES = {
     "relgnn_neighbour_sample_finish": (ctypes.c_int, [_ptr, _c_i64, _ptr, _c_i64, _ptr, _ptr]),
 }
 
+# include/relgnn_layered_sampling.h (the hop-ordered numbering of a sampled subgraph: the citation task's layered batches): its own
+# table too
+_LAYERED_SAMPLING_SIGNATURES = {
+    "relgnn_neighbour_sample_relabel_by_hop": (ctypes.c_int, [_ptr, _c_i64, _c_i64, _ptr, _c_i64, _ptr, _ptr, _c_i32, _ptr, _ptr]),
+    "relgnn_neighbour_sample_degrees_by_hop": (ctypes.c_int, [_ptr, _c_i64, _c_i64, _c_i32, _c_i64, _c_i64, _ptr, _ptr]),
+}
+
 # include/relgnn_sparse_subset.h (a row subset of sparse node features and its transpose, built on the device: sampled batches over
 # sparse features): its own table too
 _SPARSE_SUBSET_SIGNATURES = {
@@ -285,7 +292,7 @@ def load_library():
     for name, (restype, argtypes) in list(_SIGNATURES.items()) + list(_DROPOUT_SIGNATURES.items()) + list(_PREDICT_SIGNATURES.items()) \
             + list(_PARALLEL_SIGNATURES.items()) + list(_SPARSE_FEATURES_SIGNATURES.items()) + list(_SAMPLING_SIGNATURES.items()) \
             + list(_SPARSE_SUBSET_SIGNATURES.items()) + list(_SPARSE_UPDATE_SIGNATURES.items()) \
-            + list(_SPARSE_GRADIENT_SIGNATURES.items()):
+            + list(_SPARSE_GRADIENT_SIGNATURES.items()) + list(_LAYERED_SAMPLING_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the symbol is not exported
         fn.restype = restype
         fn.argtypes = argtypes
@@ -337,6 +344,11 @@ def sparse_update_signatures():
 def sparse_gradient_signatures():
     """The entry points of include/relgnn_sparse_gradient.h (not part of exported_signatures() either)."""
     return dict(_SPARSE_GRADIENT_SIGNATURES)
+
+
+def layered_sampling_signatures():
+    """The entry points of include/relgnn_layered_sampling.h (not part of exported_signatures() either)."""
+    return dict(_LAYERED_SAMPLING_SIGNATURES)
 
 
 def status_string(code: int) -> str:

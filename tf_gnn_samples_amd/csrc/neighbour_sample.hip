@@ -17,6 +17,7 @@
 #include "common.h"
 #include "philox.h"
 #include "../../include/relgnn_sampling.h"
+#include "../../include/relgnn_layered_sampling.h"
 
 #include <rocprim/device/device_scan.hpp>
 #include <rocprim/iterator/transform_iterator.hpp>
@@ -191,6 +192,43 @@ __global__ __launch_bounds__(256) void degrees_kernel(const int32_t* __restrict_
   }
 }
 
+// ---- hop-ordered numbering (NeighbourSampler.sample_by_hop) -------------------------------------------------------------------------
+// nodes = [seeds | first reached in hop 1 | ... | first reached in hop H], every segment ascending; start[d] is where the nodes at
+// distance d begin, start[levels] = n.  A node's distance is in its stamp until finish clears it (-1: a seed).
+struct HopStarts { int64_t start[kMaxHops + 2]; };
+
+// start[d] + the rank of v inside segment d: the bounded search of local_id over one segment; a node that is not there (never, for
+// what the hops emitted) gives an index inside the list all the same
+__device__ __forceinline__ int32_t hop_local_id(const int32_t* __restrict__ stamp, int64_t V, const int32_t* __restrict__ nodes,
+                                                const HopStarts& hs, int32_t levels, int32_t v) {
+  int32_t d = 0;
+  if ((uint32_t)v < (uint64_t)V) d = stamp[v];
+  d = d < 0 ? 0 : (d >= levels ? levels - 1 : d);
+  const int64_t lo = hs.start[d], hi = hs.start[d + 1], n = hs.start[levels];
+  const int64_t at = hi > lo ? lo + local_id(nodes + lo, hi - lo, v) : lo;
+  return (int32_t)(at < n ? at : n - 1);
+}
+
+__global__ __launch_bounds__(256) void relabel_by_hop_kernel(const int2* __restrict__ edges, int64_t count,
+                                                             const int32_t* __restrict__ stamp, int64_t V,
+                                                             const int32_t* __restrict__ nodes, HopStarts hs, int32_t levels,
+                                                             int2* __restrict__ out) {
+  for (int64_t e = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; e < count; e += (int64_t)gridDim.x * blockDim.x) {
+    const int2 st = edges[e];
+    out[e] = make_int2(hop_local_id(stamp, V, nodes, hs, levels, st.x), hop_local_id(stamp, V, nodes, hs, levels, st.y));
+  }
+}
+
+// the frontier of a hop is the local range [base, base + nf): its degree columns are a strided copy of counts
+__global__ __launch_bounds__(256) void degrees_by_hop_kernel(const int32_t* __restrict__ counts, int64_t B, int64_t nf, int32_t L,
+                                                             int64_t base, int64_t n, float* __restrict__ degrees) {
+  const int64_t total = nf * L;
+  for (int64_t w = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; w < total; w += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t l = w / nf, i = w - l * nf;
+    if (base + i < n) degrees[l * n + base + i] = (float)counts[l * B + i];
+  }
+}
+
 __global__ __launch_bounds__(256) void finish_kernel(const int32_t* __restrict__ nodes, int64_t n, int32_t* __restrict__ stamp, int64_t V,
                                                      float* __restrict__ seed_mask) {
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
@@ -314,6 +352,37 @@ int relgnn_neighbour_sample_degrees(const int32_t* counts, int64_t frontier_boun
   if (!counts || !frontier || !nodes || !degrees || n == 0) return RELGNN_EINVAL;
   degrees_kernel<<<flat_grid(frontier_count * num_edge_types, 256), 256, 0, as_stream(stream)>>>(
       counts, frontier_bound, frontier_count, num_edge_types, frontier, nodes, n, degrees);
+  return launch_status();
+}
+
+int relgnn_neighbour_sample_relabel_by_hop(const int32_t* edges, int64_t first, int64_t count, const int32_t* stamp,
+                                           int64_t num_nodes, const int32_t* nodes, const int64_t* hop_starts, int32_t num_levels,
+                                           int32_t* out, void* stream) {
+  if (first < 0 || count < 0 || num_nodes <= 0 || !hop_starts) return RELGNN_EINVAL;
+  if (num_levels < 1 || num_levels > kMaxHops + 1) return RELGNN_EUNSUPPORTED;
+  HopStarts hs = {};
+  for (int32_t d = 0; d <= num_levels; ++d) {
+    hs.start[d] = hop_starts[d];
+    if (hs.start[d] < 0 || (d == 0 ? hs.start[d] != 0 : hs.start[d] < hs.start[d - 1])) return RELGNN_EINVAL;
+  }
+  if (hs.start[num_levels] >= ((int64_t)1 << 31)) return RELGNN_EUNSUPPORTED;
+  if (count == 0) return RELGNN_OK;
+  if (!edges || !stamp || !nodes || !out || hs.start[num_levels] == 0) return RELGNN_EINVAL;
+  if ((reinterpret_cast<uintptr_t>(edges) | reinterpret_cast<uintptr_t>(out)) & 7u) return RELGNN_EINVAL;
+  relabel_by_hop_kernel<<<flat_grid(count, 256), 256, 0, as_stream(stream)>>>(reinterpret_cast<const int2*>(edges) + first, count, stamp,
+                                                                              num_nodes, nodes, hs, num_levels,
+                                                                              reinterpret_cast<int2*>(out));
+  return launch_status();
+}
+
+int relgnn_neighbour_sample_degrees_by_hop(const int32_t* counts, int64_t frontier_bound, int64_t frontier_count,
+                                           int32_t num_edge_types, int64_t base, int64_t n, float* degrees, void* stream) {
+  if (frontier_count < 0 || frontier_count > frontier_bound || num_edge_types <= 0 || base < 0 || n < 0) return RELGNN_EINVAL;
+  if (base + frontier_count > n) return RELGNN_EINVAL;
+  if (frontier_count == 0) return RELGNN_OK;
+  if (!counts || !degrees) return RELGNN_EINVAL;
+  degrees_by_hop_kernel<<<flat_grid(frontier_count * num_edge_types, 256), 256, 0, as_stream(stream)>>>(
+      counts, frontier_bound, frontier_count, num_edge_types, base, n, degrees);
   return launch_status();
 }
 

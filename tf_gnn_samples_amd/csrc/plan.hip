@@ -79,15 +79,36 @@ __global__ __launch_bounds__(256) void relational_keys_all_kernel(
 // rowptr[s] = first sorted position whose key >= s.  Every rowptr entry is written by
 // exactly one thread (the one that owns the position where the key changes), so the
 // result is deterministic and needs no atomics / histogram.
+// A run of more than kShortRun empty segments in front of a position (a hop-ordered sampled subgraph ends in its leaves, which are
+// nobody's target: one run of (n_H - n_{H-1}) * L segments behind the last key) is written by the whole wave, lane q the entries
+// lo + q, lo + q + 64, ...: the same values at the same places, one writer each.  The loop over positions is uniform across the
+// block (a lane beyond n holds an empty run), so every lane of a wave is there for the hand-over.
+constexpr int64_t kShortRun = 16;
+
 __global__ __launch_bounds__(256) void rowptr_from_sorted_kernel(
     const int32_t* __restrict__ sorted_keys, int64_t n, int64_t num_segments,
     int32_t* __restrict__ rowptr) {
-  for (int64_t p = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; p <= n;
-       p += (int64_t)gridDim.x * blockDim.x) {
-    int64_t lo = (p == 0) ? 0 : (int64_t)sorted_keys[p - 1] + 1;
-    int64_t hi = (p == n) ? num_segments : (int64_t)sorted_keys[p];
+  const int lane = threadIdx.x & (RELGNN_WAVE - 1);
+  for (int64_t base = blockIdx.x * (int64_t)blockDim.x; base <= n; base += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t p = base + threadIdx.x;
+    int64_t lo = 1, hi = 0;
+    if (p <= n) {
+      lo = (p == 0) ? 0 : (int64_t)sorted_keys[p - 1] + 1;
+      hi = (p == n) ? num_segments : (int64_t)sorted_keys[p];
+      if (hi > num_segments) hi = num_segments;
+      if (lo < 0) lo = 0;
+    }
     // segments lo..hi start at p (hi itself starts at p only when p < n, or is the end sentinel)
-    for (int64_t s = lo; s <= hi; ++s) rowptr[s] = (int32_t)p;
+    const bool long_run = hi - lo >= kShortRun;
+    if (!long_run)
+      for (int64_t s = lo; s <= hi; ++s) rowptr[s] = (int32_t)p;
+    unsigned long long pending = __ballot(long_run);
+    while (pending) {                                         // at most 64 rounds, each bounded by its run's length
+      const int owner = __ffsll(pending) - 1;
+      const int64_t run_lo = __shfl(lo, owner), run_hi = __shfl(hi, owner), run_p = __shfl(p, owner);
+      for (int64_t s = run_lo + lane; s <= run_hi; s += RELGNN_WAVE) rowptr[s] = (int32_t)run_p;
+      pending &= pending - 1;
+    }
   }
 }
 

@@ -227,8 +227,15 @@ class Sparse_Graph_Model(ABC):
 
     def compute_final_node_representations(self, initial_node_features: torch.Tensor,
                                            adjacency_lists, type_to_num_incoming_edges: torch.Tensor,
-                                           dropout_keep_prob: float = 1.0) -> torch.Tensor:
+                                           dropout_keep_prob: float = 1.0, layer_graphs=None) -> torch.Tensor:
         """__build_graph_propagation_model, models/sparse_graph_model.py:162-202.
+
+        layer_graphs (the citation task's `"layered": true`; tasks/neighbour_sampling.py, LevelGraph): one entry per layer.  Layer
+        l then runs on its level's graph and degree table over num_sources input rows, and its output is cut to num_targets rows
+        before the inter-layer norm and the Dense (both row-wise) read it; at a residual step the kept tensor is cut to the current
+        row count.  The result has the last level's num_targets rows: the seeds.  The row cut sits between a producer and its
+        consumer, which is what the folding of activation gradients (dense.py) must not straddle: in this mode the driver vouches
+        for nothing, the route a keep-probability below 1 takes.
 
         Dropout on the layer inputs (keep-prob < 1) is torch.nn.functional.dropout by default.  With
         config.settings.layer_dropout == "fused" a contiguous fp32 GPU input takes ops.dropout / ops.dropout_residual instead (one
@@ -243,6 +250,10 @@ class Sparse_Graph_Model(ABC):
         num_nodes = initial_node_features.shape[0]
         # bucketed once, shared by every layer; the index range check is read back at the next fetch
         graph = as_rel_graph(adjacency_lists, num_nodes, validate="deferred")
+        layered = layer_graphs is not None
+        if layered and (len(layer_graphs) != p['graph_num_layers'] or layer_graphs[0].num_sources != num_nodes):
+            raise ValueError("layer_graphs: %d levels, the first over %d nodes, for a model of %d layers and %d input rows"
+                             % (len(layer_graphs), layer_graphs[0].num_sources if layer_graphs else 0, p['graph_num_layers'], num_nodes))
         act_id = ops.activation_id(p['graph_model_activation_function'])
         num_layers, res_every = p['graph_num_layers'], p['graph_residual_connection_every_num_layers']
 
@@ -252,7 +263,7 @@ class Sparse_Graph_Model(ABC):
             product: dense.py, "activation gradients folded into the product that feeds them"; the other one is the layer's own:
             that it reads its input once.)  At a residual step the tensor is read by the average instead (and kept for the next
             residual step); at layer 0 it is kept for the first residual step too."""
-            if next_layer_idx >= num_layers or dropout_keep_prob < 1.0:
+            if next_layer_idx >= num_layers or dropout_keep_prob < 1.0 or layered:
                 return False
             if next_layer_idx % res_every == 0:
                 return next_layer_idx == 0 and res_every >= num_layers
@@ -268,6 +279,17 @@ class Sparse_Graph_Model(ABC):
         for layer_idx in range(p['graph_num_layers']):
             self._layer_weights = w.scope('gnn_layer_%i' % layer_idx)
             residual_step = layer_idx % res_every == 0
+            layer_degrees = type_to_num_incoming_edges
+            if layered:
+                level = layer_graphs[layer_idx]
+                if cur_node_representations.shape[0] != level.num_sources:
+                    raise ValueError("layer_graphs: level %d takes %d rows, the layer below it left %d"
+                                     % (layer_idx + 1, level.num_sources, cur_node_representations.shape[0]))
+                # (level 1 is the union graph: the same key, the same cached bucketing)
+                graph = as_rel_graph(level.adjacency_lists, level.num_sources, validate="deferred")
+                layer_degrees = level.type_to_num_incoming_edges
+                if residual_step and layer_idx > 0 and last_residual_representations.shape[0] > level.num_sources:
+                    last_residual_representations = last_residual_representations[:level.num_sources]
             if pass_state is not None and ops.dropout_tensor_ok(cur_node_representations):
                 # csrc/dropout.hip: one kernel for the whole layer-input stage; the layer index is the Philox stream
                 if residual_step and layer_idx > 0:
@@ -287,14 +309,16 @@ class Sparse_Graph_Model(ABC):
                         cur_node_representations = (cur_node_representations + last_residual_representations) / 2
                     last_residual_representations = t
             cur_node_representations = self._apply_gnn_layer(
-                cur_node_representations, graph, type_to_num_incoming_edges, p['graph_num_timesteps_per_layer'])
+                cur_node_representations, graph, layer_degrees, p['graph_num_timesteps_per_layer'])
+            if layered and level.num_targets < cur_node_representations.shape[0]:
+                cur_node_representations = cur_node_representations[:level.num_targets]      # (a view: it carries no activation tag)
             if p['graph_inter_layer_norm']:
                 ln = self._inter_norm_name[layer_idx]
                 cur_node_representations = layer_norm(cur_node_representations,
                                                       self._layer_weights[ln + "/gamma"], self._layer_weights[ln + "/beta"])
             if layer_idx % p['graph_dense_between_every_num_gnn_layers'] == 0:
                 # (the layer's / the norm's output is referenced nowhere else: this Dense is its only reader)
-                cur_node_representations = dense_act(vouch_sole_consumer(cur_node_representations, True),
+                cur_node_representations = dense_act(vouch_sole_consumer(cur_node_representations, not layered),
                                                      self._layer_weights["Dense/kernel"], None, act_id,
                                                      sole_consumer=only_the_next_layer_reads(layer_idx + 1), sole_reader=True)
             else:
@@ -316,6 +340,16 @@ class Sparse_Graph_Model(ABC):
         self.optimizer = TFStyleOptimizer(list(self.variables.parameters()), p['optimizer'], p['learning_rate'],
                                           p['clamp_gradient_norm'], decay=p['learning_rate_decay'],
                                           momentum=p['momentum'])
+        if getattr(self.task, "layered", False):
+            # the citation task's `sampled_batches` key "layered": one level graph per layer, one hop per level
+            fanouts = self.task.sampled_batches["fanouts"]
+            if len(fanouts) != p['graph_num_layers']:
+                raise ValueError('sampled_batches: "layered": true requires as many fanouts as graph_num_layers (got %d fanouts for %d '
+                                 'layers): layer l runs on the nodes H - l + 1 hops from a seed' % (len(fanouts), p['graph_num_layers']))
+            if p['graph_num_timesteps_per_layer'] != 1:
+                raise ValueError('sampled_batches: "layered": true requires graph_num_timesteps_per_layer 1 (got %r): a layer that '
+                                 'propagates twice needs two hops, and the layer functions take one graph'
+                                 % (p['graph_num_timesteps_per_layer'],))
         if getattr(self.task, "sparse_update", False):
             # the citation task's `sampled_batches` key "sparse_update": the weight of the sparse input projection is updated by rows.
             # CONTRACT: between training steps that parameter's tensor (and its two Adam slots) hold stale rows; everything here that
@@ -341,7 +375,7 @@ class Sparse_Graph_Model(ABC):
         return self.compute_final_node_representations(
             self.task.compute_initial_node_features(batch, self.variables.scope("")),
             graph if graph is not None else batch.adjacency_lists,
-            batch.type_to_num_incoming_edges, keep)
+            batch.type_to_num_incoming_edges, keep, layer_graphs=batch.extra.get('layer_graphs'))
 
     def forward_batch(self, batch: DeviceBatch, training: bool):
         """training=False with a row-deferred parameter (`sparse_update`): every row is brought up to date first; a training forward

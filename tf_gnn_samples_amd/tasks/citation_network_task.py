@@ -40,6 +40,15 @@ gradient exists only as the [touched, hidden] rows whose words the batch holds (
 include/relgnn_sparse_gradient.h).  The weight's `.grad` stays None, no [F, hidden] tensor is allocated in a step, the clip norm is
 computed over the touched rows with the bits of the dense norm, and the row update reads the compact rows: the optimizer still stores
 dense Adam's values bit for bit.
+
+One more optional key, "layered": true (it composes with the three above; none of them depends on the row order of a batch): a batch
+is numbered by hop (NeighbourSampler.sample_by_hop: the seeds first, then the nodes first reached in hop 1, ...) and carries one
+LevelGraph per layer under extra['layer_graphs'].  Layer l of H runs on the nodes at most H - l + 1 hops from a seed and on the edges
+whose targets are at most H - l hops away, a prefix of every type's list, and its output is cut to those targets; the head, the loss
+and the metrics see the seed rows only (labels and mask are taken for the seeds).  The model refuses the key unless it has as many
+layers as there are fanouts and one timestep per layer (models/sparse_graph_model.py).  With a layer-input keep-probability below 1
+the dropout masks differ from the un-layered run's (torch draws by shape, the fused route by element index over another row count):
+the two runs are then two draws of the same model, not equal ones.
 """
 import os
 import pickle
@@ -277,6 +286,12 @@ class Citation_Network_Task(Sparse_Graph_Task):
         return bool(sampled is not None and sampled.get("sparse_gradient", False))
 
     @property
+    def layered(self) -> bool:
+        """Does `sampled_batches` ask for hop-ordered batches whose layers run on the hops they need?"""
+        sampled = self.sampled_batches
+        return bool(sampled is not None and sampled.get("layered", False))
+
+    @property
     def num_edge_types(self) -> int:
         return self.__num_edge_types
 
@@ -496,6 +511,10 @@ class Citation_Network_Task(Sparse_Graph_Task):
         keep = self._out_keep(DataFold.TRAIN)
         for seeds in epoch_seed_batches(fold.mask, sampled["seeds_per_batch"], sampled["seed"], epoch):
             draw, self._sampling_draw = self._sampling_draw, self._sampling_draw + 1
+            if sampled.get("layered", False):
+                yield state.sampler.sample_by_hop(seeds, draw).device_batch(state.features, state.labels, state.mask, keep,
+                                                                             named_rows=sampled.get("sparse_gradient", False))
+                continue
             yield state.sampler.sample(seeds, draw).device_batch(state.features, state.labels, state.mask, keep,
                                                                   named_rows=sampled.get("sparse_gradient", False))
 

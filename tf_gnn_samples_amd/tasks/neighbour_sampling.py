@@ -7,6 +7,10 @@ device seed list), and the subgraph's sizes are read back ONCE behind the last h
 every fanout positive the hops themselves run without a read-back: their buffers are sized from frontier bound x types x fanout.  A
 hop whose fanout is 0 (take every neighbour) has no such bound and reads its edge count back before it emits: one more round trip
 per such hop.
+
+NeighbourSampler.sample_by_hop() gives the same subgraph numbered by hop (include/relgnn_layered_sampling.h) with the same round
+trips; HopSubgraph.device_batch(layered=True) puts one LevelGraph per layer beside it, so that a model with as many layers as hops
+runs each layer on the hops it needs (the citation task's `sampled_batches` key "layered"; models/sparse_graph_model.py).
 """
 import ctypes
 from typing import Dict, List, NamedTuple, Optional, Sequence
@@ -73,6 +77,65 @@ class SampledSubgraph(NamedTuple):
                                         self.type_to_num_incoming_edges, extra=extra)
 
 
+class LevelGraph(NamedTuple):
+    """What layer l of H (from the input, l = 1 .. H) of a layered batch runs on: a square graph over the first num_sources =
+    n_{H-l+1} nodes whose edges are the ones with a target among the first num_targets = n_{H-l}; the layer's output is cut to
+    num_targets rows."""
+    adjacency_lists: List[torch.Tensor]         # per type the prefix view adjacency[l][:E_{l,H-l}] (no copy)
+    num_sources: int
+    num_targets: int
+    type_to_num_incoming_edges: torch.Tensor    # float32 [L, num_sources]: the sampled in-degrees of the targets, 0 behind them
+
+
+class HopSubgraph(NamedTuple):
+    """The subgraph of SampledSubgraph under another numbering (NeighbourSampler.sample_by_hop): nodes by the hop that first
+    reached them.  With n_d = hop_nodes[d] the nodes at most d hops from a seed are the local ids [0, n_d), and the edges whose
+    target is among them are the first hop_edges[l][d] entries of type l's list (d < H): hops come out ascending."""
+    nodes: torch.Tensor                         # int32 [n]: the seeds ascending, then the nodes first reached in hop 1 ascending, ...
+    adjacency_lists: List[torch.Tensor]         # as SampledSubgraph's, in these local ids
+    type_to_num_incoming_edges: torch.Tensor    # float32 [L, n]
+    seed_mask: torch.Tensor                     # float32 [n]: ones on [0, n_0)
+    num_nodes: int
+    num_edges: int
+    hop_nodes: List[int]                        # [n_0, ..., n_H], cumulative
+    hop_edges: List[List[int]]                  # per type [E_{l,0}, ..., E_{l,H-1}]: the type-l edges emitted by hops 0 .. h
+
+    def level_graphs(self) -> List[LevelGraph]:
+        """One LevelGraph per layer of a model with as many layers as hops; level 1 is the union graph."""
+        H = len(self.hop_nodes) - 1
+        degrees, levels = self.type_to_num_incoming_edges, []
+        for layer in range(1, H + 1):
+            sources, targets = self.hop_nodes[H - layer + 1], self.hop_nodes[H - layer]
+            adjacency = [a[:edges[H - layer]] for a, edges in zip(self.adjacency_lists, self.hop_edges)]
+            if layer == 1:                      # (the nodes behind n_{H-1} are leaves: their columns are zero already)
+                table = degrees
+            else:
+                table = torch.zeros((degrees.shape[0], sources), dtype=degrees.dtype, device=degrees.device)
+                table[:, :targets] = degrees[:, :targets]
+            levels.append(LevelGraph(adjacency, sources, targets, table))
+        return levels
+
+    def device_batch(self, features, labels: torch.Tensor, fold_mask: torch.Tensor, out_keep: float = 1.0,
+                     named_rows: bool = False, layered: bool = True) -> DeviceBatch:
+        """layered=False: the union batch in hop order, through SampledSubgraph.device_batch.  layered=True: feature rows of all n
+        nodes, labels and mask of the n_0 seeds only (mask = fold_mask[seeds]: num_masked and num_correct mean what they did), and
+        extra['layer_graphs'] = level_graphs(), which models/sparse_graph_model.py runs layer by layer."""
+        union = SampledSubgraph(self.nodes, self.adjacency_lists, self.type_to_num_incoming_edges, self.seed_mask, self.num_nodes,
+                                self.num_edges)
+        if not layered:
+            return union.device_batch(features, labels, fold_mask, out_keep, named_rows=named_rows)
+        seeds = self.nodes[:self.hop_nodes[0]].long()
+        extra = {'labels': labels.index_select(0, seeds), 'mask': fold_mask.index_select(0, seeds),
+                 'out_layer_dropout_keep_prob': out_keep, 'sampled_nodes': self.nodes, 'layer_graphs': self.level_graphs()}
+        if isinstance(features, SparseRows):
+            extra['sparse_node_features'] = features.take_rows(self.nodes, validated=True, named_rows=named_rows)
+            rows = torch.zeros((self.num_nodes, 1), dtype=torch.float32, device=self.nodes.device)      # sparse_features.node_stand_in
+        else:
+            rows = features.index_select(0, self.nodes.long())
+        return DeviceBatch.from_tensors(1, self.num_nodes, self.num_edges, rows, self.adjacency_lists,
+                                        self.type_to_num_incoming_edges, extra=extra)
+
+
 class NeighbourSampler:
     """Sampler over one RelGraph (its rowptr_t / col_t are read in place).  Holds the [V] int32 stamp array, all zero between calls."""
 
@@ -125,7 +188,90 @@ class NeighbourSampler:
             self.stamp.zero_()                                    # whatever a half-run call stamped
             raise
 
+    def sample_by_hop(self, seeds, draw: int) -> "HopSubgraph":
+        """The subgraph sample(seeds, draw) gives — the same hops, draws and edges — numbered by hop: the seeds, then the nodes first
+        reached in hop 1, ..., each group in ascending id.  No read-back beyond sample()'s."""
+        seeds = self._validated(seeds)
+        try:
+            with torch.cuda.device(self.graph.device):
+                return self._sample_by_hop(seeds, int(draw) & 0xffffffff)
+        except BaseException:
+            self.stamp.zero_()
+            raise
+
     def _sample(self, seeds: torch.Tensor, draw: int) -> SampledSubgraph:
+        g = self.graph
+        V, L, dev = g.V, g.L, g.device
+        i32 = lambda n: torch.empty(int(n), dtype=torch.int32, device=dev)
+        hops, summary, _, ws, ws_bytes = self._hops(seeds, draw)
+        node_bound = min(V, seeds.numel() + sum(int(e.shape[0]) for _, _, _, e in hops))
+        nodes_buf = i32(node_bound)
+        _lib.launch("relgnn_neighbour_sample_compact", _lib.ptr(self.stamp), V, 0, _lib.ptr(nodes_buf), node_bound, _lib.ptr(summary[-1:]),
+                    _lib.ptr(ws), ws_bytes)
+        self._mark("compaction")
+        sizes = summary.tolist()                                  # the one read-back of a call whose fanouts are all positive
+        self._mark("readback")
+        n = sizes[-1]
+        nodes = nodes_buf[:n]
+        per_hop = [sizes[h * (L + 2):(h + 1) * (L + 2)] for h in range(len(self.fanouts))]
+        lengths = [int(seeds.numel())] + [p[L + 1] for p in per_hop[:-1]]              # the true length of every hop's frontier
+        type_edges = [sum(p[l] for p in per_hop) for l in range(L)]
+        adjacency = [torch.empty((e, 2), dtype=torch.int32, device=dev) for e in type_edges]
+        degrees = torch.zeros((L, n), dtype=torch.float32, device=dev)
+        written = [0] * L
+        for (hop_frontier, hop_bound, counts, edges), p, nf in zip(hops, per_hop, lengths):
+            first = 0
+            for l in range(L):
+                if p[l]:
+                    _lib.launch("relgnn_neighbour_sample_relabel", _lib.ptr(edges), first, p[l], _lib.ptr(nodes), n,
+                                _lib.ptr(adjacency[l][written[l]:written[l] + p[l]]))
+                first += p[l]
+                written[l] += p[l]
+            _lib.launch("relgnn_neighbour_sample_degrees", _lib.ptr(counts), hop_bound, nf, L, _lib.ptr(hop_frontier), _lib.ptr(nodes), n,
+                        _lib.ptr(degrees))
+        seed_mask = torch.empty(n, dtype=torch.float32, device=dev)
+        _lib.launch("relgnn_neighbour_sample_finish", _lib.ptr(nodes), n, _lib.ptr(self.stamp), V, _lib.ptr(seed_mask))
+        self._mark("relabel")
+        return SampledSubgraph(nodes, adjacency, degrees, seed_mask, n, sum(type_edges))
+
+    def _sample_by_hop(self, seeds: torch.Tensor, draw: int) -> "HopSubgraph":
+        g = self.graph
+        V, L, dev, H = g.V, g.L, g.device, len(self.fanouts)
+        hops, summary, last, _, _ = self._hops(seeds, draw)
+        sizes = summary.tolist()                                  # the same one read-back; the id-ordered list is never compacted
+        self._mark("readback")
+        per_hop = [sizes[h * (L + 2):(h + 1) * (L + 2)] for h in range(H)]
+        lengths = [int(seeds.numel())] + [p[L + 1] for p in per_hop]                   # nodes first reached in hop 0 (the seeds) .. H
+        starts = [0]
+        for length in lengths:
+            starts.append(starts[-1] + length)
+        hop_nodes, n = starts[1:], starts[-1]                     # n_0 .. n_H
+        # the frontier buffers ARE the per-hop lists: cut to their true lengths and laid end to end (a device copy, no kernel of ours)
+        nodes = torch.cat([f[:nf] for f, nf in zip([hop[0] for hop in hops] + [last], lengths)])
+        host_starts = (ctypes.c_int64 * (H + 2))(*starts)
+        type_edges = [sum(p[l] for p in per_hop) for l in range(L)]
+        adjacency = [torch.empty((e, 2), dtype=torch.int32, device=dev) for e in type_edges]
+        degrees = torch.zeros((L, n), dtype=torch.float32, device=dev)
+        written, hop_edges = [0] * L, [[] for _ in range(L)]
+        for h, ((_, hop_bound, counts, edges), p) in enumerate(zip(hops, per_hop)):
+            first = 0
+            for l in range(L):
+                if p[l]:
+                    _lib.launch("relgnn_neighbour_sample_relabel_by_hop", _lib.ptr(edges), first, p[l], _lib.ptr(self.stamp), V,
+                                _lib.ptr(nodes), host_starts, H + 1, _lib.ptr(adjacency[l][written[l]:written[l] + p[l]]))
+                first += p[l]
+                written[l] += p[l]
+                hop_edges[l].append(written[l])
+            _lib.launch("relgnn_neighbour_sample_degrees_by_hop", _lib.ptr(counts), hop_bound, lengths[h], L, starts[h], n,
+                        _lib.ptr(degrees))
+        seed_mask = torch.empty(n, dtype=torch.float32, device=dev)
+        _lib.launch("relgnn_neighbour_sample_finish", _lib.ptr(nodes), n, _lib.ptr(self.stamp), V, _lib.ptr(seed_mask))
+        self._mark("relabel")
+        return HopSubgraph(nodes, adjacency, degrees, seed_mask, n, sum(type_edges), hop_nodes, hop_edges)
+
+    def _hops(self, seeds: torch.Tensor, draw: int):
+        """begin, then count / take / compact(h + 1) per hop -> ([(frontier, bound, counts, edges) per hop], the summary still on the
+        device, the buffer of the nodes first reached in the last hop, the compaction's workspace and its size)."""
         lib, g = _lib.load_library(), self.graph
         V, L, dev = g.V, g.L, g.device
         i32 = lambda n: torch.empty(int(n), dtype=torch.int32, device=dev)
@@ -160,48 +306,21 @@ class NeighbourSampler:
                         _lib.ptr(ws), ws_bytes)
             self._mark("compaction")
             bound = next_bound
-        node_bound = min(V, seeds.numel() + sum(int(e.shape[0]) for _, _, _, e in hops))
-        nodes_buf = i32(node_bound)
-        _lib.launch("relgnn_neighbour_sample_compact", _lib.ptr(self.stamp), V, 0, _lib.ptr(nodes_buf), node_bound, _lib.ptr(summary[-1:]),
-                    _lib.ptr(ws), ws_bytes)
-        self._mark("compaction")
-        sizes = summary.tolist()                                  # the one read-back of a call whose fanouts are all positive
-        self._mark("readback")
-        n = sizes[-1]
-        nodes = nodes_buf[:n]
-        per_hop = [sizes[h * (L + 2):(h + 1) * (L + 2)] for h in range(len(self.fanouts))]
-        lengths = [int(seeds.numel())] + [p[L + 1] for p in per_hop[:-1]]              # the true length of every hop's frontier
-        type_edges = [sum(p[l] for p in per_hop) for l in range(L)]
-        adjacency = [torch.empty((e, 2), dtype=torch.int32, device=dev) for e in type_edges]
-        degrees = torch.zeros((L, n), dtype=torch.float32, device=dev)
-        written = [0] * L
-        for (hop_frontier, hop_bound, counts, edges), p, nf in zip(hops, per_hop, lengths):
-            first = 0
-            for l in range(L):
-                if p[l]:
-                    _lib.launch("relgnn_neighbour_sample_relabel", _lib.ptr(edges), first, p[l], _lib.ptr(nodes), n,
-                                _lib.ptr(adjacency[l][written[l]:written[l] + p[l]]))
-                first += p[l]
-                written[l] += p[l]
-            _lib.launch("relgnn_neighbour_sample_degrees", _lib.ptr(counts), hop_bound, nf, L, _lib.ptr(hop_frontier), _lib.ptr(nodes), n,
-                        _lib.ptr(degrees))
-        seed_mask = torch.empty(n, dtype=torch.float32, device=dev)
-        _lib.launch("relgnn_neighbour_sample_finish", _lib.ptr(nodes), n, _lib.ptr(self.stamp), V, _lib.ptr(seed_mask))
-        self._mark("relabel")
-        return SampledSubgraph(nodes, adjacency, degrees, seed_mask, n, sum(type_edges))
+        return hops, summary, frontier, ws, ws_bytes
 
 
 def parse_sampled_batches(value) -> Optional[Dict]:
     """The task parameter `sampled_batches` as {"fanouts": [ints], "seeds_per_batch": int, "seed": int}, None when it is absent;
     the optional keys "sparse_features" (a bool: the batches take their feature rows from a SparseRows), "sparse_update" (a bool:
     the optimizer updates only the rows of the input projection's weight that a batch names) and "sparse_gradient" (a bool: that
-    weight's gradient exists only as the rows a batch names) are carried only when given."""
+    weight's gradient exists only as the rows a batch names) and "layered" (a bool: the batches are numbered by hop and every layer
+    runs on the hops it needs) are carried only when given."""
     if value is None:
         return None
     if not isinstance(value, dict) or not {"fanouts", "seeds_per_batch"} <= set(value) \
-            or set(value) - {"fanouts", "seeds_per_batch", "seed", "sparse_features", "sparse_update", "sparse_gradient"}:
+            or set(value) - {"fanouts", "seeds_per_batch", "seed", "sparse_features", "sparse_update", "sparse_gradient", "layered"}:
         raise ValueError('sampled_batches must be {"fanouts": [k_1, ..., k_H], "seeds_per_batch": B, "seed": s, "sparse_features": bool, '
-                         '"sparse_update": bool, "sparse_gradient": bool}, the last four optional, got %r' % (value,))
+                         '"sparse_update": bool, "sparse_gradient": bool, "layered": bool}, the last five optional, got %r' % (value,))
     per_batch = value["seeds_per_batch"]
     if isinstance(per_batch, bool) or not isinstance(per_batch, (int, np.integer)) or per_batch < 1:
         raise ValueError("sampled_batches: seeds_per_batch must be a positive integer, got %r" % (per_batch,))
@@ -224,4 +343,8 @@ def parse_sampled_batches(value) -> Optional[Dict]:
             raise ValueError("sampled_batches: \"sparse_gradient\": true requires \"sparse_update\": true (the compact gradient is "
                              "what the row-deferred update consumes; dense Adam reads a dense one)")
         parsed["sparse_gradient"] = value["sparse_gradient"]
+    if "layered" in value:
+        if not isinstance(value["layered"], bool):
+            raise ValueError("sampled_batches: layered must be true or false, got %r" % (value["layered"],))
+        parsed["layered"] = value["layered"]
     return parsed
