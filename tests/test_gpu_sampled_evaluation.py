@@ -1,0 +1,458 @@
+"""Evaluation and predictions on sampled receptive fields, on the GPU (tasks/citation_network_task.py: evaluation_batches,
+node_prediction_batches; tasks/neighbour_sampling.py; graph.py: RelGraph.route_like; models/sparse_graph_model.py: predict(nodes=...)).
+
+With every evaluation fanout 0 a seed's receptive field is complete and every bucket of it is the full graph's bucket in the full
+graph's order: the seeds' final states and logits are then the full-graph forward's rows bit for bit, under either iterator.  With
+positive fanouts the batches are the reference sampler's under replica 0x40000000 | fold and draw = batch index."""
+import math
+import pickle
+import sys
+from pathlib import Path
+
+import numpy as np
+import pytest
+import torch
+
+HERE = Path(__file__).resolve().parent
+if str(HERE) not in sys.path:
+    sys.path.insert(0, str(HERE))
+
+import layered_sampling_reference as LR  # noqa: E402
+import neighbour_sampling_reference as R  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+
+V = 300
+HUB = 16
+BUCKETS = {10: 0, 11: 1, 12: 63, 13: 64, 14: 65, 15: 129, HUB: 5000}       # node -> entries of its (node, type 1) bucket
+VALID = list(range(10, 27))                                               # 17 validation nodes: 7 + 7 + 3 with B = 7
+MODELS = ["RGCN_Model", "GGNN_Model", "RGAT_Model", "GNN_FiLM_Model"]
+_GRAPHS = {}
+
+
+def hub_graph(L):
+    """V = 300 nodes; type 0: one self loop per node; type 1: buckets of 0, 1, 63, 64, 65, 129 and 5 000 entries at nodes 10 .. 16 (the
+    hub, longer than the 4 096 entries one wave takes), three entries at every other node, duplicates included; type 2 (L = 3): 150
+    edges, so most of its buckets are empty.  The hub feeds node 11's one-entry bucket and is a validation node itself; validation
+    node 17 feeds validation node 12.  -> (adjacency, degrees int32 [L, V])."""
+    if L not in _GRAPHS:
+        rng = np.random.default_rng(L)
+        nodes = np.arange(V)
+        counts = np.full(V, 3)
+        for node, n in BUCKETS.items():
+            counts[node] = n
+        tgt = np.repeat(nodes, counts)
+        src = rng.integers(0, V, size=len(tgt))
+        src[np.flatnonzero(tgt == 11)[0]] = HUB
+        src[np.flatnonzero(tgt == 12)[0]] = 17
+        edges = np.stack([src, tgt], axis=1)[rng.permutation(len(tgt))]
+        adjacency = [np.stack([nodes, nodes], axis=1).astype(np.int32), np.ascontiguousarray(edges, dtype=np.int32)]
+        if L == 3:
+            adjacency.append(np.ascontiguousarray(rng.integers(0, V, size=(150, 2)), dtype=np.int32))
+        degrees = np.stack([np.bincount(a[:, 1], minlength=V) for a in adjacency]).astype(np.int32)
+        _GRAPHS[L] = (adjacency, degrees)
+    return _GRAPHS[L]
+
+
+def citation_task(L, sampled, sparse=False, adjacency=None, degrees=None, num_nodes=V, valid=VALID, num_features=40):
+    """A task whose three folds are cut from one graph: train = the first 60 nodes, validation = `valid`, test = the last 50."""
+    from tf_gnn_samples_amd.tasks import Citation_Network_Task, DataFold
+    params = dict(Citation_Network_Task.default_params(), sampled_batches=sampled)
+    if sparse:
+        params["sparse_node_features"] = True
+    task = Citation_Network_Task(params)
+    task.load_synthetic(num_nodes=num_nodes, num_features=num_features, num_classes=5, num_train=60, num_valid=30, num_test=50,
+                        feature_density=0.2, seed=4)
+    task._Citation_Network_Task__num_edge_types = L
+    if adjacency is None:
+        adjacency, degrees = hub_graph(L)
+    train = task._loaded_data[DataFold.TRAIN][0]
+    labels = np.random.default_rng(1).integers(0, 5, size=num_nodes)
+    folds = []
+    for ids in (np.arange(60), np.asarray(valid), np.arange(num_nodes - 50, num_nodes)):
+        mask = np.zeros(num_nodes, dtype=bool)
+        mask[ids] = True
+        folds.append([task._fold(adjacency, degrees, train.node_features, np.where(mask, labels, 0), mask)])
+    task._loaded_data[DataFold.TRAIN], task._loaded_data[DataFold.VALIDATION], task.synthetic_test_data = folds
+    return task
+
+
+def make_model(name, task, device, num_layers, **params):
+    from tf_gnn_samples_amd import models
+    cls = getattr(models, name)
+    p = cls.default_params()
+    p.update(dict(dict(hidden_size=32, graph_num_layers=num_layers, graph_layer_input_dropout_keep_prob=1.0, random_seed=6,
+                       graph_residual_connection_every_num_layers=2), **params))
+    return cls(p, task, device=str(device))
+
+
+def sampled(evaluation, sparse=False, **more):
+    value = {"fanouts": [3, 2], "seeds_per_batch": 16, "seed": 5, "evaluation": evaluation}
+    if sparse:
+        value["sparse_features"] = True
+    value.update(more)
+    return value
+
+
+def states_and_logits(model, batch):
+    from tf_gnn_samples_amd.dense import dense
+    with torch.no_grad():
+        final = model._final_node_states(batch, training=False)
+        logits = dense(final, model.variables.scope(model._task_scope)["kernel"])
+    return final.cpu().numpy(), logits.cpu().numpy()
+
+
+def row_losses64(logits, labels):
+    x = logits.astype(np.float64)
+    top = x.max(axis=1, keepdims=True)
+    return (top[:, 0] + np.log(np.exp(x - top).sum(axis=1))) - x[np.arange(len(x)), labels]
+
+
+def same_bits(a, b):
+    return a.shape == b.shape and np.array_equal(a.view(np.uint32), b.view(np.uint32))
+
+
+# ---- exact evaluation ----------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("sparse", [False, True], ids=["dense", "sparse"])
+@pytest.mark.parametrize("norm", [False, True], ids=["plain", "norm"])
+@pytest.mark.parametrize("H, L", [(2, 2), (2, 3), (3, 2), (3, 3)])
+@pytest.mark.parametrize("model_name", MODELS)
+def test_exact_fields_reproduce_the_full_graph_rows_bit_for_bit(gpu_device, model_name, H, L, norm, sparse):
+    """All fanouts 0: for every seed of every batch (one batch of 17, and B = 7: 7 + 7 + 3) the final state and the logits are the
+    full-graph forward's rows, bit for bit, under either iterator (the resident full graph splits its hub bucket into chunks of 4 096,
+    the one the model buckets itself folds it in one wave; the level graphs follow: RelGraph.route_like).  The fold's num_masked and
+    num_correct are the full graph's counts, and the sum of total_loss lies within (n + 3) * 2^-24 * sum|row loss| of the float64 sum
+    of the row losses computed from those logits."""
+    from tf_gnn_samples_amd.tasks import DataFold, DeviceBatch
+    task = citation_task(L, sampled({"fanouts": [0] * H, "seeds_per_batch": 32}, sparse), sparse)
+    model = make_model(model_name, task, gpu_device, H, graph_inter_layer_norm=norm)
+    for native in (True, False):
+        model.params["native_batching"] = native                   # (both are read when batches are asked for)
+        for B in (32, 7):
+            task.params["sampled_batches"]["evaluation"]["seeds_per_batch"] = B
+            data = task._loaded_data[DataFold.VALIDATION]
+            fold = data[0]
+            (full_batch,) = model._batches(data, DataFold.VALIDATION, full_graph=True)
+            if not isinstance(full_batch, DeviceBatch):              # (the NumPy iterator's feed dict)
+                full_batch = DeviceBatch(full_batch, model.device)
+            assert full_batch.num_nodes == V and "layer_graphs" not in full_batch.extra
+            full_states, full_logits = states_and_logits(model, full_batch)
+            hub_is_split = bool(getattr(getattr(full_batch, "graph", None), "has_long_buckets", False))
+            assert hub_is_split == native                          # the two routes of the hub bucket are both exercised
+            batches = list(model._batches(data, DataFold.VALIDATION))
+            assert [int(b.extra["labels"].shape[0]) for b in batches] == ([17] if B == 32 else [7, 7, 3])
+            seen = []
+            for i, batch in enumerate(batches):
+                n0 = batch.extra["layer_graphs"][-1].num_targets
+                seeds = batch.extra["sampled_nodes"][:n0].cpu().numpy()
+                seen.extend(seeds.tolist())
+                assert all(level.graph is not None and level.graph.has_long_buckets == native for level in batch.extra["layer_graphs"])
+                states, logits = states_and_logits(model, batch)
+                what = (model_name, H, L, norm, sparse, native, B, i)
+                worst = float(np.abs(states.astype(np.float64) - full_states[seeds]).max())
+                print("%s: %d seeds, %d nodes in the field, largest state difference %.3g" % (what, n0, batch.num_nodes, worst))
+                assert same_bits(states, full_states[seeds]), what
+                assert same_bits(logits, full_logits[seeds]), what
+            assert seen == VALID
+            assert HUB in seen and max(b.num_nodes for b in batches) > 100           # the hub's bucket sits inside a field
+            # the metrics of the epoch
+            loss, res, graphs, _, _, _ = model._run_epoch("validation", data, DataFold.VALIDATION, quiet=True)
+            rows = row_losses64(full_logits[VALID], fold.labels[VALID])
+            first_max = full_logits[VALID].argmax(axis=1)
+            assert graphs == 1 and len(res) == len(batches)
+            assert sum(m["num_masked"] for m in res) == len(VALID)
+            assert sum(m["num_correct"] for m in res) == int((first_max == fold.labels[VALID]).sum())
+            total = float(np.sum([m["total_loss"] for m in res]))
+            bound = (len(VALID) + 3) * 2.0 ** -24 * float(np.abs(rows).sum())
+            print("%s B=%d: sum of total_loss %.9g, float64 %.9g, bound %.3g" % (model_name, B, total, rows.sum(), bound))
+            assert abs(total - rows.sum()) <= bound
+            assert loss == total / len(VALID) and task.early_stopping_metric(res, graphs) == total
+
+
+# ---- sampled evaluation --------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("fanouts", [[3, 2], [0, 4]])
+def test_sampled_batches_are_the_reference_sampler_s(gpu_device, fanouts):
+    """Every array of every batch against tests/layered_sampling_reference.py under replica 0x40000000 | fold and draw = batch index;
+    two epochs give the same subgraphs; the epoch's metrics are those of the same subgraphs hand-fed, bit for bit."""
+    from tf_gnn_samples_amd.tasks import DataFold
+    from tf_gnn_samples_amd.tasks.neighbour_sampling import NeighbourSampler
+    L = 3
+    adjacency, _ = hub_graph(L)
+    rowptr, col, _ = R.bucketing(adjacency, V)
+    task = citation_task(L, sampled({"fanouts": fanouts, "seeds_per_batch": 7}))
+    model = make_model("RGCN_Model", task, gpu_device, 2)
+    for data_fold, data in ((DataFold.VALIDATION, task._loaded_data[DataFold.VALIDATION]), (DataFold.TEST, task.synthetic_test_data)):
+        fold = data[0]
+        ids = np.flatnonzero(fold.mask)
+        epochs = [list(model._batches(data, data_fold)) for _ in range(2)]
+        assert len(epochs[0]) == len(epochs[1]) == math.ceil(len(ids) / 7)
+        for i, (batch, again) in enumerate(zip(*epochs)):
+            seeds = ids[7 * i:7 * i + 7].astype(np.int32)
+            want = LR.sample_by_hop(rowptr, col, V, L, seeds, fanouts, i, seed=5, replica=0x40000000 | data_fold.value)
+            assert batch is not again
+            for b in (batch, again):
+                assert np.array_equal(b.extra["sampled_nodes"].cpu().numpy(), want.nodes) and b.num_nodes == len(want.nodes)
+                for got, ref in zip(b.adjacency_lists, want.adjacency_lists):
+                    assert np.array_equal(got.cpu().numpy(), ref)
+                assert same_bits(b.type_to_num_incoming_edges.cpu().numpy(), want.degrees)
+                assert np.array_equal(b.extra["labels"].cpu().numpy(), fold.labels[seeds])
+                assert np.array_equal(b.extra["mask"].cpu().numpy(), np.ones(len(seeds), np.float32))
+                assert b.extra["out_layer_dropout_keep_prob"] == 1.0
+                for level, (lists, sources, targets, table) in zip(b.extra["layer_graphs"], LR.levels(want)):
+                    assert (level.num_sources, level.num_targets) == (sources, targets)
+                    assert same_bits(level.type_to_num_incoming_edges.cpu().numpy(), table)
+                    assert all(np.array_equal(g.cpu().numpy(), ref) for g, ref in zip(level.adjacency_lists, lists))
+        # hand-fed: a sampler of the documented replica over a graph of its own, no bucketing brought along
+        state = task._sampling_state_of(fold, gpu_device, fanouts, 5, 0x40000000 | data_fold.value)
+        sampler = NeighbourSampler(state.sampler.graph, fanouts, seed=5, replica=0x40000000 | data_fold.value)
+        _, res, graphs, _, _, _ = model._run_epoch("evaluation", data, data_fold, quiet=True)
+        assert graphs == 1 and len(res) == len(epochs[0])
+        for i, m in enumerate(res):
+            batch = sampler.sample_by_hop(ids[7 * i:7 * i + 7].astype(np.int32), i).device_batch(state.features, state.labels, state.mask, 1.0)
+            with torch.no_grad():
+                want = {k: float(v) for k, v in model.forward_batch(batch, training=False).items()}
+            assert {k: np.float32(m[k]).tobytes() for k in want} == {k: np.float32(v).tobytes() for k, v in want.items()}, (data_fold, i)
+    assert (task._sampling_epoch, task._sampling_draw) == (0, 0)
+
+
+# ---- train() -------------------------------------------------------------------------------------------------------------------------
+def _train(device, result_dir, model_name, sampled_batches, sparse=False, **model_params):
+    task = citation_task(2, sampled_batches, sparse)
+    result_dir.mkdir()
+    model = make_model(model_name, task, device, 2, **model_params)
+    model.run_id, model.result_dir = "run", str(result_dir)
+    record, run_epoch = [], model._run_epoch
+
+    def recording(epoch_name, data, fold, quiet=False):
+        out = run_epoch(epoch_name, data, fold, quiet)
+        record.append((epoch_name, out[0], [dict(m) for m in out[1]], out[2]))
+        return out
+    model._run_epoch = recording
+    model.train(quiet=True, max_epochs=2)
+    model._run_epoch = run_epoch
+    torch.cuda.synchronize()
+    with open(model.best_model_file, "rb") as f:
+        checkpoint = pickle.load(f)
+    return task, model, record, checkpoint
+
+
+def _validation_of(record):
+    return [r for r in record if "validation" in r[0]]
+
+
+@pytest.mark.parametrize("native_batching", [True, False], ids=["native", "numpy"])
+@pytest.mark.parametrize("model_name", ["RGCN_Model", "GGNN_Model"])
+def test_train_with_the_key_trains_what_the_full_graph_run_trains(gpu_device, tmp_path, model_name, native_batching):
+    """Two epochs from one seed with the key (fanouts 0, B = 7) and without it: equal training losses and checkpoints (evaluation touches
+    no training state, the training sampler's draw count included), equal validation accuracies, validation losses within the sum of
+    both runs' bounds against the float64 sum of the same row losses, the same best_epoch."""
+    runs = {}
+    for which, value in (("key", sampled({"fanouts": [0, 0], "seeds_per_batch": 7})), ("full", {"fanouts": [3, 2], "seeds_per_batch": 16, "seed": 5})):
+        runs[which] = _train(gpu_device, tmp_path / which, model_name, value, native_batching=native_batching)
+    (task_a, model_a, rec_a, ckpt_a), (task_b, model_b, rec_b, ckpt_b) = runs["key"], runs["full"]
+    train_a, train_b = ([r for r in rec if "training" in r[0]] for rec in (rec_a, rec_b))
+    assert len(train_a) == 2 and [[m["loss"] for m in r[2]] for r in train_a] == [[m["loss"] for m in r[2]] for r in train_b]
+    assert (task_a._sampling_epoch, task_a._sampling_draw) == (task_b._sampling_epoch, task_b._sampling_draw) == (2, 8)      # ceil(60 / 16) = 4
+    assert sorted(ckpt_a["weights"]) == sorted(ckpt_b["weights"])
+    assert all(np.array_equal(ckpt_a["weights"][k], ckpt_b["weights"][k]) for k in ckpt_a["weights"])
+    assert model_a.best_epoch == model_b.best_epoch
+    n = len(VALID)
+    for (_, loss_a, res_a, graphs_a), (_, loss_b, res_b, graphs_b) in zip(_validation_of(rec_a), _validation_of(rec_b)):
+        assert (len(res_a), graphs_a, len(res_b), graphs_b) == (3, 1, 1, 1)
+        assert sum(m["num_masked"] for m in res_a) == n
+        assert sum(m["num_correct"] for m in res_a) == round(res_b[0]["accuracy"] * n)
+        total_a, total_b = sum(m["total_loss"] for m in res_a), res_b[0]["total_loss"]
+        bound = 2 * (n + 3) * 2.0 ** -24 * max(total_a, total_b)       # (every row loss is positive: sum|row loss| is the total)
+        print("validation: with the key %.9g, full graph %.9g, bound %.3g" % (total_a, total_b, bound))
+        assert abs(total_a - total_b) <= bound and abs(loss_a - loss_b) <= bound / n
+    assert [e for e, _ in model_a.validation_history] == [1, 2]
+    assert all(abs(a - b) <= 2 * (n + 3) * 2.0 ** -24 * max(a, b) for (_, a), (_, b) in zip(model_a.validation_history, model_b.validation_history))
+
+
+def test_train_with_all_five_keys_and_kept_batches(gpu_device, tmp_path, monkeypatch):
+    """sparse_features, sparse_update, sparse_gradient, layered and evaluation in one run.  "keep": the same metrics as without it,
+    the batches of the second epoch are the first epoch's objects, and the second validation epoch builds no RelGraph."""
+    from tf_gnn_samples_amd import graph as graph_module
+    from tf_gnn_samples_amd.tasks import DataFold
+    every = dict(sparse_features=True, sparse_update=True, sparse_gradient=True, layered=True)
+    built = []
+    real = graph_module.RelGraph.__init__
+    monkeypatch.setattr(graph_module.RelGraph, "__init__", lambda self, *a, **k: (built.append(1), real(self, *a, **k))[1])
+    runs = {}
+    for keep in (False, True):
+        evaluation = {"fanouts": [0, 0], "seeds_per_batch": 7, "keep": True} if keep else {"fanouts": [0, 0], "seeds_per_batch": 7}
+        task = citation_task(2, sampled(evaluation, True, **every), True)
+        (tmp_path / str(keep)).mkdir()
+        model = make_model("RGCN_Model", task, gpu_device, 2)
+        model.run_id, model.result_dir = "run", str(tmp_path / str(keep))
+        record, run_epoch = [], model._run_epoch
+
+        def recording(epoch_name, data, fold, quiet=False, run_epoch=run_epoch, record=record):
+            before = len(built)
+            out = run_epoch(epoch_name, data, fold, quiet)
+            record.append((epoch_name, out[0], [dict(m) for m in out[1]], len(built) - before))
+            return out
+        model._run_epoch = recording
+        model.train(quiet=True, max_epochs=2)
+        model._run_epoch = run_epoch
+        assert model.optimizer.row_gradient_sink is not None and task.layered
+        runs[keep] = (task, model, record)
+    for a, b in zip(runs[False][2], runs[True][2]):
+        assert a[0] == b[0] and a[1] == b[1] and a[2] == b[2]                        # the same metrics, training and validation
+    assert all(math.isfinite(r[1]) for r in runs[True][2])
+    graphs_built = {keep: [r[3] for r in _validation_of(runs[keep][2])] for keep in runs}
+    assert graphs_built[False][0] > 0 and graphs_built[False][1] == graphs_built[False][0]       # 3 batches x 2 levels, every epoch
+    assert graphs_built[True][0] > 0 and graphs_built[True][1] == 0
+    task, model, _ = runs[True]
+    data = task._loaded_data[DataFold.VALIDATION]
+    first, second = list(model._batches(data, DataFold.VALIDATION)), list(model._batches(data, DataFold.VALIDATION))
+    assert len(first) == 3 and all(a is b for a, b in zip(first, second))
+    task, model, _ = runs[False]
+    data = task._loaded_data[DataFold.VALIDATION]
+    assert all(a is not b for a, b in zip(model._batches(data, DataFold.VALIDATION), model._batches(data, DataFold.VALIDATION)))
+
+
+# ---- predict(nodes=...) ----------------------------------------------------------------------------------------------------------------
+def _snapshot(model, device):
+    return (torch.cuda.get_rng_state(device).clone(), torch.get_rng_state().clone(), np.random.get_state()[1].copy(),
+            model.dropout_state.clone(), model.optimizer.t, [m.clone() for m in model.optimizer.m],
+            [model.variables[n].detach().clone() for n in model.variables.names()])
+
+
+def _assert_untouched(model, device, before):
+    after = _snapshot(model, device)
+    assert torch.equal(after[0], before[0]) and torch.equal(after[1], before[1]) and np.array_equal(after[2], before[2])
+    assert torch.equal(after[3], before[3]) and after[4] == before[4]
+    assert all(torch.equal(a, b) for a, b in zip(after[5], before[5])) and all(torch.equal(a, b) for a, b in zip(after[6], before[6]))
+    assert all(model.variables[n].grad is None for n in model.variables.names())
+
+
+@pytest.mark.parametrize("native_batching", [True, False], ids=["native", "numpy"])
+@pytest.mark.parametrize("sparse", [False, True], ids=["dense", "sparse"])
+def test_predict_nodes_gives_the_rows_of_predict(gpu_device, sparse, native_batching):
+    """No key at all: exact fields, batches of 1 024.  Probabilities, classes and node states of a shuffled list, a list with a
+    duplicate, one node and all nodes are predict()'s rows bit for bit; nothing a training step can see is touched."""
+    task = citation_task(3, None, sparse)
+    model = make_model("GGNN_Model", task, gpu_device, 2, native_batching=native_batching)
+    data = task.synthetic_test_data
+    (full,) = model.predict(data, return_states=True)
+    assert full["probabilities"].shape == (V, 5)
+    before = _snapshot(model, gpu_device)
+    shuffled = np.random.default_rng(2).permutation(V)[:40]
+    for nodes in (shuffled, [HUB, 11, HUB, 299, 11], [12], np.arange(V, dtype=np.int32), shuffled.astype(np.int32).tolist()):
+        out = model.predict(data, nodes=nodes, return_states=True)
+        index = np.asarray(nodes, dtype=np.int64)
+        assert sorted(out) == ["classes", "node_states", "nodes", "probabilities"]
+        assert out["nodes"].dtype == np.int64 and np.array_equal(out["nodes"], index)
+        assert out["classes"].dtype == np.int32 and np.array_equal(out["classes"], full["classes"][index])
+        assert same_bits(out["probabilities"], full["probabilities"][index]) and same_bits(out["node_states"], full["node_states"][index])
+    assert sorted(model.predict(data, nodes=[3])) == ["classes", "nodes", "probabilities"]
+    _assert_untouched(model, gpu_device, before)
+    with pytest.raises(ValueError):
+        model.predict(data, nodes=[V])
+    assert not task._kept_evaluation and task.sampled_batches is None
+
+
+def test_predict_nodes_with_the_key_runs_the_key_s_batches(gpu_device):
+    """With "evaluation" at [3, 2] and B = 7 the rows are those of the batches sample_by_hop(distinct ids i * 7 .., draw = i) of a sampler
+    with replica 0x40000000 | 3, hand-fed; predict(data) without nodes stays the full graph; a row-deferred weight is flushed first."""
+    from tf_gnn_samples_amd.tasks.neighbour_sampling import NeighbourSampler, PREDICT_FOLD, evaluation_replica
+    every = dict(sparse_features=True, sparse_update=True, sparse_gradient=True)
+    task = citation_task(2, sampled({"fanouts": [3, 2], "seeds_per_batch": 7}, True, **every), True)
+    model = make_model("RGCN_Model", task, gpu_device, 2)
+    from tf_gnn_samples_amd.tasks import DataFold
+    for batch in model._batches(task._loaded_data[DataFold.TRAIN], DataFold.TRAIN):
+        model.train_step(batch)                                          # (the projection's weight is row-deferred from here on)
+    model.optimizer.zero_grad()
+    data = task.synthetic_test_data
+    nodes = [40, 5, HUB, 5, 11, 12, 13, 14, 15, 200, 201, 202, 203, 204, 250, 7, 260]
+    before = _snapshot(model, gpu_device)
+    out = model.predict(data, nodes=nodes, return_states=True)
+    distinct = np.unique(nodes).astype(np.int32)
+    state = task._sampling_state_of(data[0], gpu_device, [3, 2], 5, evaluation_replica(PREDICT_FOLD))
+    sampler = NeighbourSampler(state.sampler.graph, [3, 2], seed=5, replica=0x40000003)
+    rows = {"probabilities": [], "classes": [], "node_states": []}
+    for i in range(0, len(distinct), 7):
+        batch = sampler.sample_by_hop(distinct[i:i + 7], i // 7).device_batch(state.features, state.labels, state.mask, 1.0)
+        with torch.no_grad():
+            final = model._final_node_states(batch, training=False)
+            got = task.compute_task_predictions(final, batch, model.variables.scope(model._task_scope))
+        rows["node_states"].append(final.cpu().numpy())
+        rows["probabilities"].append(got["probabilities"].cpu().numpy())
+        rows["classes"].append(got["classes"].cpu().numpy())
+    inverse = np.searchsorted(distinct, nodes)
+    for key, parts in rows.items():
+        want = np.concatenate(parts)[inverse]
+        assert out[key].dtype == want.dtype and np.array_equal(out[key].view(np.uint32) if want.dtype == np.float32 else out[key],
+                                                               want.view(np.uint32) if want.dtype == np.float32 else want), key
+    (full,) = model.predict(data)
+    assert full["classes"].shape == (V,)
+    assert before[4] == model.optimizer.t and torch.equal(before[3], model.dropout_state)
+    assert torch.equal(before[0], torch.cuda.get_rng_state(gpu_device)) and torch.equal(before[1], torch.get_rng_state())
+    assert all(torch.equal(a, b) for a, b in zip(before[5], model.optimizer.m))
+    assert all(model.variables[n].grad is None for n in model.variables.names())
+
+
+# ---- shared state --------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("sparse", [False, True], ids=["dense", "sparse"])
+def test_three_folds_share_one_graph_and_one_feature_table(gpu_device, sparse):
+    from tf_gnn_samples_amd.tasks import DataFold
+    task = citation_task(2, sampled({"fanouts": [0, 0], "seeds_per_batch": 7}, sparse), sparse, num_features=2000)
+    model = make_model("RGCN_Model", task, gpu_device, 2)
+    folds = ((DataFold.TRAIN, task._loaded_data[DataFold.TRAIN]), (DataFold.VALIDATION, task._loaded_data[DataFold.VALIDATION]),
+             (DataFold.TEST, task.synthetic_test_data))
+    features = folds[0][1][0].node_features
+    # (sparse: column and value of every entry, in the rows and in their transpose, at the least)
+    table_bytes = features.nnz * 16 if sparse else features.nbytes
+    torch.cuda.synchronize()
+    allocated = [torch.cuda.memory_allocated(gpu_device)]
+    for data_fold, data in folds:
+        for batch in model._batches(data, data_fold):
+            with torch.no_grad():
+                model.forward_batch(batch, training=False)
+        del batch
+        torch.cuda.synchronize()
+        allocated.append(torch.cuda.memory_allocated(gpu_device))
+    assert len(task._graph_state) == 1 and len(task._sampling_state) == 3
+    (_, _, shared), = task._graph_state.values()
+    states = [state for _, state in task._sampling_state.values()]
+    assert all(s.sampler.graph is shared.graph and s.features is shared.features for s in states)
+    assert sorted(s.sampler.replica for s in states) == [0, 0x40000001, 0x40000002]
+    assert len({id(s.labels) for s in states}) == 3 and len({id(s.sampler) for s in states}) == 3
+    print("allocated after 0..3 folds: %s; one feature table: %d bytes" % (allocated, table_bytes))
+    assert allocated[3] - allocated[1] < table_bytes // 2            # the second and third fold: labels, masks and stamps, no table
+    assert allocated[3] - allocated[0] < 2 * table_bytes             # all three: one upload, where three would be 3 x
+
+
+# ---- peak memory ---------------------------------------------------------------------------------------------------------------------
+def test_a_validation_epoch_on_small_fields_peaks_below_the_full_graph_epoch(gpu_device):
+    """A ring (node i linked to i +- 1, V = 4 096, a self loop each), H = 2, 64 contiguous validation nodes: the exact field of the fold is
+    64 + 2 + 2 = 68 nodes, at most V / 4 (checked with the reference sampler on the host).  Under that condition the peak of a validation
+    epoch with the key lies below the peak of the full-graph epoch of the same model."""
+    from tf_gnn_samples_amd.tasks import DataFold
+    n = 4096
+    nodes = np.arange(n)
+    ring = np.concatenate([np.stack([nodes, (nodes + 1) % n], axis=1), np.stack([nodes, (nodes - 1) % n], axis=1)])
+    adjacency = [np.stack([nodes, nodes], axis=1).astype(np.int32), np.ascontiguousarray(ring, dtype=np.int32)]
+    degrees = np.stack([np.bincount(a[:, 1], minlength=n) for a in adjacency]).astype(np.int32)
+    valid = np.arange(1000, 1064)
+    rowptr, col, _ = R.bucketing(adjacency, n)
+    field = LR.sample_by_hop(rowptr, col, n, 2, valid.astype(np.int32), [0, 0], 0, seed=0, replica=0)
+    assert len(field.nodes) == 68 and len(field.nodes) <= n // 4
+    peaks = {}
+    for which, value in (("full", {"fanouts": [3, 2], "seeds_per_batch": 16, "seed": 5}), ("key", sampled({"fanouts": [0, 0], "seeds_per_batch": 64}))):
+        task = citation_task(2, value, adjacency=adjacency, degrees=degrees, num_nodes=n, valid=valid, num_features=64)
+        model = make_model("RGCN_Model", task, gpu_device, 2, hidden_size=128)
+        data = task._loaded_data[DataFold.VALIDATION]
+        model._run_epoch("warm", data, DataFold.VALIDATION, quiet=True)          # tables, plans and scratch are in place
+        torch.cuda.synchronize()
+        torch.cuda.empty_cache()
+        torch.cuda.reset_peak_memory_stats(gpu_device)
+        before = torch.cuda.memory_allocated(gpu_device)
+        _, res, graphs, _, _, _ = model._run_epoch("measured", data, DataFold.VALIDATION, quiet=True)
+        torch.cuda.synchronize()
+        peaks[which] = torch.cuda.max_memory_allocated(gpu_device) - before
+        assert graphs == 1 and len(res) == 1
+        del model, task, data
+    print("peak of a validation epoch above the resting state: full graph %d bytes, exact fields %d bytes" % (peaks["full"], peaks["key"]))
+    assert 0 < peaks["key"] < peaks["full"], peaks

@@ -366,6 +366,22 @@ class RelGraph:
         with validate="deferred" keep one wave per bucket (PPI-, QM9- and VarMisuse-shaped data: longest bucket < 2 k)."""
         return self._attach_split_plans(self._longest_buckets().tolist(), threshold)
 
+    def route_like(self, other: "RelGraph") -> "RelGraph":
+        """Send this graph's reductions down the routes `other`'s take: a bucketing that carries a SplitPlan there gets one here
+        (every bucket of it then takes the two-pass route, whatever its own length), one that carries none there keeps one wave per
+        bucket, and has_long_buckets, which the RGAT, GNN-FiLM and edge-MLP layers choose their kernels by, is `other`'s.  For a
+        subgraph whose buckets are whole buckets of `other` in `other`'s order (an exact receptive field, tasks/neighbour_sampling.py):
+        every bucket is then folded in the order and the grouping of the full graph's.  One host round trip per SplitPlan."""
+        if other.L != self.L:
+            raise ValueError("route_like: %d edge types against %d" % (self.L, other.L))
+        for (rp, stride), (theirs, _) in zip(self._bucketings(), other._bucketings()):
+            if split_plan_of(theirs, stride) is not None and split_plan_of(rp, stride) is None:
+                if not hasattr(rp, "_relgnn_split"):
+                    rp._relgnn_split = {}
+                rp._relgnn_split[stride] = SplitPlan(rp, stride, self.V * self.L // stride, LONG_SEGMENT)
+        self.has_long_buckets = other.has_long_buckets
+        return self
+
     # ---- derived index arrays -----------------------------------------------------------
     @property
     def src_t(self):

@@ -286,7 +286,9 @@ class Sparse_Graph_Model(ABC):
                     raise ValueError("layer_graphs: level %d takes %d rows, the layer below it left %d"
                                      % (layer_idx + 1, level.num_sources, cur_node_representations.shape[0]))
                 # (level 1 is the union graph: the same key, the same cached bucketing)
-                graph = as_rel_graph(level.adjacency_lists, level.num_sources, validate="deferred")
+                # (an evaluation batch brings every level's bucketing along, routed as the full graph's)
+                graph = as_rel_graph(level.graph if getattr(level, "graph", None) is not None else level.adjacency_lists,
+                                     level.num_sources, validate="deferred")
                 layer_degrees = level.type_to_num_incoming_edges
                 if residual_step and layer_idx > 0 and last_residual_representations.shape[0] > level.num_sources:
                     last_residual_representations = last_residual_representations[:level.num_sources]
@@ -350,6 +352,12 @@ class Sparse_Graph_Model(ABC):
                 raise ValueError('sampled_batches: "layered": true requires graph_num_timesteps_per_layer 1 (got %r): a layer that '
                                  'propagates twice needs two hops, and the layer functions take one graph'
                                  % (p['graph_num_timesteps_per_layer'],))
+        if getattr(self.task, "evaluation", None) is not None:
+            # the citation task's `sampled_batches` key "evaluation": its batches are always hop-ordered and layered
+            problem = self._layered_prerequisites(self.task.evaluation["fanouts"])
+            if problem is not None:
+                raise ValueError('sampled_batches: "evaluation" requires %s: evaluation batches are hop-ordered and run layer l on '
+                                 'the nodes H - l + 1 hops from a seed' % problem)
         if getattr(self.task, "sparse_update", False):
             # the citation task's `sampled_batches` key "sparse_update": the weight of the sparse input projection is updated by rows.
             # CONTRACT: between training steps that parameter's tensor (and its two Adam slots) hold stale rows; everything here that
@@ -365,6 +373,15 @@ class Sparse_Graph_Model(ABC):
             if getattr(self.task, "sparse_gradient", False):
                 # "sparse_gradient": that weight's gradient exists only as the rows a batch names (_project_input hands the sink on)
                 self.optimizer.compact_row_gradient()
+
+    def _layered_prerequisites(self, fanouts) -> Optional[str]:
+        """What a layered batch of these fanouts needs and this model lacks, None when it can run one."""
+        p = self.params
+        if len(fanouts) != p['graph_num_layers']:
+            return "as many fanouts as graph_num_layers (got %d fanouts for %d layers)" % (len(fanouts), p['graph_num_layers'])
+        if p['graph_num_timesteps_per_layer'] != 1:
+            return "graph_num_timesteps_per_layer 1 (got %r)" % (p['graph_num_timesteps_per_layer'],)
+        return None
 
     # -------------------- Training Loop --------------------
     def _final_node_states(self, batch: DeviceBatch, training: bool) -> torch.Tensor:
@@ -467,20 +484,34 @@ class Sparse_Graph_Model(ABC):
         lr_n = self.params.get('lr_for_num_graphs_per_batch')
         return 1.0 if lr_n is None else float(num_graphs) / float(lr_n)
 
-    def _batches(self, data, data_fold: DataFold):
+    def _native_batching(self) -> bool:
+        return bool(self.params.get('native_batching', True) and torch.device(self.device).type == "cuda"
+                    and hasattr(self.task, "make_graph_store"))
+
+    def _batches(self, data, data_fold: DataFold, full_graph: bool = False):
         """Batches of one epoch.  On the GPU the data fold is flattened once and batches come from the C++ builder
         (tasks/batcher.py: packed in pinned memory on a background thread, one async upload each), the stand-in for
-        the reference's ThreadedIterator (:272); `native_batching: false` keeps the numpy iterator."""
-        native = self.params.get('native_batching', True) and torch.device(self.device).type == "cuda" \
-            and hasattr(self.task, "make_graph_store")
+        the reference's ThreadedIterator (:272); `native_batching: false` keeps the numpy iterator.  full_graph: the task's
+        "evaluation" key is not consulted (predict(data) without nodes)."""
+        native = self._native_batching()
         if data_fold == DataFold.TRAIN and getattr(self.task, "sampled_batches", None) is not None:
             # a single-graph task that trains on sampled subgraphs (tasks/neighbour_sampling.py): drawn on this model's device by
             # either iterator, so no flattened or resident copy of the fold is built for them
             self.task.bind_sampling_device(self.device)
             native = False
+        if data_fold != DataFold.TRAIN and not full_graph and getattr(self.task, "evaluation", None) is not None:
+            # ... and evaluates on sampled receptive fields (the key "evaluation"): no flattened or resident copy of the fold either
+            self.task.bind_sampling_device(self.device)
+            return self.task.evaluation_batches(data, data_fold, self._full_graph_route(native))
         if not native:
             return self.task.make_minibatch_iterator(data, data_fold, self.params['max_nodes_in_batch'])
         return self.task.make_native_minibatch_iterator(self._native_pipeline(data), data_fold, self.params['max_nodes_in_batch'])
+
+    def _full_graph_route(self, native: bool) -> bool:
+        """Would this model's full-graph batch of a single-graph fold be a resident one?  (tasks/resident.py splits the hub buckets
+        of such a batch; the graph the model buckets itself keeps one wave per bucket.)  A batch of receptive fields routes its
+        reductions the same way, so that an exact field reproduces the full-graph rows."""
+        return bool(native and self.params.get('resident_dataset', 'auto') is not False)
 
     def _native_pipeline(self, data):
         """The input pipeline of one data fold (ResidentDataset or NativeBatcher over its GraphStore), built once and kept."""
@@ -539,6 +570,8 @@ class Sparse_Graph_Model(ABC):
             upcoming = next(batch_iterator, None)
             late.put((readback, mb))
         late.flush()
+        if data_fold != DataFold.TRAIN and getattr(self.task, "evaluation", None) is not None:
+            return self.task.sampled_evaluation_epoch(tally.result())      # the fold's batches add up to its one graph
         return tally.result()
 
     def train(self, quiet: bool = False, max_epochs: Optional[int] = None, group=None):
@@ -593,7 +626,7 @@ class Sparse_Graph_Model(ABC):
         self.log_line("Training took %is." % (time.time() - total_time_start))
 
     # -------------------- Predictions --------------------
-    def predict_iter(self, data, return_states: bool = False):
+    def predict_iter(self, data, return_states: bool = False, nodes=None):
         """Generator over (samples of the batch, their predictions): one dict of NumPy arrays per graph, in the order of `data`
         (the task's split_predictions says which keys; return_states adds 'node_states' float32 [n, hidden], the rows of
         compute_final_node_representations).
@@ -607,29 +640,65 @@ class Sparse_Graph_Model(ABC):
         predictions of a product kernel that gave up are never handed out.
 
         Nothing a later training step can see is touched: no .grad, no optimizer state, no torch / NumPy random state, and
-        dropout_state does not advance (nothing is dropped).  No collective: under data parallelism each rank predicts its own data."""
+        dropout_state does not advance (nothing is dropped).  No collective: under data parallelism each rank predicts its own data.
+
+        nodes (the citation task): int32 / int64 ids of nodes of the ONE graph in `data`, any order, repeats allowed (validated here, on
+        the host, before the generator is made).  The distinct ids, ascending, are cut into batches; each batch is the receptive field
+        of its ids (the fanouts and batch size of the task's "evaluation" key, or every neighbour and 1024 without it) and the
+        generator yields (the batch's ids as an int32 array, [one dict whose rows are those ids']).  Everything above holds."""
         data = data if isinstance(data, list) else list(data)
+        plan = None
+        if nodes is not None:
+            plan = self._node_prediction_plan(data, nodes)
+        return self._predict_iter(data, return_states, plan)
+
+    def _node_prediction_plan(self, data, nodes):
+        if not hasattr(self.task, "node_prediction_batches"):
+            raise ValueError("predict(nodes=...) is not defined for the %s task: its predictions are per graph of `data`, and only a "
+                             "task whose data is ONE graph names single nodes" % self.task.name())
+        distinct, inverse, given = self.task.check_prediction_nodes(data, nodes)
+        settings = self.task.node_prediction_settings()
+        if settings["fanouts"] is None:
+            settings["fanouts"] = [0] * self.params['graph_num_layers']
+        problem = self._layered_prerequisites(settings["fanouts"])
+        if problem is not None:
+            raise ValueError("predict(nodes=...) runs layered batches and requires %s" % problem)
+        self.task.bind_sampling_device(self.device)
+        return dict(settings, distinct=distinct, inverse=inverse, given=given)
+
+    def _predict_iter(self, data, return_states, plan):
         # two pinned host arenas, taken in turn (batch i + 1's copy runs while batch i is read); kept with the model between calls
         # (pinning memory costs more than a small batch's forward) and taken out of it while this generator runs, so that a second
         # generator on the same model pins its own
         pinned, self._prediction_pinned = getattr(self, "_prediction_pinned", None) or [None, None], None
         try:
-            yield from self._predict_batches(data, return_states, pinned)
+            yield from self._predict_batches(data, return_states, pinned, plan)
         finally:
             self._prediction_pinned = pinned
 
-    def _predict_batches(self, data, return_states, pinned):
+    def _predict_batches(self, data, return_states, pinned, plan=None):
         cursor, turn = 0, 0
         self.optimizer.flush_deferred()    # (`sparse_update`: the projection's weight holds stale rows between training steps)
         late = LateFetch(self._fetch_predictions)
-        batch_iterator = iter(self._batches(data, DataFold.TEST))
+        if plan is None:
+            # (predict(data) stays on the full graph whatever the task's "evaluation" key says)
+            sampled_evaluation = getattr(self.task, "evaluation", None) is not None
+            batch_iterator = iter(self._batches(data, DataFold.TEST, full_graph=True) if sampled_evaluation
+                                  else self._batches(data, DataFold.TEST))
+        else:
+            native = self._native_batching()
+            batch_iterator = iter(self.task.node_prediction_batches(data, plan["distinct"], plan["fanouts"], plan["seeds_per_batch"],
+                                                                    self._full_graph_route(native)))
         upcoming = next(batch_iterator, None)
         while upcoming is not None:
             with torch.no_grad():      # (around the device work only: a generator suspended inside it would leave the grad mode of
                 #                         the CONSUMER's code switched off between two batches)
                 batch = upcoming if isinstance(upcoming, DeviceBatch) else DeviceBatch(upcoming, self.device)
-                samples = data[cursor:cursor + batch.num_graphs]
-                cursor += batch.num_graphs
+                if plan is None:
+                    samples = data[cursor:cursor + batch.num_graphs]
+                    cursor += batch.num_graphs
+                else:
+                    samples = None     # (one graph; the batch names its rows itself: extra['prediction_seeds'])
                 final = self._final_node_states(batch, training=False)
                 layout = dict(self.task.prediction_layout(batch, final.shape[1]))
                 if return_states:
@@ -652,10 +721,21 @@ class Sparse_Graph_Model(ABC):
         arena, batch, samples = pending
         host = arena.fetch()
         check_pending_graph_errors()
+        if samples is None:                # predict(nodes=...): the rows are the batch's seeds
+            return batch.extra['prediction_seeds'], [host]
         return samples, self.task.split_predictions(host, batch, samples)
 
-    def predict(self, data, return_states: bool = False, quiet: bool = True) -> List[Dict[str, np.ndarray]]:
-        """One entry per graph of `data`, in its order (predict_iter, collected)."""
+    def predict(self, data, return_states: bool = False, quiet: bool = True, nodes=None):
+        """One entry per graph of `data`, in its order (predict_iter, collected).  nodes (predict_iter): ONE dict instead, `nodes` as
+        given (int64) and one row per entry of it under every other key; a node named twice has two equal rows."""
+        if nodes is not None:
+            data = data if isinstance(data, list) else list(data)
+            plan = self._node_prediction_plan(data, nodes)
+            parts = [rows for _, (rows,) in self._predict_iter(data, return_states, plan)]
+            out = {"nodes": plan["given"]}
+            for key in parts[0]:
+                out[key] = np.concatenate([part[key] for part in parts])[plan["inverse"]]
+            return out
         results = []
         for step, (samples, predictions) in enumerate(self.predict_iter(data, return_states)):
             results.extend(predictions)

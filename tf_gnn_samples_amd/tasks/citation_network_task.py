@@ -18,8 +18,8 @@ one batch.  An epoch is a permutation of the fold's nodes cut into ceil(n_train 
 .epoch_seed_batches); every seed list becomes a fanout-limited subgraph drawn on the device (neighbour_sampling.NeighbourSampler,
 csrc/neighbour_sample.hip) whose loss counts the seeds only.  The sampler, the full graph's RelGraph and the device copies of the
 feature table, the labels and the fold's mask are built once per (fold, device).  The task counts the epochs and the sampled batches
-(the sampler's `draw`) itself.  VALIDATION, TEST, test() and predict() stay on the full graph.  GPU only; not together with
-capture_train_step or a process group.
+(the sampler's `draw`) itself.  VALIDATION, TEST, test() and predict() stay on the full graph unless the key "evaluation" (last paragraph)
+says otherwise.  GPU only; not together with capture_train_step or a process group.
 
 The two together: `sampled_batches` takes one more optional key, "sparse_features": true, which requires sparse_node_features
 (and sparse_node_features with a sampled_batches that lacks the key stays a ValueError).  The sampling state then keeps the device's
@@ -49,6 +49,21 @@ and the metrics see the seed rows only (labels and mask are taken for the seeds)
 layers as there are fanouts and one timestep per layer (models/sparse_graph_model.py).  With a layer-input keep-probability below 1
 the dropout masks differ from the un-layered run's (torch draws by shape, the fused route by element index over another row count):
 the two runs are then two draws of the same model, not equal ones.
+
+One more optional key, "evaluation": {"fanouts": [k_1, ..., k_H], "seeds_per_batch": B, "keep": bool} ("keep" optional; it composes with
+the four above and does not ask training to be layered): VALIDATION, TEST and test() run over ceil(n_fold / B) batches instead of the
+full graph.  Batch i holds the fold's masked nodes i * B .. (i + 1) * B - 1 in ascending id (no shuffle) and is
+sample_by_hop(seeds, draw=i).device_batch(..., layered=True) with keep-probability 1, labels and mask of the seeds only, drawn by a
+sampler of the fold's own whose replica is 0x40000000 | fold (neighbour_sampling.evaluation_replica): the random words are a function of
+(seed, fold, batch index), the same in every epoch and never a training batch's.  The batches are always hop-ordered and layered, so the
+model refuses the key unless it has as many layers as there are fanouts and one timestep per layer.  An epoch's loss is
+sum(total_loss) / sum(num_masked), its accuracy sum(num_correct) / sum(num_masked), the early-stopping metric sum(total_loss) over the
+fold's ONE graph (sampled_evaluation_epoch).  With every fanout 0 the seeds' states and logits are the full-graph forward's rows bit for
+bit: every level graph brings its bucketing along and routes its hub buckets as the model's full-graph batch does (RelGraph.route_like).
+"keep": the batches of a fold are built once and handed out again every epoch, released with the fold.  The three folds share ONE device
+RelGraph and ONE feature table (_graph_state_of, keyed by the adjacency and feature objects the folds share); labels, mask and sampler are
+per fold.  predict(data, nodes=...) runs the same batches over the named nodes (the key's fanouts and B, or all-zero fanouts and 1024
+without it); predict(data) without nodes stays on the full graph.
 """
 import os
 import pickle
@@ -63,7 +78,8 @@ from ..dense import dense, mark_zero_padded
 from ..graph import RelGraph
 from ..parallel import refuse_single_graph_task
 from ..predict import predict_softmax
-from .neighbour_sampling import NeighbourSampler, parse_sampled_batches, epoch_seed_batches
+from .neighbour_sampling import (PREDICT_FOLD, PREDICT_SEEDS_PER_BATCH, NeighbourSampler, check_prediction_nodes, epoch_seed_batches,
+                                 evaluation_replica, evaluation_seed_batches, parse_sampled_batches)
 from .resident import ResidentDataset
 from .sparse_features import SparseRows, node_stand_in, random_rows, resident_copy
 from .sparse_graph_task import DataFold, MinibatchData, Sparse_Graph_Task
@@ -78,8 +94,14 @@ class CitationData(NamedTuple):
     mask: np.ndarray                                       # float32 [V], 1 = the node counts in this fold
 
 
+class _GraphState(NamedTuple):
+    """What the folds of one graph share on one device: ONE bucketing and ONE feature table (or device SparseRows)."""
+    graph: RelGraph
+    features: Any                                          # float32 [V, F], or the device's SparseRows
+
+
 class _SamplingState(NamedTuple):
-    """What the sampled TRAIN batches of one fold on one device are cut from."""
+    """What the sampled batches of one fold on one device are cut from; `sampler.graph` and `features` are the _GraphState's."""
     sampler: NeighbourSampler
     features: Any                                          # float32 [V, F], or the device's SparseRows
     labels: torch.Tensor                                   # int32 [V]
@@ -236,7 +258,9 @@ class Citation_Network_Task(Sparse_Graph_Task):
         super().__init__(params)
         self._resident_batches = weakref.WeakKeyDictionary()      # resident fold -> its one assembled batch (released with the fold)
         self._device_rows = weakref.WeakKeyDictionary()           # host SparseRows -> {device: its one copy there}
-        self._sampling_state = {}                                 # (id of a fold's label array, device) -> (weak reference to the array, _SamplingState)
+        self._sampling_state = {}                                 # (id of a fold's label array, device, replica) -> (weak reference to the array, _SamplingState)
+        self._graph_state = {}                                    # (id of the first adjacency array, id of the features, device) -> (weak references, _GraphState)
+        self._kept_evaluation = {}                                # (id of a fold's label array, device, fold number, route, fanouts, B) -> (weak reference, its batches)
         self._sampling_device = None                              # where the model runs (bind_sampling_device)
         self._sampling_epoch = self._sampling_draw = 0            # TRAIN epochs started / batches sampled so far
         self.sampled_batches                                      # (a malformed parameter fails here, not in the first epoch)
@@ -290,6 +314,13 @@ class Citation_Network_Task(Sparse_Graph_Task):
         """Does `sampled_batches` ask for hop-ordered batches whose layers run on the hops they need?"""
         sampled = self.sampled_batches
         return bool(sampled is not None and sampled.get("layered", False))
+
+    @property
+    def evaluation(self) -> Optional[Dict[str, Any]]:
+        """The "evaluation" key of `sampled_batches` ({"fanouts", "seeds_per_batch"}, "keep" when given), None when VALIDATION, TEST and
+        test() run on the full graph."""
+        sampled = self.sampled_batches
+        return None if sampled is None else sampled.get("evaluation")
 
     @property
     def num_edge_types(self) -> int:
@@ -417,7 +448,8 @@ class Citation_Network_Task(Sparse_Graph_Task):
         return int(sample.node_features.shape[0])
 
     def prediction_layout(self, batch, hidden_size: int):
-        num_nodes = int(batch.num_nodes)
+        # (a layered batch, predict(nodes=...): the head sees the seed rows only)
+        num_nodes = int(batch.extra['layer_graphs'][-1].num_targets) if 'layer_graphs' in batch.extra else int(batch.num_nodes)
         return {"probabilities": ((num_nodes, self.__num_output_classes), torch.float32), "classes": ((num_nodes,), torch.int32)}
 
     def compute_task_predictions(self, final_node_representations: torch.Tensor, batch, weights, out=None) -> Dict[str, torch.Tensor]:
@@ -482,31 +514,127 @@ class Citation_Network_Task(Sparse_Graph_Task):
                                "fallback (the model is on %s)" % device)
         self._sampling_device = device
 
-    def _sampling_state_of(self, fold: CitationData, device):
-        key = (id(fold.labels), str(device))
+    def _graph_state_of(self, fold: CitationData, device) -> _GraphState:
+        """The device RelGraph (validated once: it knows its hub buckets) and the device feature table of the graph `fold` belongs
+        to, built once for all folds that share the adjacency and feature objects (_load_folds, load_synthetic) and released with them."""
+        anchor, features = fold.adjacency_lists[0], fold.node_features
+        key = (id(anchor), id(features), str(device))
+        held = self._graph_state.get(key)
+        if held is not None and held[0]() is anchor and held[1]() is features:
+            return held[2]
+        from_host = lambda a, dtype: torch.as_tensor(np.ascontiguousarray(a), dtype=dtype).to(device)
+        graph = RelGraph([from_host(a.reshape(-1, 2), torch.int32) for a in fold.adjacency_lists], len(fold.labels))
+        if isinstance(features, SparseRows):                      # the device's one copy of the container: no dense table anywhere
+            table = resident_copy(self._device_rows, features, device)
+        else:
+            table = from_host(features, torch.float32)
+        drop = lambda _, key=key, table=self._graph_state: table.pop(key, None)
+        self._graph_state[key] = (weakref.ref(anchor, drop), weakref.ref(features, drop), _GraphState(graph, table))
+        return self._graph_state[key][2]
+
+    def _sampling_state_of(self, fold: CitationData, device, fanouts=None, seed=None, replica: int = 0):
+        """The TRAIN fold's state by default (the parameter's fanouts and seed, replica 0); an evaluation fold names its own."""
+        key = (id(fold.labels), str(device), int(replica))
         held = self._sampling_state.get(key)
-        if held is not None and held[0]() is fold.labels:
+        if held is not None and held[0]() is fold.labels and (fanouts is None or held[1].sampler.fanouts == list(fanouts)):
             return held[1]
         from_host = lambda a, dtype: torch.as_tensor(np.ascontiguousarray(a), dtype=dtype).to(device)
-        sampled = self.sampled_batches
-        graph = RelGraph([from_host(a.reshape(-1, 2), torch.int32) for a in fold.adjacency_lists], len(fold.labels))
-        if isinstance(fold.node_features, SparseRows):            # the device's one copy of the container: no dense table anywhere
-            features = resident_copy(self._device_rows, fold.node_features, device)
-        else:
-            features = from_host(fold.node_features, torch.float32)
-        state = _SamplingState(NeighbourSampler(graph, sampled["fanouts"], seed=sampled["seed"]), features,
+        if fanouts is None:
+            sampled = self.sampled_batches
+            fanouts, seed = sampled["fanouts"], sampled["seed"]
+        shared = self._graph_state_of(fold, device)
+        state = _SamplingState(NeighbourSampler(shared.graph, fanouts, seed=seed or 0, replica=replica), shared.features,
                                from_host(fold.labels, torch.int32), from_host(fold.mask, torch.float32))
         # released with the fold's arrays, as _resident_batches is with the resident fold
         self._sampling_state[key] = (weakref.ref(fold.labels, lambda _, key=key, table=self._sampling_state: table.pop(key, None)), state)
         return state
 
-    def _sampled_batches_of(self, fold: CitationData):
-        """ceil(n_train / B) sampled batches: one TRAIN epoch."""
+    # -------------------- Evaluation and predictions on sampled receptive fields --------------------
+    def _bound_device(self):
         if self._sampling_device is None:
             raise RuntimeError("sampled_batches: no device bound (Citation_Network_Task.bind_sampling_device); the model does that "
-                               "when it asks for the TRAIN fold's batches")
+                               "when it asks for a fold's sampled batches")
+        return self._sampling_device
+
+    def _evaluation_batch(self, state: _SamplingState, seeds: np.ndarray, draw: int, full_graph_route: bool):
+        """Batch `draw` of a fold: hop-ordered and layered, keep-probability 1, labels and mask of the seeds only, every level with its
+        bucketing.  full_graph_route: the levels route their reductions as the device's full graph does (RelGraph.route_like), which
+        is what a resident full-graph batch of the same fold does (tasks/resident.py splits a fold's hubs per batch); otherwise
+        every bucket keeps one wave, as the full graph bucketed by the model itself does (validate="deferred")."""
+        sub = state.sampler.sample_by_hop(seeds, draw)
+        return sub.device_batch(state.features, state.labels, state.mask, 1.0, layered=True, bucketed=True,
+                                route_like=state.sampler.graph if full_graph_route else None)
+
+    def evaluation_batches(self, data, data_fold: DataFold, full_graph_route: bool):
+        """ceil(n_fold / B) batches: one VALIDATION or TEST epoch under the "evaluation" key.  Batch i holds the fold's masked nodes
+        i * B .. (i + 1) * B - 1 in ascending id and is drawn with draw = i by the fold's own sampler, whose replica is
+        neighbour_sampling.evaluation_replica(fold): the same subgraphs in every epoch.  "keep": built once per (fold, device, route, fanouts, B),
+        handed out again, released with the fold."""
+        refuse_single_graph_task(self.name())
+        evaluation, device = self.evaluation, self._bound_device()
+        fold = next(iter(data))
+        key = (id(fold.labels), str(device), data_fold.value, bool(full_graph_route), tuple(evaluation["fanouts"]),
+               evaluation["seeds_per_batch"])
+        if evaluation.get("keep", False):
+            held = self._kept_evaluation.get(key)
+            if held is not None and held[0]() is fold.labels:
+                yield from held[1]
+                return
+        state = self._sampling_state_of(fold, device, evaluation["fanouts"], self.sampled_batches["seed"],
+                                        evaluation_replica(data_fold.value))
+        kept = []
+        for draw, seeds in enumerate(evaluation_seed_batches(fold.mask, evaluation["seeds_per_batch"])):
+            batch = self._evaluation_batch(state, seeds, draw, full_graph_route)
+            if evaluation.get("keep", False):
+                kept.append(batch)
+            yield batch
+        if evaluation.get("keep", False):         # (only a whole epoch is kept: an abandoned iterator keeps nothing)
+            drop = lambda _, key=key, table=self._kept_evaluation: table.pop(key, None)
+            self._kept_evaluation[key] = (weakref.ref(fold.labels, drop), kept)
+
+    def node_prediction_settings(self) -> Dict[str, Any]:
+        """Fanouts and batch size of predict(nodes=...): the "evaluation" key's, or (None: one 0 per layer) and 1024 without it."""
+        evaluation = self.evaluation
+        if evaluation is not None:
+            return {"fanouts": list(evaluation["fanouts"]), "seeds_per_batch": evaluation["seeds_per_batch"]}
+        return {"fanouts": None, "seeds_per_batch": PREDICT_SEEDS_PER_BATCH}
+
+    def check_prediction_nodes(self, data, nodes):
+        """-> (distinct ids ascending int32, position of every given node among them, the given nodes as int64) for the ONE graph
+        of `data`; ValueError otherwise (neighbour_sampling.check_prediction_nodes)."""
+        folds = list(data)
+        if len(folds) != 1:
+            raise ValueError("predict(nodes=...): the ids name nodes of ONE graph; data holds %d" % len(folds))
+        return check_prediction_nodes(nodes, len(folds[0].labels))
+
+    def node_prediction_batches(self, data, distinct_nodes: np.ndarray, fanouts, seeds_per_batch: int, full_graph_route: bool):
+        """The batches of predict(nodes=...): the distinct ids ascending in runs of seeds_per_batch, batch i drawn with draw = i by a
+        sampler of replica evaluation_replica(PREDICT_FOLD); each batch carries its host seed list under extra['prediction_seeds']."""
+        refuse_single_graph_task(self.name())
+        device = self._bound_device()
+        fold = next(iter(data))
         sampled = self.sampled_batches
-        state = self._sampling_state_of(fold, self._sampling_device)
+        state = self._sampling_state_of(fold, device, list(fanouts), sampled["seed"] if sampled is not None else 0,
+                                        evaluation_replica(PREDICT_FOLD))
+        for draw, at in enumerate(range(0, len(distinct_nodes), seeds_per_batch)):
+            seeds = np.ascontiguousarray(distinct_nodes[at:at + seeds_per_batch], dtype=np.int32)
+            batch = self._evaluation_batch(state, seeds, draw, full_graph_route)
+            batch.extra['prediction_seeds'] = seeds
+            yield batch
+
+    @staticmethod
+    def sampled_evaluation_epoch(result):
+        """The result of an epoch of evaluation batches as the fold's ONE graph: loss = sum of total_loss / sum of num_masked, one
+        graph (early_stopping_metric then divides the sum of total_loss by 1: the full-graph value's definition)."""
+        loss, results, graphs, graphs_per_s, nodes_per_s, edges_per_s = result
+        masked = sum(float(m['num_masked']) for m in results)
+        total = float(np.sum([float(m['total_loss']) for m in results]))
+        return (total / masked if masked else float("nan"), results, 1, graphs_per_s / max(graphs, 1), nodes_per_s, edges_per_s)
+
+    def _sampled_batches_of(self, fold: CitationData):
+        """ceil(n_train / B) sampled batches: one TRAIN epoch."""
+        sampled = self.sampled_batches
+        state = self._sampling_state_of(fold, self._bound_device())
         epoch, self._sampling_epoch = self._sampling_epoch, self._sampling_epoch + 1
         keep = self._out_keep(DataFold.TRAIN)
         for seeds in epoch_seed_batches(fold.mask, sampled["seeds_per_batch"], sampled["seed"], epoch):

@@ -85,6 +85,8 @@ class LevelGraph(NamedTuple):
     num_sources: int
     num_targets: int
     type_to_num_incoming_edges: torch.Tensor    # float32 [L, num_sources]: the sampled in-degrees of the targets, 0 behind them
+    graph: Optional[RelGraph] = None            # the level's bucketing where the batch brings it along (evaluation batches); the
+    #                                             model buckets adjacency_lists itself otherwise
 
 
 class HopSubgraph(NamedTuple):
@@ -100,8 +102,10 @@ class HopSubgraph(NamedTuple):
     hop_nodes: List[int]                        # [n_0, ..., n_H], cumulative
     hop_edges: List[List[int]]                  # per type [E_{l,0}, ..., E_{l,H-1}]: the type-l edges emitted by hops 0 .. h
 
-    def level_graphs(self) -> List[LevelGraph]:
-        """One LevelGraph per layer of a model with as many layers as hops; level 1 is the union graph."""
+    def level_graphs(self, bucketed: bool = False, route_like: Optional[RelGraph] = None) -> List[LevelGraph]:
+        """One LevelGraph per layer of a model with as many layers as hops; level 1 is the union graph.  bucketed: every level
+        carries its RelGraph (the sampler's ids are in range: nothing is validated), routed as `route_like` routes its reductions
+        (RelGraph.route_like) when one is given."""
         H = len(self.hop_nodes) - 1
         degrees, levels = self.type_to_num_incoming_edges, []
         for layer in range(1, H + 1):
@@ -112,28 +116,39 @@ class HopSubgraph(NamedTuple):
             else:
                 table = torch.zeros((degrees.shape[0], sources), dtype=degrees.dtype, device=degrees.device)
                 table[:, :targets] = degrees[:, :targets]
-            levels.append(LevelGraph(adjacency, sources, targets, table))
+            graph = None
+            if bucketed:
+                graph = RelGraph(adjacency, sources, validate=False)
+                if route_like is not None:
+                    graph.route_like(route_like)
+            levels.append(LevelGraph(adjacency, sources, targets, table, graph))
         return levels
 
     def device_batch(self, features, labels: torch.Tensor, fold_mask: torch.Tensor, out_keep: float = 1.0,
-                     named_rows: bool = False, layered: bool = True) -> DeviceBatch:
+                     named_rows: bool = False, layered: bool = True, bucketed: bool = False,
+                     route_like: Optional[RelGraph] = None) -> DeviceBatch:
         """layered=False: the union batch in hop order, through SampledSubgraph.device_batch.  layered=True: feature rows of all n
         nodes, labels and mask of the n_0 seeds only (mask = fold_mask[seeds]: num_masked and num_correct mean what they did), and
-        extra['layer_graphs'] = level_graphs(), which models/sparse_graph_model.py runs layer by layer."""
+        extra['layer_graphs'] = level_graphs(), which models/sparse_graph_model.py runs layer by layer.  bucketed / route_like
+        (layered only; an evaluation batch): the levels bring their bucketing, level 1's is the batch's own `graph`."""
         union = SampledSubgraph(self.nodes, self.adjacency_lists, self.type_to_num_incoming_edges, self.seed_mask, self.num_nodes,
                                 self.num_edges)
         if not layered:
             return union.device_batch(features, labels, fold_mask, out_keep, named_rows=named_rows)
         seeds = self.nodes[:self.hop_nodes[0]].long()
         extra = {'labels': labels.index_select(0, seeds), 'mask': fold_mask.index_select(0, seeds),
-                 'out_layer_dropout_keep_prob': out_keep, 'sampled_nodes': self.nodes, 'layer_graphs': self.level_graphs()}
+                 'out_layer_dropout_keep_prob': out_keep, 'sampled_nodes': self.nodes,
+                 'layer_graphs': self.level_graphs(bucketed, route_like)}
         if isinstance(features, SparseRows):
             extra['sparse_node_features'] = features.take_rows(self.nodes, validated=True, named_rows=named_rows)
             rows = torch.zeros((self.num_nodes, 1), dtype=torch.float32, device=self.nodes.device)      # sparse_features.node_stand_in
         else:
             rows = features.index_select(0, self.nodes.long())
-        return DeviceBatch.from_tensors(1, self.num_nodes, self.num_edges, rows, self.adjacency_lists,
-                                        self.type_to_num_incoming_edges, extra=extra)
+        batch = DeviceBatch.from_tensors(1, self.num_nodes, self.num_edges, rows, self.adjacency_lists,
+                                         self.type_to_num_incoming_edges, extra=extra)
+        if bucketed:
+            batch.graph = extra['layer_graphs'][0].graph
+        return batch
 
 
 class NeighbourSampler:
@@ -314,13 +329,16 @@ def parse_sampled_batches(value) -> Optional[Dict]:
     the optional keys "sparse_features" (a bool: the batches take their feature rows from a SparseRows), "sparse_update" (a bool:
     the optimizer updates only the rows of the input projection's weight that a batch names) and "sparse_gradient" (a bool: that
     weight's gradient exists only as the rows a batch names) and "layered" (a bool: the batches are numbered by hop and every layer
-    runs on the hops it needs) are carried only when given."""
+    runs on the hops it needs) are carried only when given, and so is "evaluation" ({"fanouts": [k_1, ..., k_H], "seeds_per_batch": B,
+    "keep": bool}, "keep" optional: VALIDATION, TEST and predict(nodes=...) run on sampled receptive fields, parse_evaluation)."""
     if value is None:
         return None
     if not isinstance(value, dict) or not {"fanouts", "seeds_per_batch"} <= set(value) \
-            or set(value) - {"fanouts", "seeds_per_batch", "seed", "sparse_features", "sparse_update", "sparse_gradient", "layered"}:
+            or set(value) - {"fanouts", "seeds_per_batch", "seed", "sparse_features", "sparse_update", "sparse_gradient", "layered",
+                             "evaluation"}:
         raise ValueError('sampled_batches must be {"fanouts": [k_1, ..., k_H], "seeds_per_batch": B, "seed": s, "sparse_features": bool, '
-                         '"sparse_update": bool, "sparse_gradient": bool, "layered": bool}, the last five optional, got %r' % (value,))
+                         '"sparse_update": bool, "sparse_gradient": bool, "layered": bool, "evaluation": {"fanouts": [...], '
+                         '"seeds_per_batch": B, "keep": bool}}, the last six optional, got %r' % (value,))
     per_batch = value["seeds_per_batch"]
     if isinstance(per_batch, bool) or not isinstance(per_batch, (int, np.integer)) or per_batch < 1:
         raise ValueError("sampled_batches: seeds_per_batch must be a positive integer, got %r" % (per_batch,))
@@ -347,4 +365,77 @@ def parse_sampled_batches(value) -> Optional[Dict]:
         if not isinstance(value["layered"], bool):
             raise ValueError("sampled_batches: layered must be true or false, got %r" % (value["layered"],))
         parsed["layered"] = value["layered"]
+    if "evaluation" in value:
+        parsed["evaluation"] = parse_evaluation(value["evaluation"])
     return parsed
+
+
+def parse_evaluation(value) -> Dict:
+    """The "evaluation" key of `sampled_batches` as {"fanouts": [ints], "seeds_per_batch": int}, "keep" (a bool: a fold's evaluation
+    batches are built once and handed out again every epoch) carried only when given."""
+    if not isinstance(value, dict) or set(value) - {"fanouts", "seeds_per_batch", "keep"} or not {"fanouts", "seeds_per_batch"} <= set(value):
+        raise ValueError('sampled_batches: "evaluation" must be {"fanouts": [k_1, ..., k_H], "seeds_per_batch": B, "keep": bool}, the '
+                         'last one optional, got %r' % (value,))
+    per_batch = value["seeds_per_batch"]
+    if isinstance(per_batch, bool) or not isinstance(per_batch, (int, np.integer)) or per_batch < 1:
+        raise ValueError('sampled_batches: "evaluation": seeds_per_batch must be a positive integer, got %r' % (per_batch,))
+    try:
+        fanouts = check_fanouts(value["fanouts"])
+    except ValueError as error:
+        raise ValueError('sampled_batches: "evaluation": %s' % error) from None
+    parsed = {"fanouts": fanouts, "seeds_per_batch": int(per_batch)}
+    if "keep" in value:
+        if not isinstance(value["keep"], bool):
+            raise ValueError('sampled_batches: "evaluation": keep must be true or false, got %r' % (value["keep"],))
+        parsed["keep"] = value["keep"]
+    return parsed
+
+
+# ---- evaluation on sampled receptive fields ----------------------------------------------------------------------------------------
+EVALUATION_REPLICA = 0x40000000       # | the fold's number: no data-parallel rank (a training sampler's replica) reaches it
+PREDICT_SEEDS_PER_BATCH = 1024        # predict(nodes=...) without the "evaluation" key: exact fields, batches of this many nodes
+
+
+def evaluation_replica(fold_number: int) -> int:
+    """The sampler replica of a fold's evaluation batches (DataFold.VALIDATION.value, DataFold.TEST.value, or PREDICT_FOLD for
+    predict(nodes=...)): with the batch's index in the fold as the draw, the random words of an evaluation batch are a function of
+    (seed, fold, batch index) alone, the same in every epoch, and never a training batch's (replica = the rank, below 2^30)."""
+    fold_number = int(fold_number)
+    if not 0 <= fold_number < EVALUATION_REPLICA:
+        raise ValueError("fold number out of range: %r" % (fold_number,))
+    return EVALUATION_REPLICA | fold_number
+
+
+PREDICT_FOLD = 3                      # (behind DataFold.TEST.value)
+
+
+def evaluation_seed_batches(fold_mask, seeds_per_batch: int) -> List[np.ndarray]:
+    """The seed lists of an evaluation epoch: the fold's nodes (mask != 0) in ascending id cut into runs of seeds_per_batch, the last one
+    possibly short; int32.  No shuffle: batch i holds the same seeds in every epoch."""
+    seeds_per_batch = int(seeds_per_batch)
+    if seeds_per_batch < 1:
+        raise ValueError("seeds_per_batch must be positive, got %r" % (seeds_per_batch,))
+    nodes = np.flatnonzero(np.asarray(fold_mask) != 0).astype(np.int32)
+    return [nodes[i:i + seeds_per_batch] for i in range(0, len(nodes), seeds_per_batch)]
+
+
+def check_prediction_nodes(nodes, num_nodes: int):
+    """predict(nodes=...): -> (the distinct ids ascending as int32, for every entry of `nodes` its position among them, `nodes` as an
+    int64 array), or a ValueError for anything that is not a non-empty one-dimensional int32 / int64 list of ids in [0, num_nodes)."""
+    if isinstance(nodes, (list, tuple)):
+        if not all(isinstance(n, (int, np.integer)) and not isinstance(n, bool) for n in nodes):
+            raise ValueError("nodes must be a list of integer node ids, got %r" % (nodes,))
+        nodes = np.asarray(nodes, dtype=np.int64)
+    if torch.is_tensor(nodes):
+        nodes = nodes.detach().cpu().numpy()
+    if not isinstance(nodes, np.ndarray) or nodes.dtype not in (np.dtype(np.int32), np.dtype(np.int64)):
+        raise ValueError("nodes must be an int32 or int64 array or a list of node ids, got %s"
+                         % (nodes.dtype if isinstance(nodes, np.ndarray) else type(nodes).__name__,))
+    if nodes.ndim != 1:
+        raise ValueError("nodes must be one-dimensional, got shape %r" % (nodes.shape,))
+    if len(nodes) == 0:
+        raise ValueError("nodes is empty: name at least one node")
+    if nodes.min() < 0 or nodes.max() >= num_nodes:
+        raise ValueError("nodes holds an id outside [0, %d)" % num_nodes)
+    distinct, inverse = np.unique(nodes, return_inverse=True)
+    return distinct.astype(np.int32), inverse.reshape(-1).astype(np.int64), nodes.astype(np.int64)
