@@ -1,6 +1,6 @@
 """ctypes binding of librelgnn.so (C ABI: include/relgnn.h, include/relgnn_dropout.h, include/relgnn_predict.h,
 include/relgnn_parallel.h, include/relgnn_sparse_features.h, include/relgnn_sampling.h, include/relgnn_sparse_subset.h,
-include/relgnn_sparse_update.h, include/relgnn_sparse_gradient.h, include/relgnn_layered_sampling.h).
+include/relgnn_sparse_update.h, include/relgnn_sparse_gradient.h, include/relgnn_layered_sampling.h, include/relgnn_subgraph.h).
 
 This is the ONLY compute backend of the package.  There is no CPU / eager-PyTorch fallback:
 if the HIP library is missing, or a tensor is not a float32/int32 CUDA(HIP) tensor, the
@@ -272,6 +272,20 @@ _SPARSE_GRADIENT_SIGNATURES = {
                                                      _c_i32, _ptr, _c_f32, _c_f32, _c_f32, _c_f32, _c_f32, _ptr]),
 }
 
+# include/relgnn_subgraph.h (random-walk node sets and their induced subgraphs: the citation task's subgraph batches): its own table too
+_SUBGRAPH_SIGNATURES = {
+    "relgnn_subgraph_supported": (ctypes.c_int, [_c_i64, _c_i32, _c_i64, _c_i32]),
+    "relgnn_subgraph_max_walk_length": (_c_i64, []),
+    "relgnn_subgraph_workspace_bytes": (ctypes.c_size_t, [_c_i64]),
+    "relgnn_subgraph_walk": (ctypes.c_int, [_ptr, _ptr, _c_i64, _c_i32, _ptr, _c_i64, _c_i32, _c_u32, _c_u32, _c_u32, _ptr, _ptr]),
+    "relgnn_subgraph_number": (ctypes.c_int, [_ptr, _ptr, _c_i64, _ptr, _c_i64, _ptr]),
+    "relgnn_subgraph_induced_count": (ctypes.c_int, [_ptr, _ptr, _c_i64, _c_i32, _ptr, _ptr, _c_i64, _ptr, _ptr, _ptr, _ptr, _ptr,
+                                                     ctypes.c_size_t, _ptr]),
+    "relgnn_subgraph_induced_emit": (ctypes.c_int, [_ptr, _ptr, _c_i64, _c_i32, _ptr, _c_i64, _c_i64, _ptr, _ptr, _c_i64, _ptr, _ptr,
+                                                    _ptr]),
+    "relgnn_subgraph_clear": (ctypes.c_int, [_ptr, _c_i64, _ptr, _c_i64, _ptr]),
+}
+
 _lib = None
 
 
@@ -292,7 +306,8 @@ def load_library():
     for name, (restype, argtypes) in list(_SIGNATURES.items()) + list(_DROPOUT_SIGNATURES.items()) + list(_PREDICT_SIGNATURES.items()) \
             + list(_PARALLEL_SIGNATURES.items()) + list(_SPARSE_FEATURES_SIGNATURES.items()) + list(_SAMPLING_SIGNATURES.items()) \
             + list(_SPARSE_SUBSET_SIGNATURES.items()) + list(_SPARSE_UPDATE_SIGNATURES.items()) \
-            + list(_SPARSE_GRADIENT_SIGNATURES.items()) + list(_LAYERED_SAMPLING_SIGNATURES.items()):
+            + list(_SPARSE_GRADIENT_SIGNATURES.items()) + list(_LAYERED_SAMPLING_SIGNATURES.items()) \
+            + list(_SUBGRAPH_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the symbol is not exported
         fn.restype = restype
         fn.argtypes = argtypes
@@ -349,6 +364,11 @@ def sparse_gradient_signatures():
 def layered_sampling_signatures():
     """The entry points of include/relgnn_layered_sampling.h (not part of exported_signatures() either)."""
     return dict(_LAYERED_SAMPLING_SIGNATURES)
+
+
+def subgraph_signatures():
+    """The entry points of include/relgnn_subgraph.h (not part of exported_signatures() either)."""
+    return dict(_SUBGRAPH_SIGNATURES)
 
 
 def status_string(code: int) -> str:

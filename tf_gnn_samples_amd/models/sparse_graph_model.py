@@ -494,9 +494,10 @@ class Sparse_Graph_Model(ABC):
         the reference's ThreadedIterator (:272); `native_batching: false` keeps the numpy iterator.  full_graph: the task's
         "evaluation" key is not consulted (predict(data) without nodes)."""
         native = self._native_batching()
-        if data_fold == DataFold.TRAIN and getattr(self.task, "sampled_batches", None) is not None:
-            # a single-graph task that trains on sampled subgraphs (tasks/neighbour_sampling.py): drawn on this model's device by
-            # either iterator, so no flattened or resident copy of the fold is built for them
+        if data_fold == DataFold.TRAIN and (getattr(self.task, "sampled_batches", None) is not None
+                                            or getattr(self.task, "subgraph_batches", None) is not None):
+            # a single-graph task that trains on sampled subgraphs (tasks/neighbour_sampling.py, tasks/subgraph_sampling.py): drawn on
+            # this model's device by either iterator, so no flattened or resident copy of the fold is built for them
             self.task.bind_sampling_device(self.device)
             native = False
         if data_fold != DataFold.TRAIN and not full_graph and getattr(self.task, "evaluation", None) is not None:

@@ -64,6 +64,18 @@ bit: every level graph brings its bucketing along and routes its hub buckets as 
 RelGraph and ONE feature table (_graph_state_of, keyed by the adjacency and feature objects the folds share); labels, mask and sampler are
 per fold.  predict(data, nodes=...) runs the same batches over the named nodes (the key's fanouts and B, or all-zero fanouts and 1024
 without it); predict(data) without nodes stays on the full graph.
+
+Task parameter `subgraph_batches` ({"roots_per_batch": R, "walk_length": h, "seed": s, "sparse_features": bool}, the last two optional;
+absent or None by default, read with params.get and kept in the checkpoint's metadata like its siblings; a ValueError together with
+`sampled_batches`): the TRAIN fold is cut into subgraphs instead of receptive fields.  An epoch is the same permutation of the fold's
+nodes cut into ceil(n_train / R) ROOT lists (epoch_seed_batches, unchanged); a walk of h steps against the edges starts at every root,
+and the batch is the subgraph INDUCED on the visited nodes (subgraph_sampling.SubgraphSampler, csrc/subgraph_sample.hip): every edge
+of the full graph between two of them, with the induced in-degrees.  Every layer runs on that one subgraph, so a step costs the same
+at any depth.  The loss mask is fold_mask[nodes]: every TRAIN node of the subgraph counts, not only the roots.  "sparse_features": true
+requires sparse_node_features (and the reverse), as for sampled_batches; the batch then carries SparseRows.take_rows(nodes).  The
+device RelGraph and the feature table are the ones the folds share (_graph_state_of).  VALIDATION, TEST, test() and predict() stay on
+the full graph; predict(nodes=...) runs exact receptive fields as it does without the parameter.  No GraphSAINT normalisation: the
+loss and the aggregation are the induced subgraph's.  GPU only; not together with capture_train_step or a process group.
 """
 import os
 import pickle
@@ -80,6 +92,7 @@ from ..parallel import refuse_single_graph_task
 from ..predict import predict_softmax
 from .neighbour_sampling import (PREDICT_FOLD, PREDICT_SEEDS_PER_BATCH, NeighbourSampler, check_prediction_nodes, epoch_seed_batches,
                                  evaluation_replica, evaluation_seed_batches, parse_sampled_batches)
+from .subgraph_sampling import SubgraphSampler, parse_subgraph_batches
 from .resident import ResidentDataset
 from .sparse_features import SparseRows, node_stand_in, random_rows, resident_copy
 from .sparse_graph_task import DataFold, MinibatchData, Sparse_Graph_Task
@@ -102,7 +115,7 @@ class _GraphState(NamedTuple):
 
 class _SamplingState(NamedTuple):
     """What the sampled batches of one fold on one device are cut from; `sampler.graph` and `features` are the _GraphState's."""
-    sampler: NeighbourSampler
+    sampler: Any                                           # a NeighbourSampler, or the SubgraphSampler of `subgraph_batches`
     features: Any                                          # float32 [V, F], or the device's SparseRows
     labels: torch.Tensor                                   # int32 [V]
     mask: torch.Tensor                                     # float32 [V], the fold's
@@ -263,7 +276,8 @@ class Citation_Network_Task(Sparse_Graph_Task):
         self._kept_evaluation = {}                                # (id of a fold's label array, device, fold number, route, fanouts, B) -> (weak reference, its batches)
         self._sampling_device = None                              # where the model runs (bind_sampling_device)
         self._sampling_epoch = self._sampling_draw = 0            # TRAIN epochs started / batches sampled so far
-        self.sampled_batches                                      # (a malformed parameter fails here, not in the first epoch)
+        self.subgraph_batches                                     # (a malformed parameter fails here, not in the first epoch)
+        self.sampled_batches
         self.__num_edge_types = 2
         self.__initial_node_feature_size = 0
         self.__num_output_classes = 0
@@ -296,6 +310,23 @@ class Citation_Network_Task(Sparse_Graph_Task):
         if sampled.get("sparse_features", False) and not self.sparse_node_features:
             raise ValueError("sampled_batches: \"sparse_features\": true requires the task parameter sparse_node_features: True")
         return sampled
+
+    @property
+    def subgraph_batches(self) -> Optional[Dict[str, Any]]:
+        """The validated `subgraph_batches` parameter, None when the TRAIN fold is not cut into random-walk subgraphs."""
+        subgraph = parse_subgraph_batches(self.params.get('subgraph_batches'))
+        if subgraph is None:
+            return None
+        if self.params.get('sampled_batches') is not None:
+            raise ValueError("subgraph_batches cannot be combined with sampled_batches: a TRAIN epoch is cut into induced subgraphs "
+                             "or into neighbour-sampled receptive fields, not both")
+        if self.sparse_node_features and not subgraph.get("sparse_features", False):
+            raise ValueError("subgraph_batches cannot be combined with sparse_node_features unless it says \"sparse_features\": true: "
+                             "the weight gradient of the sparse input projection over a row subset needs the transposed structure of "
+                             "that subset, which is then built per batch (SparseRows.take_rows)")
+        if subgraph.get("sparse_features", False) and not self.sparse_node_features:
+            raise ValueError("subgraph_batches: \"sparse_features\": true requires the task parameter sparse_node_features: True")
+        return subgraph
 
     @property
     def sparse_update(self) -> bool:
@@ -475,6 +506,9 @@ class Citation_Network_Task(Sparse_Graph_Task):
         if data_fold == DataFold.TRAIN and self.sampled_batches is not None:
             yield from self._sampled_batches_of(fold)
             return
+        if data_fold == DataFold.TRAIN and self.subgraph_batches is not None:
+            yield from self._subgraph_batches_of(fold)
+            return
         sparse = isinstance(fold.node_features, SparseRows)
         feed = {
             'initial_node_features': node_stand_in(len(fold.node_features)) if sparse else fold.node_features,
@@ -646,6 +680,31 @@ class Citation_Network_Task(Sparse_Graph_Task):
             yield state.sampler.sample(seeds, draw).device_batch(state.features, state.labels, state.mask, keep,
                                                                   named_rows=sampled.get("sparse_gradient", False))
 
+    def _subgraph_state_of(self, fold: CitationData, device) -> _SamplingState:
+        """The TRAIN fold's SubgraphSampler over the device RelGraph the folds share, with the fold's labels and mask."""
+        key = (id(fold.labels), str(device), "subgraph")
+        held = self._sampling_state.get(key)
+        if held is not None and held[0]() is fold.labels:
+            return held[1]
+        from_host = lambda a, dtype: torch.as_tensor(np.ascontiguousarray(a), dtype=dtype).to(device)
+        subgraph = self.subgraph_batches
+        shared = self._graph_state_of(fold, device)
+        state = _SamplingState(SubgraphSampler(shared.graph, subgraph["walk_length"], seed=subgraph["seed"]), shared.features,
+                               from_host(fold.labels, torch.int32), from_host(fold.mask, torch.float32))
+        self._sampling_state[key] = (weakref.ref(fold.labels, lambda _, key=key, table=self._sampling_state: table.pop(key, None)), state)
+        return state
+
+    def _subgraph_batches_of(self, fold: CitationData):
+        """ceil(n_train / R) subgraph batches: one TRAIN epoch.  Every train node is a root once; the loss mask is the fold's mask over
+        ALL nodes of the subgraph (seed_mask is ones)."""
+        subgraph = self.subgraph_batches
+        state = self._subgraph_state_of(fold, self._bound_device())
+        epoch, self._sampling_epoch = self._sampling_epoch, self._sampling_epoch + 1
+        keep = self._out_keep(DataFold.TRAIN)
+        for roots in epoch_seed_batches(fold.mask, subgraph["roots_per_batch"], subgraph["seed"], epoch):
+            draw, self._sampling_draw = self._sampling_draw, self._sampling_draw + 1
+            yield state.sampler.sample(roots, draw).device_batch(state.features, state.labels, state.mask, keep)
+
     def compute_initial_node_features(self, batch, weights):
         """The batch's feature table, or in the sparse mode the SparseRows on the batch's device: one copy per device, kept weakly
         with the host container."""
@@ -664,6 +723,9 @@ class Citation_Network_Task(Sparse_Graph_Task):
             raise ValueError("a citation-network fold is ONE graph; got %d" % batcher.store.num_graphs)
         if data_fold == DataFold.TRAIN and self.sampled_batches is not None:
             yield from self._sampled_batches_of(batcher.store.citation_fold)
+            return
+        if data_fold == DataFold.TRAIN and self.subgraph_batches is not None:
+            yield from self._subgraph_batches_of(batcher.store.citation_fold)
             return
         keep = self._out_keep(data_fold)
         batcher.constants['out_layer_dropout_keep_prob'] = keep

@@ -1,0 +1,180 @@
+"""Subgraph mini-batches of ONE graph (csrc/subgraph_sample.hip, include/relgnn_subgraph.h): a node set found by random walks from a
+root list, against the edges of the by-target bucketing the full graph's RelGraph already holds, and the node-induced subgraph over
+it as a SampledSubgraph.  Every layer of a model runs on that one subgraph, so a batch costs the same at any depth; a neighbour-sampled
+batch (tasks/neighbour_sampling.py) grows with every hop instead.
+
+Host round trips of SubgraphSampler.sample() and induced_subgraph(): the root (node) list is validated on the host (in range,
+distinct; one small copy of a device list), and the subgraph's sizes — n, the per-type edge counts and their total — are read back
+ONCE, because its tensors are sized by them.  The buffers in front of that read-back are sized from the bound min(V, R * (h + 1)).
+"""
+from typing import Dict, Optional
+
+import numpy as np
+import torch
+
+from .. import _lib
+from ..graph import RelGraph
+from .neighbour_sampling import SampledSubgraph
+
+# relgnn_subgraph_max_walk_length (the library is not loaded to validate a parameter; tests/test_gpu_subgraph_batches.py holds the
+# two against each other)
+MAX_WALK_LENGTH = 64
+
+
+def check_walk_length(walk_length) -> int:
+    """The walk length as a python int, or a ValueError that says what include/relgnn_subgraph.h supports."""
+    if isinstance(walk_length, bool) or not isinstance(walk_length, (int, np.integer)) or not 0 <= walk_length <= MAX_WALK_LENGTH:
+        raise ValueError("walk_length must be an integer in [0, %d] (0: the subgraph induced on the roots alone), got %r"
+                         % (MAX_WALK_LENGTH, walk_length))
+    return int(walk_length)
+
+
+def _validated(ids, num_nodes: int, device, what: str) -> torch.Tensor:
+    """`ids` (int32, one-dimensional, non-empty, in range, distinct) ascending on the device; NeighbourSampler._validated's rules."""
+    host = ids.detach().cpu().numpy() if torch.is_tensor(ids) else np.asarray(ids)
+    if host.ndim != 1 or host.dtype != np.int32:
+        raise ValueError("%ss must be a one-dimensional int32 array" % what)
+    if len(host) == 0:
+        raise ValueError("the %s list is empty" % what)
+    if host.min() < 0 or host.max() >= num_nodes:
+        raise ValueError("%s outside [0, %d)" % (what, num_nodes))
+    ordered = np.sort(host)
+    if (ordered[1:] == ordered[:-1]).any():
+        raise ValueError("the %s list names a node twice" % what)
+    if torch.is_tensor(ids) and ids.is_cuda and np.array_equal(ordered, host):
+        return ids.contiguous()
+    return torch.as_tensor(ordered, device=device)
+
+
+class _Extractor:
+    """The induced-edge path over one RelGraph and one [V] int32 stamp array, all zero between calls."""
+
+    def __init__(self, graph: RelGraph, what: str):
+        if not graph.rowptr_t.is_cuda:
+            raise _lib.RelGnnLibraryError("%s runs on the GPU only; the graph is on %s" % (what, graph.rowptr_t.device))
+        lib = _lib.load_library()
+        if not lib.relgnn_subgraph_supported(1, 0, graph.V, graph.L):
+            raise ValueError("%s does not support a graph of %d nodes and %d edge types (relgnn_subgraph_supported)"
+                             % (what, graph.V, graph.L))
+        graph.check()                                             # (node ids in range: the kernels trust col_t)
+        self.graph = graph
+        self.stamp = torch.zeros(graph.V, dtype=torch.int32, device=graph.device)
+        self._compact_bytes = lib.relgnn_neighbour_sample_workspace_bytes(graph.V)
+        self.trace = None            # a list collects (phase, timed event recorded behind it) of every call (scripts/bench_subgraph_batches.py)
+
+    def _mark(self, phase: str) -> None:
+        if self.trace is not None:
+            event = torch.cuda.Event(enable_timing=True)
+            event.record()
+            self.trace.append((phase, event))
+
+    def _run(self, stamp_the_set, node_bound: int) -> SampledSubgraph:
+        """stamp_the_set() enqueues what stamps the node set (at most node_bound nodes); everything behind it is the same."""
+        try:
+            with torch.cuda.device(self.graph.device):
+                return self._induced(stamp_the_set, int(node_bound))
+        except BaseException:
+            self.stamp.zero_()                                    # whatever a half-run call stamped
+            raise
+
+    def _induced(self, stamp_the_set, B: int) -> SampledSubgraph:
+        lib, g = _lib.load_library(), self.graph
+        V, L, dev = g.V, g.L, g.device
+        i32 = lambda n: torch.empty(int(n), dtype=torch.int32, device=dev)
+        self._mark("start")
+        stamp_the_set()
+        self._mark("walks")
+        summary = torch.zeros(L + 2, dtype=torch.int32, device=dev)       # [edges per type | edge total | n]: read back once
+        nodes_buf = i32(B)
+        ws = _lib.scratch(self._compact_bytes, dev)
+        _lib.launch("relgnn_neighbour_sample_compact", _lib.ptr(self.stamp), V, 0, _lib.ptr(nodes_buf), B, _lib.ptr(summary[L + 1:]),
+                    _lib.ptr(ws), self._compact_bytes)
+        _lib.launch("relgnn_subgraph_number", _lib.ptr(nodes_buf), _lib.ptr(summary[L + 1:]), B, _lib.ptr(self.stamp), V)
+        self._mark("node_list")
+        counts, offsets = i32(B * L + 1), i32(B * L + 1)
+        scan_bytes = lib.relgnn_subgraph_workspace_bytes(B * L + 1)
+        scan_ws = _lib.scratch(scan_bytes, dev)
+        _lib.launch("relgnn_subgraph_induced_count", _lib.ptr(g.rowptr_t), _lib.ptr(g.col_t), V, L, _lib.ptr(nodes_buf),
+                    _lib.ptr(summary[L + 1:]), B, _lib.ptr(self.stamp), _lib.ptr(counts), _lib.ptr(offsets), _lib.ptr(summary[:L + 1]),
+                    _lib.ptr(scan_ws), scan_bytes)
+        self._mark("induced_count")
+        sizes = summary.tolist()                                  # the one read-back of a call
+        self._mark("readback")
+        type_edges, total, n = sizes[:L], sizes[L], sizes[L + 1]
+        nodes = nodes_buf[:n]
+        edges = torch.empty((total, 2), dtype=torch.int32, device=dev)
+        degrees = torch.empty((L, n), dtype=torch.float32, device=dev)
+        _lib.launch("relgnn_subgraph_induced_emit", _lib.ptr(g.rowptr_t), _lib.ptr(g.col_t), V, L, _lib.ptr(nodes_buf), n, B,
+                    _lib.ptr(self.stamp), _lib.ptr(offsets), total, _lib.ptr(edges) if total else None, _lib.ptr(degrees))
+        _lib.launch("relgnn_subgraph_clear", _lib.ptr(nodes_buf), n, _lib.ptr(self.stamp), V)
+        self._mark("induced_emit")
+        adjacency, first = [], 0
+        for e in type_edges:                                      # the types' lists lie one behind the other: views, no copy
+            adjacency.append(edges[first:first + e])
+            first += e
+        seed_mask = torch.ones(n, dtype=torch.float32, device=dev)        # every node of the subgraph may count in the loss
+        return SampledSubgraph(nodes, adjacency, degrees, seed_mask, n, total)
+
+
+class SubgraphSampler(_Extractor):
+    """Random-walk subgraph sampler over one RelGraph (its rowptr_t / col_t are read in place).  Holds the [V] int32 stamp array, all
+    zero between calls (and after a call that raised)."""
+
+    def __init__(self, graph: RelGraph, walk_length: int, seed: int = 0, replica: int = 0):
+        self.walk_length = check_walk_length(walk_length)
+        if not 0 <= int(replica) < 2 ** 31:
+            raise ValueError("replica must be in [0, 2^31), got %r" % (replica,))
+        super().__init__(graph, "subgraph sampling")
+        self.seed, self.replica = int(seed) & 0xffffffff, int(replica)
+
+    def sample(self, roots, draw: int) -> SampledSubgraph:
+        """roots: int32 device tensor (a host array is uploaded), distinct node ids, one walk each; draw: the count of sampled batches
+        so far.  -> the subgraph induced on the nodes the walks visit, seed_mask all ones."""
+        g = self.graph
+        roots = _validated(roots, g.V, g.device, "root")
+        R, draw = int(roots.numel()), int(draw) & 0xffffffff
+
+        def walks():
+            _lib.launch("relgnn_subgraph_walk", _lib.ptr(g.rowptr_t), _lib.ptr(g.col_t), g.V, g.L, _lib.ptr(roots), R, self.walk_length,
+                        draw, self.seed, self.replica, _lib.ptr(self.stamp))
+        return self._run(walks, min(g.V, R * (self.walk_length + 1)))
+
+
+def induced_subgraph(graph: RelGraph, nodes) -> SampledSubgraph:
+    """The subgraph of `graph` induced on a node set the caller brings (a partition, say): int32 ids, distinct, any order.  The
+    induced-edge path of SubgraphSampler.sample without the walks; one read-back."""
+    extractor = _Extractor(graph, "induced_subgraph")
+    nodes = _validated(nodes, graph.V, graph.device, "node")
+
+    def given():
+        _lib.launch("relgnn_neighbour_sample_begin", _lib.ptr(nodes), nodes.numel(), _lib.ptr(extractor.stamp), graph.V)
+    return extractor._run(given, int(nodes.numel()))
+
+
+def parse_subgraph_batches(value) -> Optional[Dict]:
+    """The task parameter `subgraph_batches` as {"roots_per_batch": int, "walk_length": int, "seed": int}, None when it is absent;
+    the optional key "sparse_features" (a bool: the batches take their feature rows from a SparseRows) is carried only when given."""
+    if value is None:
+        return None
+    known = {"roots_per_batch", "walk_length", "seed", "sparse_features"}
+    unknown = sorted(set(value) - known, key=str) if isinstance(value, dict) else []
+    if not isinstance(value, dict) or unknown or not {"roots_per_batch", "walk_length"} <= set(value):
+        said = "; unknown key %s" % ", ".join(repr(k) for k in unknown) if unknown else ""
+        raise ValueError('subgraph_batches must be {"roots_per_batch": R, "walk_length": h, "seed": s, "sparse_features": bool}, the last '
+                         'two optional%s, got %r' % (said, value))
+    per_batch = value["roots_per_batch"]
+    if isinstance(per_batch, bool) or not isinstance(per_batch, (int, np.integer)) or per_batch < 1:
+        raise ValueError("subgraph_batches: roots_per_batch must be a positive integer, got %r" % (per_batch,))
+    try:
+        walk_length = check_walk_length(value["walk_length"])
+    except ValueError as error:
+        raise ValueError("subgraph_batches: %s" % error) from None
+    seed = value.get("seed", 0)
+    if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)):
+        raise ValueError("subgraph_batches: seed must be an integer, got %r" % (seed,))
+    parsed = {"roots_per_batch": int(per_batch), "walk_length": walk_length, "seed": int(seed)}
+    if "sparse_features" in value:
+        if not isinstance(value["sparse_features"], bool):
+            raise ValueError("subgraph_batches: sparse_features must be true or false, got %r" % (value["sparse_features"],))
+        parsed["sparse_features"] = value["sparse_features"]
+    return parsed
