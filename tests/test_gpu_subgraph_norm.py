@@ -1,0 +1,583 @@
+"""GraphSAINT normalisation of the subgraph batches on the GPU (csrc/subgraph_sample.hip: visit counts and the weighted emit;
+csrc/train_utils.hip: the weighted loss pair; include/relgnn_subgraph_norm.h): the counts and the per-edge weights against
+tests/subgraph_norm_reference.py array for array, the loss pair against float64 and against the unweighted pair's bits, the loss estimator
+over the replayed pre-sampled subgraphs, a per-message scale through the layers' reduction routes against a float64 restatement, and
+train() with the key."""
+import pickle
+import sys
+from pathlib import Path
+
+import numpy as np
+import pytest
+import torch
+
+HERE = Path(__file__).resolve().parent
+if str(HERE) not in sys.path:
+    sys.path.insert(0, str(HERE))
+
+import subgraph_norm_reference as N  # noqa: E402
+from helpers import glorot, layer_norm_weights, rgcn_weights, set_switch  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+
+V, L = N.V, N.L
+R, H, SEED = 16, 3, 5
+_REFERENCE = {}
+
+
+def reference_counts(which, epochs):
+    """(node sets, node_visits, edge_visits) of the reference, computed once and left unchanged."""
+    if (which, epochs) not in _REFERENCE:
+        _, (rowptr, col, _), mask = N.norm_graph(which)
+        sets = N.presampled_node_sets(rowptr, col, V, L, mask, R, H, SEED, epochs)
+        _REFERENCE[(which, epochs)] = (sets,) + N.visit_counts(rowptr, col, V, L, sets)
+    return _REFERENCE[(which, epochs)]
+
+
+def device_graph(which, device):
+    from tf_gnn_samples_amd.graph import RelGraph
+    adjacency, (rowptr, col, _), _ = N.norm_graph(which)
+    g = RelGraph([torch.as_tensor(a, device=device) for a in adjacency], V)
+    assert np.array_equal(g.rowptr_t.cpu().numpy(), rowptr) and np.array_equal(g.col_t.cpu().numpy(), col)
+    return g
+
+
+def bits(t):
+    return (t.detach().cpu().numpy() if torch.is_tensor(t) else np.asarray(t)).view(np.uint32)
+
+
+# ---- 1. the counts --------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("epochs", [1, 3])
+@pytest.mark.parametrize("which", ["bucket", "walk"])
+def test_visit_counts_equal_the_reference_and_nothing_is_read_back(gpu_device, monkeypatch, which, epochs):
+    from tf_gnn_samples_amd.tasks.subgraph_sampling import SubgraphSampler
+    mask = N.norm_graph(which)[2]
+    sets, node_visits, edge_visits = reference_counts(which, epochs)
+    sampler = SubgraphSampler(device_graph(which, gpu_device), H, seed=SEED)         # (the graph is checked here, once per graph)
+    reads = []
+    for name in ("tolist", "item", "cpu", "numpy"):
+        original = getattr(torch.Tensor, name)
+
+        def counting(self, *args, _name=name, _original=original, **kwargs):
+            if self.is_cuda:
+                reads.append((_name, tuple(self.shape)))
+            return _original(self, *args, **kwargs)
+        monkeypatch.setattr(torch.Tensor, name, counting)
+    counts = sampler.presample(mask, R, epochs)
+    assert reads == [], reads                                                         # no device-to-host copy in the whole loop
+    monkeypatch.undo()
+    assert counts.num_subgraphs == len(sets) == epochs * 8
+    assert counts.node_visits.dtype == counts.edge_visits.dtype == torch.int32
+    assert np.array_equal(counts.node_visits.cpu().numpy(), node_visits)
+    assert np.array_equal(counts.edge_visits.cpu().numpy(), edge_visits)
+    assert not sampler.stamp.any()                                                    # all zero afterwards
+    if epochs == 1:
+        side = torch.cuda.Stream(device=gpu_device)
+        side.wait_stream(torch.cuda.current_stream(gpu_device))
+        with torch.cuda.stream(side):
+            again = sampler.presample(mask, R, epochs)
+            side.synchronize()
+            assert torch.equal(again.node_visits, counts.node_visits) and torch.equal(again.edge_visits, counts.edge_visits)
+            assert not sampler.stamp.any()
+        torch.cuda.current_stream(gpu_device).wait_stream(side)
+    # node weights: N / max(C_v, 1) in float32
+    some = torch.arange(0, V, 3, dtype=torch.int32, device=gpu_device)
+    want = N.node_weights(node_visits, some.cpu().numpy(), len(sets))
+    assert np.array_equal(bits(counts.node_weights(some)), want.view(np.uint32))
+
+
+# ---- 2. the weighted emit -------------------------------------------------------------------------------------------------------------
+def _counts_on(device, which, epochs=1):
+    from tf_gnn_samples_amd.tasks.subgraph_sampling import VisitCounts
+    sets, node_visits, edge_visits = reference_counts(which, epochs)
+    return VisitCounts(torch.as_tensor(node_visits, device=device), torch.as_tensor(edge_visits, device=device), len(sets))
+
+
+def _root_lists(which):
+    """(walk length, roots, draw): the whole graph (every bucket whole, the hub's 5 000 entries too), the hub's neighbourhood, the first
+    two training batches."""
+    mask = N.norm_graph(which)[2]
+    train = N.seed_batches(mask, R, SEED, 0)
+    with_hub = np.union1d(train[0], np.arange(len(N.LENGTHS))).astype(np.int32)
+    return [(0, np.arange(V, dtype=np.int32), 0), (H, with_hub, 5), (H, train[0], 0), (H, train[1], 1)]
+
+
+@pytest.mark.parametrize("which", ["bucket", "walk"])
+def test_weighted_emit_writes_the_unweighted_lists_and_the_reference_s_weights(gpu_device, which):
+    from tf_gnn_samples_amd.tasks.subgraph_sampling import SubgraphSampler
+    _, (rowptr, col, _), _ = N.norm_graph(which)
+    _, node_visits, edge_visits = reference_counts(which, 1)
+    g = device_graph(which, gpu_device)
+    counts = _counts_on(gpu_device, which)
+    samplers = {0: SubgraphSampler(g, 0, seed=SEED), H: SubgraphSampler(g, H, seed=SEED)}
+    seen = {"unseen entry": 0, "clipped": 0, "hub": 0}
+    for h, roots, draw in _root_lists(which):
+        plain = samplers[h].sample(roots, draw)
+        assert plain.message_weights is None
+        nodes = plain.nodes.cpu().numpy()
+        assert np.array_equal(nodes, N.S.walk_nodes(rowptr, col, V, L, roots, h, draw, SEED, 0))
+        at = np.concatenate(N.kept_positions(rowptr, col, V, L, nodes))
+        for cap in (1e4, 2.0):
+            sub = samplers[h].sample(roots, draw, (counts, cap))
+            assert sub.num_nodes == plain.num_nodes and sub.num_edges == plain.num_edges == len(at) and torch.equal(sub.nodes, plain.nodes)
+            for a, b in zip(sub.adjacency_lists, plain.adjacency_lists):
+                assert a.dtype == torch.int32 and torch.equal(a, b)
+            assert np.array_equal(bits(sub.type_to_num_incoming_edges), bits(plain.type_to_num_incoming_edges))      # the INDUCED degrees
+            want = N.edge_weights(rowptr, col, V, L, nodes, node_visits, edge_visits, cap)
+            got = sub.message_weights
+            assert got.dtype == torch.float32 and tuple(got.shape) == (len(at),)
+            assert np.array_equal(bits(got), want.view(np.uint32)), (which, h, draw, cap)
+            assert not samplers[h].stamp.any()
+        ratio = np.maximum(node_visits[N._positions(rowptr, col, V, L)[0][at]], 1) / np.maximum(edge_visits[at], 1)
+        seen["unseen entry"] += int((edge_visits[at] == 0).sum())
+        seen["clipped"] += int((ratio > 2).sum())
+        if which == "bucket":
+            hub = (at >= rowptr[N.HUB * L]) & (at < rowptr[N.HUB * L + 1])
+            seen["hub"] += int(hub.sum())
+    print(which, seen)
+    assert seen["unseen entry"] > 0 and seen["clipped"] > 0 and (which != "bucket" or seen["hub"] > 5000)
+
+
+# ---- 3. the weighted loss pair --------------------------------------------------------------------------------------------------------
+def _loss_case(rows, cols, seed):
+    rng = np.random.default_rng(seed)
+    x = (rng.standard_normal((rows, cols)) * 3).astype(np.float32)
+    labels = rng.integers(0, cols, size=rows)
+    mask = (rng.random(rows) < 0.6).astype(np.float32)
+    weights = (2.0 ** rng.integers(-10, 11, size=rows)).astype(np.float32)
+    if rows:
+        mask[0] = 1.0
+        weights[0] = 2.0 ** 10
+        for r in range(0, rows, 5):                                     # a -inf column that is not the label's
+            x[r, (labels[r] + 1 + r % (cols - 1)) % cols if cols > 1 else 0] = -np.inf
+    if rows > 1:
+        mask[1], weights[1] = 0.0, 2.0 ** -10
+    return x, labels, mask, weights
+
+
+def _run_weighted(x, labels, mask, weights, denominator, device, ld=None):
+    from tf_gnn_samples_amd.tasks.citation_network_task import softmax_ce_weighted_stats
+    rows, cols = x.shape
+    ld = ld or cols
+    base = torch.full((rows, ld), float("nan"), device=device)              # whatever sits behind a row must not be read
+    base[:, :cols] = torch.as_tensor(x, device=device)
+    logits = base[:, :cols].requires_grad_(True)
+    out = softmax_ce_weighted_stats(logits, torch.as_tensor(labels.astype(np.int32), device=device), torch.as_tensor(mask, device=device),
+                                    torch.as_tensor(weights, device=device), denominator)
+    return logits, out
+
+
+@pytest.mark.parametrize("cols", [7, 16])
+@pytest.mark.parametrize("rows", [0, 1, 300])
+def test_weighted_loss_pair_against_float64(gpu_device, rows, cols):
+    """The existing pair's bars (tests/test_gpu_citation.py: 1e-5 relative on the total, 1e-5 on a gradient element whose scale is 1),
+    applied to sum mask * w * |loss| and, per gradient row, to mask * w * |g_total + g_loss / denominator|."""
+    from tf_gnn_samples_amd import _lib, config
+    x, labels, mask, weights = _loss_case(rows, cols, rows * 100 + cols)
+    denominator = 37.0
+    want, scale = N.weighted_stats(x, labels, mask, weights, denominator)
+    results = []
+    for ld in (cols, cols + 3):
+        _, (loss, total, accuracy, counts) = _run_weighted(x, labels, mask, weights, denominator, gpu_device, ld)
+        got = torch.stack([counts[0], counts[1], counts[2], loss, accuracy]).detach().cpu().numpy()
+        results.append(got)
+        print("rows %d cols %d ld %d: total %.9g (want %.9g, scale %.6g) loss %.9g (want %.9g)" % (rows, cols, ld, got[0], want[0], scale, got[3], want[3]))
+        assert float(total.detach()) == got[0] and got[1] == np.float32(want[1]) and got[2] == np.float32(want[2])       # the unweighted counts, exactly
+        assert abs(float(got[0]) - want[0]) <= 1e-5 * scale
+        assert abs(float(got[3]) - want[3]) <= 1e-5 * scale / denominator
+        assert (np.isnan(got[4]) and want[1] == 0) or got[4] == np.float32(want[2]) / np.float32(want[1])
+    assert np.array_equal(results[0].view(np.uint32), results[1].view(np.uint32))                                  # the same bits on every run
+    if rows == 0:
+        return
+    for pad in ("0", "1"):
+        for g_loss, g_total in ((1.0, 0.0), (0.0, 1.0), (0.7, -0.25)):
+            with config.override(head_pad=pad):
+                logits, (loss, total, accuracy, counts) = _run_weighted(x, labels, mask, weights, denominator, gpu_device)
+                assert not accuracy.requires_grad and not counts.requires_grad
+                (loss * g_loss + total * g_total if g_loss and g_total else (loss * g_loss if g_loss else total * g_total)).backward()
+            got = logits.grad.cpu().numpy()
+            ref = N.weighted_gradient(x, labels, mask, weights, denominator, g_loss, g_total)
+            bar = 1e-5 * (mask * weights).astype(np.float64)[:, None] * abs(g_total + g_loss / denominator)
+            assert (np.abs(got - ref) <= bar).all(), float((np.abs(got - ref) - bar).max())
+            assert not got[mask == 0].any()                             # masked-out rows: exactly zero
+    # the kernel itself into rows of the next multiple of 16 floats: zeros behind the classes, zeros in masked-out rows whatever they hold
+    lib = _lib.load_library()
+    ldg = (cols + 15) // 16 * 16 + 16
+    xd = torch.as_tensor(x, device=gpu_device)
+    xd[torch.as_tensor(mask == 0, device=gpu_device)] = float("inf")
+    out = torch.full((rows, ldg), float("nan"), device=gpu_device)
+    g = torch.tensor([0.5], device=gpu_device)
+    dev = lambda a, dtype: torch.as_tensor(a.astype(dtype), device=gpu_device)
+    ld_, md, wd = dev(labels, np.int32), dev(mask, np.float32), dev(weights, np.float32)
+    _lib.check(lib.relgnn_softmax_ce_weighted_bwd(xd.data_ptr(), cols, ld_.data_ptr(), md.data_ptr(), wd.data_ptr(), denominator, rows, cols,
+                                                  g.data_ptr(), None, out.data_ptr(), ldg, _lib.current_stream()), "relgnn_softmax_ce_weighted_bwd")
+    out = out.cpu().numpy()
+    assert not out[:, cols:].any() and not np.isnan(out).any() and not out[mask == 0].any()
+    keep = mask != 0
+    ref = N.weighted_gradient(x[keep], labels[keep], mask[keep], weights[keep], denominator, 0.5, 0.0)
+    assert (np.abs(out[keep][:, :cols] - ref) <= 1e-5 * weights[keep].astype(np.float64)[:, None] * 0.5 / denominator).all()
+
+
+@pytest.mark.parametrize("cols", [7, 16, 200])
+@pytest.mark.parametrize("rows", [1, 300, 4099])
+def test_unit_weights_and_the_mask_sum_give_the_existing_pair_s_bits(gpu_device, rows, cols):
+    from tf_gnn_samples_amd import config
+    from tf_gnn_samples_amd.tasks.citation_network_task import softmax_ce_stats
+    x, labels, mask, _ = _loss_case(rows, cols, rows + cols)
+    ones = np.ones(rows, np.float32)
+    ld, md = torch.as_tensor(labels.astype(np.int32), device=gpu_device), torch.as_tensor(mask, device=gpu_device)
+    for pad in ("0", "1"):
+        with config.override(head_pad=pad):
+            plain = torch.as_tensor(x, device=gpu_device).requires_grad_(True)
+            loss_p, total_p, accuracy_p, counts_p = softmax_ce_stats(plain, ld, md)
+            denominator = float(counts_p[1])
+            logits, (loss, total, accuracy, counts) = _run_weighted(x, labels, mask, ones, denominator, gpu_device)
+            for a, b in ((loss, loss_p), (total, total_p), (accuracy, accuracy_p), (counts, counts_p)):
+                assert np.array_equal(bits(a), bits(b))
+            (loss_p * 0.7 - total_p * 0.25).backward()
+            (loss * 0.7 - total * 0.25).backward()
+        assert np.array_equal(bits(logits.grad), bits(plain.grad)), (rows, cols, pad)
+
+
+# ---- 4. the loss estimator over the replayed pre-sampled subgraphs ----------------------------------------------------------------------
+@pytest.mark.parametrize("which", ["bucket", "walk"])
+def test_the_weighted_head_averages_to_the_fold_s_mean_loss_and_the_plain_head_does_not(gpu_device, which):
+    """Fixed full-graph logits (tests/test_subgraph_norm_cpu.py shows on the reference that these inputs separate the two heads):
+    sum_b stats[3] / N within 1e-5 relative of the float64 masked mean loss, the head's own bar; the unweighted head over the same batches
+    further than ten times that."""
+    from tf_gnn_samples_amd.tasks.citation_network_task import softmax_ce_stats, softmax_ce_weighted_stats
+    from test_subgraph_norm_cpu import fixed_logits
+    mask = N.norm_graph(which)[2]
+    sets, node_visits, _ = reference_counts(which, 2)
+    counts = _counts_on(gpu_device, which, 2)
+    x, labels = fixed_logits(which)
+    n_train = float(mask.sum())
+    full = float((N.row_losses(x, labels) * mask).sum() / n_train)
+    xd, ld, md = (torch.as_tensor(a, device=gpu_device) for a in (x, labels.astype(np.int32), mask))
+    weighted = plain = 0.0
+    for s in sets:
+        at = torch.as_tensor(s, device=gpu_device)
+        rows = (xd.index_select(0, at.long()), ld.index_select(0, at.long()), md.index_select(0, at.long()))
+        weighted += float(softmax_ce_weighted_stats(*rows, counts.node_weights(at), n_train)[0]) / len(sets)
+        plain += float(softmax_ce_stats(*rows)[0]) / len(sets)
+    bar = 1e-5 * full
+    print("%s: full %.9g weighted %.9g plain %.9g bar %.3g" % (which, full, weighted, plain, bar))
+    assert abs(weighted - full) <= bar
+    assert abs(plain - full) > 10 * bar
+
+
+# ---- 5. a per-message scale through the layers --------------------------------------------------------------------------------------------
+def _weighted_batch(device, kind):
+    """A weighted batch of the bucket graph as the task builds it: "all" holds every node (the hub's bucket whole: 5 000 entries, beyond
+    the 4 096 at which a bucket is split over several waves), "walk" the hub's neighbourhood.  The counts are those of three
+    pre-sampling epochs and the clip is 4: the hub's bucket then holds the factors 1, 5/4, 5/3, 5/2 and 4, and a bucket's weights add up
+    to at most four times the degree scale's, so that the states stay O(1), where the suite's absolute bars on these layers were set
+    (helpers.assert_parity: sums bounded by construction)."""
+    from tf_gnn_samples_amd.tasks.subgraph_sampling import SubgraphSampler
+    h, roots, draw = _root_lists("bucket")[0 if kind == "all" else 1]
+    sub = SubgraphSampler(device_graph("bucket", device), h, seed=SEED).sample(roots, draw, (_counts_on(device, "bucket", 3), 4.0))
+    n = sub.num_nodes
+    batch = sub.device_batch(torch.zeros((V, 4), device=device), torch.zeros(V, dtype=torch.int32, device=device), torch.ones(V, device=device))
+    assert batch.graph is not None and not batch.graph.has_long_buckets               # as the graph the model buckets itself
+    if kind == "all":                                                                  # the hub's bucket through the split plans
+        assert batch.graph.split_long_segments() and batch.graph.has_long_buckets
+    return sub, batch, n
+
+
+def _reference_layers(name, h, weights, adjacency, w_edges, D):
+    """Two layers in float64 torch with one scale per message (the package's layers: scale the message, sum by target)."""
+    from oracle.tf_ops import layer_norm_scope
+    src = torch.cat([a[:, 0] for a in adjacency]).long()
+    tgt = torch.cat([a[:, 1] for a in adjacency]).long()
+    first = np.cumsum([0] + [len(a) for a in adjacency])
+    gelu = lambda x: x * (0.5 * (1.0 + torch.erf(x / np.sqrt(2.0))))
+
+    def norm(x, gamma, beta):
+        mean = x.mean(-1, keepdim=True)
+        inv = torch.rsqrt(((x - mean) ** 2).mean(-1, keepdim=True) + 1e-12) * gamma
+        return x * inv + (beta - mean * inv)
+    cur = h
+    for layer in range(2):
+        w = {k[len("%d/" % layer):]: v for k, v in weights.items() if k.startswith("%d/" % layer)}
+        msgs = []
+        for l in range(len(adjacency)):
+            s, t, scale = src[first[l]:first[l + 1]], tgt[first[l]:first[l + 1]], w_edges[first[l]:first[l + 1], None]
+            if name == "rgcn":
+                msgs.append(scale * (cur.index_select(0, s) @ w["Edge_%i_Weight/kernel" % l]))
+            elif name == "film":
+                m = scale * (cur.index_select(0, s) @ w["Edge_%i_Weight/kernel" % l])
+                film = (cur @ w["Edge_%i_FiLM_Computations/kernel" % l]).index_select(0, t)
+                msgs.append(torch.relu(film[:, :D] * m + film[:, D:]))
+            elif name == "edge_mlp0":
+                x = torch.cat([cur.index_select(0, s), cur.index_select(0, t)], 1)
+                msgs.append(torch.nn.functional.elu(scale * (x @ w["Edge_%i_MLP/dense/kernel" % l])))
+            else:
+                x = torch.cat([cur.index_select(0, s), cur.index_select(0, t)], 1)
+                m = torch.nn.functional.elu(x @ w["Edge_%i_MLP/dense/kernel" % l]) @ w["Edge_%i_MLP/dense_1/kernel" % l]
+                msgs.append(gelu(scale * m))
+        new = torch.zeros((cur.shape[0], D), dtype=cur.dtype).index_add(0, tgt, torch.cat(msgs, 0))
+        cur = torch.tanh(new) if name == "rgcn" else norm(new, w[layer_norm_scope(0) + "/gamma"], w[layer_norm_scope(0) + "/beta"])
+    return cur
+
+
+def _package_layers(name, h, weights, graph, degrees, D):
+    from tf_gnn_samples_amd import gnns
+    cur = h
+    for layer in range(2):
+        w = {k[len("%d/" % layer):]: v for k, v in weights.items() if k.startswith("%d/" % layer)}
+        if name == "rgcn":
+            cur = gnns.sparse_rgcn_layer(cur, graph, degrees, D, 1, "tanh", "sum", True, weights=w)
+        elif name == "film":
+            cur = gnns.sparse_gnn_film_layer(cur, graph, degrees, D, 1, "ReLU", "sum", True, weights=w)
+        elif name == "edge_mlp0":
+            cur = gnns.sparse_gnn_edge_mlp_layer(cur, graph, degrees, D, 1, "elu", "sum", True, True, 0, weights=w)
+        else:
+            cur = gnns.sparse_gnn_edge_mlp_layer(cur, graph, degrees, D, 1, "gelu", "sum", True, True, 1, weights=w)
+    return cur
+
+
+def _layer_weights(name, rng, D):
+    weights = {}
+    for layer in range(2):
+        w = dict(rgcn_weights(rng, L, D, D)) if name in ("rgcn", "film") else {}
+        if name != "rgcn":
+            w.update(layer_norm_weights(D, 1, rng))
+        for l in range(L):
+            if name == "film":
+                w["Edge_%i_FiLM_Computations/kernel" % l] = glorot(rng, (D, 2 * D))
+            if name in ("edge_mlp", "edge_mlp0"):
+                w["Edge_%i_MLP/dense/kernel" % l] = glorot(rng, (2 * D, D))
+            if name == "edge_mlp":
+                w["Edge_%i_MLP/dense_1/kernel" % l] = glorot(rng, (D, D))
+        weights.update({"%d/%s" % (layer, k): v for k, v in w.items()})
+    return weights
+
+
+ROUTES = [("rgcn", "aggregate_first", {"RELGNN_RGCN_ORDER": "aggregate_first"}, 32),
+          ("rgcn", "transform_first", {"RELGNN_RGCN_ORDER": "transform_first"}, 32),
+          ("rgcn", "pair_tables", {"RELGNN_PAIR_TABLES": "1"}, 32),
+          ("rgcn", "rgcn_fused", {"RELGNN_RGCN_ORDER": "aggregate_first", "RELGNN_RGCN_FUSED": "1"}, 256),
+          ("film", "pair kernel", {}, 32), ("film", "regather", {"RELGNN_EDGE_BWD": "regather"}, 32),
+          ("edge_mlp0", "pair kernel", {}, 32), ("edge_mlp0", "regather", {"RELGNN_EDGE_BWD": "regather"}, 32),
+          ("edge_mlp", "materialize", {}, 32), ("edge_mlp", "fused", {"RELGNN_EDGE_MLP": "fused"}, 128)]
+
+
+@pytest.mark.parametrize("kind", ["all", "walk"])
+@pytest.mark.parametrize("name, route, switches, D", ROUTES, ids=["%s-%s" % (r[0], r[1].replace(" ", "_")) for r in ROUTES])
+def test_a_scale_that_varies_inside_a_bucket_reaches_every_reduction_route(gpu_device, monkeypatch, name, route, switches, D, kind):
+    """Two layers on a weighted batch against float64 with the same per-edge weights: the output and every variable's gradient.  The bars
+    are the ones tests/test_gpu_layers.py holds these layers to against float64 (1e-5 for RGCN, 2e-5 for GNN-FiLM and GNN-Edge-MLP, on the
+    output relative to max(1, max|reference|), four times that on a gradient): a comparison with float64 cannot be bit for bit, and the
+    weights change the scale of a message, not the number or the order of the sums."""
+    from tf_gnn_samples_amd.graph import clear_graph_cache
+    for k, v in switches.items():
+        set_switch(monkeypatch, k, v)
+    clear_graph_cache()
+    sub, batch, n = _weighted_batch(gpu_device, kind)
+    graph, degrees = batch.graph, batch.type_to_num_incoming_edges
+    w_t = graph.degree_scale(degrees)
+    w_list = sub.message_weights
+    assert torch.equal(w_t, w_list.index_select(0, graph.perm_t.long())) and torch.equal(graph.w_original_order(w_t), w_list)
+    hub = int(np.searchsorted(sub.nodes.cpu().numpy(), N.HUB))
+    in_hub = w_list[:int(sub.adjacency_lists[0].shape[0])][sub.adjacency_lists[0][:, 1] == hub]
+    assert in_hub.numel() > 64 and in_hub.unique().numel() > 2 and float(in_hub.min()) > 0     # not one scale per bucket
+    rng = np.random.default_rng(D)
+    h = np.tanh(rng.standard_normal((n, D))).astype(np.float32)
+    weights = _layer_weights(name, rng, D)
+    tol = 1e-5 if name == "rgcn" else 2e-5
+    hd = torch.as_tensor(h, device=gpu_device).requires_grad_(True)
+    wd = {k: torch.as_tensor(v, device=gpu_device).requires_grad_(True) for k, v in weights.items()}
+    out = _package_layers(name, hd, wd, graph, degrees, D)
+    gout = np.random.default_rng(0).standard_normal(tuple(out.shape)).astype(np.float32)
+    out.backward(torch.as_tensor(gout, device=gpu_device))
+    from tf_gnn_samples_amd import ops
+    ops.join_deferred()
+    hr = torch.as_tensor(h, dtype=torch.float64).requires_grad_(True)
+    wr = {k: torch.as_tensor(v, dtype=torch.float64).requires_grad_(True) for k, v in weights.items()}
+    ref = _reference_layers(name, hr, wr, [a.cpu() for a in sub.adjacency_lists], w_list.cpu().double(), D)
+    ref.backward(torch.as_tensor(gout, dtype=torch.float64))
+    scale = max(1.0, float(ref.detach().abs().max()))
+    err = float(np.abs(out.detach().cpu().numpy() - ref.detach().numpy()).max())
+    print("%s %s %s: output error %.3g (scale %.3g)" % (name, route, kind, err, scale))
+    assert err <= tol * scale
+    for key, a, b in [("h", hd.grad, hr.grad)] + [(k, wd[k].grad, wr[k].grad) for k in weights]:
+        assert (a is None) == (b is None), key
+        if b is not None:
+            scale = max(1.0, float(b.abs().max()))
+            err = float(np.abs(a.cpu().numpy() - b.numpy()).max())
+            assert err <= 4 * tol * scale, (key, err, scale)
+
+
+@pytest.mark.parametrize("model_name, params", [("RGCN_Model", {}), ("GNN_FiLM_Model", {"normalize_messages_by_num_incoming": True})])
+@pytest.mark.parametrize("kind", ["all", "walk"])
+def test_the_induced_scale_preset_gives_the_bits_of_the_batch_without_a_preset(gpu_device, model_name, params, kind):
+    """message_weights = 1 / (induced in-degree + 1e-7), the degree scale's own expression: the batch that brings its graph and a preset
+    scale gives the metrics and every gradient of the batch the model buckets itself, bit for bit."""
+    from tf_gnn_samples_amd import models
+    from tf_gnn_samples_amd.graph import clear_graph_cache
+    from tf_gnn_samples_amd.tasks import Citation_Network_Task
+    from tf_gnn_samples_amd.tasks.subgraph_sampling import SubgraphSampler
+    from test_gpu_subgraph_batches import _metrics_and_gradients
+    task = Citation_Network_Task(dict(Citation_Network_Task.default_params()))
+    task.load_synthetic(num_nodes=V, num_features=24, num_classes=5, num_train=140, num_valid=80, num_test=80, feature_density=0.2, seed=3)
+    task._Citation_Network_Task__num_edge_types = L
+    cls = getattr(models, model_name)
+    p = cls.default_params()
+    p.update(dict(hidden_size=32, graph_num_layers=2, graph_layer_input_dropout_keep_prob=1.0, random_seed=6), **params)
+    model = cls(p, task, device=str(gpu_device))
+    rng = np.random.default_rng(1)
+    features = torch.as_tensor(rng.standard_normal((V, 24)).astype(np.float32), device=gpu_device)
+    labels = torch.as_tensor(rng.integers(0, 5, size=V).astype(np.int32), device=gpu_device)
+    mask = torch.as_tensor(N.norm_graph("bucket")[2], device=gpu_device)
+    h, roots, draw = _root_lists("bucket")[0 if kind == "all" else 1]
+    sampler = SubgraphSampler(device_graph("bucket", gpu_device), h, seed=SEED)
+    results = []
+    for preset in (False, True):
+        clear_graph_cache()
+        sub = sampler.sample(roots, draw)                               # (tensors of its own: the graph cache is keyed by them)
+        if preset:
+            degrees = sub.type_to_num_incoming_edges.cpu().numpy()
+            targets = np.concatenate([a[:, 1].cpu().numpy() for a in sub.adjacency_lists])
+            types = np.repeat(np.arange(L), [len(a) for a in sub.adjacency_lists])
+            induced = np.float32(1.0) / (degrees[types, targets] + np.float32(1e-7))
+            sub = sub._replace(message_weights=torch.as_tensor(induced.astype(np.float32), device=gpu_device))
+        batch = sub.device_batch(features, labels, mask)
+        assert (getattr(batch, "graph", None) is not None) == preset
+        results.append(_metrics_and_gradients(model, batch))
+    (metrics_a, grads_a), (metrics_b, grads_b) = results
+    assert np.isfinite(metrics_a["loss"]) and any(g is not None and np.abs(g).max() > 0 for g in grads_a.values())
+    for k in metrics_a:
+        assert metrics_a[k].view(np.uint32) == metrics_b[k].view(np.uint32), k
+    for name in grads_a:
+        assert (grads_a[name] is None) == (grads_b[name] is None), name
+        if grads_a[name] is not None:
+            assert np.array_equal(grads_a[name].view(np.uint32), grads_b[name].view(np.uint32)), name
+
+
+# ---- 6. end to end --------------------------------------------------------------------------------------------------------------------
+def _subgraph(normalisation=None):
+    value = {"roots_per_batch": 32, "walk_length": 4, "seed": 1}
+    if normalisation is not None:
+        value["normalisation"] = normalisation
+    return {"subgraph_batches": value}
+
+
+def _train_two_epochs(device, result_dir, model_name, params, **model_params):
+    from tf_gnn_samples_amd import models
+    from tf_gnn_samples_amd.tasks import Citation_Network_Task
+    task = Citation_Network_Task(dict(Citation_Network_Task.default_params(), **params))
+    task.load_synthetic(seed=2)                                       # synthetic Cora: 2708 nodes, 140 of them in the train fold
+    cls = getattr(models, model_name)
+    p = cls.default_params()
+    p.update(hidden_size=32, graph_num_layers=2, graph_layer_input_dropout_keep_prob=1.0, random_seed=3, **model_params)
+    result_dir.mkdir()
+    model = cls(p, task, run_id="norm", result_dir=str(result_dir), device=str(device))
+    record, run_epoch = [], model._run_epoch
+
+    def recording(epoch_name, data, fold, quiet=False):
+        out = run_epoch(epoch_name, data, fold, quiet)
+        record.append((epoch_name, [np.float32(float(m["loss"])).tobytes() for m in out[1]], [float(m["total_loss"]) for m in out[1]],
+                       [m.get("num_masked") is not None and float(m["num_masked"]) for m in out[1]]))
+        return out
+    model._run_epoch = recording
+    try:
+        model.train(quiet=True, max_epochs=2)
+    finally:
+        model._run_epoch = run_epoch
+    torch.cuda.synchronize()
+    return task, model, record, {n: model.variables[n].detach().cpu().numpy().copy() for n in model.variables.names()}
+
+
+def _counts_of(task):
+    (held,) = [state for _, state in task._sampling_state.values() if state.visit_counts is not None]
+    return held.visit_counts
+
+
+def test_train_with_the_key(gpu_device, tmp_path):
+    from tf_gnn_samples_amd import models
+    from tf_gnn_samples_amd.tasks import DataFold
+    params = _subgraph({"presample_epochs": 2})
+    task, model, record, first = _train_two_epochs(gpu_device, tmp_path / "a", "RGCN_Model", params)
+    assert [len(r[1]) for r in record] == [5, 1, 5, 1]               # ceil(140 / 32) steps, one full-graph validation pass
+    losses = [np.frombuffer(b, np.float32)[0] for r in record for b in r[1]]
+    assert np.isfinite(losses).all() and len(record[0][1]) == 5 and all(m >= 1 for m in record[0][3])
+    counts = _counts_of(task)
+    assert counts.num_subgraphs == 2 * 5 and int(counts.node_visits.max()) <= 10 and int(counts.edge_visits.max()) <= 10
+    train_nodes = np.flatnonzero(task._loaded_data[DataFold.TRAIN][0].mask)
+    assert (counts.node_visits.cpu().numpy()[train_nodes] >= 2).all()                  # a root once per pre-sampling epoch
+    # again: the same losses and the same weights, bit for bit
+    other_task, _, again_record, again = _train_two_epochs(gpu_device, tmp_path / "b", "RGCN_Model", params)
+    assert again_record == record
+    for n in first:
+        assert np.array_equal(first[n].view(np.uint32), again[n].view(np.uint32)), n
+    # restore(): the key comes back with the checkpoint and the counts are recomputed, identical
+    restored = models.restore(model.best_model_file, str(tmp_path), device=str(gpu_device))
+    assert restored.task.subgraph_batches == task.subgraph_batches and "normalisation" in restored.task.subgraph_batches
+    with open(model.best_model_file, "rb") as f:
+        assert not any("visit" in str(k) for k in pickle.load(f))                       # nothing of them in the checkpoint
+    restored.task.load_synthetic(seed=2)
+    loss, results, *_ = restored._run_epoch("train", restored.task._loaded_data[DataFold.TRAIN], DataFold.TRAIN, quiet=True)
+    assert len(results) == 5 and np.isfinite(loss)
+    recomputed = _counts_of(restored.task)
+    assert recomputed.num_subgraphs == counts.num_subgraphs
+    assert torch.equal(recomputed.node_visits, counts.node_visits) and torch.equal(recomputed.edge_visits, counts.edge_visits)
+    # a normalised batch: the weights in the place of the degree scale, the loss weights beside the mask
+    batch = next(iter(task.make_minibatch_iterator(task._loaded_data[DataFold.TRAIN], DataFold.TRAIN, 10 ** 6)))
+    node_weights, denominator = batch.extra["loss_normalisation"]
+    assert denominator == 140.0 and tuple(node_weights.shape) == (batch.num_nodes,) and float(node_weights.min()) >= 1.0
+    assert batch.graph is not None and batch.graph.degree_scale(batch.type_to_num_incoming_edges).shape[0] == batch.num_edges
+
+
+@pytest.mark.parametrize("model_name, params", [("GGNN_Model", {}), ("RGAT_Model", {}), ("RGCN_Model", {"message_aggregation_function": "mean"})])
+def test_aggregation_weights_are_refused_by_models_that_cannot_take_them(gpu_device, tmp_path, model_name, params):
+    from tf_gnn_samples_amd import models
+    from tf_gnn_samples_amd.tasks import Citation_Network_Task
+    task = Citation_Network_Task(dict(Citation_Network_Task.default_params(), **_subgraph({"presample_epochs": 1, "aggregation": True})))
+    task.load_synthetic(num_nodes=300, num_features=16, num_classes=3, num_train=40, num_valid=40, num_test=40, seed=2)
+    cls = getattr(models, model_name)
+    p = cls.default_params()
+    p.update(hidden_size=16, graph_num_layers=1, random_seed=3, **params)
+    with pytest.raises(ValueError, match='subgraph_batches: normalisation: "aggregation": true requires'):
+        cls(p, task, result_dir=str(tmp_path), device=str(gpu_device))
+
+
+@pytest.mark.parametrize("model_name", ["RGCN_Model", "GGNN_Model", "RGAT_Model", "GNN_FiLM_Model"])
+def test_the_loss_normalisation_alone_trains_every_model(gpu_device, tmp_path, model_name):
+    params = _subgraph({"presample_epochs": 1, "aggregation": False})
+    task, model, record, _ = _train_two_epochs(gpu_device, tmp_path / "a", model_name, params)
+    losses = [np.frombuffer(b, np.float32)[0] for r in record for b in r[1]]
+    assert len(losses) == 12 and np.isfinite(losses).all()
+    from tf_gnn_samples_amd.tasks import DataFold
+    batch = next(iter(task.make_minibatch_iterator(task._loaded_data[DataFold.TRAIN], DataFold.TRAIN, 10 ** 6)))
+    assert "loss_normalisation" in batch.extra and getattr(batch, "graph", None) is None         # the induced degree scale, as ever
+
+
+def test_without_the_key_a_batch_is_the_sampler_s_plain_batch(gpu_device, tmp_path):
+    """A task without the key: no counts, no weights, no preset graph, and one step's metrics equal, bit for bit, the metrics of the
+    batch built by hand from SubgraphSampler.sample().device_batch(), the only path there was before the key."""
+    from tf_gnn_samples_amd import models
+    from tf_gnn_samples_amd.tasks import Citation_Network_Task, DataFold
+    from tf_gnn_samples_amd.tasks.neighbour_sampling import epoch_seed_batches
+    from test_gpu_subgraph_batches import _metrics_and_gradients
+    task = Citation_Network_Task(dict(Citation_Network_Task.default_params(), **_subgraph()))
+    task.load_synthetic(seed=2)
+    p = models.RGCN_Model.default_params()
+    p.update(hidden_size=32, graph_num_layers=2, graph_layer_input_dropout_keep_prob=1.0, random_seed=3)
+    model = models.RGCN_Model(p, task, result_dir=str(tmp_path), device=str(gpu_device))
+    train = task._loaded_data[DataFold.TRAIN]
+    batch = next(iter(model._batches(train, DataFold.TRAIN)))
+    assert "loss_normalisation" not in batch.extra and getattr(batch, "graph", None) is None
+    state = task._subgraph_state_of(train[0], gpu_device)
+    assert state.visit_counts is None
+    roots = epoch_seed_batches(train[0].mask, 32, 1, 0)[0]
+    sub = state.sampler.sample(roots, 0)
+    assert sub.message_weights is None
+    by_hand = sub.device_batch(state.features, state.labels, state.mask, 1.0)
+    metrics_a, grads_a = _metrics_and_gradients(model, batch)
+    metrics_b, grads_b = _metrics_and_gradients(model, by_hand)
+    assert sorted(metrics_a) == ["accuracy", "loss", "num_correct", "num_masked", "total_loss"]
+    for k in metrics_a:
+        assert metrics_a[k].view(np.uint32) == metrics_b[k].view(np.uint32), k
+    for name in grads_a:
+        if grads_a[name] is not None:
+            assert np.array_equal(grads_a[name].view(np.uint32), grads_b[name].view(np.uint32)), name

@@ -1,6 +1,6 @@
 """Build librelgnn.so (the C-ABI HIP library, include/relgnn.h, relgnn_dropout.h, relgnn_predict.h, relgnn_parallel.h, relgnn_sparse_features.h,
-relgnn_sampling.h, relgnn_sparse_subset.h, relgnn_sparse_update.h, relgnn_sparse_gradient.h, relgnn_layered_sampling.h and
-relgnn_subgraph.h) in-tree for gfx950.
+relgnn_sampling.h, relgnn_sparse_subset.h, relgnn_sparse_update.h, relgnn_sparse_gradient.h, relgnn_layered_sampling.h,
+relgnn_subgraph.h and relgnn_subgraph_norm.h) in-tree for gfx950.
 
 hipcc cross-compiles without a GPU, so this runs in the CPU-only build container; the
 resulting tf_gnn_samples_amd/librelgnn.so travels with the repo snapshot to the GPU box.
@@ -17,7 +17,8 @@ HEADERS = [PKG_DIR.parent / "include" / name for name in ("relgnn.h", "relgnn_dr
                                                                "relgnn_parallel.h", "relgnn_sparse_features.h",
                                                                "relgnn_sampling.h", "relgnn_sparse_subset.h",
                                                                "relgnn_sparse_update.h", "relgnn_sparse_gradient.h",
-                                                               "relgnn_layered_sampling.h", "relgnn_subgraph.h")]      # the C ABI
+                                                               "relgnn_layered_sampling.h", "relgnn_subgraph.h",
+                                                               "relgnn_subgraph_norm.h")]                             # the C ABI
 HIPCC_FLAGS = [
     "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC",
     # product and add of `scale * row` then `acc + msg` are rounded separately, like the

@@ -1,6 +1,7 @@
 """ctypes binding of librelgnn.so (C ABI: include/relgnn.h, include/relgnn_dropout.h, include/relgnn_predict.h,
 include/relgnn_parallel.h, include/relgnn_sparse_features.h, include/relgnn_sampling.h, include/relgnn_sparse_subset.h,
-include/relgnn_sparse_update.h, include/relgnn_sparse_gradient.h, include/relgnn_layered_sampling.h, include/relgnn_subgraph.h).
+include/relgnn_sparse_update.h, include/relgnn_sparse_gradient.h, include/relgnn_layered_sampling.h, include/relgnn_subgraph.h,
+include/relgnn_subgraph_norm.h).
 
 This is the ONLY compute backend of the package.  There is no CPU / eager-PyTorch fallback:
 if the HIP library is missing, or a tensor is not a float32/int32 CUDA(HIP) tensor, the
@@ -286,6 +287,19 @@ _SUBGRAPH_SIGNATURES = {
     "relgnn_subgraph_clear": (ctypes.c_int, [_ptr, _c_i64, _ptr, _c_i64, _ptr]),
 }
 
+# include/relgnn_subgraph_norm.h (GraphSAINT normalisation of the subgraph batches: visit counts, per-edge weights, the weighted loss
+# head): its own table too
+_SUBGRAPH_NORM_SIGNATURES = {
+    "relgnn_subgraph_visit_count": (ctypes.c_int, [_ptr, _ptr, _c_i64, _c_i32, _c_i64, _ptr, _ptr, _c_i64, _ptr, _ptr, _ptr, _ptr]),
+    "relgnn_subgraph_induced_emit_weighted": (ctypes.c_int, [_ptr, _ptr, _c_i64, _c_i32, _c_i64, _ptr, _c_i64, _c_i64, _ptr, _ptr, _ptr,
+                                                             _ptr, _c_f32, _c_i64, _ptr, _ptr, _ptr, _ptr]),
+    "relgnn_softmax_ce_weighted_stats_workspace_bytes": (ctypes.c_size_t, []),
+    "relgnn_softmax_ce_weighted_stats": (ctypes.c_int, [_ptr, _c_i64, _ptr, _ptr, _ptr, _c_f32, _c_i64, _c_i32, _ptr, _ptr,
+                                                        ctypes.c_size_t, _ptr]),
+    "relgnn_softmax_ce_weighted_bwd": (ctypes.c_int, [_ptr, _c_i64, _ptr, _ptr, _ptr, _c_f32, _c_i64, _c_i32, _ptr, _ptr, _ptr, _c_i64,
+                                                      _ptr]),
+}
+
 _lib = None
 
 
@@ -307,7 +321,7 @@ def load_library():
             + list(_PARALLEL_SIGNATURES.items()) + list(_SPARSE_FEATURES_SIGNATURES.items()) + list(_SAMPLING_SIGNATURES.items()) \
             + list(_SPARSE_SUBSET_SIGNATURES.items()) + list(_SPARSE_UPDATE_SIGNATURES.items()) \
             + list(_SPARSE_GRADIENT_SIGNATURES.items()) + list(_LAYERED_SAMPLING_SIGNATURES.items()) \
-            + list(_SUBGRAPH_SIGNATURES.items()):
+            + list(_SUBGRAPH_SIGNATURES.items()) + list(_SUBGRAPH_NORM_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the symbol is not exported
         fn.restype = restype
         fn.argtypes = argtypes
@@ -369,6 +383,11 @@ def layered_sampling_signatures():
 def subgraph_signatures():
     """The entry points of include/relgnn_subgraph.h (not part of exported_signatures() either)."""
     return dict(_SUBGRAPH_SIGNATURES)
+
+
+def subgraph_norm_signatures():
+    """The entry points of include/relgnn_subgraph_norm.h (not part of exported_signatures() either)."""
+    return dict(_SUBGRAPH_NORM_SIGNATURES)
 
 
 def status_string(code: int) -> str:

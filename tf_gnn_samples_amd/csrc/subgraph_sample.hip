@@ -12,9 +12,14 @@
 // the kept entries come out in the bucket's own order.  A source's local id is its stamp - 1 (relgnn_subgraph_number wrote the
 // positions into the stamps), the target's is the bucket's position in the node list.  Every loop is bounded by a bucket length
 // or a launch argument.  No atomics anywhere.
+//
+// GraphSAINT normalisation (include/relgnn_subgraph_norm.h): the visit count walks the buckets as the count does and adds 1 to the
+// position of every kept entry and to the node of every type-0 wave, plain load-add-store: a position belongs to one lane of one
+// wave of a launch, and the launches of a stream are ordered.  The weighted emit is the emit with one more store per kept entry.
 #include "common.h"
 #include "philox.h"
 #include "../../include/relgnn_subgraph.h"
+#include "../../include/relgnn_subgraph_norm.h"
 
 #include <rocprim/device/device_scan.hpp>
 
@@ -114,16 +119,56 @@ __global__ __launch_bounds__(256) void induced_count_kernel(const int32_t* __res
   }
 }
 
+// one pre-sampled subgraph: edge_visits[b + j] += 1 for every kept entry j of bucket (nodes[i], l), node_visits[nodes[i]] += 1 from the
+// wave of type 0.  One writer per address (a node is in the list once; a position belongs to one lane in one pass): no atomics.
+__global__ __launch_bounds__(256) void visit_count_kernel(const int32_t* __restrict__ rowptr, const int32_t* __restrict__ col, int64_t V,
+                                                          int32_t L, int64_t M, const int32_t* __restrict__ nodes,
+                                                          const int32_t* __restrict__ count, int64_t B,
+                                                          const int32_t* __restrict__ stamp, int32_t* __restrict__ node_visits,
+                                                          int32_t* __restrict__ edge_visits) {
+  const int lane = threadIdx.x & (RELGNN_WAVE - 1);
+  const int64_t n = set_size(count, B), total = n * L;
+  const int64_t waves = (int64_t)gridDim.x * (blockDim.x / RELGNN_WAVE);
+  for (int64_t w = blockIdx.x * (int64_t)(blockDim.x / RELGNN_WAVE) + (threadIdx.x / RELGNN_WAVE); w < total; w += waves) {
+    const int64_t l = w / n, i = w - l * n;
+    const int32_t t = nodes[i];
+    if ((uint32_t)t >= (uint64_t)V) continue;
+    if (l == 0 && lane == 0) node_visits[t] += 1;
+    const int64_t row = (int64_t)t * L + l;
+    const int32_t b = rowptr[row], deg = rowptr[row + 1] - b;
+    for (int32_t first = 0; first < deg; first += kPasses * RELGNN_WAVE) {
+      int32_t s[kPasses];
+      load_stamps(col + b, first + lane, deg, L, V, stamp, s);
+#pragma unroll
+      for (int u = 0; u < kPasses; ++u) {
+        const int64_t p = (int64_t)b + first + lane + u * RELGNN_WAVE;
+        if (s[u] != 0 && p < M) edge_visits[p] += 1;
+      }
+    }
+  }
+}
+
 __global__ __launch_bounds__(64) void induced_totals_kernel(const int32_t* __restrict__ offsets, int64_t B, int32_t L,
                                                            int32_t* __restrict__ totals) {
   for (int32_t l = threadIdx.x; l <= L; l += blockDim.x)
     totals[l] = l < L ? offsets[(int64_t)(l + 1) * B] - offsets[(int64_t)l * B] : offsets[(int64_t)L * B];
 }
 
+// what a weighted emit reads and writes on top (include/relgnn_subgraph_norm.h); kWeighted == false: not touched
+struct EmitWeights {
+  const int32_t* node_visits;
+  const int32_t* edge_visits;
+  float* edge_weights;
+  int64_t M;
+  float cap;
+};
+
+template <bool kWeighted>
 __global__ __launch_bounds__(256) void induced_emit_kernel(const int32_t* __restrict__ rowptr, const int32_t* __restrict__ col, int64_t V,
                                                            int32_t L, const int32_t* __restrict__ nodes, int64_t n, int64_t B,
                                                            const int32_t* __restrict__ stamp, const int32_t* __restrict__ offsets,
-                                                           int64_t edge_bound, int2* __restrict__ edges, float* __restrict__ degrees) {
+                                                           int64_t edge_bound, int2* __restrict__ edges, float* __restrict__ degrees,
+                                                           EmitWeights ew) {
   const int lane = threadIdx.x & (RELGNN_WAVE - 1);
   const unsigned long long below = (1ull << lane) - 1ull;
   const int64_t total = n * L;
@@ -136,6 +181,12 @@ __global__ __launch_bounds__(256) void induced_emit_kernel(const int32_t* __rest
       const int64_t row = (int64_t)t * L + l;
       const int32_t b = rowptr[row], deg = rowptr[row + 1] - b;
       const int64_t off = offsets[l * B + i];
+      float visits = 1.f, scale = 0.f;                          // (kWeighted) max(C_t, 1) and the full graph's 1 / (deg + 1e-7)
+      if constexpr (kWeighted) {
+        const int32_t c = ew.node_visits[t];
+        visits = (float)(c > 1 ? c : 1);
+        scale = 1.0f / ((float)deg + 1e-7f);
+      }
       for (int32_t first = 0; first < deg; first += kPasses * RELGNN_WAVE) {
         int32_t s[kPasses];
         load_stamps(col + b, first + lane, deg, L, V, stamp, s);
@@ -146,6 +197,12 @@ __global__ __launch_bounds__(256) void induced_emit_kernel(const int32_t* __rest
           if (s[u] != 0 && slot < edge_bound) {
             const int64_t local = (int64_t)s[u] - 1;            // number_kernel's position, inside the list all the same
             edges[slot] = make_int2((int32_t)(local < 0 ? 0 : (local < n ? local : n - 1)), (int32_t)i);
+            if constexpr (kWeighted) {
+              const int64_t p = (int64_t)b + first + lane + u * RELGNN_WAVE;
+              const int32_t c = p < ew.M ? ew.edge_visits[p] : 1;
+              const float a = fminf(visits / (float)(c > 1 ? c : 1), ew.cap);
+              ew.edge_weights[slot] = a * scale;
+            }
           }
           kept += __popcll(mask);
         }
@@ -232,9 +289,39 @@ int relgnn_subgraph_induced_emit(const int32_t* rowptr_t, const int32_t* col_t, 
   if (n == 0) return RELGNN_OK;
   if (!rowptr_t || !col_t || !nodes || !stamp || !offsets || !degrees || (edge_bound > 0 && !edges)) return RELGNN_EINVAL;
   if (reinterpret_cast<uintptr_t>(edges) & 7u) return RELGNN_EINVAL;
-  induced_emit_kernel<<<flat_grid(n * num_edge_types * RELGNN_WAVE, 256), 256, 0, as_stream(stream)>>>(
+  induced_emit_kernel<false><<<flat_grid(n * num_edge_types * RELGNN_WAVE, 256), 256, 0, as_stream(stream)>>>(
       rowptr_t, col_t, num_nodes, num_edge_types, nodes, n, node_bound, stamp, offsets, edge_bound, reinterpret_cast<int2*>(edges),
-      degrees);
+      degrees, EmitWeights{nullptr, nullptr, nullptr, 0, 0.f});
+  return launch_status();
+}
+
+int relgnn_subgraph_visit_count(const int32_t* rowptr_t, const int32_t* col_t, int64_t num_nodes, int32_t num_edge_types,
+                                int64_t num_messages, const int32_t* nodes, const int32_t* node_count, int64_t node_bound,
+                                const int32_t* stamp, int32_t* node_visits, int32_t* edge_visits, void* stream) {
+  if (node_bound <= 0 || node_bound > num_nodes || num_messages < 0) return RELGNN_EINVAL;
+  if (!graph_ok(num_nodes, num_edge_types) || num_messages >= ((int64_t)1 << 31)) return RELGNN_EUNSUPPORTED;
+  if (!rowptr_t || !nodes || !node_count || !stamp || !node_visits || (num_messages > 0 && (!col_t || !edge_visits))) return RELGNN_EINVAL;
+  visit_count_kernel<<<flat_grid(node_bound * num_edge_types * RELGNN_WAVE, 256), 256, 0, as_stream(stream)>>>(
+      rowptr_t, col_t, num_nodes, num_edge_types, num_messages, nodes, node_count, node_bound, stamp, node_visits, edge_visits);
+  return launch_status();
+}
+
+int relgnn_subgraph_induced_emit_weighted(const int32_t* rowptr_t, const int32_t* col_t, int64_t num_nodes, int32_t num_edge_types,
+                                          int64_t num_messages, const int32_t* nodes, int64_t n, int64_t node_bound,
+                                          const int32_t* stamp, const int32_t* offsets, const int32_t* node_visits,
+                                          const int32_t* edge_visits, float max_edge_weight, int64_t edge_bound, int32_t* edges,
+                                          float* degrees, float* edge_weights, void* stream) {
+  if (n < 0 || node_bound <= 0 || n > node_bound || node_bound > num_nodes || edge_bound < 0 || num_messages < 0) return RELGNN_EINVAL;
+  if (!(max_edge_weight > 0.f)) return RELGNN_EINVAL;
+  if (!graph_ok(num_nodes, num_edge_types) || num_messages >= ((int64_t)1 << 31)) return RELGNN_EUNSUPPORTED;
+  if (n == 0) return RELGNN_OK;
+  if (!rowptr_t || !col_t || !nodes || !stamp || !offsets || !degrees || !node_visits || (num_messages > 0 && !edge_visits) ||
+      (edge_bound > 0 && (!edges || !edge_weights)))
+    return RELGNN_EINVAL;
+  if (reinterpret_cast<uintptr_t>(edges) & 7u) return RELGNN_EINVAL;
+  induced_emit_kernel<true><<<flat_grid(n * num_edge_types * RELGNN_WAVE, 256), 256, 0, as_stream(stream)>>>(
+      rowptr_t, col_t, num_nodes, num_edge_types, nodes, n, node_bound, stamp, offsets, edge_bound, reinterpret_cast<int2*>(edges),
+      degrees, EmitWeights{node_visits, edge_visits, edge_weights, num_messages, max_edge_weight});
   return launch_status();
 }
 

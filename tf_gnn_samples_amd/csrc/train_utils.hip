@@ -7,6 +7,7 @@
 #include "common.h"
 #include "adam_element.h"
 #include "norm_tree.h"
+#include "../../include/relgnn_subgraph_norm.h"
 
 using namespace relgnn;
 
@@ -414,6 +415,107 @@ __global__ __launch_bounds__(256) void softmax_ce_bwd_kernel(const float* __rest
   }
 }
 
+// ---- the same head with a weight per row (include/relgnn_subgraph_norm.h: GraphSAINT's loss normalisation) ------------------------
+// stats = {sum_v loss_v mask_v weight_v, sum_v mask_v, sum_v [argmax_v == label_v] mask_v, stats[0] / denominator, stats[2] / stats[1],
+// sum_v mask_v weight_v}: the row walk, the per-row loss and the order of every sum are softmax_ce_stats_kernel's, so that with every
+// weight 1 the first three sums are its bits (mask * 1 and l * (mask * 1) are exact).  partial[block * 4 + {0, 1, 2, 3}].
+template <int W>
+__global__ __launch_bounds__(256) void softmax_ce_weighted_stats_kernel(const float* __restrict__ logits, long long ld,
+                                                                        const int* __restrict__ labels, const float* __restrict__ mask,
+                                                                        const float* __restrict__ weights, long long rows, int cols,
+                                                                        double* __restrict__ partial) {
+  __shared__ double red[16];
+  constexpr int kRowsPerBlock = 256 / W;
+  const int j = threadIdx.x % W, g = threadIdx.x / W;
+  double loss = 0.0, msum = 0.0, correct = 0.0, wsum = 0.0;
+  for (long long base = (long long)blockIdx.x * kRowsPerBlock; base < rows; base += (long long)gridDim.x * kRowsPerBlock) {
+    const long long r = base + g;
+    const bool valid = r < rows;
+    const float* row = logits + (valid ? r : 0) * ld;
+    const RowLse a = row_lse<W>(row, valid ? cols : 0, j);
+    if (valid && j == 0) {
+      const int label = labels[r];
+      const float mk = mask[r];
+      const double mw = (double)mk * (double)weights[r];
+      const float xl = (label >= 0 && label < cols) ? row[label] : a.m;
+      const double l = (double)log1pf(a.t) + (xl == a.m ? 0.0 : (double)a.m - (double)xl);
+      loss += l * mw;
+      msum += (double)mk;
+      correct += a.idx == label ? (double)mk : 0.0;
+      wsum += mw;
+    }
+  }
+  double s;
+  s = block_sum_1024(loss, red);    if (threadIdx.x == 0) partial[blockIdx.x * 4 + 0] = s;
+  s = block_sum_1024(msum, red);    if (threadIdx.x == 0) partial[blockIdx.x * 4 + 1] = s;
+  s = block_sum_1024(correct, red); if (threadIdx.x == 0) partial[blockIdx.x * 4 + 2] = s;
+  s = block_sum_1024(wsum, red);    if (threadIdx.x == 0) partial[blockIdx.x * 4 + 3] = s;
+}
+
+// softmax_ce_stats_final_kernel's tree over four sums; the loss is divided by the caller's denominator, not by the sum of the mask
+__global__ __launch_bounds__(256) void softmax_ce_weighted_stats_final_kernel(const double* __restrict__ partial, int nblk,
+                                                                              float denominator, float* __restrict__ stats) {
+  __shared__ double red[4][4];
+  const int b = threadIdx.x;
+  double v[4];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) v[k] = b < nblk ? partial[b * 4 + k] : 0.0;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) v[k] += __shfl_xor(v[k], off);
+  }
+  const int wave = b >> 6, lane = b & 63;
+  if (lane == 0) {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) red[wave][k] = v[k];
+  }
+  __syncthreads();
+  if (b == 0) {
+    float t[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) t[k] = (float)((red[0][k] + red[1][k]) + (red[2][k] + red[3][k]));
+    stats[0] = t[0];
+    stats[1] = t[1];
+    stats[2] = t[2];
+    stats[3] = t[0] / denominator;
+    stats[4] = t[2] / t[1];
+    stats[5] = t[3];
+  }
+}
+
+// glogits[v, c] = mask_v * weight_v * (softmax(logits_v)_c - [c == label_v]) * (g_total[0] + g_loss[0] / denominator) for c < cols, 0
+// for cols <= c < ldg; a row with mask 0 is written as zeros.  Either gradient pointer may be null.
+template <int W>
+__global__ __launch_bounds__(256) void softmax_ce_weighted_bwd_kernel(const float* __restrict__ logits, long long ld,
+                                                                      const int* __restrict__ labels, const float* __restrict__ mask,
+                                                                      const float* __restrict__ weights, float denominator,
+                                                                      long long rows, int cols, const float* __restrict__ g_loss,
+                                                                      const float* __restrict__ g_total, float* __restrict__ gl,
+                                                                      long long ldg) {
+  constexpr int kRowsPerBlock = 256 / W;
+  const int j = threadIdx.x % W, g = threadIdx.x / W;
+  float gs = 0.f;
+  if (g_loss) gs = g_loss[0] / denominator;
+  if (g_total) gs = g_loss ? gs + g_total[0] : g_total[0];
+  for (long long base = (long long)blockIdx.x * kRowsPerBlock; base < rows; base += (long long)gridDim.x * kRowsPerBlock) {
+    const long long r = base + g;
+    const bool valid = r < rows;
+    const float* row = logits + (valid ? r : 0) * ld;
+    const RowLse a = row_lse<W>(row, valid ? cols : 0, j);
+    if (!valid) continue;
+    const float mk = mask[r];
+    const int label = labels[r];
+    const float scale = (mk * weights[r]) * gs, inv = 1.f / (1.f + a.t);
+    float* out = gl + r * ldg;
+    for (int c = j; c < (int)ldg; c += W) {
+      float v = 0.f;
+      if (c < cols && mk != 0.f) v = scale * (expf(row[c] - a.m) * inv - (c == label ? 1.f : 0.f));
+      out[c] = v;
+    }
+  }
+}
+
 constexpr int kSoftmaxBlocks = 256;
 
 static inline int softmax_grid(long long rows, int w) {
@@ -597,6 +699,49 @@ int relgnn_softmax_ce_bwd(const float* logits, int64_t ld, const int32_t* labels
   if (w == 1) softmax_ce_bwd_kernel<1><<<nblk, 256, 0, st>>>(logits, ld, labels, mask, rows, cols, stats, g_loss, g_total, glogits, ldg);
   else if (w == 16) softmax_ce_bwd_kernel<16><<<nblk, 256, 0, st>>>(logits, ld, labels, mask, rows, cols, stats, g_loss, g_total, glogits, ldg);
   else softmax_ce_bwd_kernel<64><<<nblk, 256, 0, st>>>(logits, ld, labels, mask, rows, cols, stats, g_loss, g_total, glogits, ldg);
+  return launch_status();
+}
+
+size_t relgnn_softmax_ce_weighted_stats_workspace_bytes(void) { return (size_t)kSoftmaxBlocks * 4 * sizeof(double); }
+
+int relgnn_softmax_ce_weighted_stats(const float* logits, int64_t ld, const int32_t* labels, const float* mask, const float* weights,
+                                     float denominator, int64_t rows, int32_t cols, float* stats, void* workspace,
+                                     size_t workspace_bytes, void* stream) {
+  if (rows < 0 || cols < 1 || ld < cols || !stats || denominator == 0.f || denominator != denominator)
+    return RELGNN_EINVAL;
+  if (!workspace || workspace_bytes < relgnn_softmax_ce_weighted_stats_workspace_bytes()) return RELGNN_ENOSPC;
+  if (rows > 0 && (!logits || !labels || !mask || !weights)) return RELGNN_EINVAL;
+  hipStream_t st = as_stream(stream);
+  double* partial = static_cast<double*>(workspace);
+  int nblk = 0;
+  if (rows > 0) {
+    const int w = softmax_group_width(cols);
+    nblk = softmax_grid(rows, w);
+    if (w == 1) softmax_ce_weighted_stats_kernel<1><<<nblk, 256, 0, st>>>(logits, ld, labels, mask, weights, rows, cols, partial);
+    else if (w == 16) softmax_ce_weighted_stats_kernel<16><<<nblk, 256, 0, st>>>(logits, ld, labels, mask, weights, rows, cols, partial);
+    else softmax_ce_weighted_stats_kernel<64><<<nblk, 256, 0, st>>>(logits, ld, labels, mask, weights, rows, cols, partial);
+  }
+  softmax_ce_weighted_stats_final_kernel<<<1, 256, 0, st>>>(partial, nblk, denominator, stats);
+  return launch_status();
+}
+
+int relgnn_softmax_ce_weighted_bwd(const float* logits, int64_t ld, const int32_t* labels, const float* mask, const float* weights,
+                                   float denominator, int64_t rows, int32_t cols, const float* g_loss, const float* g_total,
+                                   float* glogits, int64_t ldg, void* stream) {
+  if (rows < 0 || cols < 1 || ld < cols || ldg < cols || ldg > INT32_MAX || denominator == 0.f || denominator != denominator)
+    return RELGNN_EINVAL;
+  if (rows == 0) return RELGNN_OK;
+  if (!logits || !labels || !mask || !weights || (!g_loss && !g_total) || !glogits) return RELGNN_EINVAL;
+  hipStream_t st = as_stream(stream);
+  const int w = softmax_group_width(cols);
+  const int64_t per_block = 256 / w;
+  const unsigned nblk = flat_grid((rows + per_block - 1) / per_block * 256, 256);
+  if (w == 1)
+    softmax_ce_weighted_bwd_kernel<1><<<nblk, 256, 0, st>>>(logits, ld, labels, mask, weights, denominator, rows, cols, g_loss, g_total, glogits, ldg);
+  else if (w == 16)
+    softmax_ce_weighted_bwd_kernel<16><<<nblk, 256, 0, st>>>(logits, ld, labels, mask, weights, denominator, rows, cols, g_loss, g_total, glogits, ldg);
+  else
+    softmax_ce_weighted_bwd_kernel<64><<<nblk, 256, 0, st>>>(logits, ld, labels, mask, weights, denominator, rows, cols, g_loss, g_total, glogits, ldg);
   return launch_status();
 }
 

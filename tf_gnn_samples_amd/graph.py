@@ -290,6 +290,23 @@ class RelGraph:
         self._plans[("w_s", w_t.data_ptr())] = (w_t, w_s)
         self._preset = (src_t, w_t, w_s)
 
+    def preset_message_scale(self, type_to_num_incoming_edges: torch.Tensor, weights_in_list_order: torch.Tensor) -> torch.Tensor:
+        """A scale PER MESSAGE in the place of 1/(in-degree + 1e-7) for THIS degree table (GraphSAINT's aggregation weights,
+        tasks/subgraph_sampling.py): float32 [M] in the order of the adjacency lists, one list behind the other.  Gathered into
+        by-target order through perm_t and registered under the table's key, as preset_degree_scale registers its array, so that
+        degree_scale(table) returns it; the by-source order follows on demand (w_by_source / GatherReducePlan.w_bwd).  The weights
+        may differ inside a bucket: every reduction takes its scale per message."""
+        t, w = type_to_num_incoming_edges, weights_in_list_order
+        if tuple(t.shape) != (self.L, self.V):
+            raise ValueError("type_to_num_incoming_edges must have shape [%d, %d]" % (self.L, self.V))
+        if w.dtype != torch.float32 or tuple(w.shape) != (self.M,):
+            raise ValueError("the message weights must be float32 [%d], got %s %s" % (self.M, w.dtype, tuple(w.shape)))
+        w_t = torch.empty(self.M, dtype=torch.float32, device=self.device)
+        if self.M > 0:
+            _lib.launch("relgnn_gather_f32", _lib.ptr(w.contiguous()), _lib.ptr(self.perm_t), self.M, _lib.ptr(w_t))
+        self._scales[(t.data_ptr(), t._version, tuple(t.shape))] = (t, w_t)
+        return w_t
+
     # ---- bucketing on a side stream (input pipeline) --------------------------------------------
     ready_event = None
 

@@ -10,6 +10,7 @@ NB (reference behaviour kept on purpose): the RGCN and Edge-MLP adapters do not 
 layer defaults apply (RGCN normalises by in-degree, gnns/rgcn.py:15; Edge-MLP does not, gnns/gnn_edge_mlp.py:15);
 GGNN / RGAT / RGIN layers take no in-degree table.
 """
+import inspect
 from typing import Any, Callable, Dict, List, NamedTuple, Optional
 
 import torch
@@ -146,7 +147,25 @@ def build_adapter(spec: AdapterSpec):
         return spec.layer_fn(node_embeddings=node_representations, adjacency_lists=adjacency_lists,
                              num_timesteps=num_timesteps, weights=self._layer_weights, **kwargs)
 
+    def _message_scale_prerequisites(self):
+        if not spec.takes_in_degrees:
+            return "a model whose layers take the in-degree table (%s's do not)" % spec.class_name
+        key = spec.layer_kwargs.get("normalize_by_num_incoming")
+        if key is not None:
+            normalises = bool(self.params[key])
+            said = "%s true (got %r)" % (key, self.params[key])
+        else:       # the adapter forwards no flag: the layer function's own default holds (the NB in this module's docstring)
+            normalises = bool(inspect.signature(spec.layer_fn).parameters["normalize_by_num_incoming"].default)
+            said = "a layer that normalises by in-degree (%s's does not, and the adapter forwards no flag)" % spec.class_name
+        if not normalises:
+            return said
+        aggregation = self.params[spec.layer_kwargs["message_aggregation_function"]]
+        if aggregation != "sum":
+            return 'message_aggregation_function "sum" (got %r)' % (aggregation,)
+        return None
+
     return type(spec.class_name, (Sparse_Graph_Model,), {
+        "_message_scale_prerequisites": _message_scale_prerequisites,
         "__doc__": "%s adapter, generated from its AdapterSpec (models/adapters.py)." % spec.class_name,
         "default_params": classmethod(default_params),
         "name": staticmethod(spec.display_name),

@@ -358,6 +358,14 @@ class Sparse_Graph_Model(ABC):
             if problem is not None:
                 raise ValueError('sampled_batches: "evaluation" requires %s: evaluation batches are hop-ordered and run layer l on '
                                  'the nodes H - l + 1 hops from a seed' % problem)
+        normalisation = (getattr(self.task, "subgraph_batches", None) or {}).get("normalisation")
+        if normalisation is not None and normalisation["aggregation"]:
+            # the citation task's `subgraph_batches` key "normalisation": the per-edge weights reach a layer as its degree scale
+            problem = self._message_scale_prerequisites()
+            if problem is not None:
+                raise ValueError('subgraph_batches: normalisation: "aggregation": true requires %s: the per-edge weights take the place '
+                                 'of 1/(in-degree + 1e-7) in a sum over the messages; "aggregation": false (the loss normalisation '
+                                 'alone) works with every model' % problem)
         if getattr(self.task, "sparse_update", False):
             # the citation task's `sampled_batches` key "sparse_update": the weight of the sparse input projection is updated by rows.
             # CONTRACT: between training steps that parameter's tensor (and its two Adam slots) hold stale rows; everything here that
@@ -373,6 +381,12 @@ class Sparse_Graph_Model(ABC):
             if getattr(self.task, "sparse_gradient", False):
                 # "sparse_gradient": that weight's gradient exists only as the rows a batch names (_project_input hands the sink on)
                 self.optimizer.compact_row_gradient()
+
+    def _message_scale_prerequisites(self) -> Optional[str]:
+        """What a batch whose degree scale is a weight per message (the citation task's `subgraph_batches` key "normalisation" with
+        "aggregation": true) needs and this model lacks, None when its layers take that scale: the layer function reads the degree
+        table, normalises by it, and SUMS the scaled messages.  The adapters answer from their spec (models/adapters.py)."""
+        return "a model whose layers read the in-degree scale (this one says nothing about its layers)"
 
     def _layered_prerequisites(self, fanouts) -> Optional[str]:
         """What a layered batch of these fanouts needs and this model lacks, None when it can run one."""

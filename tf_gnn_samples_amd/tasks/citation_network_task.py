@@ -74,8 +74,21 @@ of the full graph between two of them, with the induced in-degrees.  Every layer
 at any depth.  The loss mask is fold_mask[nodes]: every TRAIN node of the subgraph counts, not only the roots.  "sparse_features": true
 requires sparse_node_features (and the reverse), as for sampled_batches; the batch then carries SparseRows.take_rows(nodes).  The
 device RelGraph and the feature table are the ones the folds share (_graph_state_of).  VALIDATION, TEST, test() and predict() stay on
-the full graph; predict(nodes=...) runs exact receptive fields as it does without the parameter.  No GraphSAINT normalisation: the
-loss and the aggregation are the induced subgraph's.  GPU only; not together with capture_train_step or a process group.
+the full graph; predict(nodes=...) runs exact receptive fields as it does without the parameter.  Without the next key the loss and
+the aggregation are the induced subgraph's.  GPU only; not together with capture_train_step or a process group.
+
+One more optional key, "normalisation": {"presample_epochs": E, "aggregation": bool, "max_edge_weight": c} (the last two optional: true
+and 1e4; it composes with "sparse_features"): GraphSAINT's normalisation (include/relgnn_subgraph_norm.h).  Before the first TRAIN
+batch of a (fold, device) the sampler counts, over N = E * ceil(n_train / R) pre-sampled subgraphs (root lists of the epochs
+0x80000000 + e, sampler replica 0x20000000: never a training batch's draws, and a pure function of (seed, E, the graph), so the counts
+are recomputed after restore() and not stored), how many hold node v (C_v) and both ends of edge e (C_e), without a read-back.  The
+loss term of node v then carries the weight N / max(C_v, 1) and the batch loss is divided by n_train instead of the batch's masked
+count (relgnn_softmax_ce_weighted_stats / _bwd): its expectation is the fold's mean loss.  num_masked, num_correct and the accuracy
+stay unweighted counts; total_loss is the weighted sum.  "aggregation": every message of a batch is scaled by
+min(max(C_v, 1) / max(C_e, 1), c) / (full-graph in-degree + 1e-7) instead of 1 / (induced in-degree + 1e-7) (emitted with the edges,
+preset as the batch graph's degree scale): a layer's sum is then an estimate of the aggregate evaluation computes on the full graph.
+It needs a model whose layers take the degree table, normalise by it and sum (RGCN, RGDCN, GNN-FiLM with
+normalize_messages_by_num_incoming; a ValueError from the model otherwise); "aggregation": false works with every model.
 """
 import os
 import pickle
@@ -119,6 +132,57 @@ class _SamplingState(NamedTuple):
     features: Any                                          # float32 [V, F], or the device's SparseRows
     labels: torch.Tensor                                   # int32 [V]
     mask: torch.Tensor                                     # float32 [V], the fold's
+    visit_counts: Any = None                               # subgraph_sampling.VisitCounts under `subgraph_batches`' key "normalisation"
+
+
+class _SoftmaxCEWeightedStats(torch.autograd.Function):
+    """_SoftmaxCEStats with a weight per row and a denominator the caller names (csrc/train_utils.hip:
+    relgnn_softmax_ce_weighted_stats / _bwd, include/relgnn_subgraph_norm.h): loss = sum(mask * weight * loss_v) / denominator,
+    total_loss the numerator; the accuracy and the counts behind it stay unweighted."""
+
+    @staticmethod
+    def forward(ctx, logits, labels, mask, weights, denominator):
+        lib = _lib.load_library()
+        if logits.dim() != 2 or logits.stride(1) != 1:
+            logits = logits.contiguous()
+        labels, mask, weights = labels.contiguous(), mask.contiguous(), weights.contiguous()
+        rows, cols = logits.shape
+        stats = torch.empty(6, dtype=torch.float32, device=logits.device)
+        nbytes = lib.relgnn_softmax_ce_weighted_stats_workspace_bytes()
+        ws = _lib.scratch(nbytes, logits.device)
+        _lib.launch("relgnn_softmax_ce_weighted_stats", _lib.ptr(logits, rows_strided=True), logits.stride(0) if rows > 1 else cols,
+                    _lib.ptr(labels), _lib.ptr(mask), _lib.ptr(weights), float(denominator), rows, cols, _lib.ptr(stats), _lib.ptr(ws),
+                    nbytes)
+        ctx.save_for_backward(logits, labels, mask, weights)
+        ctx.denominator = float(denominator)
+        ctx.set_materialize_grads(False)
+        loss, total, accuracy = stats[3], stats[0], stats[4]
+        counts = stats[0:3]                       # total_loss, sum of mask, masked correct count (the last two unweighted)
+        ctx.mark_non_differentiable(accuracy, counts)
+        return loss, total, accuracy, counts
+
+    @staticmethod
+    def backward(ctx, g_loss, g_total, g_accuracy, g_counts):
+        logits, labels, mask, weights = ctx.saved_tensors
+        if g_loss is None and g_total is None:
+            return None, None, None, None, None
+
+        def scalar(g):
+            return None if g is None else g.reshape(1).to(torch.float32).contiguous()
+        g_loss, g_total = scalar(g_loss), scalar(g_total)
+        rows, cols = logits.shape
+        ld = logits.stride(0) if rows > 1 else cols
+        padded = cols % 16 and _cfg.settings.limb_gemm and _cfg.settings.head_pad == "1"       # (as _SoftmaxCEStats pads)
+        ldg = (cols + 15) // 16 * 16 if padded else cols
+        gl = torch.empty((rows, ldg), dtype=torch.float32, device=logits.device)
+        _lib.launch("relgnn_softmax_ce_weighted_bwd", _lib.ptr(logits, rows_strided=True), ld, _lib.ptr(labels), _lib.ptr(mask),
+                    _lib.ptr(weights), ctx.denominator, rows, cols, _lib.ptr(g_loss), _lib.ptr(g_total), _lib.ptr(gl), ldg)
+        return (mark_zero_padded(gl[:, :cols], ldg) if padded else gl), None, None, None, None
+
+
+def softmax_ce_weighted_stats(logits: torch.Tensor, labels: torch.Tensor, mask: torch.Tensor, weights: torch.Tensor, denominator: float):
+    """-> (loss, total_loss, accuracy, counts) of float32 device logits [V, C], int32 labels [V], float32 mask and weights [V]."""
+    return _SoftmaxCEWeightedStats.apply(logits, labels, mask, weights, denominator)
 
 
 class _SoftmaxCEStats(torch.autograd.Function):
@@ -456,7 +520,11 @@ class Citation_Network_Task(Sparse_Graph_Task):
         if logits.is_cuda:
             if labels.dtype != torch.int32:           # (the numpy iterator's DeviceBatch widens integer arrays; the native one keeps int32)
                 labels = labels.to(torch.int32)
-            loss, total_loss, accuracy, counts = softmax_ce_stats(logits, labels, mask)
+            if 'loss_normalisation' in batch.extra:   # a normalised subgraph batch: (weight per node, denominator = n_train)
+                node_weights, denominator = batch.extra['loss_normalisation']
+                loss, total_loss, accuracy, counts = softmax_ce_weighted_stats(logits, labels, mask, node_weights, denominator)
+            else:
+                loss, total_loss, accuracy, counts = softmax_ce_stats(logits, labels, mask)
             metrics = {'loss': loss, 'total_loss': total_loss, 'accuracy': accuracy}
             if 'sampled_nodes' in batch.extra:        # one of several batches of an epoch: the counts the epoch's accuracy adds up
                 metrics.update(num_masked=counts[1], num_correct=counts[2])
@@ -691,19 +759,35 @@ class Citation_Network_Task(Sparse_Graph_Task):
         shared = self._graph_state_of(fold, device)
         state = _SamplingState(SubgraphSampler(shared.graph, subgraph["walk_length"], seed=subgraph["seed"]), shared.features,
                                from_host(fold.labels, torch.int32), from_host(fold.mask, torch.float32))
+        normalisation = subgraph.get("normalisation")
+        if normalisation is not None:
+            # GraphSAINT's pre-sampling, before the first TRAIN batch of this state: a pure function of (seed, E, the graph), so it
+            # is recomputed here after restore() and never stored in a checkpoint
+            state = state._replace(visit_counts=state.sampler.presample(fold.mask, subgraph["roots_per_batch"],
+                                                                        normalisation["presample_epochs"]))
         self._sampling_state[key] = (weakref.ref(fold.labels, lambda _, key=key, table=self._sampling_state: table.pop(key, None)), state)
         return state
 
     def _subgraph_batches_of(self, fold: CitationData):
         """ceil(n_train / R) subgraph batches: one TRAIN epoch.  Every train node is a root once; the loss mask is the fold's mask over
-        ALL nodes of the subgraph (seed_mask is ones)."""
+        ALL nodes of the subgraph (seed_mask is ones).  With the key "normalisation" every batch carries extra['loss_normalisation'] =
+        (N / max(node_visits, 1) per node, n_train), and with its "aggregation" the per-edge weights as its graph's degree scale."""
         subgraph = self.subgraph_batches
         state = self._subgraph_state_of(fold, self._bound_device())
         epoch, self._sampling_epoch = self._sampling_epoch, self._sampling_epoch + 1
         keep = self._out_keep(DataFold.TRAIN)
+        normalisation, counts = subgraph.get("normalisation"), state.visit_counts
+        weighting = (counts, normalisation["max_edge_weight"]) if normalisation is not None and normalisation["aggregation"] else None
+        num_train = float(np.count_nonzero(fold.mask))
         for roots in epoch_seed_batches(fold.mask, subgraph["roots_per_batch"], subgraph["seed"], epoch):
             draw, self._sampling_draw = self._sampling_draw, self._sampling_draw + 1
-            yield state.sampler.sample(roots, draw).device_batch(state.features, state.labels, state.mask, keep)
+            if normalisation is None:
+                yield state.sampler.sample(roots, draw).device_batch(state.features, state.labels, state.mask, keep)
+                continue
+            sub = state.sampler.sample(roots, draw, weighting)
+            batch = sub.device_batch(state.features, state.labels, state.mask, keep)
+            batch.extra['loss_normalisation'] = (counts.node_weights(sub.nodes), num_train)
+            yield batch
 
     def compute_initial_node_features(self, batch, weights):
         """The batch's feature table, or in the sparse mode the SparseRows on the batch's device: one copy per device, kept weakly

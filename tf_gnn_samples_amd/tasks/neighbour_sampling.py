@@ -19,7 +19,7 @@ import numpy as np
 import torch
 
 from .. import _lib
-from ..graph import RelGraph
+from ..graph import RelGraph, as_rel_graph
 from .sparse_features import SparseRows
 from .sparse_graph_task import DeviceBatch
 
@@ -58,13 +58,17 @@ class SampledSubgraph(NamedTuple):
     seed_mask: torch.Tensor                     # float32 [n]
     num_nodes: int
     num_edges: int
+    message_weights: Optional[torch.Tensor] = None      # float32 [num_edges] in the order of the lists, one behind the other: the
+    #                                                     scale of every message in the degree scale's place (subgraph_sampling.py)
 
     def device_batch(self, features, labels: torch.Tensor, fold_mask: torch.Tensor, out_keep: float = 1.0,
                      named_rows: bool = False) -> DeviceBatch:
         """The subgraph as one training batch: feature and label rows of the device-resident [V, ...] tables, the loss mask
         seed_mask * fold_mask[nodes].  `features` a SparseRows: the [n, 1] stand-in takes the table's place and the rows' subset
         (SparseRows.take_rows, csrc/sparse_subset.hip) travels under extra['sparse_node_features']; no dense row is built.
-        named_rows: the subset also carries the words it names (`"sparse_gradient": true`; SparseRows.named_rows)."""
+        named_rows: the subset also carries the words it names (`"sparse_gradient": true`; SparseRows.named_rows).
+        message_weights set: the batch brings its RelGraph with those weights preset as the scale of its degree table
+        (RelGraph.preset_message_scale), so every layer that asks graph.degree_scale(batch degrees) receives them."""
         index = self.nodes.long()
         extra = {'labels': labels.index_select(0, index), 'mask': self.seed_mask * fold_mask.index_select(0, index),
                  'out_layer_dropout_keep_prob': out_keep, 'sampled_nodes': self.nodes}
@@ -73,8 +77,15 @@ class SampledSubgraph(NamedTuple):
             rows = torch.zeros((self.num_nodes, 1), dtype=torch.float32, device=self.nodes.device)      # sparse_features.node_stand_in
         else:
             rows = features.index_select(0, index)
-        return DeviceBatch.from_tensors(1, self.num_nodes, self.num_edges, rows, self.adjacency_lists,
-                                        self.type_to_num_incoming_edges, extra=extra)
+        batch = DeviceBatch.from_tensors(1, self.num_nodes, self.num_edges, rows, self.adjacency_lists,
+                                         self.type_to_num_incoming_edges, extra=extra)
+        if self.message_weights is not None:
+            # (the sampler's ids are in range; like the graph the model buckets itself, validate="deferred", it is not inspected for
+            #  hubs: every bucket keeps one wave, so the batch takes the routes it takes without the weights)
+            graph = as_rel_graph(self.adjacency_lists, self.num_nodes, validate=False)
+            graph.preset_message_scale(batch.type_to_num_incoming_edges, self.message_weights)
+            batch.graph = graph
+        return batch
 
 
 class LevelGraph(NamedTuple):

@@ -6,15 +6,19 @@ batch (tasks/neighbour_sampling.py) grows with every hop instead.
 Host round trips of SubgraphSampler.sample() and induced_subgraph(): the root (node) list is validated on the host (in range,
 distinct; one small copy of a device list), and the subgraph's sizes — n, the per-type edge counts and their total — are read back
 ONCE, because its tensors are sized by them.  The buffers in front of that read-back are sized from the bound min(V, R * (h + 1)).
+
+GraphSAINT normalisation (include/relgnn_subgraph_norm.h; the key "normalisation" of the citation task's `subgraph_batches`):
+SubgraphSampler.presample() counts over pre-sampled subgraphs how often every node and every by-target entry is held (VisitCounts; no
+read-back at all), and sample(..., weighting=(counts, cap)) emits the per-edge aggregation weights with the batch's edges.
 """
-from typing import Dict, Optional
+from typing import Dict, NamedTuple, Optional
 
 import numpy as np
 import torch
 
 from .. import _lib
 from ..graph import RelGraph
-from .neighbour_sampling import SampledSubgraph
+from .neighbour_sampling import SampledSubgraph, epoch_seed_batches
 
 # relgnn_subgraph_max_walk_length (the library is not loaded to validate a parameter; tests/test_gpu_subgraph_batches.py holds the
 # two against each other)
@@ -68,16 +72,17 @@ class _Extractor:
             event.record()
             self.trace.append((phase, event))
 
-    def _run(self, stamp_the_set, node_bound: int) -> SampledSubgraph:
-        """stamp_the_set() enqueues what stamps the node set (at most node_bound nodes); everything behind it is the same."""
+    def _run(self, stamp_the_set, node_bound: int, weighting=None) -> SampledSubgraph:
+        """stamp_the_set() enqueues what stamps the node set (at most node_bound nodes); everything behind it is the same.
+        weighting = (VisitCounts, max_edge_weight): the emit also writes GraphSAINT's per-edge weights (message_weights)."""
         try:
             with torch.cuda.device(self.graph.device):
-                return self._induced(stamp_the_set, int(node_bound))
+                return self._induced(stamp_the_set, int(node_bound), weighting)
         except BaseException:
             self.stamp.zero_()                                    # whatever a half-run call stamped
             raise
 
-    def _induced(self, stamp_the_set, B: int) -> SampledSubgraph:
+    def _induced(self, stamp_the_set, B: int, weighting=None) -> SampledSubgraph:
         lib, g = _lib.load_library(), self.graph
         V, L, dev = g.V, g.L, g.device
         i32 = lambda n: torch.empty(int(n), dtype=torch.int32, device=dev)
@@ -104,8 +109,17 @@ class _Extractor:
         nodes = nodes_buf[:n]
         edges = torch.empty((total, 2), dtype=torch.int32, device=dev)
         degrees = torch.empty((L, n), dtype=torch.float32, device=dev)
-        _lib.launch("relgnn_subgraph_induced_emit", _lib.ptr(g.rowptr_t), _lib.ptr(g.col_t), V, L, _lib.ptr(nodes_buf), n, B,
-                    _lib.ptr(self.stamp), _lib.ptr(offsets), total, _lib.ptr(edges) if total else None, _lib.ptr(degrees))
+        message_weights = None
+        if weighting is None:
+            _lib.launch("relgnn_subgraph_induced_emit", _lib.ptr(g.rowptr_t), _lib.ptr(g.col_t), V, L, _lib.ptr(nodes_buf), n, B,
+                        _lib.ptr(self.stamp), _lib.ptr(offsets), total, _lib.ptr(edges) if total else None, _lib.ptr(degrees))
+        else:                                                     # the same edges and degrees, and the per-edge weights in their order
+            counts_of, cap = weighting
+            message_weights = torch.empty(total, dtype=torch.float32, device=dev)
+            _lib.launch("relgnn_subgraph_induced_emit_weighted", _lib.ptr(g.rowptr_t), _lib.ptr(g.col_t), V, L, g.M, _lib.ptr(nodes_buf),
+                        n, B, _lib.ptr(self.stamp), _lib.ptr(offsets), _lib.ptr(counts_of.node_visits),
+                        _lib.ptr(counts_of.edge_visits) if g.M else None, float(cap), total, _lib.ptr(edges) if total else None,
+                        _lib.ptr(degrees), _lib.ptr(message_weights) if total else None)
         _lib.launch("relgnn_subgraph_clear", _lib.ptr(nodes_buf), n, _lib.ptr(self.stamp), V)
         self._mark("induced_emit")
         adjacency, first = [], 0
@@ -113,7 +127,25 @@ class _Extractor:
             adjacency.append(edges[first:first + e])
             first += e
         seed_mask = torch.ones(n, dtype=torch.float32, device=dev)        # every node of the subgraph may count in the loss
-        return SampledSubgraph(nodes, adjacency, degrees, seed_mask, n, total)
+        return SampledSubgraph(nodes, adjacency, degrees, seed_mask, n, total, message_weights)
+
+
+class VisitCounts(NamedTuple):
+    """How often the pre-sampled subgraphs hold a node and a by-target entry (include/relgnn_subgraph_norm.h): GraphSAINT's C_v and
+    C_{u,v} for a node-induced sampler.  On the device; a pure function of (seed, E, R, h, the fold, the graph)."""
+    node_visits: torch.Tensor                   # int32 [V]
+    edge_visits: torch.Tensor                   # int32 [M], aligned with RelGraph.col_t
+    num_subgraphs: int                          # N = E * ceil(n_fold / R)
+
+    def node_weights(self, nodes: torch.Tensor) -> torch.Tensor:
+        """The loss weight of every node of a batch: (float)N / (float)max(node_visits[v], 1), float32 [n]."""
+        visits = self.node_visits.index_select(0, nodes.long()).clamp_(min=1).to(torch.float32)
+        return torch.full_like(visits, float(self.num_subgraphs)) / visits
+
+
+# the walks of the pre-sampled subgraphs: never a training batch's draws (replica 0) nor an evaluation batch's (0x40000000 | fold)
+PRESAMPLE_REPLICA = 0x20000000
+PRESAMPLE_EPOCH = 0x80000000                    # the root lists of pre-sampling epoch e are epoch_seed_batches' of epoch 0x80000000 + e
 
 
 class SubgraphSampler(_Extractor):
@@ -127,9 +159,11 @@ class SubgraphSampler(_Extractor):
         super().__init__(graph, "subgraph sampling")
         self.seed, self.replica = int(seed) & 0xffffffff, int(replica)
 
-    def sample(self, roots, draw: int) -> SampledSubgraph:
+    def sample(self, roots, draw: int, weighting=None) -> SampledSubgraph:
         """roots: int32 device tensor (a host array is uploaded), distinct node ids, one walk each; draw: the count of sampled batches
-        so far.  -> the subgraph induced on the nodes the walks visit, seed_mask all ones."""
+        so far.  -> the subgraph induced on the nodes the walks visit, seed_mask all ones.  weighting = (VisitCounts of presample(),
+        max_edge_weight): the subgraph also carries GraphSAINT's per-edge weights, message_weights float32 [num_edges] in the order of
+        the lists; the lists and the degrees are the unweighted call's."""
         g = self.graph
         roots = _validated(roots, g.V, g.device, "root")
         R, draw = int(roots.numel()), int(draw) & 0xffffffff
@@ -137,7 +171,45 @@ class SubgraphSampler(_Extractor):
         def walks():
             _lib.launch("relgnn_subgraph_walk", _lib.ptr(g.rowptr_t), _lib.ptr(g.col_t), g.V, g.L, _lib.ptr(roots), R, self.walk_length,
                         draw, self.seed, self.replica, _lib.ptr(self.stamp))
-        return self._run(walks, min(g.V, R * (self.walk_length + 1)))
+        return self._run(walks, min(g.V, R * (self.walk_length + 1)), weighting)
+
+    def presample(self, fold_mask, roots_per_batch: int, epochs: int) -> VisitCounts:
+        """GraphSAINT's pre-sampling: E = `epochs` epochs of root lists, epoch_seed_batches(fold_mask, R, seed, 0x80000000 + e), every
+        list walked with the reserved replica 0x20000000 and draw = the running index of the pre-sampled subgraph, and counted
+        (relgnn_subgraph_visit_count).  Per subgraph: walk, compact, number, count, a reset of the stamps; NOTHING is read back, the
+        set's size stays on the device and the buffers are sized from the bound min(V, R * (h + 1))."""
+        lib, g = _lib.load_library(), self.graph
+        V, L, dev = g.V, g.L, g.device
+        R, epochs = int(roots_per_batch), int(epochs)
+        if R < 1 or epochs < 1:
+            raise ValueError("presample: roots_per_batch and epochs must be positive, got %r and %r" % (roots_per_batch, epochs))
+        if not lib.relgnn_subgraph_supported(R, self.walk_length, V, L):
+            raise ValueError("presample: %d walks of %d steps are not supported (relgnn_subgraph_supported)" % (R, self.walk_length))
+        B = min(V, R * (self.walk_length + 1))
+        counts = VisitCounts(torch.zeros(V, dtype=torch.int32, device=dev), torch.zeros(g.M, dtype=torch.int32, device=dev), 0)
+        drawn = 0
+        try:
+            with torch.cuda.device(dev):
+                nodes_buf = torch.empty(B, dtype=torch.int32, device=dev)
+                count = torch.zeros(1, dtype=torch.int32, device=dev)
+                ws = _lib.scratch(self._compact_bytes, dev)
+                for e in range(epochs):
+                    for roots in epoch_seed_batches(fold_mask, R, self.seed, PRESAMPLE_EPOCH + e):       # in range, distinct, ascending
+                        roots = torch.as_tensor(roots, device=dev)
+                        _lib.launch("relgnn_subgraph_walk", _lib.ptr(g.rowptr_t), _lib.ptr(g.col_t), V, L, _lib.ptr(roots), roots.numel(),
+                                    self.walk_length, drawn & 0xffffffff, self.seed, PRESAMPLE_REPLICA, _lib.ptr(self.stamp))
+                        _lib.launch("relgnn_neighbour_sample_compact", _lib.ptr(self.stamp), V, 0, _lib.ptr(nodes_buf), B, _lib.ptr(count),
+                                    _lib.ptr(ws), self._compact_bytes)
+                        _lib.launch("relgnn_subgraph_number", _lib.ptr(nodes_buf), _lib.ptr(count), B, _lib.ptr(self.stamp), V)
+                        _lib.launch("relgnn_subgraph_visit_count", _lib.ptr(g.rowptr_t), _lib.ptr(g.col_t) if g.M else None, V, L, g.M,
+                                    _lib.ptr(nodes_buf), _lib.ptr(count), B, _lib.ptr(self.stamp), _lib.ptr(counts.node_visits),
+                                    _lib.ptr(counts.edge_visits) if g.M else None)
+                        self.stamp.zero_()                        # (the set's size never reaches the host: the whole array)
+                        drawn += 1
+        except BaseException:
+            self.stamp.zero_()
+            raise
+        return counts._replace(num_subgraphs=drawn)
 
 
 def induced_subgraph(graph: RelGraph, nodes) -> SampledSubgraph:
@@ -151,12 +223,38 @@ def induced_subgraph(graph: RelGraph, nodes) -> SampledSubgraph:
     return extractor._run(given, int(nodes.numel()))
 
 
+def parse_normalisation(value) -> Dict:
+    """The key "normalisation" of `subgraph_batches` as {"presample_epochs": int >= 1, "aggregation": bool, "max_edge_weight": float > 0}
+    (the last two optional: true and 1e4, GraphSAINT's own clip), or a ValueError that names the key."""
+    what = "subgraph_batches: normalisation"
+    known = ("presample_epochs", "aggregation", "max_edge_weight")
+    if not isinstance(value, dict):
+        raise ValueError('%s must be {"presample_epochs": E, "aggregation": bool, "max_edge_weight": c}, the last two optional, got %r'
+                         % (what, value))
+    unknown = sorted(set(value) - set(known), key=str)
+    if unknown:
+        raise ValueError("%s: unknown key %s (known: %s)" % (what, ", ".join(repr(k) for k in unknown), ", ".join(known)))
+    if "presample_epochs" not in value:
+        raise ValueError("%s: presample_epochs is required" % what)
+    epochs = value["presample_epochs"]
+    if isinstance(epochs, bool) or not isinstance(epochs, (int, np.integer)) or epochs < 1:
+        raise ValueError("%s: presample_epochs must be an integer >= 1, got %r" % (what, epochs))
+    aggregation = value.get("aggregation", True)
+    if not isinstance(aggregation, bool):
+        raise ValueError("%s: aggregation must be true or false, got %r" % (what, aggregation))
+    cap = value.get("max_edge_weight", 1e4)
+    if isinstance(cap, bool) or not isinstance(cap, (int, float, np.integer, np.floating)) or not 0 < float(cap) < float("inf"):
+        raise ValueError("%s: max_edge_weight must be a finite number > 0, got %r" % (what, cap))
+    return {"presample_epochs": int(epochs), "aggregation": aggregation, "max_edge_weight": float(cap)}
+
+
 def parse_subgraph_batches(value) -> Optional[Dict]:
     """The task parameter `subgraph_batches` as {"roots_per_batch": int, "walk_length": int, "seed": int}, None when it is absent;
-    the optional key "sparse_features" (a bool: the batches take their feature rows from a SparseRows) is carried only when given."""
+    the optional keys "sparse_features" (a bool: the batches take their feature rows from a SparseRows) and "normalisation"
+    (parse_normalisation: GraphSAINT's loss and aggregation weights) are carried only when given."""
     if value is None:
         return None
-    known = {"roots_per_batch", "walk_length", "seed", "sparse_features"}
+    known = {"roots_per_batch", "walk_length", "seed", "sparse_features", "normalisation"}
     unknown = sorted(set(value) - known, key=str) if isinstance(value, dict) else []
     if not isinstance(value, dict) or unknown or not {"roots_per_batch", "walk_length"} <= set(value):
         said = "; unknown key %s" % ", ".join(repr(k) for k in unknown) if unknown else ""
@@ -177,4 +275,6 @@ def parse_subgraph_batches(value) -> Optional[Dict]:
         if not isinstance(value["sparse_features"], bool):
             raise ValueError("subgraph_batches: sparse_features must be true or false, got %r" % (value["sparse_features"],))
         parsed["sparse_features"] = value["sparse_features"]
+    if "normalisation" in value:
+        parsed["normalisation"] = parse_normalisation(value["normalisation"])
     return parsed
