@@ -164,7 +164,7 @@ def run_case(case, task, V):
     named = bool(task.sparse_gradient)
     fold = task._loaded_data[DataFold.TRAIN][0]
     task.bind_sampling_device(dev)
-    state = task._sampling_state_of(fold, dev)
+    state = task.batches.neighbour_state(fold, dev)
     sampler = NeighbourSampler(state.sampler.graph, fanouts, seed=0)      # (the state's sampler has the fanouts of the first case)
     p = RGCN_Model.default_params()
     p.update(hidden_size=HIDDEN, graph_num_layers=H, graph_layer_input_dropout_keep_prob=1.0, random_seed=1)

@@ -66,7 +66,7 @@ def main():
     p.update(hidden_size=HIDDEN, graph_num_layers=2, graph_layer_input_dropout_keep_prob=1.0, random_seed=1)
     model = RGCN_Model(p, task, device=str(dev))
     task.bind_sampling_device(dev)
-    state = task._sampling_state_of(fold, dev)
+    state = task.batches.neighbour_state(fold, dev)
     sampler = state.sampler
     rowptr = sampler.graph.rowptr_t
     longest = int((rowptr[1:] - rowptr[:-1]).max())

@@ -113,7 +113,7 @@ def release(task, kept=True):
     """Between two timed epochs only the graph cache goes (every epoch buckets its batches, as an epoch behind a training epoch
     does); the allocator's blocks stay, as they do in a training loop."""
     if kept:
-        task._kept_evaluation.clear()
+        task.batches.kept_evaluation.clear()
         torch.cuda.empty_cache()
     clear_graph_cache()
 

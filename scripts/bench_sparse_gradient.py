@@ -148,7 +148,7 @@ def main():
     opts = {which: models[which].optimizer for which in models}
     assert opts["on"].row_gradient_sink is not None and opts["off"].row_gradient_sink is None and opts["off"]._deferred is not None
     task.bind_sampling_device(dev)
-    state = task._sampling_state_of(fold, dev)
+    state = task.batches.neighbour_state(fold, dev)
     rng = np.random.RandomState(0)
     batches = []
     for draw in range(BATCHES):

@@ -127,7 +127,7 @@ def main():
     opt = models["on"].optimizer
     assert opt._deferred is not None and models["off"].optimizer._deferred is None
     task.bind_sampling_device(dev)
-    state = task._sampling_state_of(fold, dev)
+    state = task.batches.neighbour_state(fold, dev)
     rng = np.random.RandomState(0)
     batches = []
     for draw in range(BATCHES):

@@ -82,7 +82,7 @@ def main():
     p.update(hidden_size=HIDDEN, graph_num_layers=LAYERS, graph_layer_input_dropout_keep_prob=1.0, random_seed=1)
     model = RGCN_Model(p, task, device=str(dev))
     task.bind_sampling_device(dev)
-    state = task._subgraph_state_of(fold, dev)              # the fold's labels and mask; the graph and the table the folds share
+    state = task.batches.subgraph_state(fold, dev)              # the fold's labels and mask; the graph and the table the folds share
     graph = state.sampler.graph
     samplers = {h: SubgraphSampler(graph, h, seed=0) for h in WALK_LENGTHS}
     neighbour = NeighbourSampler(graph, FANOUTS, seed=0)

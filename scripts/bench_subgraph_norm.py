@@ -87,7 +87,7 @@ def main():
     model = RGCN_Model(p, task, device=str(dev))
     task.bind_sampling_device(dev)
     t0 = time.time()
-    state = task._subgraph_state_of(fold, dev)              # pre-samples once (the first call also pays the graph's bucketing)
+    state = task.batches.subgraph_state(fold, dev)              # pre-samples once (the first call also pays the graph's bucketing)
     torch.cuda.synchronize()
     print("sampling state with the counts in %.1f s" % (time.time() - t0), flush=True)
     sampler, counts = state.sampler, state.visit_counts

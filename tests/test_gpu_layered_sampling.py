@@ -382,7 +382,7 @@ def test_train_with_the_key(gpu_device, tmp_path, native_batching):
     assert [(r[1], r[2]) for r in record] == [(5, 5), (1, 1), (5, 5), (1, 1)], record
     assert record[0][3] == [32.0, 32.0, 32.0, 32.0, 12.0] and record[1][3] == [None]              # validation: no sampled batch
     assert all(math.isfinite(x) for r in record for x in r[4])
-    assert (task._sampling_epoch, task._sampling_draw) == (2, 10)
+    assert (task.batches.epoch, task.batches.draw) == (2, 10)
     log = open(model.log_file).read()
     assert log.count(" Train: loss:") == 2 and log.count(" Valid: loss:") == 2 and "Acc:" in log
     restored = models.restore(model.best_model_file, str(tmp_path), device=str(gpu_device))

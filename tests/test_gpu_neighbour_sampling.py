@@ -255,7 +255,7 @@ def test_train_on_sampled_batches(gpu_device, tmp_path):
     # 5 steps per training epoch (140 seeds: four batches of 32 and one of 12), one full-graph validation pass
     assert [(r[1], r[2]) for r in record] == [(5, 5), (1, 1), (5, 5), (1, 1)], record
     assert record[0][3] == [32.0, 32.0, 32.0, 32.0, 12.0] and record[1][3] == [None]
-    assert (task._sampling_epoch, task._sampling_draw) == (2, 10)
+    assert (task.batches.epoch, task.batches.draw) == (2, 10)
     log = open(model.log_file).read()
     assert log.count(" Train: loss:") == 2 and log.count(" Valid: loss:") == 2 and "Acc:" in log
     for pipeline in ({}, {"native_batching": False}):                 # either iterator, and again: identical weights
@@ -285,7 +285,7 @@ def test_train_on_sampled_batches(gpu_device, tmp_path):
     for batches in (native, numpy_side):
         assert len(batches) == 5 and all(isinstance(b, DeviceBatch) and "sampled_nodes" in b.extra for b in batches)
         assert [float(b.extra["mask"].sum()) for b in batches] == [32.0, 32.0, 32.0, 32.0, 12.0]
-    assert (task._sampling_epoch, task._sampling_draw) == (4, 20)
+    assert (task.batches.epoch, task.batches.draw) == (4, 20)
     # restore() of the sampled run's best model: the parameter comes back, predict() is the full graph
     restored = models.restore(model.best_model_file, str(tmp_path), device=str(gpu_device))
     assert restored.task.sampled_batches == sampled["sampled_batches"]

@@ -203,7 +203,7 @@ def test_sampled_batches_are_the_reference_sampler_s(gpu_device, fanouts):
                     assert same_bits(level.type_to_num_incoming_edges.cpu().numpy(), table)
                     assert all(np.array_equal(g.cpu().numpy(), ref) for g, ref in zip(level.adjacency_lists, lists))
         # hand-fed: a sampler of the documented replica over a graph of its own, no bucketing brought along
-        state = task._sampling_state_of(fold, gpu_device, fanouts, 5, 0x40000000 | data_fold.value)
+        state = task.batches.neighbour_state(fold, gpu_device, fanouts, 5, 0x40000000 | data_fold.value)
         sampler = NeighbourSampler(state.sampler.graph, fanouts, seed=5, replica=0x40000000 | data_fold.value)
         _, res, graphs, _, _, _ = model._run_epoch("evaluation", data, data_fold, quiet=True)
         assert graphs == 1 and len(res) == len(epochs[0])
@@ -212,7 +212,7 @@ def test_sampled_batches_are_the_reference_sampler_s(gpu_device, fanouts):
             with torch.no_grad():
                 want = {k: float(v) for k, v in model.forward_batch(batch, training=False).items()}
             assert {k: np.float32(m[k]).tobytes() for k in want} == {k: np.float32(v).tobytes() for k, v in want.items()}, (data_fold, i)
-    assert (task._sampling_epoch, task._sampling_draw) == (0, 0)
+    assert (task.batches.epoch, task.batches.draw) == (0, 0)
 
 
 # ---- train() -------------------------------------------------------------------------------------------------------------------------
@@ -252,7 +252,7 @@ def test_train_with_the_key_trains_what_the_full_graph_run_trains(gpu_device, tm
     (task_a, model_a, rec_a, ckpt_a), (task_b, model_b, rec_b, ckpt_b) = runs["key"], runs["full"]
     train_a, train_b = ([r for r in rec if "training" in r[0]] for rec in (rec_a, rec_b))
     assert len(train_a) == 2 and [[m["loss"] for m in r[2]] for r in train_a] == [[m["loss"] for m in r[2]] for r in train_b]
-    assert (task_a._sampling_epoch, task_a._sampling_draw) == (task_b._sampling_epoch, task_b._sampling_draw) == (2, 8)      # ceil(60 / 16) = 4
+    assert (task_a.batches.epoch, task_a.batches.draw) == (task_b.batches.epoch, task_b.batches.draw) == (2, 8)      # ceil(60 / 16) = 4
     assert sorted(ckpt_a["weights"]) == sorted(ckpt_b["weights"])
     assert all(np.array_equal(ckpt_a["weights"][k], ckpt_b["weights"][k]) for k in ckpt_a["weights"])
     assert model_a.best_epoch == model_b.best_epoch
@@ -350,7 +350,7 @@ def test_predict_nodes_gives_the_rows_of_predict(gpu_device, sparse, native_batc
     _assert_untouched(model, gpu_device, before)
     with pytest.raises(ValueError):
         model.predict(data, nodes=[V])
-    assert not task._kept_evaluation and task.sampled_batches is None
+    assert not task.batches.kept_evaluation and task.sampled_batches is None
 
 
 def test_predict_nodes_with_the_key_runs_the_key_s_batches(gpu_device):
@@ -369,7 +369,7 @@ def test_predict_nodes_with_the_key_runs_the_key_s_batches(gpu_device):
     before = _snapshot(model, gpu_device)
     out = model.predict(data, nodes=nodes, return_states=True)
     distinct = np.unique(nodes).astype(np.int32)
-    state = task._sampling_state_of(data[0], gpu_device, [3, 2], 5, evaluation_replica(PREDICT_FOLD))
+    state = task.batches.neighbour_state(data[0], gpu_device, [3, 2], 5, evaluation_replica(PREDICT_FOLD))
     sampler = NeighbourSampler(state.sampler.graph, [3, 2], seed=5, replica=0x40000003)
     rows = {"probabilities": [], "classes": [], "node_states": []}
     for i in range(0, len(distinct), 7):
@@ -413,9 +413,9 @@ def test_three_folds_share_one_graph_and_one_feature_table(gpu_device, sparse):
         del batch
         torch.cuda.synchronize()
         allocated.append(torch.cuda.memory_allocated(gpu_device))
-    assert len(task._graph_state) == 1 and len(task._sampling_state) == 3
-    (_, _, shared), = task._graph_state.values()
-    states = [state for _, state in task._sampling_state.values()]
+    assert len(task.batches.graph_states) == 1 and len(task.batches.fold_states) == 3
+    (shared,) = task.batches.graph_states.values()
+    states = task.batches.fold_states.values()
     assert all(s.sampler.graph is shared.graph and s.features is shared.features for s in states)
     assert sorted(s.sampler.replica for s in states) == [0, 0x40000001, 0x40000002]
     assert len({id(s.labels) for s in states}) == 3 and len({id(s.sampler) for s in states}) == 3

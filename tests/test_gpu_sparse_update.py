@@ -351,7 +351,7 @@ def test_two_models_from_one_seed_key_on_and_key_off(gpu_device, tmp_path):
     assert restored.task.sparse_update and restored.optimizer._deferred is not None and restored.optimizer.t == off.optimizer.t == 10
     assert restored.optimizer._deferred.base == 10 and restored.optimizer.pending_rows() == 0
     restored.task.load_synthetic(**SYNTHETIC)
-    restored.task._sampling_epoch, restored.task._sampling_draw = off.task._sampling_epoch, off.task._sampling_draw
+    restored.task.batches.epoch, restored.task.batches.draw = off.task.batches.epoch, off.task.batches.draw
     assert _epoch_in_lockstep(restored, off, check_mid_epoch=False) == 4
     assert restored.optimizer.pending_rows() > 0
     # predict() and test() bring the rows up to date themselves

@@ -432,7 +432,7 @@ def test_train_on_subgraph_batches(gpu_device, tmp_path):
         assert np.isfinite(epoch[4]).all()
     assert record[0][5] != record[2][5] and record[1][3] == [None] and record[1][5] == []
     assert any(masked > len(r) for epoch in (record[0], record[2]) for masked, r in zip(epoch[3], epoch[5]))
-    assert (task._sampling_epoch, task._sampling_draw) == (2, 2 * steps)
+    assert (task.batches.epoch, task.batches.draw) == (2, 2 * steps)
     with open(model.best_model_file, "rb") as f:
         saved_bits = {k: np.asarray(v).tobytes() for k, v in pickle.load(f)["weights"].items()}
     for pipeline in ({}, {"native_batching": False}):                 # either iterator, and again: the same losses, the same checkpoint
@@ -448,8 +448,8 @@ def test_train_on_subgraph_batches(gpu_device, tmp_path):
     numpy_side = list(task.make_minibatch_iterator(train, DataFold.TRAIN, 10 ** 6))
     for batches in (native, numpy_side):
         assert len(batches) == steps and all(isinstance(b, DeviceBatch) and "sampled_nodes" in b.extra for b in batches)
-    assert (task._sampling_epoch, task._sampling_draw) == (4, 4 * steps)
-    assert len(task._graph_state) == 1                                # one device RelGraph and one feature table
+    assert (task.batches.epoch, task.batches.draw) == (4, 4 * steps)
+    assert len(task.batches.graph_states) == 1                                # one device RelGraph and one feature table
     # restore(): the parameter comes back and the restored model trains on with it
     restored = models.restore(model.best_model_file, str(tmp_path), device=str(gpu_device))
     assert restored.task.subgraph_batches == SUBGRAPH["subgraph_batches"] and restored.task.get_metadata() == task.get_metadata()

@@ -489,7 +489,7 @@ def _train_two_epochs(device, result_dir, model_name, params, **model_params):
 
 
 def _counts_of(task):
-    (held,) = [state for _, state in task._sampling_state.values() if state.visit_counts is not None]
+    (held,) = [state for state in task.batches.fold_states.values() if state.visit_counts is not None]
     return held.visit_counts
 
 
@@ -567,7 +567,7 @@ def test_without_the_key_a_batch_is_the_sampler_s_plain_batch(gpu_device, tmp_pa
     train = task._loaded_data[DataFold.TRAIN]
     batch = next(iter(model._batches(train, DataFold.TRAIN)))
     assert "loss_normalisation" not in batch.extra and getattr(batch, "graph", None) is None
-    state = task._subgraph_state_of(train[0], gpu_device)
+    state = task.batches.subgraph_state(train[0], gpu_device)
     assert state.visit_counts is None
     roots = epoch_seed_batches(train[0].mask, 32, 1, 0)[0]
     sub = state.sampler.sample(roots, 0)

@@ -345,7 +345,7 @@ def _cpu_model_with_logged_batches(monkeypatch, log):
     p.update(hidden_size=16, graph_num_layers=1, max_nodes_in_batch=125, native_batching=False)
     model = RGCN_Model(p, task, device="cpu")
     batches = model._batches
-    monkeypatch.setattr(model, "_batches", lambda data, fold: _LoggedBatches(batches(data, fold), log))
+    monkeypatch.setattr(model, "_batches", lambda data, fold, **how: _LoggedBatches(batches(data, fold, **how), log))
     return model, task._loaded_data[DataFold.TRAIN]
 
 

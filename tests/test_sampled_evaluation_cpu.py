@@ -184,17 +184,17 @@ class _Recorder:
 
     def __init__(self, monkeypatch, task):
         self.states, self.batches = [], []
-        monkeypatch.setattr(task, "_sampling_device", "cuda:0")
+        monkeypatch.setattr(task.batches, "device", "cuda:0")
 
         def state_of(fold, device, fanouts=None, seed=None, replica=0):
             self.states.append((None if fanouts is None else list(fanouts), seed, replica))
             return ("state", replica)
-        monkeypatch.setattr(task, "_sampling_state_of", state_of)
+        monkeypatch.setattr(task.batches, "neighbour_state", state_of)
 
         def batch(state, seeds, draw, full_graph_route):
             self.batches.append((state[1], draw, seeds.tolist(), full_graph_route))
             return type("Batch", (), {"extra": {}, "seeds": seeds, "draw": draw})()
-        monkeypatch.setattr(task, "_evaluation_batch", batch)
+        monkeypatch.setattr(task.batches, "evaluation_batch", batch)
 
 
 def test_the_draws_are_a_function_of_seed_fold_and_batch_index(monkeypatch):
@@ -217,11 +217,11 @@ def test_the_draws_are_a_function_of_seed_fold_and_batch_index(monkeypatch):
     rec.batches = []
     list(task.evaluation_batches(task.synthetic_test_data, DataFold.TEST, False))
     assert {b[0] for b in rec.batches} == {0x40000002} and [b[1] for b in rec.batches] == [0, 1, 2, 3, 4]
-    assert (task._sampling_epoch, task._sampling_draw) == (0, 0)
+    assert (task.batches.epoch, task.batches.draw) == (0, 0)
     # the training batches: the parameter's own fanouts and seed, replica 0
     rec.states = []
-    monkeypatch.setattr(type(task), "_sampled_batches_of", lambda self, fold: iter(()))
-    task._sampling_state_of(valid[0], "cuda:0")
+    monkeypatch.setattr(type(task.batches), "neighbour_batches", lambda self, fold: iter(()))
+    task.batches.neighbour_state(valid[0], "cuda:0")
     assert rec.states == [(None, None, 0)]
     # the reference sampler: one (seed, replica, draw) is one subgraph; the evaluation replica's is not the training one's
     _, (rowptr, col, _) = LR.graph(2)
@@ -249,17 +249,17 @@ def test_kept_batches_are_handed_out_again_and_released_with_the_fold(monkeypatc
     other_route = list(task.evaluation_batches(valid, DataFold.VALIDATION, False))              # another route: other batches
     assert len(rec.batches) == 2 * built and other_route[0] is not first[0]
     test = list(task.evaluation_batches(task.synthetic_test_data, DataFold.TEST, True))
-    assert test[0] is not first[0] and len(task._kept_evaluation) == 3
+    assert test[0] is not first[0] and len(task.batches.kept_evaluation) == 3
     # an iterator that is abandoned keeps nothing
     fresh = _loaded(_task(sampled_batches=dict(PLAIN, evaluation=dict(EVALUATION, keep=True))))
     _Recorder(monkeypatch, fresh)
     next(iter(fresh.evaluation_batches(fresh._loaded_data[DataFold.VALIDATION], DataFold.VALIDATION, True)))
-    assert not fresh._kept_evaluation
+    assert not fresh.batches.kept_evaluation
     # released with the fold
     del valid, first, second, other_route
     task._loaded_data[DataFold.VALIDATION] = None
     gc.collect()
-    assert len(task._kept_evaluation) == 1                                                   # the test fold's
+    assert len(task.batches.kept_evaluation) == 1                                                   # the test fold's
 
 
 def test_the_epoch_adds_up_to_the_fold_s_one_graph():
@@ -347,7 +347,7 @@ def test_predict_nodes_maps_duplicates_and_order_with_a_stand_in_forward(monkeyp
         rec.batches.append((state[1], draw, seeds.tolist(), full_graph_route))
         levels = [None, type("Level", (), {"num_targets": len(seeds)})()]
         return DeviceBatch.from_tensors(1, 50, 0, torch.zeros((50, 1)), [], torch.zeros((2, 50)), extra={"layer_graphs": levels})
-    monkeypatch.setattr(task, "_evaluation_batch", batch)
+    monkeypatch.setattr(task.batches, "evaluation_batch", batch)
 
     def stand_in(batch, training):
         seeds = torch.as_tensor(batch.extra["prediction_seeds"]).float()

@@ -8,6 +8,7 @@
 #include "adam_element.h"
 #include "norm_tree.h"
 #include "../../include/relgnn_subgraph_norm.h"
+#include <type_traits>
 
 using namespace relgnn;
 
@@ -355,33 +356,45 @@ __global__ __launch_bounds__(256) void softmax_ce_stats_kernel(const float* __re
   s = block_sum_1024(correct, red); if (threadIdx.x == 0) partial[blockIdx.x * 3 + 2] = s;
 }
 
-// 256 threads: thread b holds the three partial sums of block b (nblk may be 0: no rows); fixed-shape tree reduction
-__global__ __launch_bounds__(256) void softmax_ce_stats_final_kernel(const double* __restrict__ partial, int nblk,
-                                                                     float* __restrict__ stats) {
-  __shared__ double red[4][3];
+// 256 threads: thread b holds the partial sums of block b (nblk may be 0: no rows); fixed-shape tree reduction.  The loss is divided
+// by the sum of the mask, or (weighted) by the caller's denominator.
+template <bool kWeighted>
+__device__ __forceinline__ void softmax_ce_stats_tree(const double* __restrict__ partial, int nblk, float denominator,
+                                                      float* __restrict__ stats) {
+  constexpr int kSums = kWeighted ? 4 : 3;
+  __shared__ double red[4][kSums];
   const int b = threadIdx.x;
-  double v[3];
+  double v[kSums];
 #pragma unroll
-  for (int k = 0; k < 3; ++k) v[k] = b < nblk ? partial[b * 3 + k] : 0.0;
+  for (int k = 0; k < kSums; ++k) v[k] = b < nblk ? partial[b * kSums + k] : 0.0;
 #pragma unroll
-  for (int k = 0; k < 3; ++k) {
+  for (int k = 0; k < kSums; ++k) {
 #pragma unroll
     for (int off = 32; off >= 1; off >>= 1) v[k] += __shfl_xor(v[k], off);
   }
   const int wave = b >> 6, lane = b & 63;
   if (lane == 0) {
 #pragma unroll
-    for (int k = 0; k < 3; ++k) red[wave][k] = v[k];
+    for (int k = 0; k < kSums; ++k) red[wave][k] = v[k];
   }
   __syncthreads();
   if (b == 0) {
-    float t[3];
+    float t[kSums];
 #pragma unroll
-    for (int k = 0; k < 3; ++k) t[k] = stats[k] = (float)((red[0][k] + red[1][k]) + (red[2][k] + red[3][k]));
+    for (int k = 0; k < kSums; ++k) t[k] = (float)((red[0][k] + red[1][k]) + (red[2][k] + red[3][k]));
+#pragma unroll
+    for (int k = 0; k < 3; ++k) stats[k] = t[k];
     // float32 quotients of the float32 sums, as the reference's graph forms them (:141, :145); 0 / 0 stays NaN
-    stats[3] = t[0] / t[1];
+    if constexpr (kWeighted) stats[3] = t[0] / denominator;
+    else stats[3] = t[0] / t[1];
     stats[4] = t[2] / t[1];
+    if constexpr (kWeighted) stats[5] = t[3];
   }
+}
+
+__global__ __launch_bounds__(256) void softmax_ce_stats_final_kernel(const double* __restrict__ partial, int nblk,
+                                                                     float* __restrict__ stats) {
+  softmax_ce_stats_tree<false>(partial, nblk, 0.f, stats);
 }
 
 // glogits[v, c] = mask_v * (softmax(logits_v)_c - [c == label_v]) * (g_total[0] + g_loss[0] / stats[1]) for c < cols, 0 for
@@ -419,6 +432,8 @@ __global__ __launch_bounds__(256) void softmax_ce_bwd_kernel(const float* __rest
 // stats = {sum_v loss_v mask_v weight_v, sum_v mask_v, sum_v [argmax_v == label_v] mask_v, stats[0] / denominator, stats[2] / stats[1],
 // sum_v mask_v weight_v}: the row walk, the per-row loss and the order of every sum are softmax_ce_stats_kernel's, so that with every
 // weight 1 the first three sums are its bits (mask * 1 and l * (mask * 1) are exact).  partial[block * 4 + {0, 1, 2, 3}].
+// (This kernel and softmax_ce_weighted_bwd_kernel keep bodies of their own next to the plain ones: as one inlined function per pair
+// hipcc lays the row loop's blocks out differently (profiles/citation_batches.txt).  The final trees and the host wrappers are shared.)
 template <int W>
 __global__ __launch_bounds__(256) void softmax_ce_weighted_stats_kernel(const float* __restrict__ logits, long long ld,
                                                                         const int* __restrict__ labels, const float* __restrict__ mask,
@@ -452,36 +467,10 @@ __global__ __launch_bounds__(256) void softmax_ce_weighted_stats_kernel(const fl
   s = block_sum_1024(wsum, red);    if (threadIdx.x == 0) partial[blockIdx.x * 4 + 3] = s;
 }
 
-// softmax_ce_stats_final_kernel's tree over four sums; the loss is divided by the caller's denominator, not by the sum of the mask
+// softmax_ce_stats_tree over four sums; the loss is divided by the caller's denominator, not by the sum of the mask
 __global__ __launch_bounds__(256) void softmax_ce_weighted_stats_final_kernel(const double* __restrict__ partial, int nblk,
                                                                               float denominator, float* __restrict__ stats) {
-  __shared__ double red[4][4];
-  const int b = threadIdx.x;
-  double v[4];
-#pragma unroll
-  for (int k = 0; k < 4; ++k) v[k] = b < nblk ? partial[b * 4 + k] : 0.0;
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v[k] += __shfl_xor(v[k], off);
-  }
-  const int wave = b >> 6, lane = b & 63;
-  if (lane == 0) {
-#pragma unroll
-    for (int k = 0; k < 4; ++k) red[wave][k] = v[k];
-  }
-  __syncthreads();
-  if (b == 0) {
-    float t[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) t[k] = (float)((red[0][k] + red[1][k]) + (red[2][k] + red[3][k]));
-    stats[0] = t[0];
-    stats[1] = t[1];
-    stats[2] = t[2];
-    stats[3] = t[0] / denominator;
-    stats[4] = t[2] / t[1];
-    stats[5] = t[3];
-  }
+  softmax_ce_stats_tree<true>(partial, nblk, denominator, stats);
 }
 
 // glogits[v, c] = mask_v * weight_v * (softmax(logits_v)_c - [c == label_v]) * (g_total[0] + g_loss[0] / denominator) for c < cols, 0
@@ -522,6 +511,62 @@ static inline int softmax_grid(long long rows, int w) {
   const long long per_block = 256 / w;
   long long g = (rows + per_block - 1) / per_block;
   return (int)(g < 1 ? 1 : (g > kSoftmaxBlocks ? kSoftmaxBlocks : g));
+}
+
+// The argument checks, the grid and the W dispatch of both heads' entry points (kWeighted: the weights must be there, the denominator
+// a number other than 0, and the workspace holds four sums a block).
+template <bool kWeighted>
+int softmax_ce_stats_launch(const float* logits, int64_t ld, const int32_t* labels, const float* mask, const float* weights,
+                            float denominator, int64_t rows, int32_t cols, float* stats, void* workspace, size_t workspace_bytes,
+                            void* stream) {
+  if (rows < 0 || cols < 1 || ld < cols || !stats || (kWeighted && (denominator == 0.f || denominator != denominator)))
+    return RELGNN_EINVAL;
+  if (!workspace || workspace_bytes < (size_t)kSoftmaxBlocks * (kWeighted ? 4 : 3) * sizeof(double)) return RELGNN_ENOSPC;
+  if (rows > 0 && (!logits || !labels || !mask || (kWeighted && !weights))) return RELGNN_EINVAL;
+  hipStream_t st = as_stream(stream);
+  double* partial = static_cast<double*>(workspace);
+  int nblk = 0;
+  if (rows > 0) {
+    const int w = softmax_group_width(cols);
+    nblk = softmax_grid(rows, w);
+    auto walk = [&](auto width) {
+      constexpr int W = decltype(width)::value;
+      if constexpr (kWeighted) softmax_ce_weighted_stats_kernel<W><<<nblk, 256, 0, st>>>(logits, ld, labels, mask, weights, rows, cols, partial);
+      else softmax_ce_stats_kernel<W><<<nblk, 256, 0, st>>>(logits, ld, labels, mask, rows, cols, partial);
+    };
+    if (w == 1) walk(std::integral_constant<int, 1>{});
+    else if (w == 16) walk(std::integral_constant<int, 16>{});
+    else walk(std::integral_constant<int, 64>{});
+  }
+  if constexpr (kWeighted) softmax_ce_weighted_stats_final_kernel<<<1, 256, 0, st>>>(partial, nblk, denominator, stats);
+  else softmax_ce_stats_final_kernel<<<1, 256, 0, st>>>(partial, nblk, stats);
+  return launch_status();
+}
+
+template <bool kWeighted>
+int softmax_ce_bwd_launch(const float* logits, int64_t ld, const int32_t* labels, const float* mask, const float* weights,
+                          float denominator, int64_t rows, int32_t cols, const float* stats, const float* g_loss,
+                          const float* g_total, float* glogits, int64_t ldg, void* stream) {
+  if (rows < 0 || cols < 1 || ld < cols || ldg < cols || ldg > INT32_MAX
+      || (kWeighted && (denominator == 0.f || denominator != denominator)))
+    return RELGNN_EINVAL;
+  if (rows == 0) return RELGNN_OK;
+  if (!logits || !labels || !mask || (kWeighted ? !weights : !stats) || (!g_loss && !g_total) || !glogits) return RELGNN_EINVAL;
+  hipStream_t st = as_stream(stream);
+  const int w = softmax_group_width(cols);
+  const int64_t per_block = 256 / w;
+  const unsigned nblk = flat_grid((rows + per_block - 1) / per_block * 256, 256);       // one block per 256 / w rows, capped
+  auto walk = [&](auto width) {
+    constexpr int W = decltype(width)::value;
+    if constexpr (kWeighted)
+      softmax_ce_weighted_bwd_kernel<W><<<nblk, 256, 0, st>>>(logits, ld, labels, mask, weights, denominator, rows, cols, g_loss, g_total, glogits, ldg);
+    else
+      softmax_ce_bwd_kernel<W><<<nblk, 256, 0, st>>>(logits, ld, labels, mask, rows, cols, stats, g_loss, g_total, glogits, ldg);
+  };
+  if (w == 1) walk(std::integral_constant<int, 1>{});
+  else if (w == 16) walk(std::integral_constant<int, 16>{});
+  else walk(std::integral_constant<int, 64>{});
+  return launch_status();
 }
 
 constexpr int kStatsBlocks = 256;
@@ -669,37 +714,13 @@ size_t relgnn_softmax_ce_stats_workspace_bytes(void) { return (size_t)kSoftmaxBl
 
 int relgnn_softmax_ce_stats(const float* logits, int64_t ld, const int32_t* labels, const float* mask, int64_t rows, int32_t cols,
                             float* stats, void* workspace, size_t workspace_bytes, void* stream) {
-  if (rows < 0 || cols < 1 || ld < cols || !stats) return RELGNN_EINVAL;
-  if (!workspace || workspace_bytes < relgnn_softmax_ce_stats_workspace_bytes()) return RELGNN_ENOSPC;
-  if (rows > 0 && (!logits || !labels || !mask)) return RELGNN_EINVAL;
-  hipStream_t st = as_stream(stream);
-  double* partial = static_cast<double*>(workspace);
-  int nblk = 0;
-  if (rows > 0) {
-    const int w = softmax_group_width(cols);
-    nblk = softmax_grid(rows, w);
-    if (w == 1) softmax_ce_stats_kernel<1><<<nblk, 256, 0, st>>>(logits, ld, labels, mask, rows, cols, partial);
-    else if (w == 16) softmax_ce_stats_kernel<16><<<nblk, 256, 0, st>>>(logits, ld, labels, mask, rows, cols, partial);
-    else softmax_ce_stats_kernel<64><<<nblk, 256, 0, st>>>(logits, ld, labels, mask, rows, cols, partial);
-  }
-  softmax_ce_stats_final_kernel<<<1, 256, 0, st>>>(partial, nblk, stats);
-  return launch_status();
+  return softmax_ce_stats_launch<false>(logits, ld, labels, mask, nullptr, 0.f, rows, cols, stats, workspace, workspace_bytes, stream);
 }
 
 int relgnn_softmax_ce_bwd(const float* logits, int64_t ld, const int32_t* labels, const float* mask, int64_t rows, int32_t cols,
                           const float* stats, const float* g_loss, const float* g_total, float* glogits, int64_t ldg,
                           void* stream) {
-  if (rows < 0 || cols < 1 || ld < cols || ldg < cols || ldg > INT32_MAX) return RELGNN_EINVAL;
-  if (rows == 0) return RELGNN_OK;
-  if (!logits || !labels || !mask || !stats || (!g_loss && !g_total) || !glogits) return RELGNN_EINVAL;
-  hipStream_t st = as_stream(stream);
-  const int w = softmax_group_width(cols);
-  const int64_t per_block = 256 / w;
-  const unsigned nblk = flat_grid((rows + per_block - 1) / per_block * 256, 256);       // one block per 256 / w rows, capped
-  if (w == 1) softmax_ce_bwd_kernel<1><<<nblk, 256, 0, st>>>(logits, ld, labels, mask, rows, cols, stats, g_loss, g_total, glogits, ldg);
-  else if (w == 16) softmax_ce_bwd_kernel<16><<<nblk, 256, 0, st>>>(logits, ld, labels, mask, rows, cols, stats, g_loss, g_total, glogits, ldg);
-  else softmax_ce_bwd_kernel<64><<<nblk, 256, 0, st>>>(logits, ld, labels, mask, rows, cols, stats, g_loss, g_total, glogits, ldg);
-  return launch_status();
+  return softmax_ce_bwd_launch<false>(logits, ld, labels, mask, nullptr, 0.f, rows, cols, stats, g_loss, g_total, glogits, ldg, stream);
 }
 
 size_t relgnn_softmax_ce_weighted_stats_workspace_bytes(void) { return (size_t)kSoftmaxBlocks * 4 * sizeof(double); }
@@ -707,42 +728,15 @@ size_t relgnn_softmax_ce_weighted_stats_workspace_bytes(void) { return (size_t)k
 int relgnn_softmax_ce_weighted_stats(const float* logits, int64_t ld, const int32_t* labels, const float* mask, const float* weights,
                                      float denominator, int64_t rows, int32_t cols, float* stats, void* workspace,
                                      size_t workspace_bytes, void* stream) {
-  if (rows < 0 || cols < 1 || ld < cols || !stats || denominator == 0.f || denominator != denominator)
-    return RELGNN_EINVAL;
-  if (!workspace || workspace_bytes < relgnn_softmax_ce_weighted_stats_workspace_bytes()) return RELGNN_ENOSPC;
-  if (rows > 0 && (!logits || !labels || !mask || !weights)) return RELGNN_EINVAL;
-  hipStream_t st = as_stream(stream);
-  double* partial = static_cast<double*>(workspace);
-  int nblk = 0;
-  if (rows > 0) {
-    const int w = softmax_group_width(cols);
-    nblk = softmax_grid(rows, w);
-    if (w == 1) softmax_ce_weighted_stats_kernel<1><<<nblk, 256, 0, st>>>(logits, ld, labels, mask, weights, rows, cols, partial);
-    else if (w == 16) softmax_ce_weighted_stats_kernel<16><<<nblk, 256, 0, st>>>(logits, ld, labels, mask, weights, rows, cols, partial);
-    else softmax_ce_weighted_stats_kernel<64><<<nblk, 256, 0, st>>>(logits, ld, labels, mask, weights, rows, cols, partial);
-  }
-  softmax_ce_weighted_stats_final_kernel<<<1, 256, 0, st>>>(partial, nblk, denominator, stats);
-  return launch_status();
+  return softmax_ce_stats_launch<true>(logits, ld, labels, mask, weights, denominator, rows, cols, stats, workspace, workspace_bytes,
+                                       stream);
 }
 
 int relgnn_softmax_ce_weighted_bwd(const float* logits, int64_t ld, const int32_t* labels, const float* mask, const float* weights,
                                    float denominator, int64_t rows, int32_t cols, const float* g_loss, const float* g_total,
                                    float* glogits, int64_t ldg, void* stream) {
-  if (rows < 0 || cols < 1 || ld < cols || ldg < cols || ldg > INT32_MAX || denominator == 0.f || denominator != denominator)
-    return RELGNN_EINVAL;
-  if (rows == 0) return RELGNN_OK;
-  if (!logits || !labels || !mask || !weights || (!g_loss && !g_total) || !glogits) return RELGNN_EINVAL;
-  hipStream_t st = as_stream(stream);
-  const int w = softmax_group_width(cols);
-  const int64_t per_block = 256 / w;
-  const unsigned nblk = flat_grid((rows + per_block - 1) / per_block * 256, 256);
-  if (w == 1)
-    softmax_ce_weighted_bwd_kernel<1><<<nblk, 256, 0, st>>>(logits, ld, labels, mask, weights, denominator, rows, cols, g_loss, g_total, glogits, ldg);
-  else if (w == 16)
-    softmax_ce_weighted_bwd_kernel<16><<<nblk, 256, 0, st>>>(logits, ld, labels, mask, weights, denominator, rows, cols, g_loss, g_total, glogits, ldg);
-  else
-    softmax_ce_weighted_bwd_kernel<64><<<nblk, 256, 0, st>>>(logits, ld, labels, mask, weights, denominator, rows, cols, g_loss, g_total, glogits, ldg);
-  return launch_status();
+  return softmax_ce_bwd_launch<true>(logits, ld, labels, mask, weights, denominator, rows, cols, nullptr, g_loss, g_total, glogits, ldg,
+                                     stream);
 }
 
 }  // extern "C"

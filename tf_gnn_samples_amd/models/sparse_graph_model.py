@@ -342,31 +342,16 @@ class Sparse_Graph_Model(ABC):
         self.optimizer = TFStyleOptimizer(list(self.variables.parameters()), p['optimizer'], p['learning_rate'],
                                           p['clamp_gradient_norm'], decay=p['learning_rate_decay'],
                                           momentum=p['momentum'])
-        if getattr(self.task, "layered", False):
-            # the citation task's `sampled_batches` key "layered": one level graph per layer, one hop per level
-            fanouts = self.task.sampled_batches["fanouts"]
-            if len(fanouts) != p['graph_num_layers']:
-                raise ValueError('sampled_batches: "layered": true requires as many fanouts as graph_num_layers (got %d fanouts for %d '
-                                 'layers): layer l runs on the nodes H - l + 1 hops from a seed' % (len(fanouts), p['graph_num_layers']))
-            if p['graph_num_timesteps_per_layer'] != 1:
-                raise ValueError('sampled_batches: "layered": true requires graph_num_timesteps_per_layer 1 (got %r): a layer that '
-                                 'propagates twice needs two hops, and the layer functions take one graph'
-                                 % (p['graph_num_timesteps_per_layer'],))
-        if getattr(self.task, "evaluation", None) is not None:
-            # the citation task's `sampled_batches` key "evaluation": its batches are always hop-ordered and layered
-            problem = self._layered_prerequisites(self.task.evaluation["fanouts"])
+        need = self.task.model_requirements()
+        for fanouts, refusal in need.layered:
+            problem = self._layered_prerequisites(fanouts)
             if problem is not None:
-                raise ValueError('sampled_batches: "evaluation" requires %s: evaluation batches are hop-ordered and run layer l on '
-                                 'the nodes H - l + 1 hops from a seed' % problem)
-        normalisation = (getattr(self.task, "subgraph_batches", None) or {}).get("normalisation")
-        if normalisation is not None and normalisation["aggregation"]:
-            # the citation task's `subgraph_batches` key "normalisation": the per-edge weights reach a layer as its degree scale
+                raise ValueError(refusal % problem)
+        if need.message_scale is not None:
             problem = self._message_scale_prerequisites()
             if problem is not None:
-                raise ValueError('subgraph_batches: normalisation: "aggregation": true requires %s: the per-edge weights take the place '
-                                 'of 1/(in-degree + 1e-7) in a sum over the messages; "aggregation": false (the loss normalisation '
-                                 'alone) works with every model' % problem)
-        if getattr(self.task, "sparse_update", False):
+                raise ValueError(need.message_scale % problem)
+        if need.deferred_projection_rows:
             # the citation task's `sampled_batches` key "sparse_update": the weight of the sparse input projection is updated by rows.
             # CONTRACT: between training steps that parameter's tensor (and its two Adam slots) hold stale rows; everything here that
             # reads them outside a training step calls self.optimizer.flush_deferred() first (forward_batch(training=False),
@@ -378,7 +363,7 @@ class Sparse_Graph_Model(ABC):
                 raise ValueError('sampled_batches: "sparse_update": true requires a model with the input projection '
                                  'graph_model/dense/kernel (hidden_size %d equals the feature size: there is none)' % p['hidden_size'])
             self.optimizer.defer_rows(self.variables["graph_model/dense/kernel"])
-            if getattr(self.task, "sparse_gradient", False):
+            if need.compact_projection_gradient:
                 # "sparse_gradient": that weight's gradient exists only as the rows a batch names (_project_input hands the sink on)
                 self.optimizer.compact_row_gradient()
 
@@ -508,16 +493,10 @@ class Sparse_Graph_Model(ABC):
         the reference's ThreadedIterator (:272); `native_batching: false` keeps the numpy iterator.  full_graph: the task's
         "evaluation" key is not consulted (predict(data) without nodes)."""
         native = self._native_batching()
-        if data_fold == DataFold.TRAIN and (getattr(self.task, "sampled_batches", None) is not None
-                                            or getattr(self.task, "subgraph_batches", None) is not None):
-            # a single-graph task that trains on sampled subgraphs (tasks/neighbour_sampling.py, tasks/subgraph_sampling.py): drawn on
-            # this model's device by either iterator, so no flattened or resident copy of the fold is built for them
-            self.task.bind_sampling_device(self.device)
-            native = False
-        if data_fold != DataFold.TRAIN and not full_graph and getattr(self.task, "evaluation", None) is not None:
-            # ... and evaluates on sampled receptive fields (the key "evaluation"): no flattened or resident copy of the fold either
-            self.task.bind_sampling_device(self.device)
-            return self.task.evaluation_batches(data, data_fold, self._full_graph_route(native))
+        # a single-graph task draws its sampled batches itself, on this device: no flattened or resident copy of the fold is built
+        own = self.task.epoch_batches(data, data_fold, self.device, self._full_graph_route(native), full_graph)
+        if own is not None:
+            return own
         if not native:
             return self.task.make_minibatch_iterator(data, data_fold, self.params['max_nodes_in_batch'])
         return self.task.make_native_minibatch_iterator(self._native_pipeline(data), data_fold, self.params['max_nodes_in_batch'])
@@ -585,9 +564,7 @@ class Sparse_Graph_Model(ABC):
             upcoming = next(batch_iterator, None)
             late.put((readback, mb))
         late.flush()
-        if data_fold != DataFold.TRAIN and getattr(self.task, "evaluation", None) is not None:
-            return self.task.sampled_evaluation_epoch(tally.result())      # the fold's batches add up to its one graph
-        return tally.result()
+        return self.task.epoch_result(tally.result(), data_fold)
 
     def train(self, quiet: bool = False, max_epochs: Optional[int] = None, group=None):
         """:318-371 without TensorBoard: early stopping on the task's validation metric.
@@ -668,9 +645,6 @@ class Sparse_Graph_Model(ABC):
         return self._predict_iter(data, return_states, plan)
 
     def _node_prediction_plan(self, data, nodes):
-        if not hasattr(self.task, "node_prediction_batches"):
-            raise ValueError("predict(nodes=...) is not defined for the %s task: its predictions are per graph of `data`, and only a "
-                             "task whose data is ONE graph names single nodes" % self.task.name())
         distinct, inverse, given = self.task.check_prediction_nodes(data, nodes)
         settings = self.task.node_prediction_settings()
         if settings["fanouts"] is None:
@@ -697,13 +671,10 @@ class Sparse_Graph_Model(ABC):
         late = LateFetch(self._fetch_predictions)
         if plan is None:
             # (predict(data) stays on the full graph whatever the task's "evaluation" key says)
-            sampled_evaluation = getattr(self.task, "evaluation", None) is not None
-            batch_iterator = iter(self._batches(data, DataFold.TEST, full_graph=True) if sampled_evaluation
-                                  else self._batches(data, DataFold.TEST))
+            batch_iterator = iter(self._batches(data, DataFold.TEST, full_graph=True))
         else:
-            native = self._native_batching()
             batch_iterator = iter(self.task.node_prediction_batches(data, plan["distinct"], plan["fanouts"], plan["seeds_per_batch"],
-                                                                    self._full_graph_route(native)))
+                                                                    self._full_graph_route(self._native_batching())))
         upcoming = next(batch_iterator, None)
         while upcoming is not None:
             with torch.no_grad():      # (around the device work only: a generator suspended inside it would leave the grad mode of

@@ -12,83 +12,11 @@ the reference's): the features stay sparse from the file to the input projection
 carry a float32 [V, 1] stand-in under `initial_node_features`, and compute_initial_node_features hands the model the device's
 SparseRows, which its input projection takes through ops.csr_rows_project (csrc/csr_project.hip).
 
-Task parameter `sampled_batches` ({"fanouts": [k_1, ..., k_H], "seeds_per_batch": B, "seed": s}; absent or None by default, read
-with params.get like the one above and kept in the checkpoint's metadata with the other task parameters): the TRAIN fold is no longer
-one batch.  An epoch is a permutation of the fold's nodes cut into ceil(n_train / B) seed lists (neighbour_sampling
-.epoch_seed_batches); every seed list becomes a fanout-limited subgraph drawn on the device (neighbour_sampling.NeighbourSampler,
-csrc/neighbour_sample.hip) whose loss counts the seeds only.  The sampler, the full graph's RelGraph and the device copies of the
-feature table, the labels and the fold's mask are built once per (fold, device).  The task counts the epochs and the sampled batches
-(the sampler's `draw`) itself.  VALIDATION, TEST, test() and predict() stay on the full graph unless the key "evaluation" (last paragraph)
-says otherwise.  GPU only; not together with capture_train_step or a process group.
-
-The two together: `sampled_batches` takes one more optional key, "sparse_features": true, which requires sparse_node_features
-(and sparse_node_features with a sampled_batches that lacks the key stays a ValueError).  The sampling state then keeps the device's
-SparseRows instead of a dense table, and every sampled batch carries the [n, 1] stand-in plus SparseRows.take_rows(nodes): the CSR of
-the batch's rows, the CSR of that subset's transpose (what the projection's weight gradient runs over) and both long-row plans,
-built on the device per batch (csrc/sparse_subset.hip, include/relgnn_sparse_subset.h) with one read-back of eight sizes.  No
-[V, F] or [n, F] dense array exists on the host or the device.  The weight gradient itself stays a dense [F, hidden] tensor, and the
-optimizer walks all of it unless the next key says otherwise.
-
-One more optional key, "sparse_update": true (requires "sparse_features": true, optimizer Adam and a model with the input projection
-`graph_model/dense/kernel`; each is a ValueError when the task or the model is built): the optimizer registers the projection's weight
-as row-deferred (TFStyleOptimizer.defer_rows, csrc/sparse_update.hip, include/relgnn_sparse_update.h).  A training step then reads and
-writes only the rows of the weight and its two Adam slots whose words the batch holds, and every stored value is still dense Adam's,
-bit for bit.  The dense gradient and the norm over it stay unless the next key says otherwise.
-
-One more optional key, "sparse_gradient": true (requires "sparse_update": true, a ValueError otherwise): the projection's weight
-gradient exists only as the [touched, hidden] rows whose words the batch holds (csrc/sparse_gradient.hip,
-include/relgnn_sparse_gradient.h).  The weight's `.grad` stays None, no [F, hidden] tensor is allocated in a step, the clip norm is
-computed over the touched rows with the bits of the dense norm, and the row update reads the compact rows: the optimizer still stores
-dense Adam's values bit for bit.
-
-One more optional key, "layered": true (it composes with the three above; none of them depends on the row order of a batch): a batch
-is numbered by hop (NeighbourSampler.sample_by_hop: the seeds first, then the nodes first reached in hop 1, ...) and carries one
-LevelGraph per layer under extra['layer_graphs'].  Layer l of H runs on the nodes at most H - l + 1 hops from a seed and on the edges
-whose targets are at most H - l hops away, a prefix of every type's list, and its output is cut to those targets; the head, the loss
-and the metrics see the seed rows only (labels and mask are taken for the seeds).  The model refuses the key unless it has as many
-layers as there are fanouts and one timestep per layer (models/sparse_graph_model.py).  With a layer-input keep-probability below 1
-the dropout masks differ from the un-layered run's (torch draws by shape, the fused route by element index over another row count):
-the two runs are then two draws of the same model, not equal ones.
-
-One more optional key, "evaluation": {"fanouts": [k_1, ..., k_H], "seeds_per_batch": B, "keep": bool} ("keep" optional; it composes with
-the four above and does not ask training to be layered): VALIDATION, TEST and test() run over ceil(n_fold / B) batches instead of the
-full graph.  Batch i holds the fold's masked nodes i * B .. (i + 1) * B - 1 in ascending id (no shuffle) and is
-sample_by_hop(seeds, draw=i).device_batch(..., layered=True) with keep-probability 1, labels and mask of the seeds only, drawn by a
-sampler of the fold's own whose replica is 0x40000000 | fold (neighbour_sampling.evaluation_replica): the random words are a function of
-(seed, fold, batch index), the same in every epoch and never a training batch's.  The batches are always hop-ordered and layered, so the
-model refuses the key unless it has as many layers as there are fanouts and one timestep per layer.  An epoch's loss is
-sum(total_loss) / sum(num_masked), its accuracy sum(num_correct) / sum(num_masked), the early-stopping metric sum(total_loss) over the
-fold's ONE graph (sampled_evaluation_epoch).  With every fanout 0 the seeds' states and logits are the full-graph forward's rows bit for
-bit: every level graph brings its bucketing along and routes its hub buckets as the model's full-graph batch does (RelGraph.route_like).
-"keep": the batches of a fold are built once and handed out again every epoch, released with the fold.  The three folds share ONE device
-RelGraph and ONE feature table (_graph_state_of, keyed by the adjacency and feature objects the folds share); labels, mask and sampler are
-per fold.  predict(data, nodes=...) runs the same batches over the named nodes (the key's fanouts and B, or all-zero fanouts and 1024
-without it); predict(data) without nodes stays on the full graph.
-
-Task parameter `subgraph_batches` ({"roots_per_batch": R, "walk_length": h, "seed": s, "sparse_features": bool}, the last two optional;
-absent or None by default, read with params.get and kept in the checkpoint's metadata like its siblings; a ValueError together with
-`sampled_batches`): the TRAIN fold is cut into subgraphs instead of receptive fields.  An epoch is the same permutation of the fold's
-nodes cut into ceil(n_train / R) ROOT lists (epoch_seed_batches, unchanged); a walk of h steps against the edges starts at every root,
-and the batch is the subgraph INDUCED on the visited nodes (subgraph_sampling.SubgraphSampler, csrc/subgraph_sample.hip): every edge
-of the full graph between two of them, with the induced in-degrees.  Every layer runs on that one subgraph, so a step costs the same
-at any depth.  The loss mask is fold_mask[nodes]: every TRAIN node of the subgraph counts, not only the roots.  "sparse_features": true
-requires sparse_node_features (and the reverse), as for sampled_batches; the batch then carries SparseRows.take_rows(nodes).  The
-device RelGraph and the feature table are the ones the folds share (_graph_state_of).  VALIDATION, TEST, test() and predict() stay on
-the full graph; predict(nodes=...) runs exact receptive fields as it does without the parameter.  Without the next key the loss and
-the aggregation are the induced subgraph's.  GPU only; not together with capture_train_step or a process group.
-
-One more optional key, "normalisation": {"presample_epochs": E, "aggregation": bool, "max_edge_weight": c} (the last two optional: true
-and 1e4; it composes with "sparse_features"): GraphSAINT's normalisation (include/relgnn_subgraph_norm.h).  Before the first TRAIN
-batch of a (fold, device) the sampler counts, over N = E * ceil(n_train / R) pre-sampled subgraphs (root lists of the epochs
-0x80000000 + e, sampler replica 0x20000000: never a training batch's draws, and a pure function of (seed, E, the graph), so the counts
-are recomputed after restore() and not stored), how many hold node v (C_v) and both ends of edge e (C_e), without a read-back.  The
-loss term of node v then carries the weight N / max(C_v, 1) and the batch loss is divided by n_train instead of the batch's masked
-count (relgnn_softmax_ce_weighted_stats / _bwd): its expectation is the fold's mean loss.  num_masked, num_correct and the accuracy
-stay unweighted counts; total_loss is the weighted sum.  "aggregation": every message of a batch is scaled by
-min(max(C_v, 1) / max(C_e, 1), c) / (full-graph in-degree + 1e-7) instead of 1 / (induced in-degree + 1e-7) (emitted with the edges,
-preset as the batch graph's degree scale): a layer's sum is then an estimate of the aggregate evaluation computes on the full graph.
-It needs a model whose layers take the degree table, normalise by it and sum (RGCN, RGDCN, GNN-FiLM with
-normalize_messages_by_num_incoming; a ValueError from the model otherwise); "aggregation": false works with every model.
+The batching modes live in tasks/single_graph_batches.py (`self.batches`), which describes every parameter and key:
+  `sampled_batches` {"fanouts", "seeds_per_batch", "seed"; optional "sparse_features", "sparse_update", "sparse_gradient", "layered",
+      "evaluation"}: TRAIN epochs of neighbour-sampled receptive fields; "evaluation": VALIDATION, TEST and predict(nodes=...) on them too.
+  `subgraph_batches` {"roots_per_batch", "walk_length", "seed"; optional "sparse_features", "normalisation"}: TRAIN epochs of random-walk
+      induced subgraphs; "normalisation": GraphSAINT's loss and aggregation weights.
 """
 import os
 import pickle
@@ -100,15 +28,14 @@ import torch
 
 from .. import _lib, config as _cfg
 from ..dense import dense, mark_zero_padded
-from ..graph import RelGraph
 from ..parallel import refuse_single_graph_task
 from ..predict import predict_softmax
-from .neighbour_sampling import (PREDICT_FOLD, PREDICT_SEEDS_PER_BATCH, NeighbourSampler, check_prediction_nodes, epoch_seed_batches,
-                                 evaluation_replica, evaluation_seed_batches, parse_sampled_batches)
-from .subgraph_sampling import SubgraphSampler, parse_subgraph_batches
+from .neighbour_sampling import PREDICT_SEEDS_PER_BATCH, check_prediction_nodes, check_sparse_node_features, parse_sampled_batches
+from .subgraph_sampling import parse_subgraph_batches
 from .resident import ResidentDataset
+from .single_graph_batches import SingleGraphBatches
 from .sparse_features import SparseRows, node_stand_in, random_rows, resident_copy
-from .sparse_graph_task import DataFold, MinibatchData, Sparse_Graph_Task
+from .sparse_graph_task import DataFold, MinibatchData, ModelRequirements, Sparse_Graph_Task
 
 
 class CitationData(NamedTuple):
@@ -120,42 +47,33 @@ class CitationData(NamedTuple):
     mask: np.ndarray                                       # float32 [V], 1 = the node counts in this fold
 
 
-class _GraphState(NamedTuple):
-    """What the folds of one graph share on one device: ONE bucketing and ONE feature table (or device SparseRows)."""
-    graph: RelGraph
-    features: Any                                          # float32 [V, F], or the device's SparseRows
-
-
-class _SamplingState(NamedTuple):
-    """What the sampled batches of one fold on one device are cut from; `sampler.graph` and `features` are the _GraphState's."""
-    sampler: Any                                           # a NeighbourSampler, or the SubgraphSampler of `subgraph_batches`
-    features: Any                                          # float32 [V, F], or the device's SparseRows
-    labels: torch.Tensor                                   # int32 [V]
-    mask: torch.Tensor                                     # float32 [V], the fold's
-    visit_counts: Any = None                               # subgraph_sampling.VisitCounts under `subgraph_batches`' key "normalisation"
-
-
-class _SoftmaxCEWeightedStats(torch.autograd.Function):
-    """_SoftmaxCEStats with a weight per row and a denominator the caller names (csrc/train_utils.hip:
-    relgnn_softmax_ce_weighted_stats / _bwd, include/relgnn_subgraph_norm.h): loss = sum(mask * weight * loss_v) / denominator,
-    total_loss the numerator; the accuracy and the counts behind it stay unweighted."""
+class _SoftmaxCEStats(torch.autograd.Function):
+    """(loss, total_loss, accuracy, [total_loss, sum of mask, masked correct count]) of the whole graph in one pass over the logits
+    (csrc/train_utils.hip).  log_softmax, gather, mul, sum, argmax, eq, sum, div and their autograd mirrors would be a dozen ~5 us
+    launches around a step that is launch-bound by construction (a few thousand nodes); see _SigmoidCEStats in ppi_task.py.
+    With `weights` and `denominator` (relgnn_softmax_ce_weighted_stats / _bwd, include/relgnn_subgraph_norm.h): a weight per row and
+    a denominator the caller names, loss = sum(mask * weight * loss_v) / denominator, total_loss the numerator; the accuracy and the
+    counts behind it stay unweighted."""
 
     @staticmethod
-    def forward(ctx, logits, labels, mask, weights, denominator):
+    def forward(ctx, logits, labels, mask, weights=None, denominator=None):
         lib = _lib.load_library()
         if logits.dim() != 2 or logits.stride(1) != 1:
             logits = logits.contiguous()
-        labels, mask, weights = labels.contiguous(), mask.contiguous(), weights.contiguous()
+        labels, mask = labels.contiguous(), mask.contiguous()
         rows, cols = logits.shape
-        stats = torch.empty(6, dtype=torch.float32, device=logits.device)
-        nbytes = lib.relgnn_softmax_ce_weighted_stats_workspace_bytes()
+        weighted = weights is not None
+        name = "relgnn_softmax_ce_weighted_stats" if weighted else "relgnn_softmax_ce_stats"
+        stats = torch.empty(6 if weighted else 5, dtype=torch.float32, device=logits.device)
+        nbytes = getattr(lib, name + "_workspace_bytes")()
         ws = _lib.scratch(nbytes, logits.device)
-        _lib.launch("relgnn_softmax_ce_weighted_stats", _lib.ptr(logits, rows_strided=True), logits.stride(0) if rows > 1 else cols,
-                    _lib.ptr(labels), _lib.ptr(mask), _lib.ptr(weights), float(denominator), rows, cols, _lib.ptr(stats), _lib.ptr(ws),
-                    nbytes)
-        ctx.save_for_backward(logits, labels, mask, weights)
-        ctx.denominator = float(denominator)
-        ctx.set_materialize_grads(False)
+        weights = weights.contiguous() if weighted else None
+        _lib.launch(name, _lib.ptr(logits, rows_strided=True), logits.stride(0) if rows > 1 else cols, _lib.ptr(labels), _lib.ptr(mask),
+                    *((_lib.ptr(weights), float(denominator)) if weighted else ()), rows, cols, _lib.ptr(stats), _lib.ptr(ws), nbytes)
+        # (the plain backward divides by the sum of the mask, stats[1]; the weighted one takes the denominator as a launch scalar)
+        ctx.save_for_backward(logits, labels, mask, weights if weighted else stats)
+        ctx.denominator = float(denominator) if weighted else None
+        ctx.set_materialize_grads(False)          # an unused output's gradient arrives as None, not as a zero tensor
         loss, total, accuracy = stats[3], stats[0], stats[4]
         counts = stats[0:3]                       # total_loss, sum of mask, masked correct count (the last two unweighted)
         ctx.mark_non_differentiable(accuracy, counts)
@@ -163,80 +81,37 @@ class _SoftmaxCEWeightedStats(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g_loss, g_total, g_accuracy, g_counts):
-        logits, labels, mask, weights = ctx.saved_tensors
+        logits, labels, mask, stats_or_weights = ctx.saved_tensors
         if g_loss is None and g_total is None:
             return None, None, None, None, None
-
-        def scalar(g):
-            return None if g is None else g.reshape(1).to(torch.float32).contiguous()
-        g_loss, g_total = scalar(g_loss), scalar(g_total)
-        rows, cols = logits.shape
-        ld = logits.stride(0) if rows > 1 else cols
-        padded = cols % 16 and _cfg.settings.limb_gemm and _cfg.settings.head_pad == "1"       # (as _SoftmaxCEStats pads)
-        ldg = (cols + 15) // 16 * 16 if padded else cols
-        gl = torch.empty((rows, ldg), dtype=torch.float32, device=logits.device)
-        _lib.launch("relgnn_softmax_ce_weighted_bwd", _lib.ptr(logits, rows_strided=True), ld, _lib.ptr(labels), _lib.ptr(mask),
-                    _lib.ptr(weights), ctx.denominator, rows, cols, _lib.ptr(g_loss), _lib.ptr(g_total), _lib.ptr(gl), ldg)
-        return (mark_zero_padded(gl[:, :cols], ldg) if padded else gl), None, None, None, None
-
-
-def softmax_ce_weighted_stats(logits: torch.Tensor, labels: torch.Tensor, mask: torch.Tensor, weights: torch.Tensor, denominator: float):
-    """-> (loss, total_loss, accuracy, counts) of float32 device logits [V, C], int32 labels [V], float32 mask and weights [V]."""
-    return _SoftmaxCEWeightedStats.apply(logits, labels, mask, weights, denominator)
-
-
-class _SoftmaxCEStats(torch.autograd.Function):
-    """(loss, total_loss, accuracy, [total_loss, sum of mask, masked correct count]) of the whole graph in one pass over the logits
-    (csrc/train_utils.hip).  log_softmax, gather, mul, sum, argmax, eq, sum, div and their autograd mirrors would be a dozen ~5 us
-    launches around a step that is launch-bound by construction (a few thousand nodes); see _SigmoidCEStats in ppi_task.py."""
-
-    @staticmethod
-    def forward(ctx, logits, labels, mask):
-        lib = _lib.load_library()
-        if logits.dim() != 2 or logits.stride(1) != 1:
-            logits = logits.contiguous()
-        labels, mask = labels.contiguous(), mask.contiguous()
-        rows, cols = logits.shape
-        stats = torch.empty(5, dtype=torch.float32, device=logits.device)
-        nbytes = lib.relgnn_softmax_ce_stats_workspace_bytes()
-        ws = _lib.scratch(nbytes, logits.device)
-        _lib.launch("relgnn_softmax_ce_stats", _lib.ptr(logits, rows_strided=True), logits.stride(0) if rows > 1 else cols,
-                    _lib.ptr(labels), _lib.ptr(mask), rows, cols, _lib.ptr(stats), _lib.ptr(ws), nbytes)
-        ctx.save_for_backward(logits, labels, mask, stats)
-        ctx.set_materialize_grads(False)          # an unused output's gradient arrives as None, not as a zero tensor
-        loss, total, accuracy = stats[3], stats[0], stats[4]
-        counts = stats[0:3]                       # total_loss, sum of mask, masked correct count
-        ctx.mark_non_differentiable(accuracy, counts)
-        return loss, total, accuracy, counts
-
-    @staticmethod
-    def backward(ctx, g_loss, g_total, g_accuracy, g_counts):
-        logits, labels, mask, stats = ctx.saved_tensors
-        if g_loss is None and g_total is None:
-            return None, None, None
 
         def scalar(g):                            # the incoming gradients stay on the device: the kernel reads them (and sum of mask)
             return None if g is None else g.reshape(1).to(torch.float32).contiguous()
         g_loss, g_total = scalar(g_loss), scalar(g_total)
         rows, cols = logits.shape
         ld = logits.stride(0) if rows > 1 else cols
-        if cols % 16 and _cfg.settings.limb_gemm and _cfg.settings.head_pad == "1":
-            # rows of the next multiple of 16 floats, zeros behind the classes: the head's input-gradient product then runs on the limb
-            # route with the activation gradient of the last GNN layer's Dense in its epilogue (dense.mark_zero_padded), as PPI's
-            ldg = (cols + 15) // 16 * 16
-            buf = torch.empty((rows, ldg), dtype=torch.float32, device=logits.device)
+        # padded: rows of the next multiple of 16 floats, zeros behind the classes: the head's input-gradient product then runs on the
+        # limb route with the activation gradient of the last GNN layer's Dense in its epilogue (dense.mark_zero_padded), as PPI's
+        padded = cols % 16 and _cfg.settings.limb_gemm and _cfg.settings.head_pad == "1"
+        ldg = (cols + 15) // 16 * 16 if padded else cols
+        gl = torch.empty((rows, ldg), dtype=torch.float32, device=logits.device)
+        if ctx.denominator is None:
             _lib.launch("relgnn_softmax_ce_bwd", _lib.ptr(logits, rows_strided=True), ld, _lib.ptr(labels), _lib.ptr(mask), rows, cols,
-                        _lib.ptr(stats), _lib.ptr(g_loss), _lib.ptr(g_total), _lib.ptr(buf), ldg)
-            return mark_zero_padded(buf[:, :cols], ldg), None, None
-        gl = torch.empty((rows, cols), dtype=torch.float32, device=logits.device)
-        _lib.launch("relgnn_softmax_ce_bwd", _lib.ptr(logits, rows_strided=True), ld, _lib.ptr(labels), _lib.ptr(mask), rows, cols,
-                    _lib.ptr(stats), _lib.ptr(g_loss), _lib.ptr(g_total), _lib.ptr(gl), cols)
-        return gl, None, None
+                        _lib.ptr(stats_or_weights), _lib.ptr(g_loss), _lib.ptr(g_total), _lib.ptr(gl), ldg)
+        else:
+            _lib.launch("relgnn_softmax_ce_weighted_bwd", _lib.ptr(logits, rows_strided=True), ld, _lib.ptr(labels), _lib.ptr(mask),
+                        _lib.ptr(stats_or_weights), ctx.denominator, rows, cols, _lib.ptr(g_loss), _lib.ptr(g_total), _lib.ptr(gl), ldg)
+        return (mark_zero_padded(gl[:, :cols], ldg) if padded else gl), None, None, None, None
 
 
 def softmax_ce_stats(logits: torch.Tensor, labels: torch.Tensor, mask: torch.Tensor):
     """-> (loss, total_loss, accuracy, counts) of float32 device logits [V, C], int32 labels [V], float32 mask [V]."""
     return _SoftmaxCEStats.apply(logits, labels, mask)
+
+
+def softmax_ce_weighted_stats(logits: torch.Tensor, labels: torch.Tensor, mask: torch.Tensor, weights: torch.Tensor, denominator: float):
+    """-> (loss, total_loss, accuracy, counts) of float32 device logits [V, C], int32 labels [V], float32 mask and weights [V]."""
+    return _SoftmaxCEStats.apply(logits, labels, mask, weights, denominator)
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------
@@ -335,11 +210,7 @@ class Citation_Network_Task(Sparse_Graph_Task):
         super().__init__(params)
         self._resident_batches = weakref.WeakKeyDictionary()      # resident fold -> its one assembled batch (released with the fold)
         self._device_rows = weakref.WeakKeyDictionary()           # host SparseRows -> {device: its one copy there}
-        self._sampling_state = {}                                 # (id of a fold's label array, device, replica) -> (weak reference to the array, _SamplingState)
-        self._graph_state = {}                                    # (id of the first adjacency array, id of the features, device) -> (weak references, _GraphState)
-        self._kept_evaluation = {}                                # (id of a fold's label array, device, fold number, route, fanouts, B) -> (weak reference, its batches)
-        self._sampling_device = None                              # where the model runs (bind_sampling_device)
-        self._sampling_epoch = self._sampling_draw = 0            # TRAIN epochs started / batches sampled so far
+        self.batches = SingleGraphBatches(self)                   # the sampled batches of every mode, their device, counters and caches
         self.subgraph_batches                                     # (a malformed parameter fails here, not in the first epoch)
         self.sampled_batches
         self.__num_edge_types = 2
@@ -367,12 +238,7 @@ class Citation_Network_Task(Sparse_Graph_Task):
         sampled = parse_sampled_batches(self.params.get('sampled_batches'))
         if sampled is None:
             return None
-        if self.sparse_node_features and not sampled.get("sparse_features", False):
-            raise ValueError("sampled_batches cannot be combined with sparse_node_features unless it says \"sparse_features\": true: "
-                             "the weight gradient of the sparse input projection over a row subset needs the transposed structure of "
-                             "that subset, which is then built per batch (SparseRows.take_rows)")
-        if sampled.get("sparse_features", False) and not self.sparse_node_features:
-            raise ValueError("sampled_batches: \"sparse_features\": true requires the task parameter sparse_node_features: True")
+        check_sparse_node_features("sampled_batches", sampled, self.sparse_node_features)
         return sampled
 
     @property
@@ -384,12 +250,7 @@ class Citation_Network_Task(Sparse_Graph_Task):
         if self.params.get('sampled_batches') is not None:
             raise ValueError("subgraph_batches cannot be combined with sampled_batches: a TRAIN epoch is cut into induced subgraphs "
                              "or into neighbour-sampled receptive fields, not both")
-        if self.sparse_node_features and not subgraph.get("sparse_features", False):
-            raise ValueError("subgraph_batches cannot be combined with sparse_node_features unless it says \"sparse_features\": true: "
-                             "the weight gradient of the sparse input projection over a row subset needs the transposed structure of "
-                             "that subset, which is then built per batch (SparseRows.take_rows)")
-        if subgraph.get("sparse_features", False) and not self.sparse_node_features:
-            raise ValueError("subgraph_batches: \"sparse_features\": true requires the task parameter sparse_node_features: True")
+        check_sparse_node_features("subgraph_batches", subgraph, self.sparse_node_features)
         return subgraph
 
     @property
@@ -571,11 +432,9 @@ class Citation_Network_Task(Sparse_Graph_Task):
         """Exactly one minibatch per epoch, the whole graph; max_nodes_per_batch is not consulted (:157-177)."""
         refuse_single_graph_task(self.name())
         fold = next(iter(data))
-        if data_fold == DataFold.TRAIN and self.sampled_batches is not None:
-            yield from self._sampled_batches_of(fold)
-            return
-        if data_fold == DataFold.TRAIN and self.subgraph_batches is not None:
-            yield from self._subgraph_batches_of(fold)
+        sampled = self.batches.train_batches(fold) if data_fold == DataFold.TRAIN else None
+        if sampled is not None:
+            yield from sampled
             return
         sparse = isinstance(fold.node_features, SparseRows)
         feed = {
@@ -606,93 +465,48 @@ class Citation_Network_Task(Sparse_Graph_Task):
         store.citation_fold = folds[0]
         return store
 
-    # -------------------- Sampled mini-batches of the TRAIN fold --------------------
+    # -------------------- Sampled batches (tasks/single_graph_batches.py) and what the model is asked for them --------------------
     def bind_sampling_device(self, device) -> None:
-        """The model tells the task where it runs (the NumPy iterator is not told otherwise).  The sampler is a HIP kernel and the
-        package has no CPU fallback: a model on the CPU is refused."""
-        device = torch.device(device)
-        if device.type != "cuda":
-            raise RuntimeError("sampled_batches needs a model on the GPU: the neighbour sampler is a HIP kernel and there is no CPU "
-                               "fallback (the model is on %s)" % device)
-        self._sampling_device = device
-
-    def _graph_state_of(self, fold: CitationData, device) -> _GraphState:
-        """The device RelGraph (validated once: it knows its hub buckets) and the device feature table of the graph `fold` belongs
-        to, built once for all folds that share the adjacency and feature objects (_load_folds, load_synthetic) and released with them."""
-        anchor, features = fold.adjacency_lists[0], fold.node_features
-        key = (id(anchor), id(features), str(device))
-        held = self._graph_state.get(key)
-        if held is not None and held[0]() is anchor and held[1]() is features:
-            return held[2]
-        from_host = lambda a, dtype: torch.as_tensor(np.ascontiguousarray(a), dtype=dtype).to(device)
-        graph = RelGraph([from_host(a.reshape(-1, 2), torch.int32) for a in fold.adjacency_lists], len(fold.labels))
-        if isinstance(features, SparseRows):                      # the device's one copy of the container: no dense table anywhere
-            table = resident_copy(self._device_rows, features, device)
-        else:
-            table = from_host(features, torch.float32)
-        drop = lambda _, key=key, table=self._graph_state: table.pop(key, None)
-        self._graph_state[key] = (weakref.ref(anchor, drop), weakref.ref(features, drop), _GraphState(graph, table))
-        return self._graph_state[key][2]
-
-    def _sampling_state_of(self, fold: CitationData, device, fanouts=None, seed=None, replica: int = 0):
-        """The TRAIN fold's state by default (the parameter's fanouts and seed, replica 0); an evaluation fold names its own."""
-        key = (id(fold.labels), str(device), int(replica))
-        held = self._sampling_state.get(key)
-        if held is not None and held[0]() is fold.labels and (fanouts is None or held[1].sampler.fanouts == list(fanouts)):
-            return held[1]
-        from_host = lambda a, dtype: torch.as_tensor(np.ascontiguousarray(a), dtype=dtype).to(device)
-        if fanouts is None:
-            sampled = self.sampled_batches
-            fanouts, seed = sampled["fanouts"], sampled["seed"]
-        shared = self._graph_state_of(fold, device)
-        state = _SamplingState(NeighbourSampler(shared.graph, fanouts, seed=seed or 0, replica=replica), shared.features,
-                               from_host(fold.labels, torch.int32), from_host(fold.mask, torch.float32))
-        # released with the fold's arrays, as _resident_batches is with the resident fold
-        self._sampling_state[key] = (weakref.ref(fold.labels, lambda _, key=key, table=self._sampling_state: table.pop(key, None)), state)
-        return state
-
-    # -------------------- Evaluation and predictions on sampled receptive fields --------------------
-    def _bound_device(self):
-        if self._sampling_device is None:
-            raise RuntimeError("sampled_batches: no device bound (Citation_Network_Task.bind_sampling_device); the model does that "
-                               "when it asks for a fold's sampled batches")
-        return self._sampling_device
-
-    def _evaluation_batch(self, state: _SamplingState, seeds: np.ndarray, draw: int, full_graph_route: bool):
-        """Batch `draw` of a fold: hop-ordered and layered, keep-probability 1, labels and mask of the seeds only, every level with its
-        bucketing.  full_graph_route: the levels route their reductions as the device's full graph does (RelGraph.route_like), which
-        is what a resident full-graph batch of the same fold does (tasks/resident.py splits a fold's hubs per batch); otherwise
-        every bucket keeps one wave, as the full graph bucketed by the model itself does (validate="deferred")."""
-        sub = state.sampler.sample_by_hop(seeds, draw)
-        return sub.device_batch(state.features, state.labels, state.mask, 1.0, layered=True, bucketed=True,
-                                route_like=state.sampler.graph if full_graph_route else None)
+        self.batches.bind(device)
 
     def evaluation_batches(self, data, data_fold: DataFold, full_graph_route: bool):
-        """ceil(n_fold / B) batches: one VALIDATION or TEST epoch under the "evaluation" key.  Batch i holds the fold's masked nodes
-        i * B .. (i + 1) * B - 1 in ascending id and is drawn with draw = i by the fold's own sampler, whose replica is
-        neighbour_sampling.evaluation_replica(fold): the same subgraphs in every epoch.  "keep": built once per (fold, device, route, fanouts, B),
-        handed out again, released with the fold."""
-        refuse_single_graph_task(self.name())
-        evaluation, device = self.evaluation, self._bound_device()
-        fold = next(iter(data))
-        key = (id(fold.labels), str(device), data_fold.value, bool(full_graph_route), tuple(evaluation["fanouts"]),
-               evaluation["seeds_per_batch"])
-        if evaluation.get("keep", False):
-            held = self._kept_evaluation.get(key)
-            if held is not None and held[0]() is fold.labels:
-                yield from held[1]
-                return
-        state = self._sampling_state_of(fold, device, evaluation["fanouts"], self.sampled_batches["seed"],
-                                        evaluation_replica(data_fold.value))
-        kept = []
-        for draw, seeds in enumerate(evaluation_seed_batches(fold.mask, evaluation["seeds_per_batch"])):
-            batch = self._evaluation_batch(state, seeds, draw, full_graph_route)
-            if evaluation.get("keep", False):
-                kept.append(batch)
-            yield batch
-        if evaluation.get("keep", False):         # (only a whole epoch is kept: an abandoned iterator keeps nothing)
-            drop = lambda _, key=key, table=self._kept_evaluation: table.pop(key, None)
-            self._kept_evaluation[key] = (weakref.ref(fold.labels, drop), kept)
+        return self.batches.evaluation_batches(data, data_fold, full_graph_route)
+
+    def node_prediction_batches(self, data, distinct_nodes: np.ndarray, fanouts, seeds_per_batch: int, full_graph_route: bool):
+        return self.batches.node_prediction_batches(data, distinct_nodes, fanouts, seeds_per_batch, full_graph_route)
+
+    def resident_rows(self, rows: SparseRows, device) -> SparseRows:
+        return resident_copy(self._device_rows, rows, device)
+
+    def model_requirements(self) -> ModelRequirements:
+        sampled, subgraph = self.sampled_batches or {}, self.subgraph_batches or {}
+        layered = []
+        if sampled.get("layered", False):         # one level graph per layer, one hop per level
+            layered.append((sampled["fanouts"], 'sampled_batches: "layered": true requires %s: layer l runs on the nodes H - l + 1 hops '
+                                                'from a seed, and the layer functions take one graph'))
+        if sampled.get("evaluation") is not None:
+            layered.append((sampled["evaluation"]["fanouts"], 'sampled_batches: "evaluation" requires %s: evaluation batches are '
+                                                              'hop-ordered and run layer l on the nodes H - l + 1 hops from a seed'))
+        message_scale = None
+        if (subgraph.get("normalisation") or {}).get("aggregation", False):    # the per-edge weights reach a layer as its degree scale
+            message_scale = ('subgraph_batches: normalisation: "aggregation": true requires %s: the per-edge weights take the place '
+                             'of 1/(in-degree + 1e-7) in a sum over the messages; "aggregation": false (the loss normalisation '
+                             'alone) works with every model')
+        return ModelRequirements(tuple(layered), message_scale, self.sparse_update, self.sparse_gradient)
+
+    def epoch_batches(self, data, data_fold: DataFold, device, full_graph_route: bool, full_graph: bool = False):
+        if data_fold == DataFold.TRAIN and (self.sampled_batches is not None or self.subgraph_batches is not None):
+            self.bind_sampling_device(device)
+            return self.make_minibatch_iterator(data, data_fold, 0)
+        if data_fold != DataFold.TRAIN and not full_graph and self.evaluation is not None:
+            self.bind_sampling_device(device)
+            return self.evaluation_batches(data, data_fold, full_graph_route)
+        return None
+
+    def epoch_result(self, result, data_fold: DataFold):
+        if data_fold != DataFold.TRAIN and self.evaluation is not None:
+            return self.sampled_evaluation_epoch(result)      # the fold's batches add up to its one graph
+        return result
 
     def node_prediction_settings(self) -> Dict[str, Any]:
         """Fanouts and batch size of predict(nodes=...): the "evaluation" key's, or (None: one 0 per layer) and 1024 without it."""
@@ -709,21 +523,6 @@ class Citation_Network_Task(Sparse_Graph_Task):
             raise ValueError("predict(nodes=...): the ids name nodes of ONE graph; data holds %d" % len(folds))
         return check_prediction_nodes(nodes, len(folds[0].labels))
 
-    def node_prediction_batches(self, data, distinct_nodes: np.ndarray, fanouts, seeds_per_batch: int, full_graph_route: bool):
-        """The batches of predict(nodes=...): the distinct ids ascending in runs of seeds_per_batch, batch i drawn with draw = i by a
-        sampler of replica evaluation_replica(PREDICT_FOLD); each batch carries its host seed list under extra['prediction_seeds']."""
-        refuse_single_graph_task(self.name())
-        device = self._bound_device()
-        fold = next(iter(data))
-        sampled = self.sampled_batches
-        state = self._sampling_state_of(fold, device, list(fanouts), sampled["seed"] if sampled is not None else 0,
-                                        evaluation_replica(PREDICT_FOLD))
-        for draw, at in enumerate(range(0, len(distinct_nodes), seeds_per_batch)):
-            seeds = np.ascontiguousarray(distinct_nodes[at:at + seeds_per_batch], dtype=np.int32)
-            batch = self._evaluation_batch(state, seeds, draw, full_graph_route)
-            batch.extra['prediction_seeds'] = seeds
-            yield batch
-
     @staticmethod
     def sampled_evaluation_epoch(result):
         """The result of an epoch of evaluation batches as the fold's ONE graph: loss = sum of total_loss / sum of num_masked, one
@@ -733,69 +532,13 @@ class Citation_Network_Task(Sparse_Graph_Task):
         total = float(np.sum([float(m['total_loss']) for m in results]))
         return (total / masked if masked else float("nan"), results, 1, graphs_per_s / max(graphs, 1), nodes_per_s, edges_per_s)
 
-    def _sampled_batches_of(self, fold: CitationData):
-        """ceil(n_train / B) sampled batches: one TRAIN epoch."""
-        sampled = self.sampled_batches
-        state = self._sampling_state_of(fold, self._bound_device())
-        epoch, self._sampling_epoch = self._sampling_epoch, self._sampling_epoch + 1
-        keep = self._out_keep(DataFold.TRAIN)
-        for seeds in epoch_seed_batches(fold.mask, sampled["seeds_per_batch"], sampled["seed"], epoch):
-            draw, self._sampling_draw = self._sampling_draw, self._sampling_draw + 1
-            if sampled.get("layered", False):
-                yield state.sampler.sample_by_hop(seeds, draw).device_batch(state.features, state.labels, state.mask, keep,
-                                                                             named_rows=sampled.get("sparse_gradient", False))
-                continue
-            yield state.sampler.sample(seeds, draw).device_batch(state.features, state.labels, state.mask, keep,
-                                                                  named_rows=sampled.get("sparse_gradient", False))
-
-    def _subgraph_state_of(self, fold: CitationData, device) -> _SamplingState:
-        """The TRAIN fold's SubgraphSampler over the device RelGraph the folds share, with the fold's labels and mask."""
-        key = (id(fold.labels), str(device), "subgraph")
-        held = self._sampling_state.get(key)
-        if held is not None and held[0]() is fold.labels:
-            return held[1]
-        from_host = lambda a, dtype: torch.as_tensor(np.ascontiguousarray(a), dtype=dtype).to(device)
-        subgraph = self.subgraph_batches
-        shared = self._graph_state_of(fold, device)
-        state = _SamplingState(SubgraphSampler(shared.graph, subgraph["walk_length"], seed=subgraph["seed"]), shared.features,
-                               from_host(fold.labels, torch.int32), from_host(fold.mask, torch.float32))
-        normalisation = subgraph.get("normalisation")
-        if normalisation is not None:
-            # GraphSAINT's pre-sampling, before the first TRAIN batch of this state: a pure function of (seed, E, the graph), so it
-            # is recomputed here after restore() and never stored in a checkpoint
-            state = state._replace(visit_counts=state.sampler.presample(fold.mask, subgraph["roots_per_batch"],
-                                                                        normalisation["presample_epochs"]))
-        self._sampling_state[key] = (weakref.ref(fold.labels, lambda _, key=key, table=self._sampling_state: table.pop(key, None)), state)
-        return state
-
-    def _subgraph_batches_of(self, fold: CitationData):
-        """ceil(n_train / R) subgraph batches: one TRAIN epoch.  Every train node is a root once; the loss mask is the fold's mask over
-        ALL nodes of the subgraph (seed_mask is ones).  With the key "normalisation" every batch carries extra['loss_normalisation'] =
-        (N / max(node_visits, 1) per node, n_train), and with its "aggregation" the per-edge weights as its graph's degree scale."""
-        subgraph = self.subgraph_batches
-        state = self._subgraph_state_of(fold, self._bound_device())
-        epoch, self._sampling_epoch = self._sampling_epoch, self._sampling_epoch + 1
-        keep = self._out_keep(DataFold.TRAIN)
-        normalisation, counts = subgraph.get("normalisation"), state.visit_counts
-        weighting = (counts, normalisation["max_edge_weight"]) if normalisation is not None and normalisation["aggregation"] else None
-        num_train = float(np.count_nonzero(fold.mask))
-        for roots in epoch_seed_batches(fold.mask, subgraph["roots_per_batch"], subgraph["seed"], epoch):
-            draw, self._sampling_draw = self._sampling_draw, self._sampling_draw + 1
-            if normalisation is None:
-                yield state.sampler.sample(roots, draw).device_batch(state.features, state.labels, state.mask, keep)
-                continue
-            sub = state.sampler.sample(roots, draw, weighting)
-            batch = sub.device_batch(state.features, state.labels, state.mask, keep)
-            batch.extra['loss_normalisation'] = (counts.node_weights(sub.nodes), num_train)
-            yield batch
-
     def compute_initial_node_features(self, batch, weights):
         """The batch's feature table, or in the sparse mode the SparseRows on the batch's device: one copy per device, kept weakly
         with the host container."""
         rows = batch.extra.get('sparse_node_features')
         if rows is None:
             return batch.initial_node_features
-        return resident_copy(self._device_rows, rows, batch.initial_node_features.device)
+        return self.resident_rows(rows, batch.initial_node_features.device)
 
     def make_native_minibatch_iterator(self, batcher, data_fold: DataFold, max_nodes_per_batch: int,
                                        rng: Optional[np.random.RandomState] = None):
@@ -805,11 +548,9 @@ class Citation_Network_Task(Sparse_Graph_Task):
         refuse_single_graph_task(self.name())
         if batcher.store.num_graphs != 1:
             raise ValueError("a citation-network fold is ONE graph; got %d" % batcher.store.num_graphs)
-        if data_fold == DataFold.TRAIN and self.sampled_batches is not None:
-            yield from self._sampled_batches_of(batcher.store.citation_fold)
-            return
-        if data_fold == DataFold.TRAIN and self.subgraph_batches is not None:
-            yield from self._subgraph_batches_of(batcher.store.citation_fold)
+        sampled = self.batches.train_batches(batcher.store.citation_fold) if data_fold == DataFold.TRAIN else None
+        if sampled is not None:
+            yield from sampled
             return
         keep = self._out_keep(data_fold)
         batcher.constants['out_layer_dropout_keep_prob'] = keep

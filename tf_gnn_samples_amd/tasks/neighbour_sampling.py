@@ -51,6 +51,33 @@ def epoch_seed_batches(fold_mask, seeds_per_batch: int, seed: int, epoch: int) -
     return [np.sort(shuffled[i:i + seeds_per_batch]).astype(np.int32) for i in range(0, len(shuffled), seeds_per_batch)]
 
 
+def validated_ids(ids, num_nodes: int, device, what: str) -> torch.Tensor:
+    """`ids` (int32, one-dimensional, non-empty, in range, distinct) ascending on the device; `what` ("seed", "root", "node") names them."""
+    host = ids.detach().cpu().numpy() if torch.is_tensor(ids) else np.asarray(ids)
+    if host.ndim != 1 or host.dtype != np.int32:
+        raise ValueError("%ss must be a one-dimensional int32 array" % what)
+    if len(host) == 0:
+        raise ValueError("the %s list is empty" % what)
+    if host.min() < 0 or host.max() >= num_nodes:
+        raise ValueError("%s outside [0, %d)" % (what, num_nodes))
+    ordered = np.sort(host)
+    if (ordered[1:] == ordered[:-1]).any():
+        raise ValueError("the %s list names a node twice" % what)
+    if torch.is_tensor(ids) and ids.is_cuda and np.array_equal(ordered, host):
+        return ids.contiguous()
+    return torch.as_tensor(ordered, device=device)
+
+
+def _batch_rows(sub, features, labels, mask, out_keep: float, named_rows: bool, **more):
+    """-> (the feature rows of `sub.nodes`, the batch's `extra`).  `features` a SparseRows: the [n, 1] stand-in takes the table's place and
+    the rows' subset (SparseRows.take_rows, csrc/sparse_subset.hip) travels under extra['sparse_node_features']; no dense row is built."""
+    extra = dict(labels=labels, mask=mask, out_layer_dropout_keep_prob=out_keep, sampled_nodes=sub.nodes, **more)
+    if isinstance(features, SparseRows):
+        extra['sparse_node_features'] = features.take_rows(sub.nodes, validated=True, named_rows=named_rows)
+        return torch.zeros((sub.num_nodes, 1), dtype=torch.float32, device=sub.nodes.device), extra      # sparse_features.node_stand_in
+    return features.index_select(0, sub.nodes.long()), extra
+
+
 class SampledSubgraph(NamedTuple):
     nodes: torch.Tensor                         # int32 [n]: ascending global ids; local id = position
     adjacency_lists: List[torch.Tensor]         # per edge type int32 [E_l, 2] = (source, target) in local ids
@@ -64,19 +91,13 @@ class SampledSubgraph(NamedTuple):
     def device_batch(self, features, labels: torch.Tensor, fold_mask: torch.Tensor, out_keep: float = 1.0,
                      named_rows: bool = False) -> DeviceBatch:
         """The subgraph as one training batch: feature and label rows of the device-resident [V, ...] tables, the loss mask
-        seed_mask * fold_mask[nodes].  `features` a SparseRows: the [n, 1] stand-in takes the table's place and the rows' subset
-        (SparseRows.take_rows, csrc/sparse_subset.hip) travels under extra['sparse_node_features']; no dense row is built.
+        seed_mask * fold_mask[nodes] (the rows and the rest of `extra`: _batch_rows).
         named_rows: the subset also carries the words it names (`"sparse_gradient": true`; SparseRows.named_rows).
         message_weights set: the batch brings its RelGraph with those weights preset as the scale of its degree table
         (RelGraph.preset_message_scale), so every layer that asks graph.degree_scale(batch degrees) receives them."""
         index = self.nodes.long()
-        extra = {'labels': labels.index_select(0, index), 'mask': self.seed_mask * fold_mask.index_select(0, index),
-                 'out_layer_dropout_keep_prob': out_keep, 'sampled_nodes': self.nodes}
-        if isinstance(features, SparseRows):
-            extra['sparse_node_features'] = features.take_rows(self.nodes, validated=True, named_rows=named_rows)
-            rows = torch.zeros((self.num_nodes, 1), dtype=torch.float32, device=self.nodes.device)      # sparse_features.node_stand_in
-        else:
-            rows = features.index_select(0, index)
+        rows, extra = _batch_rows(self, features, labels.index_select(0, index), self.seed_mask * fold_mask.index_select(0, index),
+                                  out_keep, named_rows)
         batch = DeviceBatch.from_tensors(1, self.num_nodes, self.num_edges, rows, self.adjacency_lists,
                                          self.type_to_num_incoming_edges, extra=extra)
         if self.message_weights is not None:
@@ -147,14 +168,8 @@ class HopSubgraph(NamedTuple):
         if not layered:
             return union.device_batch(features, labels, fold_mask, out_keep, named_rows=named_rows)
         seeds = self.nodes[:self.hop_nodes[0]].long()
-        extra = {'labels': labels.index_select(0, seeds), 'mask': fold_mask.index_select(0, seeds),
-                 'out_layer_dropout_keep_prob': out_keep, 'sampled_nodes': self.nodes,
-                 'layer_graphs': self.level_graphs(bucketed, route_like)}
-        if isinstance(features, SparseRows):
-            extra['sparse_node_features'] = features.take_rows(self.nodes, validated=True, named_rows=named_rows)
-            rows = torch.zeros((self.num_nodes, 1), dtype=torch.float32, device=self.nodes.device)      # sparse_features.node_stand_in
-        else:
-            rows = features.index_select(0, self.nodes.long())
+        rows, extra = _batch_rows(self, features, labels.index_select(0, seeds), fold_mask.index_select(0, seeds), out_keep, named_rows,
+                                  layer_graphs=self.level_graphs(bucketed, route_like))
         batch = DeviceBatch.from_tensors(1, self.num_nodes, self.num_edges, rows, self.adjacency_lists,
                                          self.type_to_num_incoming_edges, extra=extra)
         if bucketed:
@@ -189,24 +204,9 @@ class NeighbourSampler:
             event.record()
             self.trace.append((phase, event))
 
-    def _validated(self, seeds) -> torch.Tensor:
-        host = seeds.detach().cpu().numpy() if torch.is_tensor(seeds) else np.asarray(seeds)
-        if host.ndim != 1 or host.dtype != np.int32:
-            raise ValueError("seeds must be a one-dimensional int32 array")
-        if len(host) == 0:
-            raise ValueError("the seed list is empty")
-        if host.min() < 0 or host.max() >= self.graph.V:
-            raise ValueError("seed outside [0, %d)" % self.graph.V)
-        ordered = np.sort(host)
-        if (ordered[1:] == ordered[:-1]).any():
-            raise ValueError("the seed list names a node twice")
-        if torch.is_tensor(seeds) and seeds.is_cuda and np.array_equal(ordered, host):
-            return seeds.contiguous()
-        return torch.as_tensor(ordered, device=self.graph.device)
-
     def sample(self, seeds, draw: int) -> SampledSubgraph:
         """seeds: int32 device tensor (a host array is uploaded), distinct node ids; draw: the count of sampled batches so far."""
-        seeds = self._validated(seeds)
+        seeds = validated_ids(seeds, self.graph.V, self.graph.device, "seed")
         try:
             with torch.cuda.device(self.graph.device):
                 return self._sample(seeds, int(draw) & 0xffffffff)
@@ -217,7 +217,7 @@ class NeighbourSampler:
     def sample_by_hop(self, seeds, draw: int) -> "HopSubgraph":
         """The subgraph sample(seeds, draw) gives — the same hops, draws and edges — numbered by hop: the seeds, then the nodes first
         reached in hop 1, ..., each group in ascending id.  No read-back beyond sample()'s."""
-        seeds = self._validated(seeds)
+        seeds = validated_ids(seeds, self.graph.V, self.graph.device, "seed")
         try:
             with torch.cuda.device(self.graph.device):
                 return self._sample_by_hop(seeds, int(draw) & 0xffffffff)
@@ -354,31 +354,34 @@ def parse_sampled_batches(value) -> Optional[Dict]:
     if isinstance(per_batch, bool) or not isinstance(per_batch, (int, np.integer)) or per_batch < 1:
         raise ValueError("sampled_batches: seeds_per_batch must be a positive integer, got %r" % (per_batch,))
     parsed = {"fanouts": check_fanouts(value["fanouts"]), "seeds_per_batch": int(per_batch), "seed": int(value.get("seed", 0))}
-    if "sparse_features" in value:
-        if not isinstance(value["sparse_features"], bool):
-            raise ValueError("sampled_batches: sparse_features must be true or false, got %r" % (value["sparse_features"],))
-        parsed["sparse_features"] = value["sparse_features"]
-    if "sparse_update" in value:
-        if not isinstance(value["sparse_update"], bool):
-            raise ValueError("sampled_batches: sparse_update must be true or false, got %r" % (value["sparse_update"],))
-        if value["sparse_update"] and not parsed.get("sparse_features", False):
-            raise ValueError("sampled_batches: \"sparse_update\": true requires \"sparse_features\": true (the rows a batch names are "
-                             "read from the transposed structure of its SparseRows)")
-        parsed["sparse_update"] = value["sparse_update"]
-    if "sparse_gradient" in value:
-        if not isinstance(value["sparse_gradient"], bool):
-            raise ValueError("sampled_batches: sparse_gradient must be true or false, got %r" % (value["sparse_gradient"],))
-        if value["sparse_gradient"] and not parsed.get("sparse_update", False):
-            raise ValueError("sampled_batches: \"sparse_gradient\": true requires \"sparse_update\": true (the compact gradient is "
-                             "what the row-deferred update consumes; dense Adam reads a dense one)")
-        parsed["sparse_gradient"] = value["sparse_gradient"]
-    if "layered" in value:
-        if not isinstance(value["layered"], bool):
-            raise ValueError("sampled_batches: layered must be true or false, got %r" % (value["layered"],))
-        parsed["layered"] = value["layered"]
+    parse_bool_keys("sampled_batches", value, parsed, ("sparse_features", "sparse_update", "sparse_gradient", "layered"), {
+        "sparse_update": ("sparse_features", "the rows a batch names are read from the transposed structure of its SparseRows"),
+        "sparse_gradient": ("sparse_update", "the compact gradient is what the row-deferred update consumes; dense Adam reads a dense one")})
     if "evaluation" in value:
         parsed["evaluation"] = parse_evaluation(value["evaluation"])
     return parsed
+
+
+def parse_bool_keys(what: str, value: Dict, parsed: Dict, keys, needs=None) -> None:
+    """The optional bool keys of the parameter `what`, in the order of `keys`: each must be true or false and is carried into `parsed`
+    only when given.  needs: key -> (the key that must be true for it to be true, why)."""
+    for key in (key for key in keys if key in value):
+        if not isinstance(value[key], bool):
+            raise ValueError("%s: %s must be true or false, got %r" % (what, key, value[key]))
+        needed, why = (needs or {}).get(key, (None, None))
+        if needed is not None and value[key] and not parsed.get(needed, False):
+            raise ValueError('%s: "%s": true requires "%s": true (%s)' % (what, key, needed, why))
+        parsed[key] = value[key]
+
+
+def check_sparse_node_features(what: str, parsed: Dict, sparse_node_features: bool) -> None:
+    """The key "sparse_features" of the parameter `what` ("sampled_batches", "subgraph_batches") and sparse_node_features go together."""
+    if sparse_node_features and not parsed.get("sparse_features", False):
+        raise ValueError("%s cannot be combined with sparse_node_features unless it says \"sparse_features\": true: "
+                         "the weight gradient of the sparse input projection over a row subset needs the transposed structure of "
+                         "that subset, which is then built per batch (SparseRows.take_rows)" % what)
+    if parsed.get("sparse_features", False) and not sparse_node_features:
+        raise ValueError("%s: \"sparse_features\": true requires the task parameter sparse_node_features: True" % what)
 
 
 def parse_evaluation(value) -> Dict:

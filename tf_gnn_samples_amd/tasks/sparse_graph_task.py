@@ -98,6 +98,15 @@ class DeviceBatch:
         return self
 
 
+class ModelRequirements(NamedTuple):
+    """What a task's batches need from the model that runs them (Sparse_Graph_Task.model_requirements); the model checks each and
+    raises the task's text with what it lacks in the place of %s."""
+    layered: tuple = ()                         # ((fanouts, text), ...): batches with one level graph per layer for these fanouts
+    message_scale: Optional[str] = None         # the text, when batches bring a per-message scale in the degree scale's place
+    deferred_projection_rows: bool = False      # the input projection's weight is updated by the rows a batch names
+    compact_projection_gradient: bool = False   # ... and its gradient exists only as those rows
+
+
 class Sparse_Graph_Task:
     """Minimal task interface used by Sparse_Graph_Model (tasks/sparse_graph_task.py:23-254)."""
 
@@ -199,6 +208,23 @@ class Sparse_Graph_Task:
             batcher.constants['out_layer_dropout_keep_prob'] = 1.0
         for batch in batcher.iterate(ids, max_nodes_per_batch):
             yield self._finish_native_batch(batch)
+
+    # ---- what the model driver asks a task with batching modes of its own (the citation task); the defaults ask for nothing ----
+    def model_requirements(self) -> ModelRequirements:
+        return ModelRequirements()
+
+    def epoch_batches(self, data, data_fold: DataFold, device, full_graph_route: bool, full_graph: bool = False):
+        """The batches of one epoch on `device` when the task cuts them itself, None for the general input pipelines.
+        full_graph_route: would the model's full-graph batch of a single-graph fold be a resident one?  full_graph: predict(data)."""
+        return None
+
+    def epoch_result(self, result, data_fold: DataFold):
+        """The result of an epoch (EpochTally.result) as the task reports it."""
+        return result
+
+    def check_prediction_nodes(self, data, nodes):
+        raise ValueError("predict(nodes=...) is not defined for the %s task: its predictions are per graph of `data`, and only a "
+                         "task whose data is ONE graph names single nodes" % self.name())
 
     def loss_weight(self, num_graphs: int, num_nodes: int) -> float:
         """The normaliser of the task's loss for a batch of that many graphs and nodes: what the batch weighs in the mean over a

@@ -18,7 +18,7 @@ import torch
 
 from .. import _lib
 from ..graph import RelGraph
-from .neighbour_sampling import SampledSubgraph, epoch_seed_batches
+from .neighbour_sampling import SampledSubgraph, epoch_seed_batches, parse_bool_keys, validated_ids
 
 # relgnn_subgraph_max_walk_length (the library is not loaded to validate a parameter; tests/test_gpu_subgraph_batches.py holds the
 # two against each other)
@@ -31,23 +31,6 @@ def check_walk_length(walk_length) -> int:
         raise ValueError("walk_length must be an integer in [0, %d] (0: the subgraph induced on the roots alone), got %r"
                          % (MAX_WALK_LENGTH, walk_length))
     return int(walk_length)
-
-
-def _validated(ids, num_nodes: int, device, what: str) -> torch.Tensor:
-    """`ids` (int32, one-dimensional, non-empty, in range, distinct) ascending on the device; NeighbourSampler._validated's rules."""
-    host = ids.detach().cpu().numpy() if torch.is_tensor(ids) else np.asarray(ids)
-    if host.ndim != 1 or host.dtype != np.int32:
-        raise ValueError("%ss must be a one-dimensional int32 array" % what)
-    if len(host) == 0:
-        raise ValueError("the %s list is empty" % what)
-    if host.min() < 0 or host.max() >= num_nodes:
-        raise ValueError("%s outside [0, %d)" % (what, num_nodes))
-    ordered = np.sort(host)
-    if (ordered[1:] == ordered[:-1]).any():
-        raise ValueError("the %s list names a node twice" % what)
-    if torch.is_tensor(ids) and ids.is_cuda and np.array_equal(ordered, host):
-        return ids.contiguous()
-    return torch.as_tensor(ordered, device=device)
 
 
 class _Extractor:
@@ -165,7 +148,7 @@ class SubgraphSampler(_Extractor):
         max_edge_weight): the subgraph also carries GraphSAINT's per-edge weights, message_weights float32 [num_edges] in the order of
         the lists; the lists and the degrees are the unweighted call's."""
         g = self.graph
-        roots = _validated(roots, g.V, g.device, "root")
+        roots = validated_ids(roots, g.V, g.device, "root")
         R, draw = int(roots.numel()), int(draw) & 0xffffffff
 
         def walks():
@@ -216,7 +199,7 @@ def induced_subgraph(graph: RelGraph, nodes) -> SampledSubgraph:
     """The subgraph of `graph` induced on a node set the caller brings (a partition, say): int32 ids, distinct, any order.  The
     induced-edge path of SubgraphSampler.sample without the walks; one read-back."""
     extractor = _Extractor(graph, "induced_subgraph")
-    nodes = _validated(nodes, graph.V, graph.device, "node")
+    nodes = validated_ids(nodes, graph.V, graph.device, "node")
 
     def given():
         _lib.launch("relgnn_neighbour_sample_begin", _lib.ptr(nodes), nodes.numel(), _lib.ptr(extractor.stamp), graph.V)
@@ -271,10 +254,7 @@ def parse_subgraph_batches(value) -> Optional[Dict]:
     if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)):
         raise ValueError("subgraph_batches: seed must be an integer, got %r" % (seed,))
     parsed = {"roots_per_batch": int(per_batch), "walk_length": walk_length, "seed": int(seed)}
-    if "sparse_features" in value:
-        if not isinstance(value["sparse_features"], bool):
-            raise ValueError("subgraph_batches: sparse_features must be true or false, got %r" % (value["sparse_features"],))
-        parsed["sparse_features"] = value["sparse_features"]
+    parse_bool_keys("subgraph_batches", value, parsed, ("sparse_features",))
     if "normalisation" in value:
         parsed["normalisation"] = parse_normalisation(value["normalisation"])
     return parsed
