@@ -1,9 +1,9 @@
 """Data-parallel train() / test() (Sparse_Graph_Model.train(group=...)), the host side: the schedule every
 rank derives from the exchanged batch plans, the plan over a real GraphStore, the exchange and the metric merge over gloo, the
-tasks' loss_weight hook and the fourth header of the C ABI (include/relgnn_parallel.h).  The GPU half is tests/test_gpu_dp_train.py."""
+tasks' loss_weight hook and the host-side argument checks of include/relgnn_parallel.h (tests/test_abi.py holds the header itself).
+The GPU half is tests/test_gpu_dp_train.py."""
 import ctypes
 import os
-import re
 import socket
 import sys
 from pathlib import Path
@@ -193,55 +193,6 @@ def test_loss_weight_is_what_each_task_normalises_its_loss_by():
         Citation_Network_Task(Citation_Network_Task.default_params()).loss_weight(1, 2708)
     with pytest.raises(NotImplementedError, match="loss_weight"):
         Sparse_Graph_Task({}).loss_weight(1, 1)
-
-
-# ---- include/relgnn_parallel.h: what tests/test_abi.py does for include/relgnn.h --------------------------------------------------
-_C_TYPES = {"int32_t": ctypes.c_int32, "uint32_t": ctypes.c_uint32, "int64_t": ctypes.c_int64, "float": ctypes.c_float,
-            "size_t": ctypes.c_size_t, "int": ctypes.c_int}
-
-
-def _stripped(header):
-    text = (ROOT / "include" / header).read_text()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    return re.sub(r"//[^\n]*", "", text)
-
-
-def _c_type(text):
-    if "*" in text:
-        return ctypes.c_void_p
-    return _C_TYPES[[w for w in text.split() if w != "const"][0]]
-
-
-def _declared(header):
-    out = {}
-    for ret, name, params in re.findall(r"^\s*((?:const\s+)?\w+\s*\**)\s*\b(relgnn_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", _stripped(header), flags=re.M):
-        params = " ".join(params.split())
-        out[name] = (_c_type(ret), [] if params in ("", "void") else [_c_type(a) for a in params.split(",")])
-    return out
-
-
-def test_the_parallel_header_is_exported_and_bound_argument_for_argument():
-    from tf_gnn_samples_amd import _build, _lib
-    declared = _declared("relgnn_parallel.h")
-    assert sorted(declared) == ["relgnn_mt_pack_scaled_f32"]
-    assert sorted(declared) == sorted(set(re.findall(r"\b(relgnn_[a-z0-9_]+)\s*\(", _stripped("relgnn_parallel.h"))))
-    assert declared["relgnn_mt_pack_scaled_f32"] == (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_float,
-                                                                    ctypes.c_void_p, ctypes.c_void_p])
-    if not _lib.LIB_PATH.exists():
-        _build.build_library()
-    raw = ctypes.CDLL(str(_lib.LIB_PATH))
-    assert not [n for n in declared if not hasattr(raw, n)]
-    bound = _lib.parallel_signatures()
-    assert sorted(bound) == sorted(declared)
-    wrong = {n: (bound[n], declared[n]) for n in declared if (bound[n][0], list(bound[n][1])) != declared[n]}
-    assert not wrong, "bound (restype, argtypes) vs the header's: %s" % wrong
-    lib = _lib.load_library()                           # the loader types the fourth table too
-    for n, (restype, argtypes) in bound.items():
-        assert getattr(lib, n).restype is restype and list(getattr(lib, n).argtypes) == list(argtypes), n
-    others = set(_lib.exported_signatures()) | set(_lib.dropout_signatures()) | set(_lib.predict_signatures())
-    assert not set(bound) & others
-    assert (ROOT / "include" / "relgnn_parallel.h") in _build.HEADERS
-    assert (ROOT / "tf_gnn_samples_amd" / "csrc" / "parallel.hip") in _build._sources()
 
 
 def test_the_pack_refuses_bad_arguments_without_a_launch():

@@ -1,7 +1,5 @@
-"""Layer-input dropout, the parts that need no GPU: the Philox restatement the GPU tests lean on, the layer_dropout switch, the
-second header of the C ABI (include/relgnn_dropout.h) and the CPU model's route."""
-import ctypes
-import re
+"""Layer-input dropout, the parts that need no GPU: the Philox restatement the GPU tests lean on, the layer_dropout switch and the
+CPU model's route.  (Its header of the C ABI, include/relgnn_dropout.h, is held by tests/test_abi.py.)"""
 from pathlib import Path
 
 import numpy as np
@@ -54,63 +52,6 @@ def test_the_switch_is_in_the_table_and_in_the_readme():
             pass
     text = (ROOT / "README.md").read_text()
     assert "`RELGNN_LAYER_DROPOUT`" in text[text.index("## Switches"):]
-
-
-# ---- include/relgnn_dropout.h: what tests/test_abi.py does for include/relgnn.h ------------------------------------------------
-_C_TYPES = {"int32_t": ctypes.c_int32, "uint32_t": ctypes.c_uint32, "int64_t": ctypes.c_int64, "float": ctypes.c_float,
-            "size_t": ctypes.c_size_t, "int": ctypes.c_int}
-
-
-def _stripped(header):
-    text = (ROOT / "include" / header).read_text()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    return re.sub(r"//[^\n]*", "", text)
-
-
-def _c_type(text):
-    if "*" in text:
-        return ctypes.c_void_p
-    return _C_TYPES[[w for w in text.split() if w != "const"][0]]
-
-
-def declared_signatures(header="relgnn_dropout.h"):
-    out = {}
-    for ret, name, params in re.findall(r"^\s*((?:const\s+)?\w+\s*\**)\s*\b(relgnn_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", _stripped(header), flags=re.M):
-        params = " ".join(params.split())
-        out[name] = (_c_type(ret), [] if params in ("", "void") else [_c_type(a) for a in params.split(",")])
-    return out
-
-
-def test_the_dropout_header_is_exported_and_bound_argument_for_argument():
-    from tf_gnn_samples_amd import _build, _lib
-    declared = declared_signatures()
-    assert sorted(declared) == ["relgnn_dropout_bwd", "relgnn_dropout_fwd", "relgnn_dropout_residual_bwd", "relgnn_dropout_residual_fwd"]
-    assert sorted(declared) == sorted(set(re.findall(r"\b(relgnn_[a-z0-9_]+)\s*\(", _stripped("relgnn_dropout.h"))))
-    if not _lib.LIB_PATH.exists():
-        _build.build_library()
-    raw = ctypes.CDLL(str(_lib.LIB_PATH))
-    assert not [n for n in declared if not hasattr(raw, n)]
-    bound = _lib.dropout_signatures()
-    assert sorted(bound) == sorted(declared)
-    wrong = {n: (bound[n], declared[n]) for n in declared if (bound[n][0], list(bound[n][1])) != declared[n]}
-    assert not wrong, "bound (restype, argtypes) vs the header's: %s" % wrong
-    lib = _lib.load_library()                           # the loader types the second table too
-    for n, (restype, argtypes) in bound.items():
-        assert getattr(lib, n).restype is restype and list(getattr(lib, n).argtypes) == list(argtypes), n
-
-
-def test_the_first_header_and_its_table_are_untouched():
-    from tf_gnn_samples_amd import _lib
-    names = sorted(set(re.findall(r"\b(relgnn_[a-z0-9_]+)\s*\(", re.sub(r"/\*.*?\*/", "", (ROOT / "include" / "relgnn.h").read_text(), flags=re.S))))
-    assert len(names) == 126 and not [n for n in names if "dropout" in n]
-    assert sorted(_lib.exported_signatures()) == names
-    assert not set(_lib.dropout_signatures()) & set(_lib.exported_signatures())
-
-
-def test_the_build_watches_the_dropout_header():
-    from tf_gnn_samples_amd import _build
-    assert (ROOT / "include" / "relgnn_dropout.h") in _build.HEADERS and (ROOT / "include" / "relgnn.h") in _build.HEADERS
-    assert (ROOT / "tf_gnn_samples_amd" / "csrc" / "dropout.hip") in _build._sources()
 
 
 def test_a_cpu_model_keeps_the_torch_call_under_the_fused_switch(monkeypatch):

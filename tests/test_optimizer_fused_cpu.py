@@ -1,20 +1,19 @@
 """The fused RMSProp / SGD update (csrc/train_utils.hip) as seen without a GPU: the two entries are declared and bound, CPU
 parameters keep the foreach path bit for bit, and a CPU model cannot be captured."""
 import re
-from pathlib import Path
 
 import pytest
 import torch
 
-ROOT = Path(__file__).resolve().parent.parent
+from abi_reference import declared_names, stripped
+
 NEW_ENTRIES = ("relgnn_mt_rmsprop_clip", "relgnn_mt_sgd_clip")
 
 
 def test_header_and_ctypes_table_carry_the_two_entries():
     from tf_gnn_samples_amd import _lib
-    text = re.sub(r"/\*.*?\*/", "", (ROOT / "include" / "relgnn.h").read_text(), flags=re.S)
-    declared = set(re.findall(r"\b(relgnn_[a-z0-9_]+)\s*\(", text))
-    sigs = _lib.exported_signatures()
+    text, declared = stripped("relgnn.h"), declared_names("relgnn.h")
+    sigs = _lib.signatures("relgnn.h")
     for name in NEW_ENTRIES:
         assert name in declared, name
         assert name in sigs, name

@@ -1,60 +1,8 @@
-"""Predictions without a GPU: the C ABI of include/relgnn_predict.h against its binding, the four task hooks on CPU tensors against
-hand-written expectations, and the per-graph split."""
-import ctypes
-import re
-from pathlib import Path
-
+"""Predictions without a GPU: the four task hooks on CPU tensors against hand-written expectations, and the per-graph split.  (The
+C ABI of include/relgnn_predict.h is held against its binding by tests/test_abi.py.)"""
 import numpy as np
 import pytest
 import torch
-
-ROOT = Path(__file__).resolve().parent.parent
-HEADER = ROOT / "include" / "relgnn_predict.h"
-
-_C_TYPES = {"int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64, "float": ctypes.c_float, "size_t": ctypes.c_size_t, "int": ctypes.c_int}
-
-
-def _c_type(text):
-    if "*" in text:
-        return ctypes.c_void_p
-    return _C_TYPES[[w for w in text.split() if w != "const"][0]]
-
-
-def declared_signatures():
-    """name -> (restype, [argtypes]) of every function the header declares, read from its text with the comments stripped."""
-    text = re.sub(r"/\*.*?\*/", "", HEADER.read_text(), flags=re.S)
-    text = re.sub(r"//[^\n]*", "", text)
-    out = {}
-    for ret, name, params in re.findall(r"^\s*((?:const\s+)?\w+\s*\**)\s*\b(relgnn_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", text, flags=re.M):
-        out[name] = (_c_type(ret), [_c_type(a) for a in " ".join(params.split()).split(",")])
-    return out
-
-
-# ---------------------------------------------------------------------------------------------------------------------------------
-# header <-> exported symbols <-> predict_signatures()
-# ---------------------------------------------------------------------------------------------------------------------------------
-def test_header_binding_and_library_agree():
-    from tf_gnn_samples_amd import _build, _lib
-    declared, bound = declared_signatures(), _lib.predict_signatures()
-    assert sorted(declared) == ["relgnn_predict_candidates_f32", "relgnn_predict_sigmoid_f32", "relgnn_predict_softmax_f32"]
-    assert sorted(bound) == sorted(declared)
-    wrong = {n: (bound[n], declared[n]) for n in declared if (bound[n][0], list(bound[n][1])) != declared[n]}
-    assert not wrong, "bound (restype, argtypes) vs the header's: %s" % wrong
-    if not _lib.LIB_PATH.exists():
-        _build.build_library()
-    raw = ctypes.CDLL(str(_lib.LIB_PATH))
-    assert not [n for n in declared if not hasattr(raw, n)]
-    lib = _lib.load_library()
-    for name, (restype, argtypes) in bound.items():
-        assert getattr(lib, name).restype == restype and list(getattr(lib, name).argtypes) == list(argtypes)
-
-
-def test_exported_signatures_is_still_the_list_of_relgnn_h():
-    from tf_gnn_samples_amd import _lib
-    text = re.sub(r"/\*.*?\*/", "", (ROOT / "include" / "relgnn.h").read_text(), flags=re.S)
-    assert sorted(_lib.exported_signatures()) == sorted(set(re.findall(r"\b(relgnn_[a-z0-9_]+)\s*\(", text)))
-    assert not set(_lib.exported_signatures()) & set(_lib.predict_signatures())
-    assert not set(_lib.dropout_signatures()) & set(_lib.predict_signatures())
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------

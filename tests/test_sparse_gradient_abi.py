@@ -1,44 +1,5 @@
-"""include/relgnn_sparse_gradient.h <-> exported symbols <-> _lib.sparse_gradient_signatures(), as the other side headers are held; the
-argument checks that need no GPU (every refusal returns before anything is launched)."""
-import ctypes
-import re
-from pathlib import Path
-
-ROOT = Path(__file__).resolve().parent.parent
-HEADER = ROOT / "include" / "relgnn_sparse_gradient.h"
-ENTRIES = ["relgnn_named_rows_count", "relgnn_named_rows_fill", "relgnn_named_rows_workspace_bytes", "relgnn_rows_adam_step_compact",
-           "relgnn_rows_l2norm", "relgnn_rows_l2norm_workspace_bytes"]
-
-C_TYPES = {"int32_t": ctypes.c_int32, "uint32_t": ctypes.c_uint32, "int64_t": ctypes.c_int64, "float": ctypes.c_float,
-           "size_t": ctypes.c_size_t, "int": ctypes.c_int}
-
-
-def declared_signatures():
-    c_type = lambda text: ctypes.c_void_p if "*" in text else C_TYPES[[w for w in text.split() if w != "const"][0]]
-    text = re.sub(r"//[^\n]*", "", re.sub(r"/\*.*?\*/", "", HEADER.read_text(), flags=re.S))
-    declared = {}
-    for ret, name, params in re.findall(r"^\s*((?:const\s+)?\w+\s*\**)\s*\b(relgnn_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", text, flags=re.M):
-        params = " ".join(params.split())
-        declared[name] = (c_type(ret), [] if params == "void" else [c_type(a) for a in params.split(",")])
-    return declared
-
-
-def test_header_binding_and_library_agree():
-    from tf_gnn_samples_amd import _build, _lib
-    assert HEADER in _build.HEADERS
-    declared, bound = declared_signatures(), _lib.sparse_gradient_signatures()
-    assert sorted(declared) == sorted(bound) == ENTRIES
-    wrong = {n: (bound[n], declared[n]) for n in declared if (bound[n][0], list(bound[n][1])) != declared[n]}
-    assert not wrong, "bound (restype, argtypes) vs the header's: %s" % wrong
-    assert len(declared["relgnn_rows_adam_step_compact"][1]) == 21 and len(declared["relgnn_rows_l2norm"][1]) == 10
-    others = [_lib.exported_signatures(), _lib.dropout_signatures(), _lib.predict_signatures(), _lib.parallel_signatures(),
-              _lib.sparse_features_signatures(), _lib.sampling_signatures(), _lib.sparse_subset_signatures(),
-              _lib.sparse_update_signatures()]
-    assert all(not set(o) & set(bound) for o in others)
-    if not _lib.LIB_PATH.exists():
-        _build.build_library()
-    raw = ctypes.CDLL(str(_lib.LIB_PATH))
-    assert not [n for n in declared if not hasattr(raw, n)]
+"""include/relgnn_sparse_gradient.h: the argument checks that need no GPU (every refusal returns before anything is launched).  The
+header is held against the binding and the library by tests/test_abi.py."""
 
 
 def test_refusals_before_any_launch():

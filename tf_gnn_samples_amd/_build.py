@@ -1,6 +1,4 @@
-"""Build librelgnn.so (the C-ABI HIP library, include/relgnn.h, relgnn_dropout.h, relgnn_predict.h, relgnn_parallel.h, relgnn_sparse_features.h,
-relgnn_sampling.h, relgnn_sparse_subset.h, relgnn_sparse_update.h, relgnn_sparse_gradient.h, relgnn_layered_sampling.h,
-relgnn_subgraph.h and relgnn_subgraph_norm.h) in-tree for gfx950.
+"""Build librelgnn.so (the C-ABI HIP library of the headers include/relgnn*.h) in-tree for gfx950.
 
 hipcc cross-compiles without a GPU, so this runs in the CPU-only build container; the
 resulting tf_gnn_samples_amd/librelgnn.so travels with the repo snapshot to the GPU box.
@@ -13,12 +11,7 @@ from pathlib import Path
 PKG_DIR = Path(__file__).resolve().parent
 CSRC = PKG_DIR / "csrc"
 LIB_PATH = PKG_DIR / "librelgnn.so"
-HEADERS = [PKG_DIR.parent / "include" / name for name in ("relgnn.h", "relgnn_dropout.h", "relgnn_predict.h",
-                                                               "relgnn_parallel.h", "relgnn_sparse_features.h",
-                                                               "relgnn_sampling.h", "relgnn_sparse_subset.h",
-                                                               "relgnn_sparse_update.h", "relgnn_sparse_gradient.h",
-                                                               "relgnn_layered_sampling.h", "relgnn_subgraph.h",
-                                                               "relgnn_subgraph_norm.h")]                             # the C ABI
+HEADERS = sorted((PKG_DIR.parent / "include").glob("relgnn*.h"))       # the C ABI: every header is a build dependency
 HIPCC_FLAGS = [
     "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC",
     # product and add of `scale * row` then `acc + msg` are rounded separately, like the

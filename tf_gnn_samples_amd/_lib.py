@@ -1,7 +1,4 @@
-"""ctypes binding of librelgnn.so (C ABI: include/relgnn.h, include/relgnn_dropout.h, include/relgnn_predict.h,
-include/relgnn_parallel.h, include/relgnn_sparse_features.h, include/relgnn_sampling.h, include/relgnn_sparse_subset.h,
-include/relgnn_sparse_update.h, include/relgnn_sparse_gradient.h, include/relgnn_layered_sampling.h, include/relgnn_subgraph.h,
-include/relgnn_subgraph_norm.h).
+"""ctypes binding of librelgnn.so (C ABI: the headers include/relgnn*.h, one table of `ABI` each).
 
 This is the ONLY compute backend of the package.  There is no CPU / eager-PyTorch fallback:
 if the HIP library is missing, or a tensor is not a float32/int32 CUDA(HIP) tensor, the
@@ -28,8 +25,12 @@ _c_i32, _c_i64, _c_f32 = ctypes.c_int32, ctypes.c_int64, ctypes.c_float
 _c_u32 = ctypes.c_uint32
 _ptr = ctypes.c_void_p
 
-# name -> (restype, argtypes); must list every function declared in include/relgnn.h
-_SIGNATURES = {
+# header file name -> {name: (restype, argtypes)}: one table per header of include/, each listing every function its header declares
+# (tests/test_abi.py holds every table to its header, to the library's exports and to what load_library() sets)
+ABI = {}
+
+# include/relgnn.h (the kernels behind the layer functions, the heads, the optimizers and the batch builder)
+ABI["relgnn.h"] = {
     "relgnn_abi_version": (ctypes.c_int, []),
     "relgnn_status_string": (ctypes.c_char_p, [ctypes.c_int]),
     "relgnn_relational_keys": (ctypes.c_int, [_ptr, _c_i64, _c_i32, _c_i32, _c_i32, _c_i64, _ptr, _ptr, _ptr, _ptr]),
@@ -183,29 +184,28 @@ _SIGNATURES = {
     "relgnn_batch_pack": (ctypes.c_int, [_c_i32, _c_i64, _ptr, _ptr, _ptr, _ptr, _ptr, _c_i32, _ptr, _ptr, _ptr, _ptr, ctypes.c_size_t, _c_i32]),
 }
 
-# include/relgnn_dropout.h (the opt-in layer-input dropout route): typed by load_library() like the table above, kept apart
-# from it because exported_signatures() is the list of include/relgnn.h
-_DROPOUT_SIGNATURES = {
+# include/relgnn_dropout.h (the opt-in layer-input dropout route)
+ABI["relgnn_dropout.h"] = {
     "relgnn_dropout_fwd": (ctypes.c_int, [_ptr, _c_i64, _c_i64, _ptr, _c_i32, _c_u32, _c_f32, _ptr, _ptr]),
     "relgnn_dropout_bwd": (ctypes.c_int, [_ptr, _c_i64, _c_i64, _ptr, _c_i32, _c_u32, _c_f32, _ptr, _ptr]),
     "relgnn_dropout_residual_fwd": (ctypes.c_int, [_ptr, _ptr, _c_i64, _c_i64, _ptr, _c_i32, _c_u32, _c_f32, _ptr, _ptr, _ptr]),
     "relgnn_dropout_residual_bwd": (ctypes.c_int, [_ptr, _ptr, _c_i64, _c_i64, _ptr, _c_i32, _c_u32, _c_f32, _ptr, _ptr, _ptr]),
 }
 
-# include/relgnn_predict.h (probabilities and labels out of the heads' logits): a table of its own for the same reason
-_PREDICT_SIGNATURES = {
+# include/relgnn_predict.h (probabilities and labels out of the heads' logits)
+ABI["relgnn_predict.h"] = {
     "relgnn_predict_sigmoid_f32": (ctypes.c_int, [_ptr, _c_i64, _c_i64, _c_i64, _ptr, _c_i64, _ptr, _c_i64, _ptr]),
     "relgnn_predict_softmax_f32": (ctypes.c_int, [_ptr, _c_i64, _c_i64, _c_i32, _ptr, _c_i64, _ptr, _ptr]),
     "relgnn_predict_candidates_f32": (ctypes.c_int, [_ptr, _c_i64, _c_i32, _ptr, _ptr, _ptr]),
 }
 
-# include/relgnn_parallel.h (data-parallel training: the scaled pack in front of the gradient all-reduce): its own table too
-_PARALLEL_SIGNATURES = {
+# include/relgnn_parallel.h (data-parallel training: the scaled pack in front of the gradient all-reduce)
+ABI["relgnn_parallel.h"] = {
     "relgnn_mt_pack_scaled_f32": (ctypes.c_int, [_ptr, _ptr, _c_i32, _c_f32, _ptr, _ptr]),
 }
 
-# include/relgnn_sparse_features.h (CSR rows times a row table: the citation task's sparse node features): its own table too
-_SPARSE_FEATURES_SIGNATURES = {
+# include/relgnn_sparse_features.h (CSR rows times a row table: the citation task's sparse node features)
+ABI["relgnn_sparse_features.h"] = {
     "relgnn_csr_project_supported": (ctypes.c_int, [_c_i32]),
     "relgnn_csr_project_split_above": (_c_i64, []),
     "relgnn_csr_project_slab": (_c_i64, []),
@@ -213,8 +213,8 @@ _SPARSE_FEATURES_SIGNATURES = {
                                               _c_i64, _ptr, _c_i64, _ptr, _c_i64, _ptr, _c_i64, _ptr]),
 }
 
-# include/relgnn_sampling.h (neighbour sampling from the by-target bucketing: the citation task's sampled batches): its own table too
-_SAMPLING_SIGNATURES = {
+# include/relgnn_sampling.h (neighbour sampling from the by-target bucketing: the citation task's sampled batches)
+ABI["relgnn_sampling.h"] = {
     "relgnn_neighbour_sample_supported": (ctypes.c_int, [_ptr, _c_i32, _c_i64, _c_i32]),
     "relgnn_neighbour_sample_max_fanout": (_c_i64, []),
     "relgnn_neighbour_sample_max_hops": (_c_i64, []),
@@ -230,16 +230,15 @@ _SAMPLING_SIGNATURES = {
     "relgnn_neighbour_sample_finish": (ctypes.c_int, [_ptr, _c_i64, _ptr, _c_i64, _ptr, _ptr]),
 }
 
-# include/relgnn_layered_sampling.h (the hop-ordered numbering of a sampled subgraph: the citation task's layered batches): its own
-# table too
-_LAYERED_SAMPLING_SIGNATURES = {
+# include/relgnn_layered_sampling.h (the hop-ordered numbering of a sampled subgraph: the citation task's layered batches)
+ABI["relgnn_layered_sampling.h"] = {
     "relgnn_neighbour_sample_relabel_by_hop": (ctypes.c_int, [_ptr, _c_i64, _c_i64, _ptr, _c_i64, _ptr, _ptr, _c_i32, _ptr, _ptr]),
     "relgnn_neighbour_sample_degrees_by_hop": (ctypes.c_int, [_ptr, _c_i64, _c_i64, _c_i32, _c_i64, _c_i64, _ptr, _ptr]),
 }
 
 # include/relgnn_sparse_subset.h (a row subset of sparse node features and its transpose, built on the device: sampled batches over
-# sparse features): its own table too
-_SPARSE_SUBSET_SIGNATURES = {
+# sparse features)
+ABI["relgnn_sparse_subset.h"] = {
     "relgnn_sparse_subset_supported": (ctypes.c_int, [_c_i64, _c_i64, _c_i64]),
     "relgnn_split_plan_workspace_bytes": (ctypes.c_size_t, [_c_i64]),
     "relgnn_split_plan_count": (ctypes.c_int, [_ptr, _c_i64, _ptr, _ptr, _ptr, ctypes.c_size_t, _ptr]),
@@ -252,8 +251,8 @@ _SPARSE_SUBSET_SIGNATURES = {
     "relgnn_sparse_subset_transpose": (ctypes.c_int, [_ptr, _c_i64, _ptr, _ptr, _c_i64, _c_i64, _ptr, _ptr, _ptr, ctypes.c_size_t, _ptr]),
 }
 
-# include/relgnn_sparse_update.h (row-deferred Adam for a row table whose gradient is +0 outside the rows a batch names): its own table too
-_SPARSE_UPDATE_SIGNATURES = {
+# include/relgnn_sparse_update.h (row-deferred Adam for a row table whose gradient is +0 outside the rows a batch names)
+ABI["relgnn_sparse_update.h"] = {
     "relgnn_rows_adam_supported": (ctypes.c_int, [_c_i32]),
     "relgnn_rows_adam_catch_up": (ctypes.c_int, [_ptr, _c_i64, _ptr, _ptr, _ptr, _c_i64, _c_i32, _ptr, _ptr, _c_i32, _c_i32, _c_f32, _c_f32,
                                                  _c_f32, _ptr]),
@@ -262,8 +261,8 @@ _SPARSE_UPDATE_SIGNATURES = {
 }
 
 # include/relgnn_sparse_gradient.h (the compact gradient of that row table: named rows, the dense norm's bits over them, the row step
-# on compact rows): its own table too
-_SPARSE_GRADIENT_SIGNATURES = {
+# on compact rows)
+ABI["relgnn_sparse_gradient.h"] = {
     "relgnn_named_rows_workspace_bytes": (ctypes.c_size_t, [_c_i64]),
     "relgnn_named_rows_count": (ctypes.c_int, [_ptr, _c_i64, _ptr, _ptr, _ptr, ctypes.c_size_t, _ptr]),
     "relgnn_named_rows_fill": (ctypes.c_int, [_ptr, _c_i64, _ptr, _c_i64, _ptr, _ptr, _ptr, _ptr, _c_i64, _ptr, _ptr, _c_i64, _ptr]),
@@ -273,8 +272,8 @@ _SPARSE_GRADIENT_SIGNATURES = {
                                                      _c_i32, _ptr, _c_f32, _c_f32, _c_f32, _c_f32, _c_f32, _ptr]),
 }
 
-# include/relgnn_subgraph.h (random-walk node sets and their induced subgraphs: the citation task's subgraph batches): its own table too
-_SUBGRAPH_SIGNATURES = {
+# include/relgnn_subgraph.h (random-walk node sets and their induced subgraphs: the citation task's subgraph batches)
+ABI["relgnn_subgraph.h"] = {
     "relgnn_subgraph_supported": (ctypes.c_int, [_c_i64, _c_i32, _c_i64, _c_i32]),
     "relgnn_subgraph_max_walk_length": (_c_i64, []),
     "relgnn_subgraph_workspace_bytes": (ctypes.c_size_t, [_c_i64]),
@@ -288,8 +287,8 @@ _SUBGRAPH_SIGNATURES = {
 }
 
 # include/relgnn_subgraph_norm.h (GraphSAINT normalisation of the subgraph batches: visit counts, per-edge weights, the weighted loss
-# head): its own table too
-_SUBGRAPH_NORM_SIGNATURES = {
+# head)
+ABI["relgnn_subgraph_norm.h"] = {
     "relgnn_subgraph_visit_count": (ctypes.c_int, [_ptr, _ptr, _c_i64, _c_i32, _c_i64, _ptr, _ptr, _c_i64, _ptr, _ptr, _ptr, _ptr]),
     "relgnn_subgraph_induced_emit_weighted": (ctypes.c_int, [_ptr, _ptr, _c_i64, _c_i32, _c_i64, _ptr, _c_i64, _c_i64, _ptr, _ptr, _ptr,
                                                              _ptr, _c_f32, _c_i64, _ptr, _ptr, _ptr, _ptr]),
@@ -317,11 +316,7 @@ def load_library():
             "%s not found: the HIP extension is not built. Run `python -c 'import __graft_entry__ as g; "
             "g.build()'` (needs hipcc). There is no CPU fallback for this path." % LIB_PATH)
     lib = ctypes.CDLL(str(LIB_PATH))
-    for name, (restype, argtypes) in list(_SIGNATURES.items()) + list(_DROPOUT_SIGNATURES.items()) + list(_PREDICT_SIGNATURES.items()) \
-            + list(_PARALLEL_SIGNATURES.items()) + list(_SPARSE_FEATURES_SIGNATURES.items()) + list(_SAMPLING_SIGNATURES.items()) \
-            + list(_SPARSE_SUBSET_SIGNATURES.items()) + list(_SPARSE_UPDATE_SIGNATURES.items()) \
-            + list(_SPARSE_GRADIENT_SIGNATURES.items()) + list(_LAYERED_SAMPLING_SIGNATURES.items()) \
-            + list(_SUBGRAPH_SIGNATURES.items()) + list(_SUBGRAPH_NORM_SIGNATURES.items()):
+    for name, (restype, argtypes) in signatures().items():
         fn = getattr(lib, name)  # AttributeError if the symbol is not exported
         fn.restype = restype
         fn.argtypes = argtypes
@@ -331,63 +326,19 @@ def load_library():
     return lib
 
 
-def exported_signatures():
-    return dict(_SIGNATURES)
-
-
-def dropout_signatures():
-    """The entry points of include/relgnn_dropout.h (not part of exported_signatures(): that is relgnn.h's list)."""
-    return dict(_DROPOUT_SIGNATURES)
-
-
-def predict_signatures():
-    """The entry points of include/relgnn_predict.h (not part of exported_signatures() either)."""
-    return dict(_PREDICT_SIGNATURES)
-
-
-def parallel_signatures():
-    """The entry points of include/relgnn_parallel.h (not part of exported_signatures() either)."""
-    return dict(_PARALLEL_SIGNATURES)
-
-
-def sparse_features_signatures():
-    """The entry points of include/relgnn_sparse_features.h (not part of exported_signatures() either)."""
-    return dict(_SPARSE_FEATURES_SIGNATURES)
-
-
-def sampling_signatures():
-    """The entry points of include/relgnn_sampling.h (not part of exported_signatures() either)."""
-    return dict(_SAMPLING_SIGNATURES)
-
-
-def sparse_subset_signatures():
-    """The entry points of include/relgnn_sparse_subset.h (not part of exported_signatures() either)."""
-    return dict(_SPARSE_SUBSET_SIGNATURES)
-
-
-def sparse_update_signatures():
-    """The entry points of include/relgnn_sparse_update.h (not part of exported_signatures() either)."""
-    return dict(_SPARSE_UPDATE_SIGNATURES)
-
-
-def sparse_gradient_signatures():
-    """The entry points of include/relgnn_sparse_gradient.h (not part of exported_signatures() either)."""
-    return dict(_SPARSE_GRADIENT_SIGNATURES)
-
-
-def layered_sampling_signatures():
-    """The entry points of include/relgnn_layered_sampling.h (not part of exported_signatures() either)."""
-    return dict(_LAYERED_SAMPLING_SIGNATURES)
-
-
-def subgraph_signatures():
-    """The entry points of include/relgnn_subgraph.h (not part of exported_signatures() either)."""
-    return dict(_SUBGRAPH_SIGNATURES)
-
-
-def subgraph_norm_signatures():
-    """The entry points of include/relgnn_subgraph_norm.h (not part of exported_signatures() either)."""
-    return dict(_SUBGRAPH_NORM_SIGNATURES)
+def signatures(header=None):
+    """A copy of one header's table (`header` is its file name, a key of ABI), or with None the union of all of them: every entry
+    point load_library() types.  Raises if two headers bind one name, where the later table would silently win."""
+    if header is not None:
+        return dict(ABI[header])
+    union, owner = {}, {}
+    for h, table in ABI.items():
+        for name in table:
+            if name in owner:
+                raise RelGnnLibraryError("%s is bound by both %s and %s" % (name, owner[name], h))
+            owner[name] = h
+        union.update(table)
+    return union
 
 
 def status_string(code: int) -> str:
