@@ -6,7 +6,12 @@
         [--result-dir D] [--backend nccl|gloo] [--share-gpu]
 
 init_distributed(), the task and the model through the registries, train(group=WORLD), then test(validation fold, group=WORLD).
---synthetic fills the folds of PPI / VarMisuse with generated graphs and those of QM9 with the 256 committed molecules.
+--synthetic fills the folds of PPI / VarMisuse / the citation networks with generated graphs and those of QM9 with the 256 committed
+molecules.  The citation task (cora, citeseer, pubmed) trains on ONE graph: it is accepted with sampled epochs and the key
+"data_parallel", which deals the batches of an epoch out to the ranks, e.g.
+    --task-param-overrides '{"sampled_batches": {"fanouts": [10, 10], "seeds_per_batch": 1024, "data_parallel": true}}'
+(or "subgraph_batches": {"roots_per_batch": R, "walk_length": h, "data_parallel": true}); without the key it is refused before
+anything is loaded, with the reason.
 --share-gpu puts every rank on cuda:0 over gloo: a rehearsal of the protocol on a box with one GPU, not a speed.
 An example and the thing a leased node runs, not a command-line interface of the package."""
 import argparse
@@ -55,6 +60,10 @@ task_params = task_cls.default_params()
 task_params.update(task_extra)
 task_params.update(json.loads(args.task_param_overrides))
 task = task_cls(task_params)
+if world > 1 and task.name() == "CitationNetwork" and not task.single_graph_data_parallel():
+    raise SystemExit('the citation task trains on ONE graph: under %d ranks it needs sampled epochs with the key "data_parallel", e.g. '
+                     '--task-param-overrides \'{"sampled_batches": {"fanouts": [10, 10], "seeds_per_batch": 1024, "data_parallel": true}}\''
+                     % world)
 if args.synthetic:
     if hasattr(task, "load_synthetic"):
         task.load_synthetic()

@@ -326,6 +326,58 @@ def dp_schedule(per_rank_steps: Sequence[Sequence[Tuple[float, int]]]) -> DpSche
     return DpSchedule(steps, weight_sums, g.sum(axis=0), scales)
 
 
+class SingleGraphSchedule(NamedTuple):
+    """One TRAIN epoch of a task whose data is ONE graph, handed out to the ranks batch by batch."""
+    steps: int                      # ceil(batches / world): every rank issues this many reductions
+    owner: np.ndarray               # int64 [batches]: global batch j belongs to rank j mod world ...
+    step: np.ndarray                # int64 [batches]: ... at step j // world
+    draws: np.ndarray               # int64 [batches]: the sampler's draw index of batch j, the single-GPU loop's: epoch * batches + j
+    scales: np.ndarray              # float32 [world, steps]: dp_schedule's; 0 where a rank holds no batch in the last step
+
+
+def single_graph_schedule(batch_weights: Sequence[float], world_size: int, epoch: int = 0) -> SingleGraphSchedule:
+    """batch_weights[j]: what batch j of the epoch weighs in the mean over its step (the citation task: its seed count under
+    `sampled_batches`, the same for every batch under `subgraph_batches`).  The ranks together run the batches of the single-GPU
+    epoch, world_size at a time; every epoch has the same number of batches, so the draws of epoch e start at e * batches."""
+    batches = len(batch_weights)
+    j = np.arange(batches, dtype=np.int64)
+    schedule = dp_schedule([[(float(batch_weights[i]), 1) for i in range(r, batches, world_size)] for r in range(world_size)])
+    return SingleGraphSchedule(schedule.steps, j % world_size, j // world_size, int(epoch) * batches + j, schedule.scales)
+
+
+def dp_order_by_batch(per_rank: Sequence[Sequence[Any]]) -> List[Any]:
+    """per_rank[r]: what rank r holds for its batches r, r + W, r + 2W, ... of an epoch, in that order.  -> the same items in the
+    order of the global batch index, which is the order a single process meets them in."""
+    world = len(per_rank)
+    total = sum(len(part) for part in per_rank)
+    for r, part in enumerate(per_rank):
+        if len(part) != len(range(r, total, world)):
+            raise ValueError("dp_order_by_batch: rank %d holds %d of %d batches dealt out in turn to %d ranks, not %d"
+                             % (r, len(part), total, world, len(range(r, total, world))))
+    return [per_rank[j % world][j // world] for j in range(total)]
+
+
+def dp_gather_by_batch(items: Sequence[Any], group=None) -> List[Any]:
+    """End of an epoch whose batches were dealt out in turn: every rank's per-batch items, in batch order, on every rank."""
+    gathered = [None] * dist.get_world_size(group)
+    dist.all_gather_object(gathered, list(items), group=group)
+    return dp_order_by_batch(gathered)
+
+
+def dp_check_fingerprints(fingerprints: Sequence[Dict[str, Any]]) -> None:
+    """fingerprints[r]: what rank r says of the graph, the folds and the sampling parameter it holds.  Every rank must hold the
+    same: a RuntimeError names every field in which a rank differs from rank 0, with both values."""
+    first = fingerprints[0]
+    differing = []
+    for r, other in enumerate(fingerprints[1:], start=1):
+        for key in sorted(set(first) | set(other), key=str):
+            if key not in first or key not in other or first[key] != other[key]:
+                differing.append("%s (rank 0: %r, rank %d: %r)" % (key, first.get(key), r, other.get(key)))
+    if differing:
+        raise RuntimeError("data-parallel training on ONE graph needs the same graph, the same folds and the same sampling parameter "
+                           "on every rank; the ranks differ in " + "; ".join(differing))
+
+
 def dp_merge_epoch(metric_results: List[Dict[str, Any]], sums: Sequence[float], group=None) -> Tuple[List[Dict[str, Any]], List[float]]:
     """End of an epoch: every rank's per-batch metric dicts concatenated in rank order and the ranks' sums (loss * graphs, graphs,
     nodes, edges) added in rank order: the same list and the same totals on every rank."""

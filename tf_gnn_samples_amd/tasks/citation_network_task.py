@@ -17,6 +17,7 @@ The batching modes live in tasks/single_graph_batches.py (`self.batches`), which
       "evaluation"}: TRAIN epochs of neighbour-sampled receptive fields; "evaluation": VALIDATION, TEST and predict(nodes=...) on them too.
   `subgraph_batches` {"roots_per_batch", "walk_length", "seed"; optional "sparse_features", "normalisation"}: TRAIN epochs of random-walk
       induced subgraphs; "normalisation": GraphSAINT's loss and aggregation weights.
+  Either takes the optional key "data_parallel": train(group=...) / test(group=...) deal the batches of an epoch out to the ranks.
 """
 import os
 import pickle
@@ -28,7 +29,7 @@ import torch
 
 from .. import _lib, config as _cfg
 from ..dense import dense, mark_zero_padded
-from ..parallel import refuse_single_graph_task
+from ..parallel import refuse_single_graph_task, single_graph_schedule
 from ..predict import predict_softmax
 from .neighbour_sampling import PREDICT_SEEDS_PER_BATCH, check_prediction_nodes, check_sparse_node_features, parse_sampled_batches
 from .subgraph_sampling import parse_subgraph_batches
@@ -270,6 +271,10 @@ class Citation_Network_Task(Sparse_Graph_Task):
         """Does `sampled_batches` ask for hop-ordered batches whose layers run on the hops they need?"""
         sampled = self.sampled_batches
         return bool(sampled is not None and sampled.get("layered", False))
+
+    def single_graph_data_parallel(self) -> bool:
+        """Does `sampled_batches` or `subgraph_batches` carry "data_parallel": true?"""
+        return bool((self.sampled_batches or self.subgraph_batches or {}).get("data_parallel", False))
 
     @property
     def evaluation(self) -> Optional[Dict[str, Any]]:
@@ -552,6 +557,10 @@ class Citation_Network_Task(Sparse_Graph_Task):
         if sampled is not None:
             yield from sampled
             return
+        yield self._full_graph_batch(batcher, data_fold)
+
+    def _full_graph_batch(self, batcher, data_fold: DataFold):
+        """The fold's one full-graph batch from its input pipeline."""
         keep = self._out_keep(data_fold)
         batcher.constants['out_layer_dropout_keep_prob'] = keep
         rows = getattr(batcher.store, "sparse_rows", None)
@@ -565,7 +574,31 @@ class Citation_Network_Task(Sparse_Graph_Task):
             batch.extra['out_layer_dropout_keep_prob'] = keep
         else:
             batch = batcher.pack(ids)
-        yield batch
+        return batch
+
+    # -------------------- Data parallelism over the sampled batches of the ONE graph (the key "data_parallel"; models/data_parallel.py) ----
+    def rank_epoch_batches(self, data, data_fold: DataFold, device, full_graph_route: bool, rank: int, world: int, pipeline):
+        """-> (the batches rank `rank` of `world` runs in one epoch, are they its share of the fold's).  TRAIN: global batch j when
+        j mod world == rank.  VALIDATION / TEST under "evaluation": batch i when i mod world == rank.  Without "evaluation" every
+        rank runs the full graph itself from `pipeline()` (the model's input pipeline of the fold, built when asked for)."""
+        if data_fold == DataFold.TRAIN:
+            self.bind_sampling_device(device)
+            return self.batches.rank_train_batches(next(iter(data)), rank, world), True
+        if self.evaluation is not None:
+            self.bind_sampling_device(device)
+            return self.batches.rank_evaluation_batches(data, data_fold, full_graph_route, rank, world), True
+        batcher = pipeline()
+        if batcher.store.num_graphs != 1:
+            raise ValueError("a citation-network fold is ONE graph; got %d" % batcher.store.num_graphs)
+        return iter((self._full_graph_batch(batcher, data_fold),)), False
+
+    def train_schedule(self, data, world: int):
+        """Who runs which batch of the NEXT TRAIN epoch, with what share of its step (parallel.single_graph_schedule)."""
+        return single_graph_schedule(self.batches.train_batch_weights(next(iter(data))), world, self.batches.epoch)
+
+    def data_parallel_fingerprint(self) -> Dict[str, Any]:
+        """Of the loaded TRAIN and VALIDATION folds (single_graph_batches.SingleGraphBatches.fingerprint)."""
+        return self.batches.fingerprint({"train": self._loaded_data[DataFold.TRAIN][0], "validation": self._loaded_data[DataFold.VALIDATION][0]})
 
     def loss_weight(self, num_graphs: int, num_nodes: int) -> float:
         raise RuntimeError("the %s task trains on ONE graph that is the whole batch: it cannot be split by graph across ranks; "

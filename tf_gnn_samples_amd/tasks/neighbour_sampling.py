@@ -340,23 +340,30 @@ def parse_sampled_batches(value) -> Optional[Dict]:
     the optional keys "sparse_features" (a bool: the batches take their feature rows from a SparseRows), "sparse_update" (a bool:
     the optimizer updates only the rows of the input projection's weight that a batch names) and "sparse_gradient" (a bool: that
     weight's gradient exists only as the rows a batch names) and "layered" (a bool: the batches are numbered by hop and every layer
-    runs on the hops it needs) are carried only when given, and so is "evaluation" ({"fanouts": [k_1, ..., k_H], "seeds_per_batch": B,
-    "keep": bool}, "keep" optional: VALIDATION, TEST and predict(nodes=...) run on sampled receptive fields, parse_evaluation)."""
+    runs on the hops it needs) and "data_parallel" (a bool: train(group=...) hands the batches of an epoch out to the ranks; not
+    together with "sparse_update" / "sparse_gradient") are carried only when given, and so is "evaluation" ({"fanouts": [k_1, ..., k_H],
+    "seeds_per_batch": B, "keep": bool}, "keep" optional: VALIDATION, TEST and predict(nodes=...) run on sampled receptive fields,
+    parse_evaluation)."""
     if value is None:
         return None
     if not isinstance(value, dict) or not {"fanouts", "seeds_per_batch"} <= set(value) \
             or set(value) - {"fanouts", "seeds_per_batch", "seed", "sparse_features", "sparse_update", "sparse_gradient", "layered",
-                             "evaluation"}:
+                             "data_parallel", "evaluation"}:
         raise ValueError('sampled_batches must be {"fanouts": [k_1, ..., k_H], "seeds_per_batch": B, "seed": s, "sparse_features": bool, '
-                         '"sparse_update": bool, "sparse_gradient": bool, "layered": bool, "evaluation": {"fanouts": [...], '
-                         '"seeds_per_batch": B, "keep": bool}}, the last six optional, got %r' % (value,))
+                         '"sparse_update": bool, "sparse_gradient": bool, "layered": bool, "data_parallel": bool, "evaluation": '
+                         '{"fanouts": [...], "seeds_per_batch": B, "keep": bool}}, the last seven optional, got %r' % (value,))
     per_batch = value["seeds_per_batch"]
     if isinstance(per_batch, bool) or not isinstance(per_batch, (int, np.integer)) or per_batch < 1:
         raise ValueError("sampled_batches: seeds_per_batch must be a positive integer, got %r" % (per_batch,))
     parsed = {"fanouts": check_fanouts(value["fanouts"]), "seeds_per_batch": int(per_batch), "seed": int(value.get("seed", 0))}
-    parse_bool_keys("sampled_batches", value, parsed, ("sparse_features", "sparse_update", "sparse_gradient", "layered"), {
+    parse_bool_keys("sampled_batches", value, parsed, ("sparse_features", "sparse_update", "sparse_gradient", "layered", "data_parallel"), {
         "sparse_update": ("sparse_features", "the rows a batch names are read from the transposed structure of its SparseRows"),
         "sparse_gradient": ("sparse_update", "the compact gradient is what the row-deferred update consumes; dense Adam reads a dense one")})
+    by_rows = [key for key in ("sparse_update", "sparse_gradient") if parsed.get(key, False)]
+    if parsed.get("data_parallel", False) and by_rows:
+        raise ValueError('sampled_batches: "data_parallel": true cannot be combined with %s: the row stamps of the deferred update and '
+                         'the compact gradient sink do not pass through the packed gradient all-reduce'
+                         % " and ".join('"%s": true' % key for key in by_rows))
     if "evaluation" in value:
         parsed["evaluation"] = parse_evaluation(value["evaluation"])
     return parsed

@@ -9,7 +9,7 @@ one batch.  An epoch is a permutation of the fold's nodes cut into ceil(n_train 
 csrc/neighbour_sample.hip) whose loss counts the seeds only.  The sampler, the full graph's RelGraph and the device copies of the
 feature table, the labels and the fold's mask are built once per (fold, device).  The epochs and the sampled batches (the sampler's
 `draw`) are counted here.  VALIDATION, TEST, test() and predict() stay on the full graph unless the key "evaluation" (below)
-says otherwise.  GPU only; not together with capture_train_step or a process group.
+says otherwise.  GPU only; not together with capture_train_step, nor with a process group unless the key "data_parallel" says so.
 
 The two together: `sampled_batches` takes one more optional key, "sparse_features": true, which requires sparse_node_features
 (and sparse_node_features with a sampled_batches that lacks the key stays a ValueError).  The sampling state then keeps the device's
@@ -65,7 +65,8 @@ at any depth.  The loss mask is fold_mask[nodes]: every TRAIN node of the subgra
 requires sparse_node_features (and the reverse), as for sampled_batches; the batch then carries SparseRows.take_rows(nodes).  The
 device RelGraph and the feature table are the ones the folds share (graph_state).  VALIDATION, TEST, test() and predict() stay on
 the full graph; predict(nodes=...) runs exact receptive fields as it does without the parameter.  Without the next key the loss and
-the aggregation are the induced subgraph's.  GPU only; not together with capture_train_step or a process group.
+the aggregation are the induced subgraph's.  GPU only; not together with capture_train_step, nor with a process group unless the key
+"data_parallel" (below) says so.
 
 One more optional key, "normalisation": {"presample_epochs": E, "aggregation": bool, "max_edge_weight": c} (the last two optional: true
 and 1e4; it composes with "sparse_features"): GraphSAINT's normalisation (include/relgnn_subgraph_norm.h).  Before the first TRAIN
@@ -79,8 +80,16 @@ min(max(C_v, 1) / max(C_e, 1), c) / (full-graph in-degree + 1e-7) instead of 1 /
 preset as the batch graph's degree scale): a layer's sum is then an estimate of the aggregate evaluation computes on the full graph.
 It needs a model whose layers take the degree table, normalise by it and sum (RGCN, RGDCN, GNN-FiLM with
 normalize_messages_by_num_incoming; a ValueError from the model otherwise); "aggregation": false works with every model.
+
+Both parameters take one more optional key, "data_parallel": true (a ValueError together with "sparse_update" / "sparse_gradient"; it
+composes with every other key): train(group=...) and test(group=...) of a process group of W > 1 ranks are no longer refused
+(models/data_parallel.py).  Every rank holds the whole graph; global batch j of a TRAIN epoch goes to rank
+j mod W at step j // W with the draw index the single-GPU loop gives it (rank_train_batches), and a step's gradient is the weighted mean
+of its batches' (train_batch_weights).  Under "evaluation" batch i of a fold goes to rank i mod W (rank_evaluation_batches); without it
+every rank evaluates the full graph itself.  The task's two batch iterators and predict() stay refused under a process group.
 """
 import weakref
+import zlib
 from typing import Any, NamedTuple
 
 import numpy as np
@@ -213,28 +222,57 @@ class SingleGraphBatches:
     # -------------------- TRAIN --------------------
     def train_batches(self, fold):
         """One TRAIN epoch of sampled batches, None when the TRAIN fold is one full-graph batch."""
+        return self.rank_train_batches(fold, 0, 1)
+
+    def rank_train_batches(self, fold, rank: int, world: int):
+        """The batches of the TRAIN epoch that rank `rank` of `world` runs under the key "data_parallel": batch j of train_batches'
+        list when j mod world == rank, each drawn with the draw index it has in that list.  The epoch and draw counters advance as
+        train_batches advances them for the whole list, once the generator has run to its end."""
         if self.task.sampled_batches is not None:
-            return self.neighbour_batches(fold)
+            return self.neighbour_batches(fold, rank, world)
         if self.task.subgraph_batches is not None:
-            return self.subgraph_batches(fold)
+            return self.subgraph_batches(fold, rank, world)
         return None
 
-    def neighbour_batches(self, fold):
-        """ceil(n_train / B) sampled batches: one TRAIN epoch."""
+    def train_batch_weights(self, fold):
+        """What every batch of the NEXT TRAIN epoch weighs in the mean over a data-parallel step (parallel.single_graph_schedule): its
+        seed count under `sampled_batches`, whose batch loss is the mean over the seeds; 1 under `subgraph_batches`, with or
+        without "normalisation": a batch's loss is its own estimate of the fold's, and its count of TRAIN nodes is not on the host."""
+        sampled, subgraph = self.task.sampled_batches, self.task.subgraph_batches
+        if sampled is not None:
+            return [float(len(seeds)) for seeds in epoch_seed_batches(fold.mask, sampled["seeds_per_batch"], sampled["seed"], self.epoch)]
+        return [1.0] * len(epoch_seed_batches(fold.mask, subgraph["roots_per_batch"], subgraph["seed"], self.epoch))
+
+    def fingerprint(self, folds):
+        """What every rank of a data-parallel run must hold alike (parallel.dp_check_fingerprints): the graph's size, the masked count
+        of every fold in `folds` (name -> fold, "train" among them), a CRC of the TRAIN mask and the parsed sampling parameters."""
+        train = folds["train"]
+        said = {"nodes": len(train.labels), "edges_per_type": [len(a) for a in train.adjacency_lists],
+                "train_mask_crc": zlib.crc32(np.ascontiguousarray(train.mask).tobytes()),
+                "sampled_batches": self.task.sampled_batches, "subgraph_batches": self.task.subgraph_batches}
+        for name, fold in folds.items():
+            said["%s_nodes" % name] = int(np.count_nonzero(fold.mask))
+        return said
+
+    def neighbour_batches(self, fold, rank: int = 0, world: int = 1):
+        """ceil(n_train / B) sampled batches: one TRAIN epoch; of these, the ones dealt to `rank` of `world`."""
         sampled = self.task.sampled_batches
         state = self.neighbour_state(fold, self.bound_device())
         epoch, self.epoch = self.epoch, self.epoch + 1
         keep = self.task._out_keep(DataFold.TRAIN)
-        for seeds in epoch_seed_batches(fold.mask, sampled["seeds_per_batch"], sampled["seed"], epoch):
+        for j, seeds in enumerate(epoch_seed_batches(fold.mask, sampled["seeds_per_batch"], sampled["seed"], epoch)):
             draw, self.draw = self.draw, self.draw + 1
+            if j % world != rank:
+                continue
             sample = state.sampler.sample_by_hop if sampled.get("layered", False) else state.sampler.sample
             yield sample(seeds, draw).device_batch(state.features, state.labels, state.mask, keep,
                                                    named_rows=sampled.get("sparse_gradient", False))
 
-    def subgraph_batches(self, fold):
-        """ceil(n_train / R) subgraph batches: one TRAIN epoch.  Every train node is a root once; the loss mask is the fold's mask over
-        ALL nodes of the subgraph (seed_mask is ones).  With the key "normalisation" every batch carries extra['loss_normalisation'] =
-        (N / max(node_visits, 1) per node, n_train), and with its "aggregation" the per-edge weights as its graph's degree scale."""
+    def subgraph_batches(self, fold, rank: int = 0, world: int = 1):
+        """ceil(n_train / R) subgraph batches: one TRAIN epoch; of these, the ones dealt to `rank` of `world`.  Every train node is a
+        root once; the loss mask is the fold's mask over ALL nodes of the subgraph (seed_mask is ones).  With the key "normalisation"
+        every batch carries extra['loss_normalisation'] = (N / max(node_visits, 1) per node, n_train), and with its "aggregation" the
+        per-edge weights as its graph's degree scale."""
         subgraph = self.task.subgraph_batches
         state = self.subgraph_state(fold, self.bound_device())
         epoch, self.epoch = self.epoch, self.epoch + 1
@@ -242,8 +280,10 @@ class SingleGraphBatches:
         normalisation, counts = subgraph.get("normalisation"), state.visit_counts
         weighting = (counts, normalisation["max_edge_weight"]) if normalisation is not None and normalisation["aggregation"] else None
         num_train = float(np.count_nonzero(fold.mask))
-        for roots in epoch_seed_batches(fold.mask, subgraph["roots_per_batch"], subgraph["seed"], epoch):
+        for j, roots in enumerate(epoch_seed_batches(fold.mask, subgraph["roots_per_batch"], subgraph["seed"], epoch)):
             draw, self.draw = self.draw, self.draw + 1
+            if j % world != rank:
+                continue
             if normalisation is None:
                 yield state.sampler.sample(roots, draw).device_batch(state.features, state.labels, state.mask, keep)
                 continue
@@ -268,9 +308,15 @@ class SingleGraphBatches:
         neighbour_sampling.evaluation_replica(fold): the same subgraphs in every epoch.  "keep": built once per (fold, device, route, fanouts, B),
         handed out again, released with the fold."""
         refuse_single_graph_task(self.task.name())
+        yield from self.rank_evaluation_batches(data, data_fold, full_graph_route, 0, 1)
+
+    def rank_evaluation_batches(self, data, data_fold: DataFold, full_graph_route: bool, rank: int, world: int):
+        """The batches of evaluation_batches' list that rank `rank` of `world` runs under the key "data_parallel": batch i when
+        i mod world == rank, drawn as it is there.  "keep" keeps the rank's own batches."""
         evaluation, device = self.task.evaluation, self.bound_device()
         fold = next(iter(data))
-        key = (str(device), data_fold.value, bool(full_graph_route), tuple(evaluation["fanouts"]), evaluation["seeds_per_batch"])
+        key = (str(device), data_fold.value, bool(full_graph_route), tuple(evaluation["fanouts"]), evaluation["seeds_per_batch"],
+               int(rank), int(world))
         if evaluation.get("keep", False):
             held = self.kept_evaluation.get((fold.labels,), key)
             if held is not None:
@@ -280,6 +326,8 @@ class SingleGraphBatches:
                                      evaluation_replica(data_fold.value))
         kept = []
         for draw, seeds in enumerate(evaluation_seed_batches(fold.mask, evaluation["seeds_per_batch"])):
+            if draw % world != rank:
+                continue
             batch = self.evaluation_batch(state, seeds, draw, full_graph_route)
             if evaluation.get("keep", False):
                 kept.append(batch)

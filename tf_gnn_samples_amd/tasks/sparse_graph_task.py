@@ -232,5 +232,11 @@ class Sparse_Graph_Task:
         raise NotImplementedError("the %s task does not say what its loss is normalised by (loss_weight): it cannot be trained "
                                   "data-parallel" % type(self).__name__)
 
+    def single_graph_data_parallel(self) -> bool:
+        """Does the task train its ONE graph data-parallel, by handing the sampled batches of an epoch out to the ranks (the citation
+        task's key "data_parallel")?  models/data_parallel.py asks this before loss_weight and then drives the epochs through the
+        task's rank_epoch_batches, train_schedule and data_parallel_fingerprint."""
+        return False
+
     def restore_from_metadata(self, metadata: Dict[str, Any]) -> None:
         pass

@@ -233,16 +233,17 @@ def parse_normalisation(value) -> Dict:
 
 def parse_subgraph_batches(value) -> Optional[Dict]:
     """The task parameter `subgraph_batches` as {"roots_per_batch": int, "walk_length": int, "seed": int}, None when it is absent;
-    the optional keys "sparse_features" (a bool: the batches take their feature rows from a SparseRows) and "normalisation"
-    (parse_normalisation: GraphSAINT's loss and aggregation weights) are carried only when given."""
+    the optional keys "sparse_features" (a bool: the batches take their feature rows from a SparseRows), "data_parallel" (a bool:
+    train(group=...) hands the batches of an epoch out to the ranks) and "normalisation" (parse_normalisation: GraphSAINT's loss and
+    aggregation weights) are carried only when given."""
     if value is None:
         return None
-    known = {"roots_per_batch", "walk_length", "seed", "sparse_features", "normalisation"}
+    known = {"roots_per_batch", "walk_length", "seed", "sparse_features", "data_parallel", "normalisation"}
     unknown = sorted(set(value) - known, key=str) if isinstance(value, dict) else []
     if not isinstance(value, dict) or unknown or not {"roots_per_batch", "walk_length"} <= set(value):
         said = "; unknown key %s" % ", ".join(repr(k) for k in unknown) if unknown else ""
-        raise ValueError('subgraph_batches must be {"roots_per_batch": R, "walk_length": h, "seed": s, "sparse_features": bool}, the last '
-                         'two optional%s, got %r' % (said, value))
+        raise ValueError('subgraph_batches must be {"roots_per_batch": R, "walk_length": h, "seed": s, "sparse_features": bool, '
+                         '"data_parallel": bool, "normalisation": {...}}, the last four optional%s, got %r' % (said, value))
     per_batch = value["roots_per_batch"]
     if isinstance(per_batch, bool) or not isinstance(per_batch, (int, np.integer)) or per_batch < 1:
         raise ValueError("subgraph_batches: roots_per_batch must be a positive integer, got %r" % (per_batch,))
@@ -254,7 +255,7 @@ def parse_subgraph_batches(value) -> Optional[Dict]:
     if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)):
         raise ValueError("subgraph_batches: seed must be an integer, got %r" % (seed,))
     parsed = {"roots_per_batch": int(per_batch), "walk_length": walk_length, "seed": int(seed)}
-    parse_bool_keys("subgraph_batches", value, parsed, ("sparse_features",))
+    parse_bool_keys("subgraph_batches", value, parsed, ("sparse_features", "data_parallel"))
     if "normalisation" in value:
         parsed["normalisation"] = parse_normalisation(value["normalisation"])
     return parsed
