@@ -32,6 +32,8 @@ static inline int launch_status() {
 
 static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
+static inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }      // (a workspace's segments start on 256 bytes)
+
 // Grid size helper for flat elementwise kernels: cap at 256 CUs x 8 blocks and grid-stride.
 static inline unsigned flat_grid(int64_t n, int block) {
   int64_t g = (n + block - 1) / block;

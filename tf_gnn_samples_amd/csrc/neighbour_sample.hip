@@ -14,13 +14,12 @@
 // The hop's offsets come from min(deg, k) alone (rocPRIM's device scan, the library plan.hip sorts with), so nothing counts sampled
 // edges, and new nodes are found by a flag scan over the stamps.  No atomics anywhere: a stamp is written with a plain store of the
 // one value every writer of the hop writes.
-#include "common.h"
+// What the stamps mean, the clamped device count and the scan of a hop's counts into offsets and totals are node_set.h's, shared with
+// subgraph_sample.hip; the compaction of the stamped set (relgnn_neighbour_sample_compact) is defined here and serves both samplers.
+#include "node_set.h"
 #include "philox.h"
 #include "../../include/relgnn_sampling.h"
 #include "../../include/relgnn_layered_sampling.h"
-
-#include <rocprim/device/device_scan.hpp>
-#include <rocprim/iterator/transform_iterator.hpp>
 
 using namespace relgnn;
 
@@ -29,13 +28,6 @@ namespace {
 constexpr int kMaxFanout = 64;
 constexpr int kMaxHops = 8;
 constexpr int32_t kSeedStamp = -1;
-
-inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
-
-__device__ __forceinline__ int64_t frontier_length(const int32_t* __restrict__ count, int64_t bound) {
-  const int64_t n = *count;
-  return n < 0 ? 0 : (n > bound ? bound : n);
-}
 
 __global__ __launch_bounds__(256) void begin_kernel(const int32_t* __restrict__ seeds, int64_t num_seeds, int32_t* __restrict__ stamp,
                                                     int64_t V) {
@@ -49,7 +41,7 @@ __global__ __launch_bounds__(256) void begin_kernel(const int32_t* __restrict__ 
 __global__ __launch_bounds__(256) void count_kernel(const int32_t* __restrict__ rowptr, int32_t L, const int32_t* __restrict__ frontier,
                                                     const int32_t* __restrict__ frontier_count, int64_t B, int32_t k,
                                                     int32_t* __restrict__ counts) {
-  const int64_t nf = frontier_length(frontier_count, B), total = B * L;
+  const int64_t nf = set_size(frontier_count, B), total = B * L;
   for (int64_t w = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; w <= total; w += (int64_t)gridDim.x * blockDim.x) {
     int32_t c = 0;
     if (w < total) {
@@ -62,11 +54,6 @@ __global__ __launch_bounds__(256) void count_kernel(const int32_t* __restrict__ 
     }
     counts[w] = c;
   }
-}
-
-__global__ __launch_bounds__(64) void totals_kernel(const int32_t* __restrict__ offsets, int64_t B, int32_t L, int32_t* __restrict__ totals) {
-  for (int32_t l = threadIdx.x; l <= L; l += blockDim.x)
-    totals[l] = l < L ? offsets[(int64_t)(l + 1) * B] - offsets[(int64_t)l * B] : offsets[(int64_t)L * B];
 }
 
 __device__ __forceinline__ uint64_t key_of(int32_t j, uint32_t row, uint32_t hop, uint32_t draw, uint32_t k0, uint32_t k1) {
@@ -106,7 +93,7 @@ __global__ __launch_bounds__(256) void take_kernel(const int32_t* __restrict__ r
                                                    uint32_t draw, uint32_t k0, uint32_t k1, const int32_t* __restrict__ offsets,
                                                    int64_t edge_bound, int32_t* __restrict__ stamp, int2* __restrict__ edges) {
   const int lane = threadIdx.x & (RELGNN_WAVE - 1);
-  const int64_t nf = frontier_length(frontier_count, B), total = B * L;
+  const int64_t nf = set_size(frontier_count, B), total = B * L;
   const int64_t waves = (int64_t)gridDim.x * (blockDim.x / RELGNN_WAVE);
   const int32_t mark = (int32_t)hop + 1;
   for (int64_t w = blockIdx.x * (int64_t)(blockDim.x / RELGNN_WAVE) + (threadIdx.x / RELGNN_WAVE); w < total; w += waves) {
@@ -144,11 +131,6 @@ __global__ __launch_bounds__(256) void take_kernel(const int32_t* __restrict__ r
     if (lane < k) emit(off + rank, edge_bound, col[b + mine], L, t, V, mark, stamp, edges);
   }
 }
-
-struct StampFlag {
-  int32_t value;
-  __device__ __forceinline__ int32_t operator()(int32_t s) const { return (value != 0 ? s == value : s != 0) ? 1 : 0; }
-};
 
 __global__ __launch_bounds__(256) void scatter_kernel(const int32_t* __restrict__ stamp, const int32_t* __restrict__ pos, int64_t V,
                                                       StampFlag flag, int32_t* __restrict__ out, int64_t capacity,
@@ -242,17 +224,6 @@ __global__ __launch_bounds__(256) void finish_kernel(const int32_t* __restrict__
   }
 }
 
-size_t scan_temp_bytes(int64_t items) {
-  size_t plain = 0, flagged = 0;
-  int32_t* p = nullptr;
-  rocprim::exclusive_scan(nullptr, plain, p, p, (int32_t)0, (size_t)items, rocprim::plus<int32_t>(), (hipStream_t)0);
-  auto flags = rocprim::make_transform_iterator(static_cast<const int32_t*>(nullptr), StampFlag{0});
-  rocprim::exclusive_scan(nullptr, flagged, flags, p, (int32_t)0, (size_t)items, rocprim::plus<int32_t>(), (hipStream_t)0);
-  return plain > flagged ? plain : flagged;
-}
-
-inline bool graph_ok(int64_t V, int32_t L) { return V > 0 && L > 0 && V * (int64_t)L < ((int64_t)1 << 31); }
-
 }  // namespace
 
 extern "C" {
@@ -269,8 +240,8 @@ int64_t relgnn_neighbour_sample_max_hops(void) { return kMaxHops; }
 
 size_t relgnn_neighbour_sample_workspace_bytes(int64_t max_items) {
   if (max_items < 1) max_items = 1;
-  // [positions of a compaction: max_items int32 | rocPRIM's scan storage]
-  return align_up((size_t)max_items * 4, 256) + align_up(scan_temp_bytes(max_items + 1), 256) + 256;
+  // [positions of a compaction: max_items int32 | rocPRIM's scan storage, for a hop's counts or a compaction's flags]
+  return align_up((size_t)max_items * 4, 256) + align_up(scan_temp_bytes<true>(max_items + 1), 256) + 256;
 }
 
 int relgnn_neighbour_sample_begin(const int32_t* seeds, int64_t num_seeds, int32_t* stamp, int64_t num_nodes, void* stream) {
@@ -291,13 +262,9 @@ int relgnn_neighbour_sample_count(const int32_t* rowptr_t, int64_t num_nodes, in
   if (workspace_bytes < relgnn_neighbour_sample_workspace_bytes(items)) return RELGNN_ENOSPC;
   hipStream_t st = as_stream(stream);
   count_kernel<<<flat_grid(items, 256), 256, 0, st>>>(rowptr_t, num_edge_types, frontier, frontier_count, frontier_bound, fanout, counts);
-  const size_t front = align_up((size_t)items * 4, 256);
-  size_t temp_bytes = workspace_bytes - front;
-  if (rocprim::exclusive_scan(static_cast<char*>(workspace) + front, temp_bytes, counts, offsets, (int32_t)0, (size_t)items,
-                              rocprim::plus<int32_t>(), st) != hipSuccess)
-    return RELGNN_EHIP;
-  totals_kernel<<<1, 64, 0, st>>>(offsets, frontier_bound, num_edge_types, totals);
-  return launch_status();
+  const size_t front = align_up((size_t)items * 4, 256);          // (the scan storage lies where a compaction's does)
+  return scan_bucket_counts(counts, offsets, frontier_bound, num_edge_types, totals, static_cast<char*>(workspace) + front,
+                            workspace_bytes - front, st);
 }
 
 int relgnn_neighbour_sample_take(const int32_t* rowptr_t, const int32_t* col_t, int64_t num_nodes, int32_t num_edge_types,

@@ -192,8 +192,6 @@ inline int key_bits(int64_t num_segments) {
   return bits;
 }
 
-inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
-
 }  // namespace
 
 extern "C" {

@@ -27,8 +27,6 @@ namespace {
 
 constexpr int64_t kIndexLimit = INT32_MAX;
 
-inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
-
 // item f of the scan: 1 when word f has entries; the closing item (f == F) is 0
 struct NamedFlag {
   const int32_t* rowptr;

@@ -29,8 +29,6 @@ namespace {
 
 constexpr int64_t kIndexLimit = INT32_MAX;      // nnz, rows and columns stay below 2^31 - 1 (the container's own limit)
 
-inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
-
 inline int key_bits(int64_t num_keys) {
   int bits = 1;
   while (bits < 32 && ((int64_t)1 << bits) < num_keys) ++bits;

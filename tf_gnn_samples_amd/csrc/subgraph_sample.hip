@@ -3,25 +3,23 @@
 // subgraph over the stamped node set.
 //
 // One LANE owns one walk: a step is two rowptr loads, one Philox call and one col load; the walk's nodes are stamped with plain
-// stores of the one value every writer writes.  The node list is neighbour_sample.hip's flag scan (relgnn_neighbour_sample_compact).
+// stores of the one value every writer writes.  The stamp array and what its values mean are node_set.h's; the node list is the node
+// set's compaction (relgnn_neighbour_sample_compact, a flag scan over the stamps, defined in neighbour_sample.hip).
 // One WAVE owns one (subgraph node, edge type) bucket of the full graph, of any length: the lanes stride over it 64 entries at a
 // pass (the loads of eight passes are issued together); an entry is kept when its source is stamped.  The count is the popcount of
-// the pass's ballot; the offsets come from rocPRIM's device scan over the counts, the per-type totals from the offsets.  The emit
-// walks the bucket the same way: a kept
-// entry's slot is the bucket's offset + the kept entries of the earlier passes + the popcount of the kept-mask below the lane, so
-// the kept entries come out in the bucket's own order.  A source's local id is its stamp - 1 (relgnn_subgraph_number wrote the
-// positions into the stamps), the target's is the bucket's position in the node list.  Every loop is bounded by a bucket length
-// or a launch argument.  No atomics anywhere.
+// the pass's ballot; offsets and per-type totals are node_set.h's scan_bucket_counts, as for a hop of neighbour sampling.  The emit
+// walks the bucket the same way: a kept entry's slot is the bucket's offset + the kept entries of the earlier passes + the popcount
+// of the kept-mask below the lane, so the kept entries come out in the bucket's own order.  A source's local id is its stamp - 1
+// (relgnn_subgraph_number wrote the positions into the stamps), the target's is the bucket's position in the node list.  Every loop
+// is bounded by a bucket length or a launch argument.  No atomics anywhere.
 //
 // GraphSAINT normalisation (include/relgnn_subgraph_norm.h): the visit count walks the buckets as the count does and adds 1 to the
 // position of every kept entry and to the node of every type-0 wave, plain load-add-store: a position belongs to one lane of one
 // wave of a launch, and the launches of a stream are ordered.  The weighted emit is the emit with one more store per kept entry.
-#include "common.h"
+#include "node_set.h"
 #include "philox.h"
 #include "../../include/relgnn_subgraph.h"
 #include "../../include/relgnn_subgraph_norm.h"
-
-#include <rocprim/device/device_scan.hpp>
 
 using namespace relgnn;
 
@@ -30,15 +28,6 @@ namespace {
 constexpr int kMaxWalkLength = 64;
 constexpr int32_t kWalkStamp = 1;
 constexpr int kPasses = 8;                  // 64-entry passes of a bucket whose loads are in flight together
-
-inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
-
-inline bool graph_ok(int64_t V, int32_t L) { return V > 0 && L > 0 && V * (int64_t)L < ((int64_t)1 << 31); }
-
-__device__ __forceinline__ int64_t set_size(const int32_t* __restrict__ count, int64_t bound) {
-  const int64_t n = *count;
-  return n < 0 ? 0 : (n > bound ? bound : n);
-}
 
 __global__ __launch_bounds__(256) void walk_kernel(const int32_t* __restrict__ rowptr, const int32_t* __restrict__ col, int64_t V,
                                                    int32_t L, const int32_t* __restrict__ roots, int64_t R, int32_t h, uint32_t draw,
@@ -148,12 +137,6 @@ __global__ __launch_bounds__(256) void visit_count_kernel(const int32_t* __restr
   }
 }
 
-__global__ __launch_bounds__(64) void induced_totals_kernel(const int32_t* __restrict__ offsets, int64_t B, int32_t L,
-                                                           int32_t* __restrict__ totals) {
-  for (int32_t l = threadIdx.x; l <= L; l += blockDim.x)
-    totals[l] = l < L ? offsets[(int64_t)(l + 1) * B] - offsets[(int64_t)l * B] : offsets[(int64_t)L * B];
-}
-
 // what a weighted emit reads and writes on top (include/relgnn_subgraph_norm.h); kWeighted == false: not touched
 struct EmitWeights {
   const int32_t* node_visits;
@@ -219,13 +202,6 @@ __global__ __launch_bounds__(256) void clear_kernel(const int32_t* __restrict__ 
   }
 }
 
-size_t scan_temp_bytes(int64_t items) {
-  size_t bytes = 0;
-  int32_t* p = nullptr;
-  rocprim::exclusive_scan(nullptr, bytes, p, p, (int32_t)0, (size_t)items, rocprim::plus<int32_t>(), (hipStream_t)0);
-  return bytes;
-}
-
 }  // namespace
 
 extern "C" {
@@ -238,7 +214,7 @@ int64_t relgnn_subgraph_max_walk_length(void) { return kMaxWalkLength; }
 
 size_t relgnn_subgraph_workspace_bytes(int64_t max_items) {
   if (max_items < 1) max_items = 1;
-  return align_up(scan_temp_bytes(max_items), 256) + 256;
+  return align_up(scan_temp_bytes<false>(max_items), 256) + 256;      // the plain scan alone: nothing is compacted in here
 }
 
 int relgnn_subgraph_walk(const int32_t* rowptr_t, const int32_t* col_t, int64_t num_nodes, int32_t num_edge_types,
@@ -273,12 +249,7 @@ int relgnn_subgraph_induced_count(const int32_t* rowptr_t, const int32_t* col_t,
   hipStream_t st = as_stream(stream);
   induced_count_kernel<<<flat_grid(items * RELGNN_WAVE, 256), 256, 0, st>>>(rowptr_t, col_t, num_nodes, num_edge_types, nodes, node_count,
                                                                             node_bound, stamp, counts);
-  size_t temp_bytes = workspace_bytes;
-  if (rocprim::exclusive_scan(workspace, temp_bytes, counts, offsets, (int32_t)0, (size_t)items, rocprim::plus<int32_t>(), st) !=
-      hipSuccess)
-    return RELGNN_EHIP;
-  induced_totals_kernel<<<1, 64, 0, st>>>(offsets, node_bound, num_edge_types, totals);
-  return launch_status();
+  return scan_bucket_counts(counts, offsets, node_bound, num_edge_types, totals, workspace, workspace_bytes, st);
 }
 
 int relgnn_subgraph_induced_emit(const int32_t* rowptr_t, const int32_t* col_t, int64_t num_nodes, int32_t num_edge_types,

@@ -8,6 +8,9 @@ every fanout positive the hops themselves run without a read-back: their buffers
 hop whose fanout is 0 (take every neighbour) has no such bound and reads its edge count back before it emits: one more round trip
 per such hop.
 
+NeighbourSampler stands on StampedNodeSet (a RelGraph plus its stamp array; csrc/node_set.h), as the subgraph sampler does; sample()
+and sample_by_hop() share the hops, the read-back and the loop behind it; they differ in the node list and the relabel / degree kernels.
+
 NeighbourSampler.sample_by_hop() gives the same subgraph numbered by hop (include/relgnn_layered_sampling.h) with the same round
 trips; HopSubgraph.device_batch(layered=True) puts one LevelGraph per layer beside it, so that a model with as many layers as hops
 runs each layer on the hops it needs (the citation task's `sampled_batches` key "layered"; models/sparse_graph_model.py).
@@ -20,7 +23,7 @@ import torch
 
 from .. import _lib
 from ..graph import RelGraph, as_rel_graph
-from .sparse_features import SparseRows
+from .sparse_features import PhaseTrace, SparseRows
 from .sparse_graph_task import DeviceBatch
 
 # relgnn_neighbour_sample_max_fanout / _max_hops (the library is not loaded to validate a parameter; tests/test_gpu_neighbour_sampling.py
@@ -177,134 +180,144 @@ class HopSubgraph(NamedTuple):
         return batch
 
 
-class NeighbourSampler:
-    """Sampler over one RelGraph (its rowptr_t / col_t are read in place).  Holds the [V] int32 stamp array, all zero between calls."""
+class StampedNodeSet(PhaseTrace):
+    """One RelGraph on the GPU (rowptr_t / col_t are read in place) and its [V] int32 stamp array, all zero between calls and after a
+    call that raised.  A call stamps a node set (`begin`, or a launch of the sampler's own) and lists it ascending (`compact`)."""
 
-    def __init__(self, graph: RelGraph, fanouts: Sequence[int], seed: int = 0, replica: int = 0):
-        self.fanouts = check_fanouts(fanouts)
+    def __init__(self, graph, what: str, refuse_unsupported):
+        """what: names the sampler in the refusals; refuse_unsupported(lib) raises ValueError for what the library does not support."""
         if not graph.rowptr_t.is_cuda:
-            raise _lib.RelGnnLibraryError("neighbour sampling runs on the GPU only; the graph is on %s" % graph.rowptr_t.device)
+            raise _lib.RelGnnLibraryError("%s runs on the GPU only; the graph is on %s" % (what, graph.rowptr_t.device))
         lib = _lib.load_library()
-        host = (ctypes.c_int32 * len(self.fanouts))(*self.fanouts)
-        if not lib.relgnn_neighbour_sample_supported(host, len(self.fanouts), graph.V, graph.L):
-            raise ValueError("neighbour sampling does not support fanouts %r on a graph of %d nodes and %d edge types "
-                             "(relgnn_neighbour_sample_supported)" % (self.fanouts, graph.V, graph.L))
-        if not 0 <= int(replica) < 2 ** 31:
-            raise ValueError("replica must be in [0, 2^31), got %r" % (replica,))
+        refuse_unsupported(lib)
         graph.check()                                             # (node ids in range: the kernels trust col_t)
-        self.graph, self.seed, self.replica = graph, int(seed) & 0xffffffff, int(replica)
+        self.graph = graph
         self.stamp = torch.zeros(graph.V, dtype=torch.int32, device=graph.device)
-        self._ws_bytes = lib.relgnn_neighbour_sample_workspace_bytes(graph.V)     # the compaction's; a hop's count fits unless L * bound > V
-        self.synced_hops = [h for h, k in enumerate(self.fanouts) if k == 0]     # the hops that read their edge count back
-        self.trace = None            # a list collects (phase, timed event recorded behind it) of every call (scripts/bench_neighbour_sampling.py)
+        self._compact_bytes = lib.relgnn_neighbour_sample_workspace_bytes(graph.V)
+        self._compact_ws = None                                   # the compaction's workspace, for the length of a call
 
-    def _mark(self, phase: str) -> None:
-        if self.trace is not None:
-            event = torch.cuda.Event(enable_timing=True)
-            event.record()
-            self.trace.append((phase, event))
-
-    def sample(self, seeds, draw: int) -> SampledSubgraph:
-        """seeds: int32 device tensor (a host array is uploaded), distinct node ids; draw: the count of sampled batches so far."""
-        seeds = validated_ids(seeds, self.graph.V, self.graph.device, "seed")
+    def _guarded(self, body, *args):
+        """body(*args) on the graph's device with the compaction's workspace in place; the stamps are zeroed if anything raises."""
         try:
             with torch.cuda.device(self.graph.device):
-                return self._sample(seeds, int(draw) & 0xffffffff)
+                self._compact_ws = _lib.scratch(self._compact_bytes, self.graph.device)
+                return body(*args)
         except BaseException:
             self.stamp.zero_()                                    # whatever a half-run call stamped
             raise
+        finally:
+            self._compact_ws = None
+
+    def begin(self, ids: torch.Tensor) -> None:
+        """Stamps the listed nodes (validated ids) -1."""
+        _lib.launch("relgnn_neighbour_sample_begin", _lib.ptr(ids), ids.numel(), _lib.ptr(self.stamp), self.graph.V)
+
+    def compact(self, value: int, out: torch.Tensor, bound: int, count: torch.Tensor) -> None:
+        """out[:count] = the nodes stamped `value` (0: any stamp) ascending, at most `bound`; `count` stays on the device.  The
+        compaction belongs to the node set, whatever the entry point is called."""
+        _lib.launch("relgnn_neighbour_sample_compact", _lib.ptr(self.stamp), self.graph.V, value, _lib.ptr(out), bound, _lib.ptr(count),
+                    _lib.ptr(self._compact_ws), self._compact_bytes)
+
+
+class NeighbourSampler(StampedNodeSet):
+    """Sampler over one RelGraph (its rowptr_t / col_t are read in place).  Holds the [V] int32 stamp array, all zero between calls
+    (StampedNodeSet; `trace`: scripts/bench_neighbour_sampling.py)."""
+
+    def __init__(self, graph: RelGraph, fanouts: Sequence[int], seed: int = 0, replica: int = 0):
+        self.fanouts = check_fanouts(fanouts)
+
+        def refuse_unsupported(lib):
+            host = (ctypes.c_int32 * len(self.fanouts))(*self.fanouts)
+            if not lib.relgnn_neighbour_sample_supported(host, len(self.fanouts), graph.V, graph.L):
+                raise ValueError("neighbour sampling does not support fanouts %r on a graph of %d nodes and %d edge types "
+                                 "(relgnn_neighbour_sample_supported)" % (self.fanouts, graph.V, graph.L))
+            if not 0 <= int(replica) < 2 ** 31:                   # (refused here, behind the fanouts and in front of graph.check(), as ever)
+                raise ValueError("replica must be in [0, 2^31), got %r" % (replica,))
+        super().__init__(graph, "neighbour sampling", refuse_unsupported)
+        self.seed, self.replica = int(seed) & 0xffffffff, int(replica)
+        self.synced_hops = [h for h, k in enumerate(self.fanouts) if k == 0]     # the hops that read their edge count back
+
+    def sample(self, seeds, draw: int) -> SampledSubgraph:
+        """seeds: int32 device tensor (a host array is uploaded), distinct node ids; draw: the count of sampled batches so far."""
+        return self._call(self._sample, seeds, draw)
 
     def sample_by_hop(self, seeds, draw: int) -> "HopSubgraph":
         """The subgraph sample(seeds, draw) gives — the same hops, draws and edges — numbered by hop: the seeds, then the nodes first
         reached in hop 1, ..., each group in ascending id.  No read-back beyond sample()'s."""
+        return self._call(self._sample_by_hop, seeds, draw)
+
+    def _call(self, body, seeds, draw: int):
         seeds = validated_ids(seeds, self.graph.V, self.graph.device, "seed")
-        try:
-            with torch.cuda.device(self.graph.device):
-                return self._sample_by_hop(seeds, int(draw) & 0xffffffff)
-        except BaseException:
-            self.stamp.zero_()
-            raise
+        return self._guarded(body, seeds, int(draw) & 0xffffffff)
 
     def _sample(self, seeds: torch.Tensor, draw: int) -> SampledSubgraph:
         g = self.graph
-        V, L, dev = g.V, g.L, g.device
-        i32 = lambda n: torch.empty(int(n), dtype=torch.int32, device=dev)
-        hops, summary, _, ws, ws_bytes = self._hops(seeds, draw)
-        node_bound = min(V, seeds.numel() + sum(int(e.shape[0]) for _, _, _, e in hops))
-        nodes_buf = i32(node_bound)
-        _lib.launch("relgnn_neighbour_sample_compact", _lib.ptr(self.stamp), V, 0, _lib.ptr(nodes_buf), node_bound, _lib.ptr(summary[-1:]),
-                    _lib.ptr(ws), ws_bytes)
+        hops, summary, _ = self._hops(seeds, draw)
+        node_bound = min(g.V, seeds.numel() + sum(int(e.shape[0]) for _, _, _, e in hops))
+        nodes_buf = torch.empty(node_bound, dtype=torch.int32, device=g.device)
+        self.compact(0, nodes_buf, node_bound, summary[-1:])
         self._mark("compaction")
-        sizes = summary.tolist()                                  # the one read-back of a call whose fanouts are all positive
-        self._mark("readback")
-        n = sizes[-1]
+        per_hop, n = self._read_back(summary)                     # the one read-back of a call whose fanouts are all positive
         nodes = nodes_buf[:n]
-        per_hop = [sizes[h * (L + 2):(h + 1) * (L + 2)] for h in range(len(self.fanouts))]
-        lengths = [int(seeds.numel())] + [p[L + 1] for p in per_hop[:-1]]              # the true length of every hop's frontier
-        type_edges = [sum(p[l] for p in per_hop) for l in range(L)]
-        adjacency = [torch.empty((e, 2), dtype=torch.int32, device=dev) for e in type_edges]
-        degrees = torch.zeros((L, n), dtype=torch.float32, device=dev)
-        written = [0] * L
-        for (hop_frontier, hop_bound, counts, edges), p, nf in zip(hops, per_hop, lengths):
-            first = 0
-            for l in range(L):
-                if p[l]:
-                    _lib.launch("relgnn_neighbour_sample_relabel", _lib.ptr(edges), first, p[l], _lib.ptr(nodes), n,
-                                _lib.ptr(adjacency[l][written[l]:written[l] + p[l]]))
-                first += p[l]
-                written[l] += p[l]
-            _lib.launch("relgnn_neighbour_sample_degrees", _lib.ptr(counts), hop_bound, nf, L, _lib.ptr(hop_frontier), _lib.ptr(nodes), n,
-                        _lib.ptr(degrees))
-        seed_mask = torch.empty(n, dtype=torch.float32, device=dev)
-        _lib.launch("relgnn_neighbour_sample_finish", _lib.ptr(nodes), n, _lib.ptr(self.stamp), V, _lib.ptr(seed_mask))
-        self._mark("relabel")
-        return SampledSubgraph(nodes, adjacency, degrees, seed_mask, n, sum(type_edges))
+        lengths = [int(seeds.numel())] + [p[g.L + 1] for p in per_hop[:-1]]            # the true length of every hop's frontier
+        adjacency, degrees, seed_mask, num_edges, _ = self._relabelled(
+            hops, per_hop, lengths, nodes, n, "relgnn_neighbour_sample_relabel", (_lib.ptr(nodes), n),
+            "relgnn_neighbour_sample_degrees", lambda h, frontier: (_lib.ptr(frontier), _lib.ptr(nodes), n))
+        return SampledSubgraph(nodes, adjacency, degrees, seed_mask, n, num_edges)
 
     def _sample_by_hop(self, seeds: torch.Tensor, draw: int) -> "HopSubgraph":
-        g = self.graph
-        V, L, dev, H = g.V, g.L, g.device, len(self.fanouts)
-        hops, summary, last, _, _ = self._hops(seeds, draw)
-        sizes = summary.tolist()                                  # the same one read-back; the id-ordered list is never compacted
-        self._mark("readback")
-        per_hop = [sizes[h * (L + 2):(h + 1) * (L + 2)] for h in range(H)]
-        lengths = [int(seeds.numel())] + [p[L + 1] for p in per_hop]                   # nodes first reached in hop 0 (the seeds) .. H
-        starts = [0]
-        for length in lengths:
-            starts.append(starts[-1] + length)
+        g, H = self.graph, len(self.fanouts)
+        hops, summary, last = self._hops(seeds, draw)
+        per_hop, _ = self._read_back(summary)                     # the same one read-back; the id-ordered list is never compacted
+        lengths = [int(seeds.numel())] + [p[g.L + 1] for p in per_hop]                 # nodes first reached in hop 0 (the seeds) .. H
+        starts = [0] + np.cumsum(lengths).tolist()
         hop_nodes, n = starts[1:], starts[-1]                     # n_0 .. n_H
         # the frontier buffers ARE the per-hop lists: cut to their true lengths and laid end to end (a device copy, no kernel of ours)
         nodes = torch.cat([f[:nf] for f, nf in zip([hop[0] for hop in hops] + [last], lengths)])
         host_starts = (ctypes.c_int64 * (H + 2))(*starts)
+        adjacency, degrees, seed_mask, num_edges, hop_edges = self._relabelled(
+            hops, per_hop, lengths, nodes, n, "relgnn_neighbour_sample_relabel_by_hop",
+            (_lib.ptr(self.stamp), g.V, _lib.ptr(nodes), host_starts, H + 1),
+            "relgnn_neighbour_sample_degrees_by_hop", lambda h, frontier: (starts[h], n))
+        return HopSubgraph(nodes, adjacency, degrees, seed_mask, n, num_edges, hop_nodes, hop_edges)
+
+    def _read_back(self, summary: torch.Tensor):
+        """-> ([L + 1 totals | next frontier's length] per hop, the summary's last entry: the node count where a compaction wrote it)."""
+        sizes, L = summary.tolist(), self.graph.L
+        self._mark("readback")
+        return [sizes[h * (L + 2):(h + 1) * (L + 2)] for h in range(len(self.fanouts))], sizes[-1]
+
+    def _relabelled(self, hops, per_hop, lengths, nodes: torch.Tensor, n: int, relabel: str, relabel_args, degrees_of: str, degree_args):
+        """What sample and sample_by_hop share behind the read-back.  Per hop: `relabel`(edges, first, count, *relabel_args, out) for every
+        type that has edges, `degrees_of`(counts, bound, the frontier's length, L, *degree_args(h, frontier), degrees); then finish, which
+        clears the stamps of `nodes`.  -> (adjacency, degrees, seed_mask, the edge total, per type the edges written by hops 0 .. h)."""
+        L, dev = self.graph.L, self.graph.device
         type_edges = [sum(p[l] for p in per_hop) for l in range(L)]
         adjacency = [torch.empty((e, 2), dtype=torch.int32, device=dev) for e in type_edges]
         degrees = torch.zeros((L, n), dtype=torch.float32, device=dev)
         written, hop_edges = [0] * L, [[] for _ in range(L)]
-        for h, ((_, hop_bound, counts, edges), p) in enumerate(zip(hops, per_hop)):
+        for h, ((frontier, bound, counts, edges), p) in enumerate(zip(hops, per_hop)):
             first = 0
             for l in range(L):
                 if p[l]:
-                    _lib.launch("relgnn_neighbour_sample_relabel_by_hop", _lib.ptr(edges), first, p[l], _lib.ptr(self.stamp), V,
-                                _lib.ptr(nodes), host_starts, H + 1, _lib.ptr(adjacency[l][written[l]:written[l] + p[l]]))
+                    _lib.launch(relabel, _lib.ptr(edges), first, p[l], *relabel_args, _lib.ptr(adjacency[l][written[l]:written[l] + p[l]]))
                 first += p[l]
                 written[l] += p[l]
                 hop_edges[l].append(written[l])
-            _lib.launch("relgnn_neighbour_sample_degrees_by_hop", _lib.ptr(counts), hop_bound, lengths[h], L, starts[h], n,
-                        _lib.ptr(degrees))
+            _lib.launch(degrees_of, _lib.ptr(counts), bound, lengths[h], L, *degree_args(h, frontier), _lib.ptr(degrees))
         seed_mask = torch.empty(n, dtype=torch.float32, device=dev)
-        _lib.launch("relgnn_neighbour_sample_finish", _lib.ptr(nodes), n, _lib.ptr(self.stamp), V, _lib.ptr(seed_mask))
+        _lib.launch("relgnn_neighbour_sample_finish", _lib.ptr(nodes), n, _lib.ptr(self.stamp), self.graph.V, _lib.ptr(seed_mask))
         self._mark("relabel")
-        return HopSubgraph(nodes, adjacency, degrees, seed_mask, n, sum(type_edges), hop_nodes, hop_edges)
+        return adjacency, degrees, seed_mask, sum(type_edges), hop_edges
 
     def _hops(self, seeds: torch.Tensor, draw: int):
         """begin, then count / take / compact(h + 1) per hop -> ([(frontier, bound, counts, edges) per hop], the summary still on the
-        device, the buffer of the nodes first reached in the last hop, the compaction's workspace and its size)."""
+        device, the buffer of the nodes first reached in the last hop)."""
         lib, g = _lib.load_library(), self.graph
         V, L, dev = g.V, g.L, g.device
         i32 = lambda n: torch.empty(int(n), dtype=torch.int32, device=dev)
-        ws_bytes = self._ws_bytes
-        ws = _lib.scratch(ws_bytes, dev)
         self._mark("start")
-        _lib.launch("relgnn_neighbour_sample_begin", _lib.ptr(seeds), seeds.numel(), _lib.ptr(self.stamp), V)
+        self.begin(seeds)
         frontier, bound = seeds, int(seeds.numel())
         count = torch.full((1,), bound, dtype=torch.int32, device=dev)
         hops = []
@@ -313,8 +326,8 @@ class NeighbourSampler:
         for h, k in enumerate(self.fanouts):
             counts, offsets = i32(bound * L + 1), i32(bound * L + 1)
             totals = summary[h * (L + 2):h * (L + 2) + L + 1]
-            hop_ws, hop_ws_bytes = ws, ws_bytes
-            if bound * L + 1 > V:                                 # (the compaction's workspace covers V items)
+            hop_ws, hop_ws_bytes = self._compact_ws, self._compact_bytes             # (covers V items: a hop's count fits unless L * bound > V)
+            if bound * L + 1 > V:
                 hop_ws_bytes = lib.relgnn_neighbour_sample_workspace_bytes(bound * L + 1)
                 hop_ws = _lib.scratch(hop_ws_bytes, dev)
             _lib.launch("relgnn_neighbour_sample_count", _lib.ptr(g.rowptr_t), V, L, _lib.ptr(frontier), _lib.ptr(count), bound, k,
@@ -328,11 +341,22 @@ class NeighbourSampler:
             self._mark("hops")
             next_bound = max(1, min(V, edge_bound))
             frontier, count = i32(next_bound), summary[h * (L + 2) + L + 1:h * (L + 2) + L + 2]
-            _lib.launch("relgnn_neighbour_sample_compact", _lib.ptr(self.stamp), V, h + 1, _lib.ptr(frontier), next_bound, _lib.ptr(count),
-                        _lib.ptr(ws), ws_bytes)
+            self.compact(h + 1, frontier, next_bound, count)
             self._mark("compaction")
             bound = next_bound
-        return hops, summary, frontier, ws, ws_bytes
+        return hops, summary, frontier
+
+
+def integer_at_least(value, minimum: int, message: str) -> int:
+    """`value` as a python int when it is an integer (not a bool) >= minimum, or ValueError(message % (value,))."""
+    if isinstance(value, bool) or not isinstance(value, (int, np.integer)) or value < minimum:
+        raise ValueError(message % (value,))
+    return int(value)
+
+
+def unknown_keys(value, known) -> list:
+    """The keys of the dict `value` that are not among `known`, by their text ([] for what is no dict: the caller refuses that)."""
+    return sorted(set(value) - set(known), key=str) if isinstance(value, dict) else []
 
 
 def parse_sampled_batches(value) -> Optional[Dict]:
@@ -347,15 +371,13 @@ def parse_sampled_batches(value) -> Optional[Dict]:
     if value is None:
         return None
     if not isinstance(value, dict) or not {"fanouts", "seeds_per_batch"} <= set(value) \
-            or set(value) - {"fanouts", "seeds_per_batch", "seed", "sparse_features", "sparse_update", "sparse_gradient", "layered",
-                             "data_parallel", "evaluation"}:
+            or unknown_keys(value, ("fanouts", "seeds_per_batch", "seed", "sparse_features", "sparse_update", "sparse_gradient", "layered",
+                                    "data_parallel", "evaluation")):
         raise ValueError('sampled_batches must be {"fanouts": [k_1, ..., k_H], "seeds_per_batch": B, "seed": s, "sparse_features": bool, '
                          '"sparse_update": bool, "sparse_gradient": bool, "layered": bool, "data_parallel": bool, "evaluation": '
                          '{"fanouts": [...], "seeds_per_batch": B, "keep": bool}}, the last seven optional, got %r' % (value,))
-    per_batch = value["seeds_per_batch"]
-    if isinstance(per_batch, bool) or not isinstance(per_batch, (int, np.integer)) or per_batch < 1:
-        raise ValueError("sampled_batches: seeds_per_batch must be a positive integer, got %r" % (per_batch,))
-    parsed = {"fanouts": check_fanouts(value["fanouts"]), "seeds_per_batch": int(per_batch), "seed": int(value.get("seed", 0))}
+    per_batch = integer_at_least(value["seeds_per_batch"], 1, "sampled_batches: seeds_per_batch must be a positive integer, got %r")
+    parsed = {"fanouts": check_fanouts(value["fanouts"]), "seeds_per_batch": per_batch, "seed": int(value.get("seed", 0))}
     parse_bool_keys("sampled_batches", value, parsed, ("sparse_features", "sparse_update", "sparse_gradient", "layered", "data_parallel"), {
         "sparse_update": ("sparse_features", "the rows a batch names are read from the transposed structure of its SparseRows"),
         "sparse_gradient": ("sparse_update", "the compact gradient is what the row-deferred update consumes; dense Adam reads a dense one")})
@@ -394,17 +416,16 @@ def check_sparse_node_features(what: str, parsed: Dict, sparse_node_features: bo
 def parse_evaluation(value) -> Dict:
     """The "evaluation" key of `sampled_batches` as {"fanouts": [ints], "seeds_per_batch": int}, "keep" (a bool: a fold's evaluation
     batches are built once and handed out again every epoch) carried only when given."""
-    if not isinstance(value, dict) or set(value) - {"fanouts", "seeds_per_batch", "keep"} or not {"fanouts", "seeds_per_batch"} <= set(value):
+    if not isinstance(value, dict) or unknown_keys(value, ("fanouts", "seeds_per_batch", "keep")) or not {"fanouts", "seeds_per_batch"} <= set(value):
         raise ValueError('sampled_batches: "evaluation" must be {"fanouts": [k_1, ..., k_H], "seeds_per_batch": B, "keep": bool}, the '
                          'last one optional, got %r' % (value,))
-    per_batch = value["seeds_per_batch"]
-    if isinstance(per_batch, bool) or not isinstance(per_batch, (int, np.integer)) or per_batch < 1:
-        raise ValueError('sampled_batches: "evaluation": seeds_per_batch must be a positive integer, got %r' % (per_batch,))
+    per_batch = integer_at_least(value["seeds_per_batch"], 1,
+                                 'sampled_batches: "evaluation": seeds_per_batch must be a positive integer, got %r')
     try:
         fanouts = check_fanouts(value["fanouts"])
     except ValueError as error:
         raise ValueError('sampled_batches: "evaluation": %s' % error) from None
-    parsed = {"fanouts": fanouts, "seeds_per_batch": int(per_batch)}
+    parsed = {"fanouts": fanouts, "seeds_per_batch": per_batch}
     if "keep" in value:
         if not isinstance(value["keep"], bool):
             raise ValueError('sampled_batches: "evaluation": keep must be true or false, got %r' % (value["keep"],))

@@ -149,7 +149,18 @@ def _structure(rowptr, col, val, num_cols) -> CsrStructure:
                         t(slabs), t(combos), ws_rows, num_cols)
 
 
-class SparseRows:
+class PhaseTrace:
+    """trace = a list: every call appends (phase, timed event recorded behind it); None: nothing is recorded (scripts/bench_*sampl*)."""
+    trace = None
+
+    def _mark(self, phase: str) -> None:
+        if self.trace is not None:
+            event = torch.cuda.Event(enable_timing=True)
+            event.record()
+            self.trace.append((phase, event))
+
+
+class SparseRows(PhaseTrace):                # (the phases of a take_rows: scripts/bench_sparse_sampling.py)
     """A [V, F] float32 matrix in CSR (`rows`) and in CSR of its transpose (`transposed`: F rows over V columns), both with
     ascending ids inside a row and built once on the host with a stable sort.  The structure is validated here — monotone rowptr,
     0 <= col < F, sorted and unique columns per row, no explicit zeros — and raises ValueError: the kernels trust what they read."""
@@ -370,14 +381,6 @@ class SparseRows:
             taken._named = self._named_rows_fill(taken.transposed, slot, host_sizes[8])
             self._mark("named")
         return taken
-
-    trace = None                     # a list collects (phase, timed event recorded behind it) of every take_rows (scripts/bench_sparse_sampling.py)
-
-    def _mark(self, phase: str) -> None:
-        if self.trace is not None:
-            event = torch.cuda.Event(enable_timing=True)
-            event.record()
-            self.trace.append((phase, event))
 
 
 class _PerBatchRows(SparseRows):

@@ -6,6 +6,7 @@ batch (tasks/neighbour_sampling.py) grows with every hop instead.
 Host round trips of SubgraphSampler.sample() and induced_subgraph(): the root (node) list is validated on the host (in range,
 distinct; one small copy of a device list), and the subgraph's sizes — n, the per-type edge counts and their total — are read back
 ONCE, because its tensors are sized by them.  The buffers in front of that read-back are sized from the bound min(V, R * (h + 1)).
+The stamp array, its compaction and the guard that leaves it zero are StampedNodeSet's (tasks/neighbour_sampling.py), shared with NeighbourSampler.
 
 GraphSAINT normalisation (include/relgnn_subgraph_norm.h; the key "normalisation" of the citation task's `subgraph_batches`):
 SubgraphSampler.presample() counts over pre-sampled subgraphs how often every node and every by-target entry is held (VisitCounts; no
@@ -18,7 +19,8 @@ import torch
 
 from .. import _lib
 from ..graph import RelGraph
-from .neighbour_sampling import SampledSubgraph, epoch_seed_batches, parse_bool_keys, validated_ids
+from .neighbour_sampling import (SampledSubgraph, StampedNodeSet, epoch_seed_batches, integer_at_least, parse_bool_keys, unknown_keys,
+                                  validated_ids)
 
 # relgnn_subgraph_max_walk_length (the library is not loaded to validate a parameter; tests/test_gpu_subgraph_batches.py holds the
 # two against each other)
@@ -33,39 +35,23 @@ def check_walk_length(walk_length) -> int:
     return int(walk_length)
 
 
-class _Extractor:
-    """The induced-edge path over one RelGraph and one [V] int32 stamp array, all zero between calls."""
+class _Extractor(StampedNodeSet):
+    """The induced-edge path over one RelGraph and its stamp array (StampedNodeSet; `trace`: scripts/bench_subgraph_batches.py)."""
 
     def __init__(self, graph: RelGraph, what: str):
-        if not graph.rowptr_t.is_cuda:
-            raise _lib.RelGnnLibraryError("%s runs on the GPU only; the graph is on %s" % (what, graph.rowptr_t.device))
-        lib = _lib.load_library()
-        if not lib.relgnn_subgraph_supported(1, 0, graph.V, graph.L):
-            raise ValueError("%s does not support a graph of %d nodes and %d edge types (relgnn_subgraph_supported)"
-                             % (what, graph.V, graph.L))
-        graph.check()                                             # (node ids in range: the kernels trust col_t)
-        self.graph = graph
-        self.stamp = torch.zeros(graph.V, dtype=torch.int32, device=graph.device)
-        self._compact_bytes = lib.relgnn_neighbour_sample_workspace_bytes(graph.V)
-        self.trace = None            # a list collects (phase, timed event recorded behind it) of every call (scripts/bench_subgraph_batches.py)
+        def refuse_unsupported(lib):
+            if not lib.relgnn_subgraph_supported(1, 0, graph.V, graph.L):
+                raise ValueError("%s does not support a graph of %d nodes and %d edge types (relgnn_subgraph_supported)" % (what, graph.V, graph.L))
+        super().__init__(graph, what, refuse_unsupported)
 
-    def _mark(self, phase: str) -> None:
-        if self.trace is not None:
-            event = torch.cuda.Event(enable_timing=True)
-            event.record()
-            self.trace.append((phase, event))
-
-    def _run(self, stamp_the_set, node_bound: int, weighting=None) -> SampledSubgraph:
-        """stamp_the_set() enqueues what stamps the node set (at most node_bound nodes); everything behind it is the same.
-        weighting = (VisitCounts, max_edge_weight): the emit also writes GraphSAINT's per-edge weights (message_weights)."""
-        try:
-            with torch.cuda.device(self.graph.device):
-                return self._induced(stamp_the_set, int(node_bound), weighting)
-        except BaseException:
-            self.stamp.zero_()                                    # whatever a half-run call stamped
-            raise
+    def _node_list(self, nodes_buf: torch.Tensor, B: int, count: torch.Tensor) -> None:
+        """The stamped set ascending in nodes_buf[:count] (at most B; `count` stays on the device), every listed stamp now position + 1."""
+        self.compact(0, nodes_buf, B, count)
+        _lib.launch("relgnn_subgraph_number", _lib.ptr(nodes_buf), _lib.ptr(count), B, _lib.ptr(self.stamp), self.graph.V)
 
     def _induced(self, stamp_the_set, B: int, weighting=None) -> SampledSubgraph:
+        """stamp_the_set() enqueues what stamps the node set (at most B nodes); everything behind it is the same.  Runs under _guarded.
+        weighting = (VisitCounts, max_edge_weight): the emit also writes GraphSAINT's per-edge weights (message_weights)."""
         lib, g = _lib.load_library(), self.graph
         V, L, dev = g.V, g.L, g.device
         i32 = lambda n: torch.empty(int(n), dtype=torch.int32, device=dev)
@@ -74,10 +60,7 @@ class _Extractor:
         self._mark("walks")
         summary = torch.zeros(L + 2, dtype=torch.int32, device=dev)       # [edges per type | edge total | n]: read back once
         nodes_buf = i32(B)
-        ws = _lib.scratch(self._compact_bytes, dev)
-        _lib.launch("relgnn_neighbour_sample_compact", _lib.ptr(self.stamp), V, 0, _lib.ptr(nodes_buf), B, _lib.ptr(summary[L + 1:]),
-                    _lib.ptr(ws), self._compact_bytes)
-        _lib.launch("relgnn_subgraph_number", _lib.ptr(nodes_buf), _lib.ptr(summary[L + 1:]), B, _lib.ptr(self.stamp), V)
+        self._node_list(nodes_buf, B, summary[L + 1:])
         self._mark("node_list")
         counts, offsets = i32(B * L + 1), i32(B * L + 1)
         scan_bytes = lib.relgnn_subgraph_workspace_bytes(B * L + 1)
@@ -105,10 +88,7 @@ class _Extractor:
                         _lib.ptr(degrees), _lib.ptr(message_weights) if total else None)
         _lib.launch("relgnn_subgraph_clear", _lib.ptr(nodes_buf), n, _lib.ptr(self.stamp), V)
         self._mark("induced_emit")
-        adjacency, first = [], 0
-        for e in type_edges:                                      # the types' lists lie one behind the other: views, no copy
-            adjacency.append(edges[first:first + e])
-            first += e
+        adjacency = list(edges.split(type_edges))                 # the types' lists lie one behind the other: views, no copy
         seed_mask = torch.ones(n, dtype=torch.float32, device=dev)        # every node of the subgraph may count in the loss
         return SampledSubgraph(nodes, adjacency, degrees, seed_mask, n, total, message_weights)
 
@@ -154,7 +134,7 @@ class SubgraphSampler(_Extractor):
         def walks():
             _lib.launch("relgnn_subgraph_walk", _lib.ptr(g.rowptr_t), _lib.ptr(g.col_t), g.V, g.L, _lib.ptr(roots), R, self.walk_length,
                         draw, self.seed, self.replica, _lib.ptr(self.stamp))
-        return self._run(walks, min(g.V, R * (self.walk_length + 1)), weighting)
+        return self._guarded(self._induced, walks, min(g.V, R * (self.walk_length + 1)), weighting)
 
     def presample(self, fold_mask, roots_per_batch: int, epochs: int) -> VisitCounts:
         """GraphSAINT's pre-sampling: E = `epochs` epochs of root lists, epoch_seed_batches(fold_mask, R, seed, 0x80000000 + e), every
@@ -170,29 +150,24 @@ class SubgraphSampler(_Extractor):
             raise ValueError("presample: %d walks of %d steps are not supported (relgnn_subgraph_supported)" % (R, self.walk_length))
         B = min(V, R * (self.walk_length + 1))
         counts = VisitCounts(torch.zeros(V, dtype=torch.int32, device=dev), torch.zeros(g.M, dtype=torch.int32, device=dev), 0)
-        drawn = 0
-        try:
-            with torch.cuda.device(dev):
-                nodes_buf = torch.empty(B, dtype=torch.int32, device=dev)
-                count = torch.zeros(1, dtype=torch.int32, device=dev)
-                ws = _lib.scratch(self._compact_bytes, dev)
-                for e in range(epochs):
-                    for roots in epoch_seed_batches(fold_mask, R, self.seed, PRESAMPLE_EPOCH + e):       # in range, distinct, ascending
-                        roots = torch.as_tensor(roots, device=dev)
-                        _lib.launch("relgnn_subgraph_walk", _lib.ptr(g.rowptr_t), _lib.ptr(g.col_t), V, L, _lib.ptr(roots), roots.numel(),
-                                    self.walk_length, drawn & 0xffffffff, self.seed, PRESAMPLE_REPLICA, _lib.ptr(self.stamp))
-                        _lib.launch("relgnn_neighbour_sample_compact", _lib.ptr(self.stamp), V, 0, _lib.ptr(nodes_buf), B, _lib.ptr(count),
-                                    _lib.ptr(ws), self._compact_bytes)
-                        _lib.launch("relgnn_subgraph_number", _lib.ptr(nodes_buf), _lib.ptr(count), B, _lib.ptr(self.stamp), V)
-                        _lib.launch("relgnn_subgraph_visit_count", _lib.ptr(g.rowptr_t), _lib.ptr(g.col_t) if g.M else None, V, L, g.M,
-                                    _lib.ptr(nodes_buf), _lib.ptr(count), B, _lib.ptr(self.stamp), _lib.ptr(counts.node_visits),
-                                    _lib.ptr(counts.edge_visits) if g.M else None)
-                        self.stamp.zero_()                        # (the set's size never reaches the host: the whole array)
-                        drawn += 1
-        except BaseException:
-            self.stamp.zero_()
-            raise
-        return counts._replace(num_subgraphs=drawn)
+
+        def count_visits():
+            nodes_buf = torch.empty(B, dtype=torch.int32, device=dev)
+            count = torch.zeros(1, dtype=torch.int32, device=dev)
+            drawn = 0
+            for e in range(epochs):
+                for roots in epoch_seed_batches(fold_mask, R, self.seed, PRESAMPLE_EPOCH + e):           # in range, distinct, ascending
+                    roots = torch.as_tensor(roots, device=dev)
+                    _lib.launch("relgnn_subgraph_walk", _lib.ptr(g.rowptr_t), _lib.ptr(g.col_t), V, L, _lib.ptr(roots), roots.numel(),
+                                self.walk_length, drawn & 0xffffffff, self.seed, PRESAMPLE_REPLICA, _lib.ptr(self.stamp))
+                    self._node_list(nodes_buf, B, count)
+                    _lib.launch("relgnn_subgraph_visit_count", _lib.ptr(g.rowptr_t), _lib.ptr(g.col_t) if g.M else None, V, L, g.M,
+                                _lib.ptr(nodes_buf), _lib.ptr(count), B, _lib.ptr(self.stamp), _lib.ptr(counts.node_visits),
+                                _lib.ptr(counts.edge_visits) if g.M else None)
+                    self.stamp.zero_()                            # (the set's size never reaches the host: the whole array)
+                    drawn += 1
+            return drawn
+        return counts._replace(num_subgraphs=self._guarded(count_visits))
 
 
 def induced_subgraph(graph: RelGraph, nodes) -> SampledSubgraph:
@@ -200,10 +175,7 @@ def induced_subgraph(graph: RelGraph, nodes) -> SampledSubgraph:
     induced-edge path of SubgraphSampler.sample without the walks; one read-back."""
     extractor = _Extractor(graph, "induced_subgraph")
     nodes = validated_ids(nodes, graph.V, graph.device, "node")
-
-    def given():
-        _lib.launch("relgnn_neighbour_sample_begin", _lib.ptr(nodes), nodes.numel(), _lib.ptr(extractor.stamp), graph.V)
-    return extractor._run(given, int(nodes.numel()))
+    return extractor._guarded(extractor._induced, lambda: extractor.begin(nodes), int(nodes.numel()))
 
 
 def parse_normalisation(value) -> Dict:
@@ -214,21 +186,19 @@ def parse_normalisation(value) -> Dict:
     if not isinstance(value, dict):
         raise ValueError('%s must be {"presample_epochs": E, "aggregation": bool, "max_edge_weight": c}, the last two optional, got %r'
                          % (what, value))
-    unknown = sorted(set(value) - set(known), key=str)
+    unknown = unknown_keys(value, known)
     if unknown:
         raise ValueError("%s: unknown key %s (known: %s)" % (what, ", ".join(repr(k) for k in unknown), ", ".join(known)))
     if "presample_epochs" not in value:
         raise ValueError("%s: presample_epochs is required" % what)
-    epochs = value["presample_epochs"]
-    if isinstance(epochs, bool) or not isinstance(epochs, (int, np.integer)) or epochs < 1:
-        raise ValueError("%s: presample_epochs must be an integer >= 1, got %r" % (what, epochs))
+    epochs = integer_at_least(value["presample_epochs"], 1, what + ": presample_epochs must be an integer >= 1, got %r")
     aggregation = value.get("aggregation", True)
     if not isinstance(aggregation, bool):
         raise ValueError("%s: aggregation must be true or false, got %r" % (what, aggregation))
     cap = value.get("max_edge_weight", 1e4)
     if isinstance(cap, bool) or not isinstance(cap, (int, float, np.integer, np.floating)) or not 0 < float(cap) < float("inf"):
         raise ValueError("%s: max_edge_weight must be a finite number > 0, got %r" % (what, cap))
-    return {"presample_epochs": int(epochs), "aggregation": aggregation, "max_edge_weight": float(cap)}
+    return {"presample_epochs": epochs, "aggregation": aggregation, "max_edge_weight": float(cap)}
 
 
 def parse_subgraph_batches(value) -> Optional[Dict]:
@@ -239,14 +209,12 @@ def parse_subgraph_batches(value) -> Optional[Dict]:
     if value is None:
         return None
     known = {"roots_per_batch", "walk_length", "seed", "sparse_features", "data_parallel", "normalisation"}
-    unknown = sorted(set(value) - known, key=str) if isinstance(value, dict) else []
+    unknown = unknown_keys(value, known)
     if not isinstance(value, dict) or unknown or not {"roots_per_batch", "walk_length"} <= set(value):
         said = "; unknown key %s" % ", ".join(repr(k) for k in unknown) if unknown else ""
         raise ValueError('subgraph_batches must be {"roots_per_batch": R, "walk_length": h, "seed": s, "sparse_features": bool, '
                          '"data_parallel": bool, "normalisation": {...}}, the last four optional%s, got %r' % (said, value))
-    per_batch = value["roots_per_batch"]
-    if isinstance(per_batch, bool) or not isinstance(per_batch, (int, np.integer)) or per_batch < 1:
-        raise ValueError("subgraph_batches: roots_per_batch must be a positive integer, got %r" % (per_batch,))
+    per_batch = integer_at_least(value["roots_per_batch"], 1, "subgraph_batches: roots_per_batch must be a positive integer, got %r")
     try:
         walk_length = check_walk_length(value["walk_length"])
     except ValueError as error:
@@ -254,7 +222,7 @@ def parse_subgraph_batches(value) -> Optional[Dict]:
     seed = value.get("seed", 0)
     if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)):
         raise ValueError("subgraph_batches: seed must be an integer, got %r" % (seed,))
-    parsed = {"roots_per_batch": int(per_batch), "walk_length": walk_length, "seed": int(seed)}
+    parsed = {"roots_per_batch": per_batch, "walk_length": walk_length, "seed": int(seed)}
     parse_bool_keys("subgraph_batches", value, parsed, ("sparse_features", "data_parallel"))
     if "normalisation" in value:
         parsed["normalisation"] = parse_normalisation(value["normalisation"])
