@@ -15,8 +15,9 @@ SparseRows, which its input projection takes through ops.csr_rows_project (csrc/
 The batching modes live in tasks/single_graph_batches.py (`self.batches`), which describes every parameter and key:
   `sampled_batches` {"fanouts", "seeds_per_batch", "seed"; optional "sparse_features", "sparse_update", "sparse_gradient", "layered",
       "evaluation"}: TRAIN epochs of neighbour-sampled receptive fields; "evaluation": VALIDATION, TEST and predict(nodes=...) on them too.
-  `subgraph_batches` {"roots_per_batch", "walk_length", "seed"; optional "sparse_features", "normalisation"}: TRAIN epochs of random-walk
-      induced subgraphs; "normalisation": GraphSAINT's loss and aggregation weights.
+  `subgraph_batches` {"roots_per_batch", "walk_length", "seed"; optional "sparse_features", "normalisation", "sampler"}: TRAIN epochs of
+      random-walk induced subgraphs; "normalisation": GraphSAINT's loss and aggregation weights; "sampler": the node set from a node, edge
+      or partition sampler instead of walks.
   Either takes the optional key "data_parallel": train(group=...) / test(group=...) deal the batches of an epoch out to the ranks.
 """
 import os
@@ -611,5 +612,6 @@ class Citation_Network_Task(Sparse_Graph_Task):
     def pretty_print_epoch_task_metrics(self, task_metric_results: List[Dict[str, Any]], num_graphs: int) -> str:
         if len(task_metric_results) > 1 and all('num_masked' in m for m in task_metric_results):     # an epoch of sampled batches
             masked = sum(float(m['num_masked']) for m in task_metric_results)
-            return "Acc: %.2f%%" % (sum(float(m['num_correct']) for m in task_metric_results) / masked * 100,)
+            # (the graph-wide samplers of `subgraph_batches` may meet no TRAIN node in a whole epoch: 0 of 0 is printed as 0)
+            return "Acc: %.2f%%" % (sum(float(m['num_correct']) for m in task_metric_results) / max(masked, 1.0) * 100,)
         return "Acc: %.2f%%" % (float(task_metric_results[0]['accuracy']) * 100,)

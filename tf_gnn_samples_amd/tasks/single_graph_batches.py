@@ -81,6 +81,23 @@ preset as the batch graph's degree scale): a layer's sum is then an estimate of 
 It needs a model whose layers take the degree table, normalise by it and sum (RGCN, RGDCN, GNN-FiLM with
 normalize_messages_by_num_incoming; a ValueError from the model otherwise); "aggregation": false works with every model.
 
+One more optional key, "sampler": "walk" | "node" | "edge" | "parts" (absent: "walk", and the parsed dict is the one it was; it composes
+with "sparse_features", "data_parallel" and "normalisation"): who picks the node set of a batch.  The host lists an epoch's batches in
+ONE place (subgraph_sampling.sampler_plan, built once per fold and parameter: subgraph_plan; subgraph_sampling.epoch_node_lists), which
+the TRAIN generator, train_batch_weights, the pre-sampling and the data-parallel schedule read; the device work of a batch is
+relgnn_neighbour_sample_begin or relgnn_subgraph_walk in front of the unchanged induced path.  "node" ({"roots_per_batch": R}, no
+"walk_length"; ceil(n_train / R) batches): R targets of uniformly drawn by-target entries, nodes in proportion to their in-degree, made
+distinct (SubgraphSampler.sample_nodes).  "edge" (the same keys and count): one walk step from each of R uniformly drawn roots
+(SubgraphSampler(graph, 1).sample); over a graph stored in both directions a pair {u, v} is drawn in proportion to
+1 / deg u + 1 / deg v, GraphSAINT's edge distribution.  "parts" ({"parts_path": a .npy holding int32 [V] with values 0 .. P - 1 and no
+part empty, "parts_per_batch": q}, neither "roots_per_batch" nor "walk_length"; ceil(P / q) batches): a permutation of the parts cut
+into runs of q, a batch the union of their nodes (Cluster-GCN's batches over a partition the user brings; there is no partitioner).
+The file is read and validated when the plan is built (a ValueError that names it), the path travels in the checkpoint's metadata
+and a CRC of the array joins the data-parallel fingerprint.  The three graph-wide samplers REQUIRE "normalisation" (a ValueError
+that names both keys): their batches are not anchored at TRAIN nodes, a batch may hold none, and only the loss divided by n_train is
+defined for it (0, with zero gradients).  The pre-sampling runs the same plan for the epochs 0x80000000 + e
+(SubgraphSampler.presample_lists), N = E * the epoch's batch count.
+
 Both parameters take one more optional key, "data_parallel": true (a ValueError together with "sparse_update" / "sparse_gradient"; it
 composes with every other key): train(group=...) and test(group=...) of a process group of W > 1 ranks are no longer refused
 (models/data_parallel.py).  Every rank holds the whole graph; global batch j of a TRAIN epoch goes to rank
@@ -100,7 +117,7 @@ from ..parallel import refuse_single_graph_task
 from .neighbour_sampling import (PREDICT_FOLD, NeighbourSampler, epoch_seed_batches, evaluation_replica, evaluation_seed_batches)
 from .sparse_features import SparseRows
 from .sparse_graph_task import DataFold
-from .subgraph_sampling import SubgraphSampler
+from .subgraph_sampling import SubgraphSampler, epoch_node_lists, sampler_plan
 
 
 class WeakKeyedCache:
@@ -158,6 +175,7 @@ class SingleGraphBatches:
         self.graph_states = WeakKeyedCache()      # (first adjacency array, features), device -> GraphState
         self.fold_states = WeakKeyedCache()       # (a fold's label array), (device, replica or "subgraph") -> FoldState
         self.kept_evaluation = WeakKeyedCache()   # (a fold's label array), (device, fold number, route, fanouts, B) -> its batches
+        self.sampler_plans = WeakKeyedCache()     # (a fold's label array), the parsed `subgraph_batches` -> its host SamplerPlan
 
     def bind(self, device) -> None:
         """The model tells the task where it runs (the NumPy iterator is not told otherwise).  The sampler is a HIP kernel and the
@@ -208,16 +226,30 @@ class SingleGraphBatches:
             return NeighbourSampler(graph, sampled["fanouts"], seed=sampled["seed"] or 0, replica=replica)
         return self.fold_state(fold, device, int(replica), sampler, fanouts)
 
+    def subgraph_plan(self, fold):
+        """The host plan of `subgraph_batches` over the TRAIN fold (subgraph_sampling.sampler_plan: the in-degrees of "node", the
+        validated partition of "parts"), built once per (fold, parameter): every reader of an epoch's lists asks here."""
+        subgraph = self.task.subgraph_batches
+        key = repr(sorted(subgraph.items()))
+        held = self.sampler_plans.get((fold.labels,), key)
+        if held is None:
+            held = self.sampler_plans.put((fold.labels,), key, sampler_plan(subgraph, fold.mask, fold.adjacency_lists, len(fold.labels)))
+        return held
+
     def subgraph_state(self, fold, device) -> FoldState:
-        """The TRAIN fold's SubgraphSampler over the device RelGraph the folds share, with the fold's labels and mask."""
+        """The TRAIN fold's SubgraphSampler over the device RelGraph the folds share, with the fold's labels and mask.  Its walk
+        length is the parameter's for "walk", 1 for "edge" and 0 for the samplers that bring the node set themselves."""
         subgraph = self.task.subgraph_batches
         normalisation = subgraph.get("normalisation")
+        plan = self.subgraph_plan(fold)
         # GraphSAINT's pre-sampling, before the first TRAIN batch of this state: a pure function of (seed, E, the graph), so it
         # is recomputed here after restore() and never stored in a checkpoint
         presample = None if normalisation is None else (
-            lambda sampler: sampler.presample(fold.mask, subgraph["roots_per_batch"], normalisation["presample_epochs"]))
-        return self.fold_state(fold, device, "subgraph",
-                               lambda graph: SubgraphSampler(graph, subgraph["walk_length"], seed=subgraph["seed"]), presample=presample)
+            lambda sampler: sampler.presample_lists(lambda epoch: epoch_node_lists(plan, epoch), normalisation["presample_epochs"],
+                                                    plan.longest(), plan.walked))
+        steps = subgraph["walk_length"] if plan.sampler == "walk" else plan.walk_steps
+        return self.fold_state(fold, device, "subgraph", lambda graph: SubgraphSampler(graph, steps, seed=subgraph["seed"]),
+                               presample=presample)
 
     # -------------------- TRAIN --------------------
     def train_batches(self, fold):
@@ -241,17 +273,20 @@ class SingleGraphBatches:
         sampled, subgraph = self.task.sampled_batches, self.task.subgraph_batches
         if sampled is not None:
             return [float(len(seeds)) for seeds in epoch_seed_batches(fold.mask, sampled["seeds_per_batch"], sampled["seed"], self.epoch)]
-        return [1.0] * len(epoch_seed_batches(fold.mask, subgraph["roots_per_batch"], subgraph["seed"], self.epoch))
+        return [1.0] * self.subgraph_plan(fold).batches_per_epoch()
 
     def fingerprint(self, folds):
         """What every rank of a data-parallel run must hold alike (parallel.dp_check_fingerprints): the graph's size, the masked count
-        of every fold in `folds` (name -> fold, "train" among them), a CRC of the TRAIN mask and the parsed sampling parameters."""
+        of every fold in `folds` (name -> fold, "train" among them), a CRC of the TRAIN mask, the parsed sampling parameters and, under
+        `subgraph_batches`' "sampler": "parts", a CRC of the partition array."""
         train = folds["train"]
         said = {"nodes": len(train.labels), "edges_per_type": [len(a) for a in train.adjacency_lists],
                 "train_mask_crc": zlib.crc32(np.ascontiguousarray(train.mask).tobytes()),
                 "sampled_batches": self.task.sampled_batches, "subgraph_batches": self.task.subgraph_batches}
         for name, fold in folds.items():
             said["%s_nodes" % name] = int(np.count_nonzero(fold.mask))
+        if (self.task.subgraph_batches or {}).get("sampler") == "parts":          # (every rank reads the file itself)
+            said["parts_crc"] = zlib.crc32(np.ascontiguousarray(self.subgraph_plan(train).parts).tobytes())
         return said
 
     def neighbour_batches(self, fold, rank: int = 0, world: int = 1):
@@ -269,8 +304,9 @@ class SingleGraphBatches:
                                                    named_rows=sampled.get("sparse_gradient", False))
 
     def subgraph_batches(self, fold, rank: int = 0, world: int = 1):
-        """ceil(n_train / R) subgraph batches: one TRAIN epoch; of these, the ones dealt to `rank` of `world`.  Every train node is a
-        root once; the loss mask is the fold's mask over ALL nodes of the subgraph (seed_mask is ones).  With the key "normalisation"
+        """The subgraph batches of one TRAIN epoch (subgraph_sampling.epoch_node_lists: ceil(n_train / R) of them, ceil(P / q) for
+        "parts"); of these, the ones dealt to `rank` of `world`.  Under "walk" every train node is a root once; the loss mask is
+        the fold's mask over ALL nodes of the subgraph (seed_mask is ones).  With the key "normalisation"
         every batch carries extra['loss_normalisation'] = (N / max(node_visits, 1) per node, n_train), and with its "aggregation" the
         per-edge weights as its graph's degree scale."""
         subgraph = self.task.subgraph_batches
@@ -280,14 +316,15 @@ class SingleGraphBatches:
         normalisation, counts = subgraph.get("normalisation"), state.visit_counts
         weighting = (counts, normalisation["max_edge_weight"]) if normalisation is not None and normalisation["aggregation"] else None
         num_train = float(np.count_nonzero(fold.mask))
-        for j, roots in enumerate(epoch_seed_batches(fold.mask, subgraph["roots_per_batch"], subgraph["seed"], epoch)):
+        plan = self.subgraph_plan(fold)
+        for j, ids in enumerate(epoch_node_lists(plan, epoch)):
             draw, self.draw = self.draw, self.draw + 1
             if j % world != rank:
                 continue
-            if normalisation is None:
-                yield state.sampler.sample(roots, draw).device_batch(state.features, state.labels, state.mask, keep)
+            if normalisation is None:                 # ("walk" alone: the other samplers require the key)
+                yield state.sampler.sample(ids, draw).device_batch(state.features, state.labels, state.mask, keep)
                 continue
-            sub = state.sampler.sample(roots, draw, weighting)
+            sub = state.sampler.sample(ids, draw, weighting) if plan.walked else state.sampler.sample_nodes(ids, weighting)
             batch = sub.device_batch(state.features, state.labels, state.mask, keep)
             batch.extra['loss_normalisation'] = (counts.node_weights(sub.nodes), num_train)
             yield batch

@@ -11,8 +11,13 @@ The stamp array, its compaction and the guard that leaves it zero are StampedNod
 GraphSAINT normalisation (include/relgnn_subgraph_norm.h; the key "normalisation" of the citation task's `subgraph_batches`):
 SubgraphSampler.presample() counts over pre-sampled subgraphs how often every node and every by-target entry is held (VisitCounts; no
 read-back at all), and sample(..., weighting=(counts, cap)) emits the per-edge aggregation weights with the batch's edges.
+
+Who picks the node set (the key "sampler" of `subgraph_batches`: "walk" | "node" | "edge" | "parts") is a host rule in front of that
+path: sampler_plan() and epoch_node_lists() list an epoch's batches for all four, SubgraphSampler.sample() walks a root list ("walk",
+and "edge" with walk length 1), SubgraphSampler.sample_nodes() takes a node set as it is ("node", "parts"), and presample_lists()
+pre-samples over any plan.  No kernel and no entry point belongs to a sampler.
 """
-from typing import Dict, NamedTuple, Optional
+from typing import Dict, List, NamedTuple, Optional
 
 import numpy as np
 import torch
@@ -136,30 +141,49 @@ class SubgraphSampler(_Extractor):
                         draw, self.seed, self.replica, _lib.ptr(self.stamp))
         return self._guarded(self._induced, walks, min(g.V, R * (self.walk_length + 1)), weighting)
 
+    def sample_nodes(self, nodes, weighting=None) -> SampledSubgraph:
+        """The subgraph induced on a node set the caller brings (the task's node and partition samplers): int32 ids, distinct, any
+        order.  induced_subgraph's path on THIS sampler's stamp array and inside its guard, so that `weighting` applies as in sample()."""
+        g = self.graph
+        nodes = validated_ids(nodes, g.V, g.device, "node")
+        return self._guarded(self._induced, lambda: self.begin(nodes), int(nodes.numel()), weighting)
+
     def presample(self, fold_mask, roots_per_batch: int, epochs: int) -> VisitCounts:
         """GraphSAINT's pre-sampling: E = `epochs` epochs of root lists, epoch_seed_batches(fold_mask, R, seed, 0x80000000 + e), every
         list walked with the reserved replica 0x20000000 and draw = the running index of the pre-sampled subgraph, and counted
         (relgnn_subgraph_visit_count).  Per subgraph: walk, compact, number, count, a reset of the stamps; NOTHING is read back, the
         set's size stays on the device and the buffers are sized from the bound min(V, R * (h + 1))."""
-        lib, g = _lib.load_library(), self.graph
-        V, L, dev = g.V, g.L, g.device
         R, epochs = int(roots_per_batch), int(epochs)
         if R < 1 or epochs < 1:
             raise ValueError("presample: roots_per_batch and epochs must be positive, got %r and %r" % (roots_per_batch, epochs))
-        if not lib.relgnn_subgraph_supported(R, self.walk_length, V, L):
-            raise ValueError("presample: %d walks of %d steps are not supported (relgnn_subgraph_supported)" % (R, self.walk_length))
-        B = min(V, R * (self.walk_length + 1))
+        return self.presample_lists(lambda epoch: epoch_seed_batches(fold_mask, R, self.seed, epoch), epochs, R, walked=True)
+
+    def presample_lists(self, epoch_lists, epochs: int, longest: int, walked: bool) -> VisitCounts:
+        """presample() over the lists of any plan: epoch_lists(0x80000000 + e) gives pre-sampling epoch e's lists (in range, distinct,
+        ascending; none longer than `longest`).  walked: every list is a root list and is walked as presample() walks it; otherwise it
+        IS the node set and is stamped by `begin`.  Counted alike, with no read-back."""
+        lib, g = _lib.load_library(), self.graph
+        V, L, dev = g.V, g.L, g.device
+        steps = self.walk_length if walked else 0
+        if not lib.relgnn_subgraph_supported(int(longest), steps, V, L):
+            raise ValueError("presample: %d walks of %d steps are not supported (relgnn_subgraph_supported)" % (longest, steps))
+        B = min(V, int(longest) * (steps + 1))
         counts = VisitCounts(torch.zeros(V, dtype=torch.int32, device=dev), torch.zeros(g.M, dtype=torch.int32, device=dev), 0)
 
         def count_visits():
             nodes_buf = torch.empty(B, dtype=torch.int32, device=dev)
             count = torch.zeros(1, dtype=torch.int32, device=dev)
             drawn = 0
-            for e in range(epochs):
-                for roots in epoch_seed_batches(fold_mask, R, self.seed, PRESAMPLE_EPOCH + e):           # in range, distinct, ascending
-                    roots = torch.as_tensor(roots, device=dev)
-                    _lib.launch("relgnn_subgraph_walk", _lib.ptr(g.rowptr_t), _lib.ptr(g.col_t), V, L, _lib.ptr(roots), roots.numel(),
-                                self.walk_length, drawn & 0xffffffff, self.seed, PRESAMPLE_REPLICA, _lib.ptr(self.stamp))
+            for e in range(int(epochs)):
+                for ids in epoch_lists(PRESAMPLE_EPOCH + e):
+                    if len(ids) > longest:
+                        raise ValueError("presample: a list of %d ids, longer than the %d its buffers were sized for" % (len(ids), longest))
+                    ids = torch.as_tensor(ids, device=dev)
+                    if walked:
+                        _lib.launch("relgnn_subgraph_walk", _lib.ptr(g.rowptr_t), _lib.ptr(g.col_t), V, L, _lib.ptr(ids), ids.numel(),
+                                    self.walk_length, drawn & 0xffffffff, self.seed, PRESAMPLE_REPLICA, _lib.ptr(self.stamp))
+                    else:
+                        self.begin(ids)
                     self._node_list(nodes_buf, B, count)
                     _lib.launch("relgnn_subgraph_visit_count", _lib.ptr(g.rowptr_t), _lib.ptr(g.col_t) if g.M else None, V, L, g.M,
                                 _lib.ptr(nodes_buf), _lib.ptr(count), B, _lib.ptr(self.stamp), _lib.ptr(counts.node_visits),
@@ -201,29 +225,163 @@ def parse_normalisation(value) -> Dict:
     return {"presample_epochs": epochs, "aggregation": aggregation, "max_edge_weight": float(cap)}
 
 
+# who picks the node set of a batch (the key "sampler" of `subgraph_batches`): the keys each requires and the keys each refuses
+SAMPLERS = ("walk", "node", "edge", "parts")
+_REQUIRED = {"walk": ("roots_per_batch", "walk_length"), "node": ("roots_per_batch",), "edge": ("roots_per_batch",),
+             "parts": ("parts_path", "parts_per_batch")}
+_REFUSED = {"walk": ("parts_path", "parts_per_batch"), "node": ("walk_length", "parts_path", "parts_per_batch"),
+            "edge": ("walk_length", "parts_path", "parts_per_batch"), "parts": ("roots_per_batch", "walk_length")}
+
+
 def parse_subgraph_batches(value) -> Optional[Dict]:
     """The task parameter `subgraph_batches` as {"roots_per_batch": int, "walk_length": int, "seed": int}, None when it is absent;
     the optional keys "sparse_features" (a bool: the batches take their feature rows from a SparseRows), "data_parallel" (a bool:
-    train(group=...) hands the batches of an epoch out to the ranks) and "normalisation" (parse_normalisation: GraphSAINT's loss and
-    aggregation weights) are carried only when given."""
+    train(group=...) hands the batches of an epoch out to the ranks), "normalisation" (parse_normalisation: GraphSAINT's loss and
+    aggregation weights) and "sampler" (one of SAMPLERS; absent: "walk") are carried only when given.  "node" and "edge" take
+    "roots_per_batch" (R draws per batch) and no "walk_length"; "parts" takes "parts_path" (a .npy, int32 [V], read when the TRAIN
+    state is built) and "parts_per_batch" in their place; all three require "normalisation": their batches are not anchored at
+    TRAIN nodes, and only the loss divided by n_train is defined for a batch that holds none."""
     if value is None:
         return None
-    known = {"roots_per_batch", "walk_length", "seed", "sparse_features", "data_parallel", "normalisation"}
+    known = {"roots_per_batch", "walk_length", "seed", "sparse_features", "data_parallel", "normalisation", "sampler", "parts_path",
+             "parts_per_batch"}
     unknown = unknown_keys(value, known)
-    if not isinstance(value, dict) or unknown or not {"roots_per_batch", "walk_length"} <= set(value):
+    sampler = value.get("sampler", "walk") if isinstance(value, dict) else "walk"
+    if not isinstance(value, dict) or unknown or (sampler == "walk" and not set(_REQUIRED["walk"]) <= set(value)):
         said = "; unknown key %s" % ", ".join(repr(k) for k in unknown) if unknown else ""
         raise ValueError('subgraph_batches must be {"roots_per_batch": R, "walk_length": h, "seed": s, "sparse_features": bool, '
-                         '"data_parallel": bool, "normalisation": {...}}, the last four optional%s, got %r' % (said, value))
-    per_batch = integer_at_least(value["roots_per_batch"], 1, "subgraph_batches: roots_per_batch must be a positive integer, got %r")
-    try:
-        walk_length = check_walk_length(value["walk_length"])
-    except ValueError as error:
-        raise ValueError("subgraph_batches: %s" % error) from None
+                         '"data_parallel": bool, "normalisation": {...}, "sampler": "walk" | "node" | "edge" | "parts"}, the last five '
+                         'optional ("node", "edge": no walk_length; "parts": "parts_path" and "parts_per_batch" instead of both)%s, got %r'
+                         % (said, value))
+    if not isinstance(sampler, str) or sampler not in SAMPLERS:
+        raise ValueError("subgraph_batches: sampler must be one of %s, got %r" % (", ".join('"%s"' % name for name in SAMPLERS), sampler))
+    refused = [key for key in _REFUSED[sampler] if key in value]
+    if refused:
+        raise ValueError('subgraph_batches: "sampler": "%s" takes no %s (it takes %s)'
+                         % (sampler, " and no ".join(refused), " and ".join(_REQUIRED[sampler])))
+    missing = [key for key in _REQUIRED[sampler] if key not in value]
+    if missing:
+        raise ValueError('subgraph_batches: "sampler": "%s" requires %s' % (sampler, " and ".join(missing)))
+    if sampler != "walk" and "normalisation" not in value:
+        raise ValueError('subgraph_batches: "sampler": "%s" requires the key "normalisation": its batches are not anchored at TRAIN '
+                         'nodes, and the plain mean over a batch that holds none is 0/0' % sampler)
+    parsed = {}
+    if "roots_per_batch" in value:
+        parsed["roots_per_batch"] = integer_at_least(value["roots_per_batch"], 1,
+                                                     "subgraph_batches: roots_per_batch must be a positive integer, got %r")
+    if "walk_length" in value:
+        try:
+            parsed["walk_length"] = check_walk_length(value["walk_length"])
+        except ValueError as error:
+            raise ValueError("subgraph_batches: %s" % error) from None
+    if sampler == "parts":
+        if not isinstance(value["parts_path"], str) or not value["parts_path"]:
+            raise ValueError("subgraph_batches: parts_path must be the path of a .npy file, got %r" % (value["parts_path"],))
+        parsed["parts_path"] = value["parts_path"]
+        parsed["parts_per_batch"] = integer_at_least(value["parts_per_batch"], 1,
+                                                     "subgraph_batches: parts_per_batch must be a positive integer, got %r")
     seed = value.get("seed", 0)
     if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)):
         raise ValueError("subgraph_batches: seed must be an integer, got %r" % (seed,))
-    parsed = {"roots_per_batch": per_batch, "walk_length": walk_length, "seed": int(seed)}
+    parsed["seed"] = int(seed)
     parse_bool_keys("subgraph_batches", value, parsed, ("sparse_features", "data_parallel"))
     if "normalisation" in value:
         parsed["normalisation"] = parse_normalisation(value["normalisation"])
+    if "sampler" in value:
+        parsed["sampler"] = sampler
     return parsed
+
+
+# ---- one plan per epoch: the host side of every sampler ------------------------------------------------------------------------------
+class SamplerPlan(NamedTuple):
+    """What the host needs to list an epoch's batches (epoch_node_lists), taken once per TRAIN state from the fold."""
+    sampler: str                                # one of SAMPLERS
+    seed: int
+    fold_mask: np.ndarray                       # the TRAIN mask: "walk" cuts its nodes; the other three take their batch count from it
+    per_batch: int                              # R, or q for "parts"
+    num_nodes: int                              # V
+    entry_ends: Optional[np.ndarray] = None     # "node": int64 [V], the by-target entries up to and including node v's (all types)
+    parts: Optional[np.ndarray] = None          # "parts": the validated int32 [V] array of the file
+    part_nodes: Optional[List[np.ndarray]] = None       # "parts": per part its nodes, int32 ascending
+
+    @property
+    def walk_steps(self) -> int:
+        """The walk length of the sampler's device front: "edge" is one step from every root; "node" and "parts" do not walk."""
+        return 1 if self.sampler == "edge" else 0
+
+    @property
+    def walked(self) -> bool:
+        """Are an epoch's lists root lists (walked on the device) and not the node sets themselves?"""
+        return self.sampler in ("walk", "edge")
+
+    def longest(self) -> int:
+        """No list of any epoch is longer than this."""
+        if self.sampler == "parts":
+            return int(np.sort([len(nodes) for nodes in self.part_nodes])[-self.per_batch:].sum())
+        return min(self.per_batch, self.num_nodes) if self.sampler != "walk" else self.per_batch
+
+    def batches_per_epoch(self) -> int:
+        items = len(self.part_nodes) if self.sampler == "parts" else int(np.count_nonzero(np.asarray(self.fold_mask) != 0))
+        return -(-items // self.per_batch)
+
+
+def load_parts(path: str, num_nodes: int) -> np.ndarray:
+    """The partition of "parts_path": a .npy holding int32 [V] with values 0 .. P - 1 and no part empty, or a ValueError that names
+    the file."""
+    try:
+        parts = np.load(path, allow_pickle=False)
+    except (OSError, ValueError) as error:
+        raise ValueError("subgraph_batches: parts_path %r cannot be read as a .npy array (%s)" % (path, error)) from None
+    if parts.dtype != np.int32 or parts.shape != (num_nodes,):
+        raise ValueError("subgraph_batches: parts_path %r must hold an int32 array of shape (%d,), one part per node; it holds %s %r"
+                         % (path, num_nodes, parts.dtype, parts.shape))
+    if num_nodes == 0 or parts.min() < 0:
+        raise ValueError("subgraph_batches: parts_path %r holds a negative part or no node at all" % (path,))
+    sizes = np.bincount(parts)
+    if (sizes == 0).any():
+        raise ValueError("subgraph_batches: parts_path %r: the parts must be 0 .. P - 1 with none empty; of 0 .. %d, part %d has no node"
+                         % (path, len(sizes) - 1, int(np.flatnonzero(sizes == 0)[0])))
+    return parts
+
+
+def sampler_plan(subgraph: Dict, fold_mask, adjacency_lists, num_nodes: int) -> SamplerPlan:
+    """The plan of a parsed `subgraph_batches` over one fold: "node" takes the in-degrees from the fold's adjacency lists here, once;
+    "parts" reads and validates its file here (load_parts)."""
+    sampler, V = subgraph.get("sampler", "walk"), int(num_nodes)
+    plan = SamplerPlan(sampler, int(subgraph["seed"]) & 0xffffffff, np.asarray(fold_mask),
+                       subgraph["parts_per_batch" if sampler == "parts" else "roots_per_batch"], V)
+    if sampler == "node":
+        in_degree = np.zeros(V, dtype=np.int64)
+        for edges in adjacency_lists:
+            in_degree += np.bincount(np.asarray(edges).reshape(-1, 2)[:, 1], minlength=V)
+        if not in_degree.sum():
+            raise ValueError('subgraph_batches: "sampler": "node" draws a by-target entry; the graph has none')
+        plan = plan._replace(entry_ends=np.cumsum(in_degree))
+    if sampler == "parts":
+        parts = load_parts(subgraph["parts_path"], V)
+        order = np.argsort(parts, kind="stable").astype(np.int32)           # (a part's nodes ascending)
+        plan = plan._replace(parts=parts, part_nodes=np.split(order, np.cumsum(np.bincount(parts))[:-1]))
+    return plan
+
+
+def epoch_node_lists(plan: SamplerPlan, epoch: int) -> List[np.ndarray]:
+    """The lists of one epoch, each int32, ascending and distinct: root lists for "walk" (epoch_seed_batches, its bits unchanged) and
+    "edge" (one walk step from each, SubgraphSampler(graph, 1).sample), the node sets themselves for "node" and "parts".  A pure
+    function of (the plan, epoch): the TRAIN generator, train_batch_weights, the pre-sampling (epochs 0x80000000 + e) and the
+    data-parallel schedule all read it."""
+    seed, epoch = plan.seed, int(epoch) & 0xffffffff
+    if plan.sampler == "walk":
+        return epoch_seed_batches(plan.fold_mask, plan.per_batch, seed, epoch)
+    if plan.sampler == "parts":
+        order = np.random.RandomState([seed, epoch, 3]).permutation(len(plan.part_nodes))
+        return [np.sort(np.concatenate([plan.part_nodes[p] for p in order[i:i + plan.per_batch]])).astype(np.int32)
+                for i in range(0, len(order), plan.per_batch)]
+    lists = []
+    for j in range(plan.batches_per_epoch()):
+        if plan.sampler == "node":      # the target of a uniformly drawn by-target entry: a node in proportion to its in-degree
+            at = np.random.RandomState([seed, epoch, j, 1]).randint(0, int(plan.entry_ends[-1]), size=plan.per_batch, dtype=np.int64)
+            drawn = np.searchsorted(plan.entry_ends, at, side="right")
+        else:                           # "edge": uniform roots; the step from root u takes entry (u <- v) with probability 1 / deg u
+            drawn = np.random.RandomState([seed, epoch, j, 2]).randint(0, plan.num_nodes, size=plan.per_batch)
+        lists.append(np.unique(drawn).astype(np.int32))
+    return lists
