@@ -8,7 +8,7 @@ relgnn_neighbour_sample_begin in front of the same induced path, so what is comp
            a train fold of V / 2 nodes
   model    RGCN, 8 layers, hidden 256, Adam
   samplers walk: 1024 roots, walk length 4 | node: 1024 draws | edge: 1024 roots, one step | parts: V / 1024 parts of 1024 nodes each
-           (node v in part perm(v) mod P: the project has no partitioner, and a random partition keeps few edges), 4 parts a batch
+           (node v in part perm(v) mod P: a random partition keeps few edges; a computed one: scripts/bench_graph_partition.py), 4 parts a batch
 Every sampler runs normalised (E = 1 pre-sampling epoch, "aggregation": true): the three graph-wide ones require the key.
 Reported per sampler, median [min, max] over ROUNDS alternating rounds (the four samplers in turn in every round):
   nodes, edges, longest_bucket   of the batches of the first round (means; longest_bucket: the largest induced in-degree of a batch, the

@@ -299,6 +299,18 @@ ABI["relgnn_subgraph_norm.h"] = {
                                                       _ptr]),
 }
 
+# csrc/<header> -> {name: (restype, argtypes)}: the package-internal entry points, declared beside the kernels and NOT under include/.
+# load_library() types them too; signatures() neither returns nor merges them: they are not public ABI and may change with the package.
+INTERNAL = {}
+
+# csrc/graph_partition.h (the wish pass of the device graph partitioner: tasks/graph_partition.py)
+INTERNAL["graph_partition.h"] = {
+    "relgnn_partition_supported": (ctypes.c_int, [_c_i64, _c_i32, _c_i64, _c_i32, _c_i32]),
+    "relgnn_partition_wave_row_max": (_c_i64, []),
+    "relgnn_partition_wish": (ctypes.c_int, [_ptr, _ptr, _c_i64, _c_i32, _c_i64, _ptr, _ptr, _c_i32, _ptr, _c_i32, _c_u32, _c_u32, _ptr, _ptr,
+                                             _c_i64, _c_i32, _ptr, _ptr]),
+}
+
 _lib = None
 
 
@@ -316,7 +328,13 @@ def load_library():
             "%s not found: the HIP extension is not built. Run `python -c 'import __graft_entry__ as g; "
             "g.build()'` (needs hipcc). There is no CPU fallback for this path." % LIB_PATH)
     lib = ctypes.CDLL(str(LIB_PATH))
-    for name, (restype, argtypes) in signatures().items():
+    typed = signatures()
+    for header, table in INTERNAL.items():
+        for name in table:
+            if name in typed:
+                raise RelGnnLibraryError("%s of csrc/%s is bound twice" % (name, header))
+        typed.update(table)
+    for name, (restype, argtypes) in typed.items():
         fn = getattr(lib, name)  # AttributeError if the symbol is not exported
         fn.restype = restype
         fn.argtypes = argtypes

@@ -168,6 +168,7 @@ class _SingleGraphDataParallel(_Ranks):
 
     def begin_training(self):
         said = [None] * self.world
+        self.model.task.bind_sampling_device(self.model.device)     # (a computed partition's CRC is of what this device computes)
         dist.all_gather_object(said, self.model.task.data_parallel_fingerprint(), group=self.group)
         dp_check_fingerprints(said)
         super().begin_training()

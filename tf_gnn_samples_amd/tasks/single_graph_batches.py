@@ -91,9 +91,15 @@ distinct (SubgraphSampler.sample_nodes).  "edge" (the same keys and count): one 
 (SubgraphSampler(graph, 1).sample); over a graph stored in both directions a pair {u, v} is drawn in proportion to
 1 / deg u + 1 / deg v, GraphSAINT's edge distribution.  "parts" ({"parts_path": a .npy holding int32 [V] with values 0 .. P - 1 and no
 part empty, "parts_per_batch": q}, neither "roots_per_batch" nor "walk_length"; ceil(P / q) batches): a permutation of the parts cut
-into runs of q, a batch the union of their nodes (Cluster-GCN's batches over a partition the user brings; there is no partitioner).
+into runs of q, a batch the union of their nodes (Cluster-GCN's batches over a partition the user brings).
 The file is read and validated when the plan is built (a ValueError that names it), the path travels in the checkpoint's metadata
-and a CRC of the array joins the data-parallel fingerprint.  The three graph-wide samplers REQUIRE "normalisation" (a ValueError
+and a CRC of the array joins the data-parallel fingerprint.  In place of "parts_path" (exactly one of the two) "parts" takes
+"partition": {"num_parts": P, "imbalance_percent": b, "refine_rounds": T} (the last two optional: 10 and 8): the partition is COMPUTED
+when the plan is built (computed_partition: graph_partition.partition_graph over the device RelGraph the folds share, seeded by this
+parameter's "seed"; label propagation under the size cap ceil(V (100 + b) / (100 P)), its wish pass in HIP, csrc/graph_partition.hip),
+brought to the host once and put through the file's validation.  The key travels in the checkpoint's metadata, never the array:
+restore() and every rank of a data-parallel run compute the same partition again, and its CRC joins the fingerprint alike.  GPU only
+(a ValueError from a model on the CPU).  The three graph-wide samplers REQUIRE "normalisation" (a ValueError
 that names both keys): their batches are not anchored at TRAIN nodes, a batch may hold none, and only the loss divided by n_train is
 defined for it (0, with zero gradients).  The pre-sampling runs the same plan for the epochs 0x80000000 + e
 (SubgraphSampler.presample_lists), N = E * the epoch's batch count.
@@ -114,6 +120,7 @@ import torch
 
 from ..graph import RelGraph
 from ..parallel import refuse_single_graph_task
+from .graph_partition import partition_graph
 from .neighbour_sampling import (PREDICT_FOLD, NeighbourSampler, epoch_seed_batches, evaluation_replica, evaluation_seed_batches)
 from .sparse_features import SparseRows
 from .sparse_graph_task import DataFold
@@ -181,6 +188,9 @@ class SingleGraphBatches:
         """The model tells the task where it runs (the NumPy iterator is not told otherwise).  The sampler is a HIP kernel and the
         package has no CPU fallback: a model on the CPU is refused."""
         device = torch.device(device)
+        if device.type != "cuda" and "partition" in (self.task.subgraph_batches or {}):
+            raise ValueError("subgraph_batches: partition is GPU only: the partitioner's wish pass is a HIP kernel and there is no CPU "
+                             "fallback (the model is on %s)" % device)
         if device.type != "cuda":
             raise RuntimeError("sampled_batches needs a model on the GPU: the neighbour sampler is a HIP kernel and there is no CPU "
                                "fallback (the model is on %s)" % device)
@@ -228,13 +238,28 @@ class SingleGraphBatches:
 
     def subgraph_plan(self, fold):
         """The host plan of `subgraph_batches` over the TRAIN fold (subgraph_sampling.sampler_plan: the in-degrees of "node", the
-        validated partition of "parts"), built once per (fold, parameter): every reader of an epoch's lists asks here."""
+        validated partition of "parts", read from its file or computed here under the key "partition"), built once per (fold,
+        parameter): every reader of an epoch's lists asks here."""
         subgraph = self.task.subgraph_batches
         key = repr(sorted(subgraph.items()))
         held = self.sampler_plans.get((fold.labels,), key)
         if held is None:
-            held = self.sampler_plans.put((fold.labels,), key, sampler_plan(subgraph, fold.mask, fold.adjacency_lists, len(fold.labels)))
+            held = self.sampler_plans.put((fold.labels,), key, sampler_plan(subgraph, fold.mask, fold.adjacency_lists, len(fold.labels),
+                                                                            partition=lambda: self.computed_partition(fold)))
         return held
+
+    def computed_partition(self, fold) -> np.ndarray:
+        """The partition of the key "partition", computed on the device RelGraph the folds share (graph_partition.partition_graph, with
+        `subgraph_batches`' own seed) and brought to the host once: int32 [V].  A pure function of (the graph, the key, the seed): it
+        is computed again after restore() and by every rank of a data-parallel run, and never stored."""
+        subgraph = self.task.subgraph_batches
+        asked = subgraph["partition"]
+        graph = self.graph_state(fold, self.bound_device()).graph
+        try:
+            parts = partition_graph(graph, asked["num_parts"], subgraph["seed"], asked["imbalance_percent"], asked["refine_rounds"])
+        except ValueError as error:
+            raise ValueError("subgraph_batches: partition: %s" % error) from None
+        return parts.cpu().numpy()
 
     def subgraph_state(self, fold, device) -> FoldState:
         """The TRAIN fold's SubgraphSampler over the device RelGraph the folds share, with the fold's labels and mask.  Its walk
@@ -285,7 +310,7 @@ class SingleGraphBatches:
                 "sampled_batches": self.task.sampled_batches, "subgraph_batches": self.task.subgraph_batches}
         for name, fold in folds.items():
             said["%s_nodes" % name] = int(np.count_nonzero(fold.mask))
-        if (self.task.subgraph_batches or {}).get("sampler") == "parts":          # (every rank reads the file itself)
+        if (self.task.subgraph_batches or {}).get("sampler") == "parts":          # (every rank reads the file, or computes the partition, itself)
             said["parts_crc"] = zlib.crc32(np.ascontiguousarray(self.subgraph_plan(train).parts).tobytes())
         return said
 

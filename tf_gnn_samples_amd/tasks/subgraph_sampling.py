@@ -24,6 +24,7 @@ import torch
 
 from .. import _lib
 from ..graph import RelGraph
+from .graph_partition import parse_partition
 from .neighbour_sampling import (SampledSubgraph, StampedNodeSet, epoch_seed_batches, integer_at_least, parse_bool_keys, unknown_keys,
                                   validated_ids)
 
@@ -229,8 +230,8 @@ def parse_normalisation(value) -> Dict:
 SAMPLERS = ("walk", "node", "edge", "parts")
 _REQUIRED = {"walk": ("roots_per_batch", "walk_length"), "node": ("roots_per_batch",), "edge": ("roots_per_batch",),
              "parts": ("parts_path", "parts_per_batch")}
-_REFUSED = {"walk": ("parts_path", "parts_per_batch"), "node": ("walk_length", "parts_path", "parts_per_batch"),
-            "edge": ("walk_length", "parts_path", "parts_per_batch"), "parts": ("roots_per_batch", "walk_length")}
+_REFUSED = {"walk": ("parts_path", "partition", "parts_per_batch"), "node": ("walk_length", "parts_path", "partition", "parts_per_batch"),
+            "edge": ("walk_length", "parts_path", "partition", "parts_per_batch"), "parts": ("roots_per_batch", "walk_length")}
 
 
 def parse_subgraph_batches(value) -> Optional[Dict]:
@@ -239,19 +240,22 @@ def parse_subgraph_batches(value) -> Optional[Dict]:
     train(group=...) hands the batches of an epoch out to the ranks), "normalisation" (parse_normalisation: GraphSAINT's loss and
     aggregation weights) and "sampler" (one of SAMPLERS; absent: "walk") are carried only when given.  "node" and "edge" take
     "roots_per_batch" (R draws per batch) and no "walk_length"; "parts" takes "parts_path" (a .npy, int32 [V], read when the TRAIN
-    state is built) and "parts_per_batch" in their place; all three require "normalisation": their batches are not anchored at
-    TRAIN nodes, and only the loss divided by n_train is defined for a batch that holds none."""
+    state is built) and "parts_per_batch" in their place, or "partition" (graph_partition.parse_partition: the partition is computed on
+    the device when the TRAIN state is built, from this dict's "seed") in place of "parts_path", exactly one of the two; all three
+    require "normalisation": their batches are not anchored at TRAIN nodes, and only the loss divided by n_train is defined for a
+    batch that holds none."""
     if value is None:
         return None
     known = {"roots_per_batch", "walk_length", "seed", "sparse_features", "data_parallel", "normalisation", "sampler", "parts_path",
-             "parts_per_batch"}
+             "partition", "parts_per_batch"}
     unknown = unknown_keys(value, known)
     sampler = value.get("sampler", "walk") if isinstance(value, dict) else "walk"
     if not isinstance(value, dict) or unknown or (sampler == "walk" and not set(_REQUIRED["walk"]) <= set(value)):
         said = "; unknown key %s" % ", ".join(repr(k) for k in unknown) if unknown else ""
         raise ValueError('subgraph_batches must be {"roots_per_batch": R, "walk_length": h, "seed": s, "sparse_features": bool, '
                          '"data_parallel": bool, "normalisation": {...}, "sampler": "walk" | "node" | "edge" | "parts"}, the last five '
-                         'optional ("node", "edge": no walk_length; "parts": "parts_path" and "parts_per_batch" instead of both)%s, got %r'
+                         'optional ("node", "edge": no walk_length; "parts": "parts_path" or "partition", and "parts_per_batch", instead of '
+                         'both)%s, got %r'
                          % (said, value))
     if not isinstance(sampler, str) or sampler not in SAMPLERS:
         raise ValueError("subgraph_batches: sampler must be one of %s, got %r" % (", ".join('"%s"' % name for name in SAMPLERS), sampler))
@@ -259,7 +263,10 @@ def parse_subgraph_batches(value) -> Optional[Dict]:
     if refused:
         raise ValueError('subgraph_batches: "sampler": "%s" takes no %s (it takes %s)'
                          % (sampler, " and no ".join(refused), " and ".join(_REQUIRED[sampler])))
-    missing = [key for key in _REQUIRED[sampler] if key not in value]
+    if sampler == "parts" and "parts_path" in value and "partition" in value:
+        raise ValueError('subgraph_batches: "sampler": "parts" takes exactly one of parts_path (a partition the user brings) and '
+                         'partition (one computed here), not both')
+    missing = [key for key in _REQUIRED[sampler] if key not in value and not (key == "parts_path" and "partition" in value)]
     if missing:
         raise ValueError('subgraph_batches: "sampler": "%s" requires %s' % (sampler, " and ".join(missing)))
     if sampler != "walk" and "normalisation" not in value:
@@ -275,9 +282,12 @@ def parse_subgraph_batches(value) -> Optional[Dict]:
         except ValueError as error:
             raise ValueError("subgraph_batches: %s" % error) from None
     if sampler == "parts":
-        if not isinstance(value["parts_path"], str) or not value["parts_path"]:
-            raise ValueError("subgraph_batches: parts_path must be the path of a .npy file, got %r" % (value["parts_path"],))
-        parsed["parts_path"] = value["parts_path"]
+        if "partition" in value:
+            parsed["partition"] = parse_partition(value["partition"])
+        else:
+            if not isinstance(value["parts_path"], str) or not value["parts_path"]:
+                raise ValueError("subgraph_batches: parts_path must be the path of a .npy file, got %r" % (value["parts_path"],))
+            parsed["parts_path"] = value["parts_path"]
         parsed["parts_per_batch"] = integer_at_least(value["parts_per_batch"], 1,
                                                      "subgraph_batches: parts_per_batch must be a positive integer, got %r")
     seed = value.get("seed", 0)
@@ -332,21 +342,29 @@ def load_parts(path: str, num_nodes: int) -> np.ndarray:
         parts = np.load(path, allow_pickle=False)
     except (OSError, ValueError) as error:
         raise ValueError("subgraph_batches: parts_path %r cannot be read as a .npy array (%s)" % (path, error)) from None
+    return validated_parts(parts, num_nodes, "parts_path %r" % (path,))
+
+
+def validated_parts(parts: np.ndarray, num_nodes: int, what: str) -> np.ndarray:
+    """What a partition must be wherever it comes from (`what` names the file, or the computed one): int32 [V] with values
+    0 .. P - 1 and no part empty, or a ValueError."""
     if parts.dtype != np.int32 or parts.shape != (num_nodes,):
-        raise ValueError("subgraph_batches: parts_path %r must hold an int32 array of shape (%d,), one part per node; it holds %s %r"
-                         % (path, num_nodes, parts.dtype, parts.shape))
+        raise ValueError("subgraph_batches: %s must hold an int32 array of shape (%d,), one part per node; it holds %s %r"
+                         % (what, num_nodes, parts.dtype, parts.shape))
     if num_nodes == 0 or parts.min() < 0:
-        raise ValueError("subgraph_batches: parts_path %r holds a negative part or no node at all" % (path,))
+        raise ValueError("subgraph_batches: %s holds a negative part or no node at all" % what)
     sizes = np.bincount(parts)
     if (sizes == 0).any():
-        raise ValueError("subgraph_batches: parts_path %r: the parts must be 0 .. P - 1 with none empty; of 0 .. %d, part %d has no node"
-                         % (path, len(sizes) - 1, int(np.flatnonzero(sizes == 0)[0])))
+        raise ValueError("subgraph_batches: %s: the parts must be 0 .. P - 1 with none empty; of 0 .. %d, part %d has no node"
+                         % (what, len(sizes) - 1, int(np.flatnonzero(sizes == 0)[0])))
     return parts
 
 
-def sampler_plan(subgraph: Dict, fold_mask, adjacency_lists, num_nodes: int) -> SamplerPlan:
+def sampler_plan(subgraph: Dict, fold_mask, adjacency_lists, num_nodes: int, partition=None) -> SamplerPlan:
     """The plan of a parsed `subgraph_batches` over one fold: "node" takes the in-degrees from the fold's adjacency lists here, once;
-    "parts" reads and validates its file here (load_parts)."""
+    "parts" reads and validates its file here (load_parts), or under the key "partition" takes `partition`() -> the computed int32
+    [V] host array (graph_partition.partition_graph of the TRAIN state's device RelGraph: the caller holds that graph) through the
+    same validation."""
     sampler, V = subgraph.get("sampler", "walk"), int(num_nodes)
     plan = SamplerPlan(sampler, int(subgraph["seed"]) & 0xffffffff, np.asarray(fold_mask),
                        subgraph["parts_per_batch" if sampler == "parts" else "roots_per_batch"], V)
@@ -358,7 +376,13 @@ def sampler_plan(subgraph: Dict, fold_mask, adjacency_lists, num_nodes: int) -> 
             raise ValueError('subgraph_batches: "sampler": "node" draws a by-target entry; the graph has none')
         plan = plan._replace(entry_ends=np.cumsum(in_degree))
     if sampler == "parts":
-        parts = load_parts(subgraph["parts_path"], V)
+        if "partition" in subgraph:
+            if partition is None:
+                raise ValueError('subgraph_batches: partition: the plan of a computed partition needs the device graph '
+                                 '(SingleGraphBatches.subgraph_plan computes it from the TRAIN state)')
+            parts = validated_parts(np.ascontiguousarray(partition()), V, "partition (the computed one)")
+        else:
+            parts = load_parts(subgraph["parts_path"], V)
         order = np.argsort(parts, kind="stable").astype(np.int32)           # (a part's nodes ascending)
         plan = plan._replace(parts=parts, part_nodes=np.split(order, np.cumsum(np.bincount(parts))[:-1]))
     return plan
