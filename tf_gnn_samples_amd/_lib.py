@@ -311,6 +311,16 @@ INTERNAL["graph_partition.h"] = {
                                              _c_i64, _c_i32, _ptr, _ptr]),
 }
 
+# csrc/level_plan.h (the level bucketings of a hop-ordered sampled batch derived from its union graph's: tasks/neighbour_sampling.py)
+INTERNAL["level_plan.h"] = {
+    "relgnn_level_plan_max_levels": (_c_i32, []),
+    "relgnn_level_plan_desc_stride": (_c_i64, [_c_i32]),
+    "relgnn_level_plan_tile": (_c_i64, []),
+    "relgnn_level_plan_workspace_bytes": (ctypes.c_size_t, [_c_i64, _c_i32]),
+    "relgnn_level_plan": (ctypes.c_int, [_ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _c_i64, _c_i32, _c_i64, _ptr, _c_i32, _c_i64,
+                                         _c_i64, _ptr, _c_i64, _ptr, ctypes.c_size_t, _ptr]),
+}
+
 _lib = None
 
 

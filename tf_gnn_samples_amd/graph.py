@@ -151,6 +151,7 @@ class RelGraph:
         self.adjacency_lists = adj
         self.L = L = len(adj)
         self.V = V = int(num_nodes)
+        self.num_targets = V
         self.edge_counts = [int(a.shape[0]) for a in adj]
         self.M = M = sum(self.edge_counts)
         self.device = dev
@@ -196,19 +197,24 @@ class RelGraph:
             if len(_PENDING_CHECKS) > 4096:
                 check_pending_graph_errors()
 
+    # num_targets: every message's target is among the first num_targets nodes (V for every graph but a level of a sampled batch
+    # under the citation task's "blocks": tasks/neighbour_sampling.py).  A layer route MAY then compute those rows only and return
+    # [num_targets, D] (ops/rgcn.py does); every other route ignores the attribute and returns V rows.
+
     # index arrays / adjacency lists a producer may leave out (tasks/resident.py lean assembly) and fill on first use
     _LAZY_ARRAYS = ("perm_t", "col_t", "inv_perm_t", "perm_s", "frow_s", "pos_t_of_s")
 
     @classmethod
     def from_arrays(cls, adjacency_lists, num_nodes: int, *, rowptr_t, rowptr_s, tgt_s, perm_t=None, col_t=None,
                     inv_perm_t=None, perm_s=None, frow_s=None, pos_t_of_s=None, edge_counts=None, complete=None,
-                    device=None) -> "RelGraph":
+                    device=None, num_targets=None) -> "RelGraph":
         """A RelGraph whose bucketing was produced elsewhere (tasks/resident.py: slices of a fold-level bucketing
         re-based by relgnn_plan_assemble).  The arrays must be what __init__ would compute; the node-id range check is
         the producer's job.
         Lean form: the six _LAZY_ARRAYS (and `adjacency_lists`, then give `edge_counts`) may be None when `complete` is a
         callable returning a dict with them ({"adjacency_lists": [...], "perm_t": ..., ...}); it runs on the first read
-        of any of them (the sum / mean / sqrt_n layers of the RGCN / GGNN path never do)."""
+        of any of them (the sum / mean / sqrt_n layers of the RGCN / GGNN path never do).
+        num_targets: see RelGraph.num_targets (None: num_nodes)."""
         self = cls.__new__(cls)
         lazy = {k: v for k, v in dict(perm_t=perm_t, col_t=col_t, inv_perm_t=inv_perm_t, perm_s=perm_s, frow_s=frow_s,
                                       pos_t_of_s=pos_t_of_s).items()}
@@ -223,6 +229,9 @@ class RelGraph:
             raise ValueError("from_arrays: edge_counts is required when adjacency_lists is deferred")
         self.L = L = len(edge_counts)
         self.V = V = int(num_nodes)
+        self.num_targets = V if num_targets is None else int(num_targets)
+        if not 0 <= self.num_targets <= V:
+            raise ValueError("from_arrays: num_targets %d outside [0, %d]" % (self.num_targets, V))
         self.edge_counts = [int(e) for e in edge_counts]
         self.M = M = sum(self.edge_counts)
         self.device = dev = rowptr_t.device

@@ -10,7 +10,7 @@ from ..config import settings as _cfg
 from ..graph import split_plan_of
 from ..handover import handover_word
 from ..weight_grad_stream import fork
-from .segment import _mode_factor, _raw_sum_gradient, _seg_reduce_raw, aggregation_mode_id, rowmax_supported
+from .segment import ROUTES, _mode_factor, _raw_sum_gradient, _seg_reduce_raw, aggregation_mode_id, rowmax_supported
 
 
 def aggregate_acc64() -> bool:
@@ -48,6 +48,13 @@ def _pair_products(X, rowptr, stride, V, k, n, kernels, kind) -> bool:
             and DN.weight_image_ok(list(kernels), DN.WEIGHT_NN if kind == "nn" else DN.WEIGHT_NT))
 
 
+def _target_rows(graph) -> int:
+    """The rows aggregate_then_transform computes for this graph: its num_targets (graph.RelGraph; V for every graph but a level of
+    a "blocks" batch)."""
+    T = int(getattr(graph, "num_targets", graph.V))
+    return T if 0 <= T < graph.V else graph.V
+
+
 def _fused_layer_ok(H, graph, w, kernels) -> bool:
     """relgnn_rgcn_fused_fwd applies: switch on, exact-split limb route, 256 -> 256, no hub plan on the by-target buckets."""
     if _cfg.rgcn_fused != "1" or not _cfg.limb_gemm or aggregate_acc64():
@@ -78,7 +85,14 @@ class _AggregateThenTransform(torch.autograd.Function):
     L2 of its XCD) instead of the L-times larger table of transformed states, and the GEMM gets K = L*Din.  Measured on
     MI355X, C2, one layer forward: 86.6 + 107.5 us vs 120.8 + 107.4 us (scripts/exp_agg_first.py).
     Backward: dH through the by-source buckets exactly as before (gather dOut rows, GEMM with the stacked W_l^T),
-    dW_l = A_l^T @ dOut from the saved aggregated rows."""
+    dW_l = A_l^T @ dOut from the saved aggregated rows.
+
+    Target rows only: a graph whose messages all arrive among its first graph.num_targets nodes (a level of a sampled batch under
+    the citation task's "blocks") gets bucket sums, a product, `out` and a weight gradient over those T rows alone: the by-target
+    bucketing of rows [0, T) is a prefix of the arrays, so the same gather runs with num_out = T * L on the same rowptr_t object (a
+    hub's SplitPlan stays attached to it).  The by-source gather and the input-gradient product stay over all V sources and read
+    dOut [T, Dout]: no by-source entry names a target >= T.  The fused kernel and the RELGNN_LIMB=pair route (per-bucket magnitudes
+    over V * L rows) keep all V rows; the caller cuts what it gets (ROUTES["rgcn_rows"] says which ran last)."""
 
     @staticmethod
     def forward(ctx, H, graph, w, mode: int, act: int, act_name, h_act: int, *kernels):
@@ -91,15 +105,21 @@ class _AggregateThenTransform(torch.autograd.Function):
         if _pair_products(H, graph.rowptr_t, 1, V, L * d_in, d_out, kernels, "nn"):
             amax = torch.empty(V * L, dtype=torch.float32, device=H.device)
         want_w = any(ctx.needs_input_grad[7:])
+        fused = amax is None and _fused_layer_ok(H, graph, w, kernels)
+        # the rows computed: the graph's targets alone, unless a route that needs the square graph serves this call
+        T = V if (amax is not None or fused) else _target_rows(graph)
+        ROUTES["rgcn_rows"] = "targets" if T < V else "all"
         f = _mode_factor(graph, mode)
+        if f is not None and T < V:
+            f = f[:T]
         fused_relu = act == _lib.ACT_RELU and f is None       # sum aggregation: ReLU rides in the product's epilogue
-        if amax is None and _fused_layer_ok(H, graph, w, kernels):
+        if fused:
             # one kernel: the gather waves hand the bucket sums to the matrix waves through LDS (csrc/rgcn_fused.hip); the sums are
             # also stored as fp32 when the weight gradient will read them.  Same bits as the two launches below.
             agg, out = _rgcn_fused(H, graph, w, kernels, fused_relu, want_w)
         else:
-            agg = _seg_reduce_raw(_lib.AGG_SUM, H, graph.rowptr_t, 1, graph.src_t, w, V * L,
-                                  acc64=aggregate_acc64(), rowmax=amax).view(V, L * d_in)
+            agg = _seg_reduce_raw(_lib.AGG_SUM, H, graph.rowptr_t, 1, graph.src_t, w, T * L,
+                                  acc64=aggregate_acc64(), rowmax=amax).view(T, L * d_in)
             out = DN.grouped_nn_gemm(agg, kernels, relu=fused_relu, xmax=amax, xgroups=L)
         if f is not None:
             out.mul_(f.unsqueeze(1))
@@ -110,7 +130,7 @@ class _AggregateThenTransform(torch.autograd.Function):
             out.tanh_()
         elif act != _lib.ACT_LINEAR:
             out = apply_activation(get_activation(act_name), out)
-        ctx.graph, ctx.w, ctx.mode, ctx.act, ctx.L = graph, w, mode, act, L
+        ctx.graph, ctx.w, ctx.mode, ctx.act, ctx.L, ctx.T = graph, w, mode, act, L, T
         # h_act: H is itself the output of that activation and its gradient factor may ride in the input-gradient product's
         # epilogue (dense.fusable_activation_of; needs d_in == the product's N, i.e. H's own rows as the epilogue operand)
         ctx.h_act = h_act if ctx.needs_input_grad[0] else 0
@@ -124,7 +144,9 @@ class _AggregateThenTransform(torch.autograd.Function):
         graph, w, mode, act, L = ctx.graph, ctx.w, ctx.mode, ctx.act, ctx.L
         agg, out, amax, H_in, *kernels = ctx.saved_tensors
         d_in, d_out = kernels[0].shape
-        V = graph.V
+        V, T = graph.V, ctx.T
+        if gout.shape[0] != T:
+            raise ValueError("aggregate_then_transform: the gradient has %d rows, the layer gave %d" % (gout.shape[0], T))
         # g * act'(out) — unless the consumer of `out` folded that factor into the product that made this gradient (the tag is on
         # the tensor object: look before anything copies it)
         premasked = act != _lib.ACT_LINEAR and DN.is_premasked(gout, out, act)
@@ -135,7 +157,7 @@ class _AggregateThenTransform(torch.autograd.Function):
         want_w = any(need)
 
         def weight_side():
-            gsc = _raw_sum_gradient(gout, graph, mode)  # agg holds the raw sums: the factor multiplies dOut
+            gsc = _raw_sum_gradient(gout, graph, mode, T)  # agg holds the raw sums: the factor multiplies dOut
             gW = _weight_gradient(agg, gsc, amax, L)    # dW_l = A_l^T @ dOut: row block l of [L*Din, Dout]
             return tuple(gW[l * d_in:(l + 1) * d_in] if need[l] else None for l in range(L))
 

@@ -210,7 +210,8 @@ def unsorted_segment_max(data, segment_ids, num_segments):
 
 
 # ---- CSR rows times a row table: sparse node features through the input projection (csrc/csr_project.hip) --------------------
-ROUTES = {"csr_project": None}       # which implementation the last csr_rows_project took: "hip", "composition" or "dense"
+ROUTES = {"csr_project": None,       # which implementation the last csr_rows_project took: "hip", "composition" or "dense"
+          "rgcn_rows": None}         # the rows the last aggregate_then_transform computed: "targets" (num_targets of them) or "all"
 _WARNED = set()
 
 
@@ -322,9 +323,12 @@ def _mode_factor(graph, mode: int):
     return (1.0 / n) if mode == _lib.AGG_MEAN else (1.0 / torch.sqrt(n))
 
 
-def _raw_sum_gradient(gout, graph, mode: int):
-    """The gradient of the raw bucket sums from that of the finalised aggregate: gout * _mode_factor per row, contiguous."""
+def _raw_sum_gradient(gout, graph, mode: int, rows: int = None):
+    """The gradient of the raw bucket sums from that of the finalised aggregate: gout * _mode_factor per row, contiguous.  rows: gout
+    holds the first `rows` nodes only (ops/rgcn.py, target rows only)."""
     f = _mode_factor(graph, mode)
+    if f is not None and rows is not None and rows < f.shape[0]:
+        f = f[:rows]
     return (gout * f.unsqueeze(1)).contiguous() if f is not None else gout.contiguous()
 
 

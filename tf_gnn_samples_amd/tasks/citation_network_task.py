@@ -14,7 +14,7 @@ SparseRows, which its input projection takes through ops.csr_rows_project (csrc/
 
 The batching modes live in tasks/single_graph_batches.py (`self.batches`), which describes every parameter and key:
   `sampled_batches` {"fanouts", "seeds_per_batch", "seed"; optional "sparse_features", "sparse_update", "sparse_gradient", "layered",
-      "evaluation"}: TRAIN epochs of neighbour-sampled receptive fields; "evaluation": VALIDATION, TEST and predict(nodes=...) on them too.
+      "evaluation", "blocks"}: TRAIN epochs of neighbour-sampled receptive fields; "evaluation": VALIDATION, TEST and predict(nodes=...) on them too.
   `subgraph_batches` {"roots_per_batch", "walk_length", "seed"; optional "sparse_features", "normalisation", "sampler"}: TRAIN epochs of
       random-walk induced subgraphs; "normalisation": GraphSAINT's loss and aggregation weights; "sampler": the node set from a node, edge
       or partition sampler instead of walks.
@@ -272,6 +272,12 @@ class Citation_Network_Task(Sparse_Graph_Task):
         """Does `sampled_batches` ask for hop-ordered batches whose layers run on the hops they need?"""
         sampled = self.sampled_batches
         return bool(sampled is not None and sampled.get("layered", False))
+
+    @property
+    def blocks(self) -> bool:
+        """Does `sampled_batches` ask for level graphs derived from the union graph's bucketing, target rows only?"""
+        sampled = self.sampled_batches
+        return bool(sampled is not None and sampled.get("blocks", False))
 
     def single_graph_data_parallel(self) -> bool:
         """Does `sampled_batches` or `subgraph_batches` carry "data_parallel": true?"""

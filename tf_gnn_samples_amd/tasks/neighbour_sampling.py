@@ -14,6 +14,8 @@ and sample_by_hop() share the hops, the read-back and the loop behind it; they d
 NeighbourSampler.sample_by_hop() gives the same subgraph numbered by hop (include/relgnn_layered_sampling.h) with the same round
 trips; HopSubgraph.device_batch(layered=True) puts one LevelGraph per layer beside it, so that a model with as many layers as hops
 runs each layer on the hops it needs (the citation task's `sampled_batches` key "layered"; models/sparse_graph_model.py).
+With derived=True (the key "blocks") the levels bring their bucketings, derived on the device from the union graph's one
+(derived_level_graphs; csrc/level_plan.hip, csrc/level_plan.h), and say which of their rows are targets (RelGraph.num_targets).
 """
 import ctypes
 from typing import Dict, List, NamedTuple, Optional, Sequence
@@ -22,7 +24,7 @@ import numpy as np
 import torch
 
 from .. import _lib
-from ..graph import RelGraph, as_rel_graph
+from ..graph import RelGraph, _upload, as_rel_graph
 from .sparse_features import PhaseTrace, SparseRows
 from .sparse_graph_task import DeviceBatch
 
@@ -120,7 +122,8 @@ class LevelGraph(NamedTuple):
     num_sources: int
     num_targets: int
     type_to_num_incoming_edges: torch.Tensor    # float32 [L, num_sources]: the sampled in-degrees of the targets, 0 behind them
-    graph: Optional[RelGraph] = None            # the level's bucketing where the batch brings it along (evaluation batches); the
+    graph: Optional[RelGraph] = None            # the level's bucketing where the batch brings it along (evaluation batches, and every
+    #                                             batch under "blocks", whose graphs also say graph.num_targets == num_targets); the
     #                                             model buckets adjacency_lists itself otherwise
 
 
@@ -137,12 +140,15 @@ class HopSubgraph(NamedTuple):
     hop_nodes: List[int]                        # [n_0, ..., n_H], cumulative
     hop_edges: List[List[int]]                  # per type [E_{l,0}, ..., E_{l,H-1}]: the type-l edges emitted by hops 0 .. h
 
-    def level_graphs(self, bucketed: bool = False, route_like: Optional[RelGraph] = None) -> List[LevelGraph]:
+    def level_graphs(self, bucketed: bool = False, route_like: Optional[RelGraph] = None, derived: bool = False) -> List[LevelGraph]:
         """One LevelGraph per layer of a model with as many layers as hops; level 1 is the union graph.  bucketed: every level
         carries its RelGraph (the sampler's ids are in range: nothing is validated), routed as `route_like` routes its reductions
-        (RelGraph.route_like) when one is given."""
+        (RelGraph.route_like) when one is given.  derived (the citation task's `"blocks": true`; implies bucketed): the union graph
+        is bucketed once and every smaller level's arrays are derived from its (derived_level_graphs: no further sort), and every
+        graph says which of its rows are targets (RelGraph.num_targets), so that a layer may compute those alone."""
         H = len(self.hop_nodes) - 1
         degrees, levels = self.type_to_num_incoming_edges, []
+        graphs = derived_level_graphs(self, route_like) if derived else None
         for layer in range(1, H + 1):
             sources, targets = self.hop_nodes[H - layer + 1], self.hop_nodes[H - layer]
             adjacency = [a[:edges[H - layer]] for a, edges in zip(self.adjacency_lists, self.hop_edges)]
@@ -152,7 +158,9 @@ class HopSubgraph(NamedTuple):
                 table = torch.zeros((degrees.shape[0], sources), dtype=degrees.dtype, device=degrees.device)
                 table[:, :targets] = degrees[:, :targets]
             graph = None
-            if bucketed:
+            if derived:
+                graph = graphs[layer - 1]
+            elif bucketed:
                 graph = RelGraph(adjacency, sources, validate=False)
                 if route_like is not None:
                     graph.route_like(route_like)
@@ -161,23 +169,92 @@ class HopSubgraph(NamedTuple):
 
     def device_batch(self, features, labels: torch.Tensor, fold_mask: torch.Tensor, out_keep: float = 1.0,
                      named_rows: bool = False, layered: bool = True, bucketed: bool = False,
-                     route_like: Optional[RelGraph] = None) -> DeviceBatch:
+                     route_like: Optional[RelGraph] = None, derived: bool = False) -> DeviceBatch:
         """layered=False: the union batch in hop order, through SampledSubgraph.device_batch.  layered=True: feature rows of all n
         nodes, labels and mask of the n_0 seeds only (mask = fold_mask[seeds]: num_masked and num_correct mean what they did), and
         extra['layer_graphs'] = level_graphs(), which models/sparse_graph_model.py runs layer by layer.  bucketed / route_like
-        (layered only; an evaluation batch): the levels bring their bucketing, level 1's is the batch's own `graph`."""
+        (layered only; an evaluation batch): the levels bring their bucketing, level 1's is the batch's own `graph`.  derived (layered
+        only; `"blocks": true`): the same, with the levels' bucketings derived from the union graph's (level_graphs)."""
         union = SampledSubgraph(self.nodes, self.adjacency_lists, self.type_to_num_incoming_edges, self.seed_mask, self.num_nodes,
                                 self.num_edges)
         if not layered:
             return union.device_batch(features, labels, fold_mask, out_keep, named_rows=named_rows)
         seeds = self.nodes[:self.hop_nodes[0]].long()
         rows, extra = _batch_rows(self, features, labels.index_select(0, seeds), fold_mask.index_select(0, seeds), out_keep, named_rows,
-                                  layer_graphs=self.level_graphs(bucketed, route_like))
+                                  layer_graphs=self.level_graphs(bucketed, route_like, derived))
         batch = DeviceBatch.from_tensors(1, self.num_nodes, self.num_edges, rows, self.adjacency_lists,
                                          self.type_to_num_incoming_edges, extra=extra)
-        if bucketed:
+        if bucketed or derived:
             batch.graph = extra['layer_graphs'][0].graph
         return batch
+
+
+# ---- level bucketings derived from the union graph's (csrc/level_plan.hip, csrc/level_plan.h) ------------------------------------------
+LEVEL_PLAN_FIXED = 11                 # a record of relgnn_level_plan's `desc`: T, S, P, eight offsets, then delta[L] and off'[L + 1]
+LEVEL_PLAN_ARRAYS = ("rowptr_t", "perm_t", "inv_perm_t", "rowptr_s", "tgt_s", "frow_s", "pos_t_of_s", "perm_s")
+
+
+def level_plan_layout(hop_nodes, hop_edges, num_edge_types: int):
+    """What relgnn_level_plan is told about the levels d = 0 .. H - 2 of a hop-ordered subgraph (level H - 1 is the union graph), from
+    the sizes the sampler read back: -> (desc int64 [H - 1, 12 + 2 L], the int32 length of the output arena, the largest S_d L + 1,
+    the largest P_d).  Host arithmetic only.  Every array starts on a multiple of four entries."""
+    L, H = int(num_edge_types), len(hop_nodes) - 1
+    desc = np.zeros((max(H - 1, 0), LEVEL_PLAN_FIXED + 2 * L + 1), dtype=np.int64)
+    union_offsets = np.concatenate([[0], np.cumsum([int(edges[H - 1]) for edges in hop_edges])]).astype(np.int64)
+    at, max_rows, max_messages = 0, 0, 0
+    for d in range(H - 1):
+        targets, sources = int(hop_nodes[d]), int(hop_nodes[d + 1])
+        offsets = np.concatenate([[0], np.cumsum([int(edges[d]) for edges in hop_edges])]).astype(np.int64)
+        messages, rows = int(offsets[-1]), sources * L + 1
+        desc[d, :3] = (targets, sources, messages)
+        for k, name in enumerate(LEVEL_PLAN_ARRAYS):
+            desc[d, 3 + k] = at
+            at += -(-(rows if name.startswith("rowptr") else messages) // 4) * 4
+        desc[d, LEVEL_PLAN_FIXED:LEVEL_PLAN_FIXED + L] = union_offsets[:L] - offsets[:L]
+        desc[d, LEVEL_PLAN_FIXED + L:] = offsets
+        max_rows, max_messages = max(max_rows, rows), max(max_messages, messages)
+    if at >= 2 ** 31 - 1:
+        raise ValueError("the level graphs are too large for int32 indices")
+    return desc, at, max_rows, max_messages
+
+
+def derived_level_graphs(sub: "HopSubgraph", route_like: Optional[RelGraph] = None) -> List[RelGraph]:
+    """The RelGraph of every layer's level, layer 1 (the union graph) first: ONE bucketing (the ordinary constructor over the union
+    graph: the batch's two sorts) and one relgnn_level_plan call that derives the arrays of every smaller level from it, on the
+    current stream, with no read-back (the sizes come from hop_nodes / hop_edges).  A derived level is a RelGraph.from_arrays graph
+    over its num_sources nodes whose arrays are views of one arena, whose col_t is a view of the union's and whose adjacency lists are
+    the prefix views; its num_targets is the level's.  The union graph's is n_{H-1}: its leaves have no incoming edge."""
+    H, L = len(sub.hop_nodes) - 1, len(sub.adjacency_lists)
+    union = RelGraph(sub.adjacency_lists, sub.num_nodes, validate=False)
+    union.num_targets = int(sub.hop_nodes[H - 1])
+    graphs = [union]
+    if H > 1:
+        lib = _lib.load_library()
+        if H - 1 > lib.relgnn_level_plan_max_levels() or lib.relgnn_level_plan_desc_stride(L) != LEVEL_PLAN_FIXED + 2 * L + 1:
+            raise _lib.RelGnnLibraryError("relgnn_level_plan does not take %d levels of %d edge types" % (H - 1, L))
+        desc, length, max_rows, max_messages = level_plan_layout(sub.hop_nodes, sub.hop_edges, L)
+        dev = union.device
+        arena = torch.empty(length, dtype=torch.int32, device=dev)
+        ws_bytes = lib.relgnn_level_plan_workspace_bytes(union.M, H - 1)
+        ws = _lib.scratch(ws_bytes, dev)
+        M = union.M
+        _lib.launch("relgnn_level_plan", _lib.ptr(union.rowptr_t), *[_lib.ptr(getattr(union, k)) if M else None
+                                                                      for k in ("col_t", "perm_t", "inv_perm_t")],
+                    _lib.ptr(union.rowptr_s), *[_lib.ptr(getattr(union, k)) if M else None
+                                                for k in ("tgt_s", "frow_s", "pos_t_of_s", "perm_s")],
+                    union.V, L, M, _lib.ptr(_upload(desc, dev)), H - 1, max_rows, max_messages, _lib.ptr(arena), length,
+                    _lib.ptr(ws) if M else None, ws_bytes)
+        for d in range(H - 2, -1, -1):                                 # layer 2 runs on level H - 2, ..., layer H on level 0
+            targets, sources, messages = (int(x) for x in desc[d, :3])
+            rows = sources * L + 1
+            arrays = {name: arena[int(desc[d, 3 + k]):int(desc[d, 3 + k]) + (rows if name.startswith("rowptr") else messages)]
+                      for k, name in enumerate(LEVEL_PLAN_ARRAYS)}
+            adjacency = [a[:edges[d]] for a, edges in zip(sub.adjacency_lists, sub.hop_edges)]
+            graphs.append(RelGraph.from_arrays(adjacency, sources, col_t=union.col_t[:messages], num_targets=targets, **arrays))
+    if route_like is not None:
+        for graph in graphs:
+            graph.route_like(route_like)
+    return graphs
 
 
 class StampedNodeSet(PhaseTrace):
@@ -367,15 +444,17 @@ def parse_sampled_batches(value) -> Optional[Dict]:
     runs on the hops it needs) and "data_parallel" (a bool: train(group=...) hands the batches of an epoch out to the ranks; not
     together with "sparse_update" / "sparse_gradient") are carried only when given, and so is "evaluation" ({"fanouts": [k_1, ..., k_H],
     "seeds_per_batch": B, "keep": bool}, "keep" optional: VALIDATION, TEST and predict(nodes=...) run on sampled receptive fields,
-    parse_evaluation)."""
+    parse_evaluation) and "blocks" (a bool, behind "evaluation" in the parsed dict; needs "layered": true or "evaluation": the level
+    graphs of a batch are derived from its union graph's bucketing and say which rows are targets, derived_level_graphs)."""
     if value is None:
         return None
     if not isinstance(value, dict) or not {"fanouts", "seeds_per_batch"} <= set(value) \
             or unknown_keys(value, ("fanouts", "seeds_per_batch", "seed", "sparse_features", "sparse_update", "sparse_gradient", "layered",
-                                    "data_parallel", "evaluation")):
+                                    "data_parallel", "evaluation", "blocks")):
         raise ValueError('sampled_batches must be {"fanouts": [k_1, ..., k_H], "seeds_per_batch": B, "seed": s, "sparse_features": bool, '
                          '"sparse_update": bool, "sparse_gradient": bool, "layered": bool, "data_parallel": bool, "evaluation": '
-                         '{"fanouts": [...], "seeds_per_batch": B, "keep": bool}}, the last seven optional, got %r' % (value,))
+                         '{"fanouts": [...], "seeds_per_batch": B, "keep": bool}, "blocks": bool}, the last eight optional, got %r'
+                         % (value,))
     per_batch = integer_at_least(value["seeds_per_batch"], 1, "sampled_batches: seeds_per_batch must be a positive integer, got %r")
     parsed = {"fanouts": check_fanouts(value["fanouts"]), "seeds_per_batch": per_batch, "seed": int(value.get("seed", 0))}
     parse_bool_keys("sampled_batches", value, parsed, ("sparse_features", "sparse_update", "sparse_gradient", "layered", "data_parallel"), {
@@ -388,6 +467,10 @@ def parse_sampled_batches(value) -> Optional[Dict]:
                          % " and ".join('"%s": true' % key for key in by_rows))
     if "evaluation" in value:
         parsed["evaluation"] = parse_evaluation(value["evaluation"])
+    parse_bool_keys("sampled_batches", value, parsed, ("blocks",))
+    if parsed.get("blocks", False) and not (parsed.get("layered", False) or "evaluation" in parsed):
+        raise ValueError('sampled_batches: "blocks": true requires "layered": true or an "evaluation" key: only a batch that is run '
+                         'level by level has level graphs to derive and target rows to keep')
     return parsed
 
 

@@ -104,6 +104,22 @@ that names both keys): their batches are not anchored at TRAIN nodes, a batch ma
 defined for it (0, with zero gradients).  The pre-sampling runs the same plan for the epochs 0x80000000 + e
 (SubgraphSampler.presample_lists), N = E * the epoch's batch count.
 
+One more optional key of `sampled_batches`, "blocks": true (needs "layered": true or the "evaluation" key, a ValueError that names all
+three otherwise; it composes with every other key; absent by default; `subgraph_batches` has no levels and does not take it): what
+sampled GNN training calls blocks, or message-flow graphs.  A batch that is run level by level buckets ONLY its union graph (the
+ordinary RelGraph constructor: the batch's two sorts); the arrays of every smaller level are derived from the union's on the device
+in one launch sequence (csrc/level_plan.hip, csrc/level_plan.h, package-internal; neighbour_sampling.derived_level_graphs): the
+by-target arrays of a level are a prefix of the union's, its by-source arrays the stable compaction of the union's entries whose
+target is among the level's, and no level is sorted.  Every level's graph says which of its rows are targets (RelGraph.num_targets),
+and the default RGCN route (ops.aggregate_then_transform) then gathers, multiplies and forms its weight gradient over those rows
+only; every other layer function and route ignores the attribute, computes all rows of the level and is cut by the driver as before.
+With "layered": true the TRAIN batches bring every level's derived graph and the model buckets nothing; with the "evaluation" key the
+evaluation batches and predict(nodes=...) batches take derived levels in the place of H constructor calls, routed as before
+(RelGraph.route_like), and "keep" then holds one col_t per batch (a level's is a view of the union's; its other arrays lie in one
+arena).  The same arrays run through the same
+kernels: GGNN, RGAT and GNN-FiLM give the bits they gave; RGCN gives the forward's bits, and weight gradients that differ by the
+rounding of a sum over fewer rows.
+
 Both parameters take one more optional key, "data_parallel": true (a ValueError together with "sparse_update" / "sparse_gradient"; it
 composes with every other key): train(group=...) and test(group=...) of a process group of W > 1 ranks are no longer refused
 (models/data_parallel.py).  Every rank holds the whole graph; global batch j of a TRAIN epoch goes to rank
@@ -324,9 +340,14 @@ class SingleGraphBatches:
             draw, self.draw = self.draw, self.draw + 1
             if j % world != rank:
                 continue
+            named_rows = sampled.get("sparse_gradient", False)
+            if sampled.get("layered", False) and sampled.get("blocks", False):
+                # every level's bucketing travels with the batch, derived from the union graph's: the model buckets nothing
+                yield state.sampler.sample_by_hop(seeds, draw).device_batch(state.features, state.labels, state.mask, keep,
+                                                                            named_rows=named_rows, derived=True)
+                continue
             sample = state.sampler.sample_by_hop if sampled.get("layered", False) else state.sampler.sample
-            yield sample(seeds, draw).device_batch(state.features, state.labels, state.mask, keep,
-                                                   named_rows=sampled.get("sparse_gradient", False))
+            yield sample(seeds, draw).device_batch(state.features, state.labels, state.mask, keep, named_rows=named_rows)
 
     def subgraph_batches(self, fold, rank: int = 0, world: int = 1):
         """The subgraph batches of one TRAIN epoch (subgraph_sampling.epoch_node_lists: ceil(n_train / R) of them, ceil(P / q) for
@@ -361,8 +382,11 @@ class SingleGraphBatches:
         is what a resident full-graph batch of the same fold does (tasks/resident.py splits a fold's hubs per batch); otherwise
         every bucket keeps one wave, as the full graph bucketed by the model itself does (validate="deferred")."""
         sub = state.sampler.sample_by_hop(seeds, draw)
+        blocks = (self.task.sampled_batches or {}).get("blocks", False)       # (needs the "evaluation" key here: predict(nodes=...)
+        #                                                                        without it stays on H constructor calls)
         return sub.device_batch(state.features, state.labels, state.mask, 1.0, layered=True, bucketed=True,
-                                route_like=state.sampler.graph if full_graph_route else None)
+                                route_like=state.sampler.graph if full_graph_route else None,
+                                derived=bool(blocks and self.task.evaluation is not None))
 
     def evaluation_batches(self, data, data_fold: DataFold, full_graph_route: bool):
         """ceil(n_fold / B) batches: one VALIDATION or TEST epoch under the "evaluation" key.  Batch i holds the fold's masked nodes
@@ -378,7 +402,7 @@ class SingleGraphBatches:
         evaluation, device = self.task.evaluation, self.bound_device()
         fold = next(iter(data))
         key = (str(device), data_fold.value, bool(full_graph_route), tuple(evaluation["fanouts"]), evaluation["seeds_per_batch"],
-               int(rank), int(world))
+               int(rank), int(world), bool(self.task.sampled_batches.get("blocks", False)))
         if evaluation.get("keep", False):
             held = self.kept_evaluation.get((fold.labels,), key)
             if held is not None:
