@@ -321,6 +321,17 @@ INTERNAL["level_plan.h"] = {
                                          _c_i64, _ptr, _c_i64, _ptr, ctypes.c_size_t, _ptr]),
 }
 
+# csrc/window_block.h (the block of a window of target rows, cut from the full graph's by-target bucketing: tasks/layerwise.py)
+INTERNAL["window_block.h"] = {
+    "relgnn_window_block_supported": (ctypes.c_int, [_c_i64, _c_i32]),
+    "relgnn_window_block_tile": (_c_i64, []),
+    "relgnn_window_block_workspace_bytes": (ctypes.c_size_t, [_c_i64, _c_i32]),
+    "relgnn_window_block_count": (ctypes.c_int, [_ptr, _ptr, _c_i64, _c_i32, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _ptr, _ptr, _ptr, _ptr,
+                                                 _ptr, ctypes.c_size_t, _ptr]),
+    "relgnn_window_block_emit": (ctypes.c_int, [_ptr, _ptr, _c_i64, _c_i32, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _ptr, _ptr, _ptr, _c_i64,
+                                                _ptr, _ptr, _c_i64, _ptr, _c_i64, _ptr, _c_i64, _ptr]),
+}
+
 _lib = None
 
 

@@ -26,6 +26,7 @@ from ..dense import capture_image_cache, dense_act, vouch_sole_consumer, weights
 from ..graph import as_rel_graph, check_pending_graph_errors
 from ..tasks import DataFold, DeviceBatch, Sparse_Graph_Task
 from ..tasks.batcher import NativeBatcher
+from ..tasks.layerwise import target_windows, window_blocker
 from ..tasks.resident import ResidentDataset
 from ..tasks.sparse_features import SparseRows
 from ..utils import get_activation, layer_norm, layer_norm_scope
@@ -277,55 +278,143 @@ class Sparse_Graph_Model(ABC):
                 self.dropout_state[2].add_(1)                  # on the device, stream-ordered: every replay of a captured step advances it
                 pass_state = self.dropout_state.clone()        # this pass's 24 bytes: read by its forward kernels and by its backward
         for layer_idx in range(p['graph_num_layers']):
-            self._layer_weights = w.scope('gnn_layer_%i' % layer_idx)
-            residual_step = layer_idx % res_every == 0
-            layer_degrees = type_to_num_incoming_edges
-            if layered:
-                level = layer_graphs[layer_idx]
-                if cur_node_representations.shape[0] != level.num_sources:
-                    raise ValueError("layer_graphs: level %d takes %d rows, the layer below it left %d"
-                                     % (layer_idx + 1, level.num_sources, cur_node_representations.shape[0]))
-                # (level 1 is the union graph: the same key, the same cached bucketing)
-                # (an evaluation batch brings every level's bucketing along, routed as the full graph's)
-                graph = as_rel_graph(level.graph if getattr(level, "graph", None) is not None else level.adjacency_lists,
-                                     level.num_sources, validate="deferred")
-                layer_degrees = level.type_to_num_incoming_edges
-                if residual_step and layer_idx > 0 and last_residual_representations.shape[0] > level.num_sources:
-                    last_residual_representations = last_residual_representations[:level.num_sources]
-            if pass_state is not None and ops.dropout_tensor_ok(cur_node_representations):
-                # csrc/dropout.hip: one kernel for the whole layer-input stage; the layer index is the Philox stream
-                if residual_step and layer_idx > 0:
-                    last_residual_representations, cur_node_representations = ops.dropout_residual(
-                        cur_node_representations, last_residual_representations, dropout_keep_prob, pass_state, layer_idx)
-                else:
-                    cur_node_representations = ops.dropout(cur_node_representations, dropout_keep_prob, pass_state, layer_idx)
-                    if residual_step:
-                        last_residual_representations = cur_node_representations
-            else:
-                if dropout_keep_prob < 1.0:
-                    cur_node_representations = torch.nn.functional.dropout(
-                        cur_node_representations, p=1.0 - dropout_keep_prob, training=True)
-                if residual_step:
-                    t = cur_node_representations
-                    if layer_idx > 0:
-                        cur_node_representations = (cur_node_representations + last_residual_representations) / 2
-                    last_residual_representations = t
-            cur_node_representations = self._apply_gnn_layer(
-                cur_node_representations, graph, layer_degrees, p['graph_num_timesteps_per_layer'])
-            if layered and level.num_targets < cur_node_representations.shape[0]:
-                cur_node_representations = cur_node_representations[:level.num_targets]      # (a view: it carries no activation tag)
-            if p['graph_inter_layer_norm']:
-                ln = self._inter_norm_name[layer_idx]
-                cur_node_representations = layer_norm(cur_node_representations,
-                                                      self._layer_weights[ln + "/gamma"], self._layer_weights[ln + "/beta"])
-            if layer_idx % p['graph_dense_between_every_num_gnn_layers'] == 0:
-                # (the layer's / the norm's output is referenced nowhere else: this Dense is its only reader)
-                cur_node_representations = dense_act(vouch_sole_consumer(cur_node_representations, not layered),
-                                                     self._layer_weights["Dense/kernel"], None, act_id,
-                                                     sole_consumer=only_the_next_layer_reads(layer_idx + 1), sole_reader=True)
-            else:
-                vouch_sole_consumer(cur_node_representations, only_the_next_layer_reads(layer_idx + 1))
+            cur_node_representations, last_residual_representations = self._layer_step(
+                layer_idx, cur_node_representations, last_residual_representations, graph, type_to_num_incoming_edges,
+                layer_graphs[layer_idx] if layered else None, dropout_keep_prob, pass_state, only_the_next_layer_reads(layer_idx + 1),
+                w, act_id)
         return vouch_sole_consumer(cur_node_representations, False)     # (a task head may read it more than once)
+
+    def _layer_step(self, layer_idx: int, cur_node_representations: torch.Tensor, last_residual_representations, graph,
+                    type_to_num_incoming_edges: torch.Tensor, level, dropout_keep_prob: float, pass_state,
+                    next_layer_reads_alone: bool, w, act_id: int):
+        """One iteration of the layer loop (:176-200): the residual average, the layer function on a graph, the cut to the level's
+        num_targets, the inter-layer norm and the Dense.  -> (the layer's output, the tensor kept for the next residual step).
+        level (a LevelGraph, or a WindowBlock of the layer-wise pass; None: the batch's own `graph` and degree table): the layer runs on
+        the level's graph and degree table over its num_sources rows.  Both compute_final_node_representations and
+        layerwise_final_node_representations run their layers through here; w is the scope "graph_model", act_id the model's
+        activation."""
+        p = self.params
+        layered = level is not None
+        self._layer_weights = w.scope('gnn_layer_%i' % layer_idx)
+        residual_step = layer_idx % p['graph_residual_connection_every_num_layers'] == 0
+        layer_degrees = type_to_num_incoming_edges
+        if layered:
+            if cur_node_representations.shape[0] != level.num_sources:
+                raise ValueError("layer_graphs: level %d takes %d rows, the layer below it left %d"
+                                 % (layer_idx + 1, level.num_sources, cur_node_representations.shape[0]))
+            # (level 1 is the union graph: the same key, the same cached bucketing)
+            # (an evaluation batch brings every level's bucketing along, routed as the full graph's)
+            graph = as_rel_graph(level.graph if getattr(level, "graph", None) is not None else level.adjacency_lists,
+                                 level.num_sources, validate="deferred")
+            layer_degrees = level.type_to_num_incoming_edges
+            if residual_step and layer_idx > 0 and last_residual_representations.shape[0] > level.num_sources:
+                last_residual_representations = last_residual_representations[:level.num_sources]
+        if pass_state is not None and ops.dropout_tensor_ok(cur_node_representations):
+            # csrc/dropout.hip: one kernel for the whole layer-input stage; the layer index is the Philox stream
+            if residual_step and layer_idx > 0:
+                last_residual_representations, cur_node_representations = ops.dropout_residual(
+                    cur_node_representations, last_residual_representations, dropout_keep_prob, pass_state, layer_idx)
+            else:
+                cur_node_representations = ops.dropout(cur_node_representations, dropout_keep_prob, pass_state, layer_idx)
+                if residual_step:
+                    last_residual_representations = cur_node_representations
+        else:
+            if dropout_keep_prob < 1.0:
+                cur_node_representations = torch.nn.functional.dropout(
+                    cur_node_representations, p=1.0 - dropout_keep_prob, training=True)
+            if residual_step:
+                t = cur_node_representations
+                if layer_idx > 0:
+                    cur_node_representations = (cur_node_representations + last_residual_representations) / 2
+                last_residual_representations = t
+        cur_node_representations = self._apply_gnn_layer(
+            cur_node_representations, graph, layer_degrees, p['graph_num_timesteps_per_layer'])
+        if layered and level.num_targets < cur_node_representations.shape[0]:
+            cur_node_representations = cur_node_representations[:level.num_targets]      # (a view: it carries no activation tag)
+        if p['graph_inter_layer_norm']:
+            ln = self._inter_norm_name[layer_idx]
+            cur_node_representations = layer_norm(cur_node_representations,
+                                                  self._layer_weights[ln + "/gamma"], self._layer_weights[ln + "/beta"])
+        if layer_idx % p['graph_dense_between_every_num_gnn_layers'] == 0:
+            # (the layer's / the norm's output is referenced nowhere else: this Dense is its only reader)
+            cur_node_representations = dense_act(vouch_sole_consumer(cur_node_representations, not layered),
+                                                 self._layer_weights["Dense/kernel"], None, act_id,
+                                                 sole_consumer=next_layer_reads_alone, sole_reader=True)
+        else:
+            vouch_sole_consumer(cur_node_representations, next_layer_reads_alone)
+        return cur_node_representations, last_residual_representations
+
+    def layerwise_final_node_representations(self, batch: DeviceBatch, rows_per_batch: int, blocks=None) -> torch.Tensor:
+        """The final node states of a full-graph batch, computed layer by layer over windows of `rows_per_batch` target rows (the
+        citation task's `layerwise_evaluation`; tasks/layerwise.py): layer l for ALL nodes from the [V, hidden] table of layer l - 1,
+        then layer l + 1.  Under torch.no_grad() and keep-probability 1.
+
+        The input projection runs over the whole graph as the full-graph path runs it; its result is table 0.  Per layer and window
+        the input rows are table[block.nodes], the layer step is _layer_step on the block's graph and degree table, and its T output
+        rows are rows [a, b) of the next table.  The residual average is row-wise: it is taken over the rows gathered from the kept
+        residual table; a residual step keeps its input table.  At most three [V, hidden] tables are alive (current, next, the last
+        residual step's input), two when no residual step lies ahead.
+        blocks (tasks/layerwise.KeptBlocks; `"keep": true`): the windows' blocks are built once per (device, B, route) and kept there;
+        None: they are built again for every layer and dropped.  A window's block is the same for every layer."""
+        p = self.params
+        if self.device.type != "cuda":
+            raise RuntimeError("layerwise_evaluation needs a model on the GPU: the window block is a HIP kernel and there is no CPU "
+                               "fallback (the model is on %s)" % self.device)
+        problem = self._layerwise_prerequisites()
+        if problem is not None:
+            raise ValueError("layerwise_evaluation requires %s" % problem)
+        num_layers, res_every = p['graph_num_layers'], p['graph_residual_connection_every_num_layers']
+        act_id = ops.activation_id(p['graph_model_activation_function'])
+        with torch.no_grad():
+            batch.wait_ready()
+            features = self.task.compute_initial_node_features(batch, self.variables.scope(""))
+            num_nodes = features.shape[0]
+            own = getattr(batch, "graph", None)
+            full = as_rel_graph(own if own is not None else batch.adjacency_lists, num_nodes, validate="deferred")
+            key = (str(full.device), int(rows_per_batch), bool(full.has_long_buckets))
+            kept = blocks.get(key) if blocks is not None else None
+
+            def window_blocks():
+                if kept is not None:
+                    return kept
+                blocker = window_blocker(full)
+                ends = blocker.boundaries(rows_per_batch)         # (the host copy of rowptr_t at the window boundaries: one read per (graph, B))
+                return (blocker.block(a, b, full, (ends[a], ends[b])) for a, b in target_windows(num_nodes, rows_per_batch))
+
+            w = self.variables.scope("graph_model")
+            table = self._project_input(features, w, act_id, False)
+            if table is features:                 # (no projection: the batch's own feature table is not ours to drop or overwrite)
+                features = None
+            del features
+            residual = None
+            for layer_idx in range(num_layers):
+                residual_step = layer_idx % res_every == 0
+                following = torch.empty((num_nodes, p['hidden_size']), dtype=table.dtype, device=table.device)
+                built = []
+                for block in window_blocks():
+                    index = block.nodes.long()
+                    rows = table.index_select(0, index)
+                    kept_rows = residual.index_select(0, index) if residual_step and layer_idx > 0 else None
+                    out, _ = self._layer_step(layer_idx, rows, kept_rows, None, None, block, 1.0, None, False, w, act_id)
+                    following[block.first:block.last] = out
+                    if blocks is not None and kept is None:
+                        built.append(block)
+                    del block, index, rows, kept_rows, out
+                if blocks is not None and kept is None:
+                    kept = blocks.put(key, built)         # (only a whole layer's list is kept)
+                if residual_step:
+                    residual = table              # a residual step keeps its input table
+                if not any(later % res_every == 0 for later in range(layer_idx + 1, num_layers)):
+                    residual = None               # no residual step lies ahead: two tables
+                table = following
+                del following
+            return table
+
+    def _layerwise_prerequisites(self) -> Optional[str]:
+        """What the layer-wise pass needs and this model lacks, None when it can run it: _layered_prerequisites with one hop per
+        layer, which leaves its check of the timesteps (a window's block is one hop, and a layer of several timesteps reads
+        neighbours of neighbours)."""
+        return self._layered_prerequisites([0] * self.params['graph_num_layers'])
 
     @abstractmethod
     def _apply_gnn_layer(self,
@@ -347,6 +436,10 @@ class Sparse_Graph_Model(ABC):
             problem = self._layered_prerequisites(fanouts)
             if problem is not None:
                 raise ValueError(refusal % problem)
+        if need.layerwise is not None:
+            problem = self._layerwise_prerequisites()
+            if problem is not None:
+                raise ValueError(need.layerwise % problem)
         if need.message_scale is not None:
             problem = self._message_scale_prerequisites()
             if problem is not None:
@@ -386,6 +479,9 @@ class Sparse_Graph_Model(ABC):
     def _final_node_states(self, batch: DeviceBatch, training: bool) -> torch.Tensor:
         keep = self.params['graph_layer_input_dropout_keep_prob'] if training else 1.0
         batch.wait_ready()               # assembled on a side stream (tasks/resident.py)? wait on the GPU, not the host
+        plan = None if training else batch.extra.get('layerwise_evaluation')
+        if plan is not None:             # a full-graph evaluation batch of a task that asks for the layer-wise pass (tasks/layerwise.py)
+            return self.layerwise_final_node_representations(batch, plan.rows_per_batch, blocks=plan.blocks)
         # a batch from the input pipeline may carry its bucketing, built on a side stream (tasks/batcher.py)
         graph = getattr(batch, "graph", None)
         return self.compute_final_node_representations(
@@ -412,6 +508,9 @@ class Sparse_Graph_Model(ABC):
         if 'sampled_nodes' in batch.extra:
             raise RuntimeError("capture_train_step records ONE fixed batch; a sampled batch (tasks/neighbour_sampling.py) has another "
                                "shape every step")
+        if self.task.model_requirements().layerwise is not None:
+            raise RuntimeError("capture_train_step records ONE fixed batch; a task with layerwise_evaluation (tasks/layerwise.py) runs "
+                               "its evaluation window by window, with a read-back per window")
         if self.device.type != "cuda":
             raise RuntimeError("capture_train_step needs a model on the GPU (a hipGraph records GPU work)")
         batch.wait_ready()

@@ -32,6 +32,7 @@ from .. import _lib, config as _cfg
 from ..dense import dense, mark_zero_padded
 from ..parallel import refuse_single_graph_task, single_graph_schedule
 from ..predict import predict_softmax
+from .layerwise import KeptBlocks, LayerwisePlan, check_layerwise_evaluation, parse_layerwise_evaluation
 from .neighbour_sampling import PREDICT_SEEDS_PER_BATCH, check_prediction_nodes, check_sparse_node_features, parse_sampled_batches
 from .subgraph_sampling import parse_subgraph_batches
 from .resident import ResidentDataset
@@ -215,6 +216,7 @@ class Citation_Network_Task(Sparse_Graph_Task):
         self.batches = SingleGraphBatches(self)                   # the sampled batches of every mode, their device, counters and caches
         self.subgraph_batches                                     # (a malformed parameter fails here, not in the first epoch)
         self.sampled_batches
+        self.layerwise_evaluation
         self.__num_edge_types = 2
         self.__initial_node_feature_size = 0
         self.__num_output_classes = 0
@@ -289,6 +291,22 @@ class Citation_Network_Task(Sparse_Graph_Task):
         test() run on the full graph."""
         sampled = self.sampled_batches
         return None if sampled is None else sampled.get("evaluation")
+
+    @property
+    def layerwise_evaluation(self) -> Optional[Dict[str, Any]]:
+        """The validated `layerwise_evaluation` parameter ({"rows_per_batch", "keep"}; tasks/layerwise.py), None when VALIDATION, TEST,
+        test() and predict(data) run the full graph as one batch."""
+        return check_layerwise_evaluation(parse_layerwise_evaluation(self.params.get('layerwise_evaluation')),
+                                          parse_sampled_batches(self.params.get('sampled_batches')))
+
+    def _layerwise_plan(self, fold, data_fold: DataFold) -> Optional[LayerwisePlan]:
+        """What a full-graph batch of an evaluation fold carries under extra['layerwise_evaluation'], None for a TRAIN batch and
+        without the parameter."""
+        asked = self.layerwise_evaluation
+        if asked is None or data_fold == DataFold.TRAIN:
+            return None
+        kept = KeptBlocks(self.batches.kept_layerwise, fold.labels) if asked["keep"] and fold is not None else None
+        return LayerwisePlan(asked["rows_per_batch"], kept)
 
     @property
     def num_edge_types(self) -> int:
@@ -458,6 +476,9 @@ class Citation_Network_Task(Sparse_Graph_Task):
             'mask': fold.mask,
             'out_layer_dropout_keep_prob': self._out_keep(data_fold),
         }
+        plan = self._layerwise_plan(fold, data_fold)
+        if plan is not None:
+            feed['layerwise_evaluation'] = plan                       # (not an array either)
         if sparse:
             feed['sparse_node_features'] = fold.node_features       # (not an array: DeviceBatch keeps it as it is, in `extra`)
         yield MinibatchData(feed_dict=feed, num_graphs=1, num_nodes=fold.node_features.shape[0],
@@ -504,7 +525,11 @@ class Citation_Network_Task(Sparse_Graph_Task):
             message_scale = ('subgraph_batches: normalisation: "aggregation": true requires %s: the per-edge weights take the place '
                              'of 1/(in-degree + 1e-7) in a sum over the messages; "aggregation": false (the loss normalisation '
                              'alone) works with every model')
-        return ModelRequirements(tuple(layered), message_scale, self.sparse_update, self.sparse_gradient)
+        layerwise = None
+        if self.layerwise_evaluation is not None:                              # a window's block is one hop under every layer
+            layerwise = ('layerwise_evaluation requires %s: every layer runs on the blocks of its windows, one hop each, and the '
+                         'layer functions take one graph')
+        return ModelRequirements(tuple(layered), message_scale, self.sparse_update, self.sparse_gradient, layerwise)
 
     def epoch_batches(self, data, data_fold: DataFold, device, full_graph_route: bool, full_graph: bool = False):
         if data_fold == DataFold.TRAIN and (self.sampled_batches is not None or self.subgraph_batches is not None):
@@ -513,6 +538,9 @@ class Citation_Network_Task(Sparse_Graph_Task):
         if data_fold != DataFold.TRAIN and not full_graph and self.evaluation is not None:
             self.bind_sampling_device(device)
             return self.evaluation_batches(data, data_fold, full_graph_route)
+        if data_fold != DataFold.TRAIN and self.layerwise_evaluation is not None and torch.device(device).type != "cuda":
+            raise RuntimeError("layerwise_evaluation needs a model on the GPU: the window block is a HIP kernel and there is no CPU "
+                               "fallback (the model is on %s)" % (device,))
         return None
 
     def epoch_result(self, result, data_fold: DataFold):
@@ -581,6 +609,11 @@ class Citation_Network_Task(Sparse_Graph_Task):
             batch.extra['out_layer_dropout_keep_prob'] = keep
         else:
             batch = batcher.pack(ids)
+        plan = self._layerwise_plan(getattr(batcher.store, "citation_fold", None), data_fold)
+        if plan is not None:
+            batch.extra['layerwise_evaluation'] = plan
+        else:
+            batch.extra.pop('layerwise_evaluation', None)             # (a resident fold's one batch is handed out again)
         return batch
 
     # -------------------- Data parallelism over the sampled batches of the ONE graph (the key "data_parallel"; models/data_parallel.py) ----

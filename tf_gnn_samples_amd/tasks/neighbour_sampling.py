@@ -261,13 +261,16 @@ class StampedNodeSet(PhaseTrace):
     """One RelGraph on the GPU (rowptr_t / col_t are read in place) and its [V] int32 stamp array, all zero between calls and after a
     call that raised.  A call stamps a node set (`begin`, or a launch of the sampler's own) and lists it ascending (`compact`)."""
 
-    def __init__(self, graph, what: str, refuse_unsupported):
-        """what: names the sampler in the refusals; refuse_unsupported(lib) raises ValueError for what the library does not support."""
+    def __init__(self, graph, what: str, refuse_unsupported, trusts_ids: bool = True):
+        """what: names the sampler in the refusals; refuse_unsupported(lib) raises ValueError for what the library does not support.
+        trusts_ids=False (tasks/layerwise.py): the user's kernels check every id of col_t themselves, and the graph is not inspected
+        (check() would also split the hub buckets of a graph the model bucketed with validate="deferred")."""
         if not graph.rowptr_t.is_cuda:
             raise _lib.RelGnnLibraryError("%s runs on the GPU only; the graph is on %s" % (what, graph.rowptr_t.device))
         lib = _lib.load_library()
         refuse_unsupported(lib)
-        graph.check()                                             # (node ids in range: the kernels trust col_t)
+        if trusts_ids:
+            graph.check()                                         # (node ids in range: the kernels trust col_t)
         self.graph = graph
         self.stamp = torch.zeros(graph.V, dtype=torch.int32, device=graph.device)
         self._compact_bytes = lib.relgnn_neighbour_sample_workspace_bytes(graph.V)

@@ -120,6 +120,11 @@ arena).  The same arrays run through the same
 kernels: GGNN, RGAT and GNN-FiLM give the bits they gave; RGCN gives the forward's bits, and weight gradients that differ by the
 rounding of a sum over fewer rows.
 
+Beside both stands the task parameter `layerwise_evaluation` ({"rows_per_batch": B, "keep": bool}; tasks/layerwise.py describes it):
+the full-graph batch of a VALIDATION or TEST fold then carries a LayerwisePlan and the model computes it layer by layer over windows
+of B target rows; "keep" keeps the windows' blocks in `kept_layerwise`, under the fold's label array.  A ValueError together with the
+key "evaluation"; every other key of either parameter composes with it.
+
 Both parameters take one more optional key, "data_parallel": true (a ValueError together with "sparse_update" / "sparse_gradient"; it
 composes with every other key): train(group=...) and test(group=...) of a process group of W > 1 ranks are no longer refused
 (models/data_parallel.py).  Every rank holds the whole graph; global batch j of a TRAIN epoch goes to rank
@@ -198,6 +203,7 @@ class SingleGraphBatches:
         self.graph_states = WeakKeyedCache()      # (first adjacency array, features), device -> GraphState
         self.fold_states = WeakKeyedCache()       # (a fold's label array), (device, replica or "subgraph") -> FoldState
         self.kept_evaluation = WeakKeyedCache()   # (a fold's label array), (device, fold number, route, fanouts, B) -> its batches
+        self.kept_layerwise = WeakKeyedCache()    # (a fold's label array), (device, B, route) -> the blocks of its windows (tasks/layerwise.py)
         self.sampler_plans = WeakKeyedCache()     # (a fold's label array), the parsed `subgraph_batches` -> its host SamplerPlan
 
     def bind(self, device) -> None:

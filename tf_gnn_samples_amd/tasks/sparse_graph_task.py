@@ -105,6 +105,7 @@ class ModelRequirements(NamedTuple):
     message_scale: Optional[str] = None         # the text, when batches bring a per-message scale in the degree scale's place
     deferred_projection_rows: bool = False      # the input projection's weight is updated by the rows a batch names
     compact_projection_gradient: bool = False   # ... and its gradient exists only as those rows
+    layerwise: Optional[str] = None             # the text, when evaluation batches run layer by layer over windows of target rows
 
 
 class Sparse_Graph_Task:
